@@ -13,12 +13,16 @@ one hipGraph so that the timed region contains no host work.  Batch-1 inference 
 with N GPUs every rank runs its own replica on its own image ("replicas only", weak scaling); the
 only communication is the one-time RCCL broadcast of rank 0's packed weights.
 
-Timing: W untimed warm-up steps, then WINDOWS (default 7) windows of exactly K steps each, every window
-bracketed by barrier + synchronisation on both sides and reduced with MAX over ranks; `ms_per_step` /
-`value` are the MEDIAN window (one 20-step window of a 75 us step is 1.5 ms: a single sample of that
-length is at the mercy of one scheduler hiccup), all windows are listed in `windows_ms`.
+Timing: W untimed warm-up steps, then exactly K timed steps, cut into WINDOWS (default 1, at most K) windows of
+(nearly) equal length, every window bracketed by barrier + synchronisation on both sides and reduced with MAX over
+ranks; `ms_per_step` / `value` come from the MEDIAN window's time per step, all windows are listed in `windows_ms` /
+`window_steps` of the full record.  Every window pays one launch + synchronisation latency that its steps share:
+windows of 29 MobileNetV1 steps measured 0.3 - 0.9 us per step (~1 %) above windows of 200 on the same box, so a run
+that wants a median of several windows gives each of them thousands of steps.  --dump-outputs DIR then writes the
+pass's output tensors as the last timed step left them (dump_outputs).  A plain run stops there: it sets up, warms up,
+times the K steps and prints its line.
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline     -- the dominant kernel function of the step (largest share of GPU time), its
                   algorithmic bytes per launch over its average launch duration measured with HIP
                   events on the launch stream, against the 8 TB/s HBM peak (MobileNetV1 at batch 1
@@ -33,7 +37,8 @@ The JSON line also carries
                   configs[3] MobileNetV1 binary16 NCHW batch 1 (c906_mobilenetv1_f16 shapes), and MobileNetV1 int8 at
                   batch 128 (throughput view of configs[1]).  N > 1: configs[4] -- the ResNet-50 3x3 set with a total
                   batch of 128 N SHARDED over the ranks (128 images per GPU), rank 0's packed weights broadcast once
-                  with RCCL behind the C-ABI.  --no-configs skips them; --extra adds serving views.
+                  with RCCL behind the C-ABI.  --no-configs skips them; --extra adds serving views;
+  mfma_rate, session_ms_per_image -- the measured int8 MFMA instruction rates, the whole model through csinn_session_run.
 
 --workload resnet50_3x3 --total-batch 1024 runs configs[4] as the headline instead.
 Process group: torch.distributed is bootstrap only (gloo: the 128-byte ncclUniqueId, agreement flags, barriers and
@@ -70,19 +75,29 @@ def parse_args():
     ap.add_argument("--layout", default="", choices=["", "NHWC", "NCHW"])
     ap.add_argument("--total-batch", type=int, default=0,
                     help="total batch sharded over the ranks (BASELINE configs[4]: resnet50_3x3 --total-batch 1024)")
-    ap.add_argument("--windows", type=int, default=7, help="timed windows of --steps steps each (median reported)")
-    ap.add_argument("--no-configs", action="store_true", help="headline only: skip the configs[2] / configs[3] entries")
-    ap.add_argument("--extra", action="store_true", help="serving views: concurrent streams, csinn_session_run end to end")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--windows", type=int, default=1,
+                    help="the --steps timed steps are cut into this many windows of (nearly) equal length (median reported)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: roofline + per-kernel table, measured MFMA rates, the other configurations, "
+                         "the session view and the CPU baseline (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed (the pass's output tensors) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the configs[2] / configs[3] entries")
+    ap.add_argument("--extra", action="store_true", help="serving views: concurrent streams, csinn_session_run end to end (implies --full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-fuse", action="store_true", help="every layer its own launch (no pointwise+depthwise fusion)")
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--detail", action="store_true", help="print the per-layer table to stderr")
+    ap.add_argument("--detail", action="store_true", help="print the per-layer table to stderr (implies --full)")
     ap.add_argument("--steps-only", action="store_true",
                     help="run warmup + timed steps and stop (for rocprofv3 --pmc passes: only step launches are seen)")
     ap.add_argument("--traffic-file", default="",
                     help="JSON from tools/pmc_traffic.py (default profiles/traffic_<workload>_<dtype>_<layout>_b<batch>.json)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.windows < 1:
+        ap.error("--steps and --windows must be >= 1, --warmup >= 0")
+    # the per-layer table and the serving views are measurements of their own: they ask for the full run
+    args.full = args.full or args.detail or args.extra
     # with a profiler attached every pass is launched kernel by kernel instead of as a graph replay
     # (workloads.PROFILER_ATTACHED: rocprofv3 --kernel-trace of ROCm 7.2 crashes in hipGraphLaunch)
     args.profiler = any(k.startswith(("ROCPROF_", "ROCP_TOOL")) for k in os.environ)
@@ -216,14 +231,21 @@ class CHbm:
         self.live = []
 
 
-def timed_windows(replay, sync, steps, warmup, windows, dist=None, torch=None):
-    """W warm-up steps, then `windows` windows of exactly `steps` steps, each bracketed by barrier + synchronisation on
-    both sides and reduced with MAX over ranks (CPU tensors: the process group is bootstrap only)."""
+def split_steps(steps, windows):
+    """the `steps` timed steps of a run as min(windows, steps) windows of (nearly) equal length"""
+    n = max(1, min(windows, steps))
+    return [steps // n + (1 if k < steps % n else 0) for k in range(n)]
+
+
+def timed_windows(replay, sync, sizes, warmup, dist=None, torch=None):
+    """W warm-up steps, then one window per entry of `sizes` of exactly that many steps, each bracketed by barrier +
+    synchronisation on both sides and reduced with MAX over ranks (CPU tensors: the process group is bootstrap only).
+    Returns the seconds of every window."""
     for _ in range(warmup):
         replay()
     sync()
     out = []
-    for _ in range(max(1, windows)):
+    for steps in sizes:
         sync()
         if dist:
             dist.barrier()
@@ -340,7 +362,7 @@ def measure_config(tag, name, layers_x, batch_x, dtype_x, layout_x, bound_x, cha
         how = par.broadcast_weights(rc, torch, dist, hip, opt, env["rank"], env["world"], src=0, prefer_c=bcast_from)
         par.assert_replicas_agree(rc, torch, dist, hip)
     rc.capture(stream)
-    wins = timed_windows(rc.replay, lambda: hip.shl_mi355x_stream_sync(stream), steps, warmup, windows, dist, torch)
+    wins = timed_windows(rc.replay, lambda: hip.shl_mi355x_stream_sync(stream), [steps] * windows, warmup, dist, torch)
     t_pass = float(np.median(wins)) / steps
     world = env["world"] if dist is not None else 1
     images = total_batch if total_batch else batch_x * world
@@ -378,7 +400,7 @@ def measure_config(tag, name, layers_x, batch_x, dtype_x, layout_x, bound_x, cha
             def sync2():
                 for _, sk in pairs:
                     hip.shl_mi355x_stream_sync(sk)
-            w2 = timed_windows(replay2, sync2, steps, warmup, windows)
+            w2 = timed_windows(replay2, sync2, [steps] * windows, warmup)
             entry["two_streams"] = {"ms_per_pass": float(np.median(w2)) / steps * 1e3,
                                     "note": "even / odd layers of the set as two graphs on two streams (the layers are independent): "
                                             "launch ramp / drain / boundary overlapped; not the figure of merit"}
@@ -408,7 +430,7 @@ def measure_config(tag, name, layers_x, batch_x, dtype_x, layout_x, bound_x, cha
             def sync2():
                 for _, sk in pairs:
                     hip.shl_mi355x_stream_sync(sk)
-            w2 = timed_windows(replay2, sync2, steps, warmup, windows)
+            w2 = timed_windows(replay2, sync2, [steps] * windows, warmup)
             entry["two_streams"] = {"ms_per_pass": float(np.median(w2)) / steps * 1e3,
                                     "note": "the batch as two half-batch chains on two streams (per %d images); not the figure of merit" % batch_x}
             for ck, sk in pairs:
@@ -530,6 +552,32 @@ def emit(result):
         pass
     sys.stdout.flush()
     print(json.dumps(compact_line(result), separators=(",", ":")), flush=True)
+
+
+DUMP_LIMIT_BYTES = 60 * 1000 * 1000  # all .npy files of one --dump-outputs together
+
+
+def dump_outputs(chain, hip, stream, out_dir):
+    """--dump-outputs: the tensors a caller of the timed pass receives, as the last timed step left them -- every layer
+    output no other layer of the pass reads (a chained network: the tensor in front of the average pooling and the
+    classifier's; an independent set: every layer's) -- written as <out_dir>/layer<NN>.npy in float32 (exact for int8
+    and binary16).  An array larger than its share of DUMP_LIMIT_BYTES is replaced by a fixed, seeded sample of its
+    elements (flat indices in increasing order), so that two builds can be compared output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    pkg = importlib.import_module("csi-nn2_amd")
+    pkg.check(hip.shl_mi355x_stream_sync(stream), hip, "stream_sync")
+    read = {e["d_in"] for e in chain.entries}
+    finals = [(i, e) for i, e in enumerate(chain.entries) if e["d_out"] not in read]
+    share = DUMP_LIMIT_BYTES // 4 // len(finals)
+    for i, e in finals:
+        host = np.empty(e["out_dims"], dtype=np.int8 if chain.dtype == "int8" else np.float16)
+        pkg.check(hip.shl_mi355x_download(host.ctypes.data, e["d_out"], host.nbytes, None), hip, "download")
+        pkg.check(hip.shl_mi355x_stream_sync(None), hip, "stream_sync")
+        out = host.astype(np.float32)
+        if out.size > share:
+            idx = np.sort(np.random.default_rng(20240 + i).choice(out.size, share, replace=False))
+            out = out.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, "layer%02d.npy" % i), out)
 
 
 def launch_plan(gpus, environ):
@@ -698,26 +746,30 @@ def main():
 
     stream = hip.shl_mi355x_stream_create()
     chain.capture(stream)
-    windows = timed_windows(chain.replay, lambda: hip.shl_mi355x_stream_sync(stream), args.steps, args.warmup, args.windows, dist, torch)
-    elapsed = float(np.median(windows))
+    sizes = split_steps(args.steps, args.windows)
+    windows = timed_windows(chain.replay, lambda: hip.shl_mi355x_stream_sync(stream), sizes, args.warmup, dist, torch)
+    step_s = float(np.median([w / n for w, n in zip(windows, sizes)]))  # seconds per step of the median window
+    if args.dump_outputs and rank == 0:
+        dump_outputs(chain, hip, stream, args.dump_outputs)
 
-    total_images = (args.total_batch if sharded else world * batch) * args.steps
+    step_images = args.total_batch if sharded else world * batch
     ops_per_image = chain.total_ops() // batch
-    ops_total = ops_per_image * total_images
+    step_ops = ops_per_image * step_images
     result = {
         "metric": "mobilenetv1_int8_images_per_sec" if args.workload == "mobilenetv1" else "resnet50_3x3_int8_conv_gops",
-        "value": total_images / elapsed if args.workload == "mobilenetv1" else ops_total / elapsed / 1e9,
+        "value": step_images / step_s if args.workload == "mobilenetv1" else step_ops / step_s / 1e9,
         "unit": "img/s" if args.workload == "mobilenetv1" else "GOPS",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+        "ms_per_step": step_s * 1e3, "higher_is_better": True,
         "scaling": "strong" if sharded else "weak",
         "vs_baseline": None, "dtype": "i8" if args.dtype == "int8" else "f16", "data": "synthetic",
-        "conv_gops": ops_total / elapsed / 1e9,
-        "images_per_sec": total_images / elapsed,
+        "conv_gops": step_ops / step_s / 1e9,
+        "images_per_sec": step_images / step_s,
         "windows_ms": [w * 1e3 for w in windows],
+        "window_steps": sizes,
         "profiler_attached": bool(args.profiler),
-        "timing": "median of %d windows of %d steps, each bracketed by barrier + synchronise, MAX over ranks" % (
-            len(windows), args.steps),
+        "timing": "%d timed steps in %d windows (%s steps), each bracketed by barrier + synchronise, MAX over ranks; "
+                  "ms_per_step = the median window's time per step" % (args.steps, len(sizes), "/".join(map(str, sizes))),
         "config": {"workload": "%s %s %s, %d conv layers in %d launches%s, batch %d per GPU%s, hipGraph replay via csinn_* C API"
                                % (args.workload, args.dtype, layout, len(layers), len(chain.units),
                                   " (pointwise+depthwise pairs fused as csinn_session_setup does)" if len(chain.units) < len(layers) else "",
@@ -758,7 +810,7 @@ def main():
         if rccl_error:
             sys.exit(3)
 
-    if args.steps_only:
+    if args.steps_only or not args.full:
         if rank == 0:
             emit(result)
         return finish()

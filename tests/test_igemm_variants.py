@@ -102,14 +102,15 @@ def _run_variant(variant):
 # The sub-processes are independent (own interpreter, own HIP context, small tensors) and spend most of their ~25 s
 # in process start-up, plan creation and allocation calls, not on the GPU: the first test that runs starts all of
 # them on a small pool, every test then waits for its own.  27 x 25 s one after the other was 11 of the suite's 15
-# minutes.
+# minutes.  Every sub-process opens the GPU, and so does this process: four workers keep the suite at five processes
+# with the device open, inside what a shared GPU host allows one job.
 _POOL = {}
 
 
 def _variant_result(index):
     if not _POOL:
         from concurrent.futures import ThreadPoolExecutor
-        workers = max(1, min(6, (os.cpu_count() or 2) // 2))
+        workers = max(1, min(4, (os.cpu_count() or 2) // 2))
         ex = ThreadPoolExecutor(max_workers=workers)
         _POOL["futures"] = [ex.submit(_run_variant, v) for v in VARIANTS]
         _POOL["executor"] = ex
