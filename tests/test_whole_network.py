@@ -187,6 +187,49 @@ def test_mobilenetv1_fp16_nchw_chain_with_fused_pairs(gpu):
 
 
 @pytest.mark.gpu
+def test_mobilenetv1_fp16_nchw_fused_pairs_pair_by_pair(gpu):
+    """configs[3]'s 13 fused pairs, each layer on its own bar.  A pointwise + depthwise pair
+    (csrc/pwdw_f16_nchw.hip) is relaunched on the chain's own plans and input and must reproduce the chain's output bit for bit;
+    its intermediate is read back with one-hot depthwise probes (tests/test_pwdw_f16.py) and must be within 1e-3 of the oracle's
+    pointwise layer fed the pair's GPU input (L1), and the pair's output must equal the oracle's depthwise layer fed that
+    intermediate bit for bit (L2).  The stem pair (csrc/stemdw_f16_nchw.hip) must equal the stand-alone stem and depthwise launches
+    bit for bit, with the stand-alone stem's output as the intermediate of the same two checks."""
+    from test_pwdw_f16 import check_layers, plus_zero
+    fe, hip, opt, dev = gpu
+    chain, outs = run_chain(gpu, "f16", "NCHW", True)
+    feeds = chain_inputs(chain)
+    get = opt.shl_mi355x_registry_get
+    kinds = []
+    for k, u in enumerate(chain.units):
+        if len(u) != 2:
+            continue
+        a, b = chain.entries[u[0]], chain.entries[u[1]]
+        x = feeds[u[0]] if u[0] in feeds else outs[u[0] - 1]
+        first = layer_case(a["layer"], a["ops"], "f16", "NCHW", x)
+        dw = layer_case(b["layer"], b["ops"], "f16", "NCHW", np.zeros(b["in_dims"], np.float16))
+        kind = chain.unit_kernel_name(k)
+        what = "unit %d %s (%s)" % (k, chain.unit_name(k), kind)
+        kinds.append(kind)
+        if kind == "pwdw_f16_nchw":
+            worst = check_layers(gpu, get(a["params"]), get(b["params"]), first, dw, a["d_in"], what, fused_out=outs[u[1]])
+            print("%s: relaunch bit-identical, L2 bit-exact, L1 worst relative error %.2e" % (what, worst))
+            continue
+        keep = []
+        mid = cases.csinn_run(fe, pkg.API_MI355X, first, device=dev, keep_params=keep)
+        alone = cases.csinn_run(fe, pkg.API_MI355X, dict(dw, input=mid), device=dev, keep_params=keep).view(np.uint16)
+        for p, _ in keep:
+            opt.shl_mi355x_release_params(p)
+        assert np.array_equal(plus_zero(alone), plus_zero(outs[u[1]].view(np.uint16))), "%s: the stand-alone launches differ" % what
+        golden_util.compare_f16_tol(mid, cases.oracle_run(first, "f16"), "%s: L1 stem vs oracle" % what)
+        want = cases.oracle_run(dict(dw, input=mid), "f16").view(np.uint16)
+        bad = plus_zero(alone) != plus_zero(want)
+        assert not bad.any(), "%s: L2 vs oracle depthwise fed the stem's output: %d words differ" % (what, int(bad.sum()))
+        print("%s: stand-alone launches bit-identical, L1 within 1e-3, L2 bit-exact" % what)
+    assert kinds.count("pwdw_f16_nchw") == 12 and kinds.count("stemdw_f16_nchw") == 1, kinds
+    chain.release()
+
+
+@pytest.mark.gpu
 def test_mobilenetv1_int8_batch128_chain_equals_the_oracle_chain(gpu):
     """The pass bench.py's throughput view times: MobileNetV1 int8 NHWC at batch 128 as csinn_session_setup launches it
     (depthwise -> pointwise blocks of 32 .. 256 channels in one launch each: dwpw_stream; resident-weights pointwise and
