@@ -15,11 +15,27 @@
 //              channel c (dequantise, fp32 sum in (y, x) order, / HW, requantise: global_avgpool_nhwc_i8_kernel's operations)
 // Restates shl_ref_conv2d_quant (source/reference/convolution.c:370-400) incl. the relu variants, and for POOL
 // shl_ref_global_avgpool2d_quant behind it (source/reference/global_averagepool.c:46-50, averagepool.c:21-119).
+#include <stddef.h>
 #include <stdlib.h>
 
 #include "igemm_common.h"
 
 namespace shl {
+
+// A kernel argument (or a whole argument struct: only the fields that are used are fetched) read at THIS point of the program:
+// the pointer to the argument segment passes through an empty asm, so the scalar loads depend on it and cannot be hoisted above
+// it -- arguments read the plain way are fetched wherever the compiler likes, in front of the first branch or behind the last
+// barrier.  `off`: byte offset in the kernel-argument segment (the explicit arguments come first, naturally aligned).
+template <class T>
+__device__ __forceinline__ T kernarg_here(size_t off)
+{
+    typedef const __attribute__((address_space(4))) char *KernargPtr;
+    KernargPtr p = (KernargPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    T v;
+    __builtin_memcpy(&v, (const __attribute__((address_space(4))) T *)(p + off), sizeof(T));
+    return v;
+}
 
 struct LatPoolArgs {
     void *out;            // pooled output [N][Co] int8, or null: no pooling
@@ -47,6 +63,7 @@ __global__ __launch_bounds__(512) void conv1x1_latency_kernel(ConvArgs a, LatPoo
     v4i fa[NSW];
 #pragma unroll
     for (int s = 0; s < NSW; ++s) fa[s] = *reinterpret_cast<const v4i *>(wp + s * 1024);
+    __builtin_amdgcn_sched_barrier(0);  // (the weight fragments are requested before anything of the pixel addresses is computed)
     const char *img = static_cast<const char *>(a.in) + (int64_t)n * HW * a.C + fhalf * 16 + sub0 * 32;
     v4i fb[MT][NSW];
 #pragma unroll
@@ -56,12 +73,35 @@ __global__ __launch_bounds__(512) void conv1x1_latency_kernel(ConvArgs a, LatPoo
 #pragma unroll
         for (int s = 0; s < NSW; ++s) fb[t][s] = *reinterpret_cast<const v4i *>(px + s * 32);
     }
+    // ---- the shadow (pwdw_fused.hip): every fragment load is issued, the first MFMA waits a whole global-memory latency for them.
+    // What the rest of the kernel needs and no loaded data decides is requested or computed in that window -- left to the compiler, the
+    // epilogue's and the pooling's kernel arguments are fetched behind the barriers (exposed scalar round trips) and the finishing
+    // tables are requested behind the MFMAs.  The two scheduling fences keep the window's contents where they are; the waits stay
+    // the compiler's.
+    __builtin_amdgcn_sched_barrier(0);
+    // the epilogue's and the pooling's kernel arguments, read HERE (kernarg_here: not in front of the fragment loads) and "used" by an
+    // empty asm (not behind the barriers): from here on the layer is al, the pooling pll
+    const ConvArgs al = kernarg_here<ConvArgs>(0);
+    const LatPoolArgs pll = kernarg_here<LatPoolArgs>((sizeof(ConvArgs) + alignof(LatPoolArgs) - 1) & ~(alignof(LatPoolArgs) - 1));
+    asm volatile("" ::"s"(al.out_zp), "s"(al.out_zp_f), "s"(al.clamp_lo), "s"(al.clamp_hi), "s"(al.out_scale), "s"(al.inv_out_scale), "s"(al.act),
+                 "s"(al.div_exact));
+    if constexpr (POOL) asm volatile("" ::"s"(pll.out), "s"(pll.si), "s"(pll.zi), "s"(pll.so), "s"(pll.zo), "s"(pll.store_map));
     // finishing role: wave w -> register group w & 3 (channels 8 (w & 3) + 4 half .. +3 of the slice) of tile w >> 2
     const int fgrp = wave & 3, ftile = wave >> 2;
     const int pc = slice * 32 + 8 * fgrp + 4 * fhalf;
     const int4 p_ai = *reinterpret_cast<const int4 *>(a.acc_init + pc);
     const float4 p_mu = *reinterpret_cast<const float4 *>(a.mult + pc);
     const float4 p_bi = *reinterpret_cast<const float4 *>(a.bias + pc);
+    // ... its output pixel and address, the clamp bounds and the packed zero point (the expressions of requant4_i8_t, common.h)
+    const int fp = (t0 + ftile) * 32 + frow;
+    uint32_t *const fout = reinterpret_cast<uint32_t *>(static_cast<char *>(a.out) + ((int64_t)n * HW + fp) * a.Co + pc);
+    const uint32_t fslot = (uint32_t)(fp * 8 + 2 * fgrp + fhalf);  // POOL: the dword of the LDS map
+    {
+        const float cl = al.clamp_lo - al.out_zp_f, ch = al.clamp_hi - al.out_zp_f;
+        const uint32_t zp2 = (uint32_t)(al.out_zp & 0xffff) * 0x00010001u;
+        asm volatile("" ::"v"(fp), "v"(fout), "v"(fslot), "v"(cl), "v"(ch), "s"(zp2));
+    }
+    __builtin_amdgcn_sched_barrier(0);
 
     const v16i zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     v16i acc[MT];
@@ -87,11 +127,10 @@ __global__ __launch_bounds__(512) void conv1x1_latency_kernel(ConvArgs a, LatPoo
         v4i v = part[((ftile * 8) * 4 + fgrp) * 64 + lane];
 #pragma unroll
         for (int k = 1; k < 8; ++k) v += part[((ftile * 8 + k) * 4 + fgrp) * 64 + lane];
-        const uint32_t pk = requant4_i8_sel<EPI>(v[0] + p_ai.x, v[1] + p_ai.y, v[2] + p_ai.z, v[3] + p_ai.w, p_mu, p_bi, a);
-        const int p = (t0 + ftile) * 32 + frow;
-        if (p < HW) {
-            if (!POOL || pl.store_map) *reinterpret_cast<uint32_t *>(static_cast<char *>(a.out) + ((int64_t)n * HW + p) * a.Co + pc) = pk;
-            if constexpr (POOL) pmap[p * 8 + 2 * fgrp + fhalf] = pk;
+        const uint32_t pk = requant4_i8_sel<EPI>(v[0] + p_ai.x, v[1] + p_ai.y, v[2] + p_ai.z, v[3] + p_ai.w, p_mu, p_bi, al);
+        if (fp < HW) {
+            if (!POOL || pll.store_map) *fout = pk;
+            if constexpr (POOL) pmap[fslot] = pk;
         }
     }
     if constexpr (POOL) {
@@ -100,9 +139,9 @@ __global__ __launch_bounds__(512) void conv1x1_latency_kernel(ConvArgs a, LatPoo
             // global_avgpool_nhwc_i8_kernel's operations (pool_softmax.hip) on channel tid of the slice
             const int8_t *col = reinterpret_cast<const int8_t *>(pmap) + tid;
             float total = 0.f;
-            for (int p = 0; p < HW; ++p) total = __fadd_rn(total, __fmul_rn(__fsub_rn((float)col[p * 32], pl.zi), pl.si));
-            const int q = sat8_from_float(__fadd_rn(rintf(__fdiv_rn(__fdiv_rn(total, (float)HW), pl.so)), pl.zo));
-            static_cast<int8_t *>(pl.out)[(int64_t)n * a.Co + slice * 32 + tid] = (int8_t)q;
+            for (int p = 0; p < HW; ++p) total = __fadd_rn(total, __fmul_rn(__fsub_rn((float)col[p * 32], pll.zi), pll.si));
+            const int q = sat8_from_float(__fadd_rn(rintf(__fdiv_rn(__fdiv_rn(total, (float)HW), pll.so)), pll.zo));
+            static_cast<int8_t *>(pll.out)[(int64_t)n * a.Co + slice * 32 + tid] = (int8_t)q;
         }
     }
 }

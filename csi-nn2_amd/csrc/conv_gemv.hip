@@ -26,6 +26,12 @@ template <bool kI8, int OPW>
 __global__ __launch_bounds__(256) void conv_gemv_kernel(ConvArgs a)
 {
     constexpr int ESIZE = kI8 ? 1 : 2;
+    // every kernel argument in ONE batch of scalar loads in front of the first branch (an empty asm "uses" them here; pwdw_fused.hip):
+    // the compiler otherwise fetches each in the block that first reads it -- three dependent round trips in front of the weight
+    // stream and another behind the butterfly
+    asm volatile("" ::"s"(a.in), "s"(a.w), "s"(a.out), "s"(a.acc_init), "s"(a.mult), "s"(a.bias), "s"(a.C), "s"(a.Co), "s"(a.kstride));
+    asm volatile("" ::"s"(a.out_zp_f), "s"(a.clamp_lo), "s"(a.clamp_hi), "s"(a.act), "s"(a.act_clamp), "s"(a.div_exact), "s"(a.out_scale),
+                 "s"(a.inv_out_scale), "s"(a.scale_out));
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int p = blockIdx.y;
@@ -38,6 +44,17 @@ __global__ __launch_bounds__(256) void conv_gemv_kernel(ConvArgs a)
     float acc_f[OPW];
 #pragma unroll
     for (int o = 0; o < OPW; ++o) acc_i[o] = 0, acc_f[o] = 0.f;
+    // lane o < OPW finishes channel oc0 + o: its epilogue tables depend on no loaded data.  Left to the compiler, the three table
+    // loads are issued where they are first used -- behind the dot products AND the butterfly -- and waited for at once: a whole memory
+    // round trip in a 2.7-us launch, with the epilogue's kernel arguments fetched in front of it.  They are requested here instead, in
+    // uniform control flow right in front of the weight stream (the loop's trip count differs per lane, so no place inside it serves
+    // every finishing lane; ~10 instructions in front of the first weight load against a round trip behind the last), and their
+    // latency passes under the stream's.
+    const int oc = oc0 + lane < a.Co ? oc0 + lane : a.Co - 1;  // (lanes without a channel read a valid one)
+    int32_t e_ai = 0;
+    float e_mu = 0.f;
+    if constexpr (kI8) e_ai = a.acc_init[oc], e_mu = a.mult[oc];
+    const float e_bi = a.bias[oc];
     for (int off = lane * 16; off < kb; off += 1024) {
         const v4i x = *reinterpret_cast<const v4i *>(in + off);
         v4i wv[OPW];
@@ -72,16 +89,14 @@ __global__ __launch_bounds__(256) void conv_gemv_kernel(ConvArgs a)
                 acc_f[o] += __shfl_xor(acc_f[o], s, 64);
         }
     if (lane < OPW && oc0 + lane < a.Co) {
-        const int oc = oc0 + lane;
         int32_t S = acc_i[0];
         float F = acc_f[0];
 #pragma unroll
         for (int o = 1; o < OPW; ++o) S = lane == o ? acc_i[o] : S, F = lane == o ? acc_f[o] : F;
         if constexpr (kI8) {
-            static_cast<int8_t *>(a.out)[(int64_t)p * a.Co + oc] =
-                (int8_t)requant_i8_fast(S + a.acc_init[oc], a.mult[oc], a.bias[oc], a);
+            static_cast<int8_t *>(a.out)[(int64_t)p * a.Co + oc] = (int8_t)requant_i8_fast(S + e_ai, e_mu, e_bi, a);
         } else {
-            static_cast<uint16_t *>(a.out)[(int64_t)p * a.Co + oc] = finish_f16(F, a.bias[oc], a);
+            static_cast<uint16_t *>(a.out)[(int64_t)p * a.Co + oc] = finish_f16(F, e_bi, a);
         }
     }
 }

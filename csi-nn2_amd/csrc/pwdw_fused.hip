@@ -95,8 +95,11 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
     asm volatile("" ::"s"(f.bh), "s"(f.bw), "s"(f.rw), "s"(f.npx), "s"(f.mt), "s"(f.ks), "s"(f.nsw), "s"(f.nsub), "s"(f.rw_magic),
                  "s"(f.ks_log2), "s"(f.mwn), "s"(f.img_stride));
     asm volatile("" ::"s"(q.in), "s"(q.w_frag), "s"(q.H), "s"(q.W), "s"(q.C), "s"(d.sh), "s"(d.sw), "s"(d.pt), "s"(d.pl), "s"(d.N));
-    // (only what stands in front of the fragment loads: with the epilogue's and the depthwise phase's arguments in the batch as well the
-    // pass got 0.5 us SLOWER -- those loads hide under the fragments' latency where the compiler puts them)
+    // (only what stands in front of the fragment loads: with the epilogue's and the depthwise phase's arguments in THIS batch the pass
+    // got 0.5 us slower in round 6 -- that trial had put them IN FRONT of the fragment loads.  Nor do those arguments "hide under the fragments'
+    // latency where the compiler puts them", as this comment used to say: the compiler fetches each in the block of its first use,
+    // behind the MFMAs and the barriers -- four exposed scalar round trips.  They get a batch of their own BEHIND the fragment loads:
+    // "the shadow" below.)
     int slice = blockIdx.x, tx = blockIdx.y, ty = blockIdx.z, n = 0;
     {
         // (computed whether or not the grid is XCD-mapped and then selected: inside `if (f.xg)` the fields below were fetched
@@ -147,6 +150,7 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
 #pragma unroll
     for (int s = 0; s < NSW; ++s)
         if (s < nsw) fa[s] = *reinterpret_cast<const v4i *>(wp + s * wstep);
+    if constexpr (FIXED) __builtin_amdgcn_sched_barrier(0);  // (the weight fragments are requested before anything of the pixel addresses is computed)
     v4i fb[MTW][NSW];
 #pragma unroll
     for (int i = 0; i < MTW; ++i) {
@@ -165,17 +169,63 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
                 if (s < nsw) fb[i][s] = *reinterpret_cast<const v4i *>(px + s * 32);
         }
     }
-    // ---- constants of the finishing roles, requested BEHIND the fragments (round 6; they were first: "they arrive under the K
+    // ---- the shadow: from here (every fragment load issued) to the first MFMA's wait the wave idles for a whole global-memory
+    // latency.  Everything the rest of the kernel needs that depends on no loaded data is requested or computed here; the two
+    // scheduling fences keep the window's contents between the fragment loads and the MFMAs, the compiler's own vmcnt / lgkmcnt
+    // accounting stays in charge of the waits.
+    __builtin_amdgcn_sched_barrier(0);
+    // every kernel argument of the finishing roles and the depthwise phase in ONE batch of scalar loads, HERE: read through
+    // kernarg_here (dw_patch.h) they cannot rise in front of the fragment loads, "used" by an empty asm they cannot sink behind the
+    // barriers.  From here on the two layers are ql and dl.
+    const uint32_t bw_magic = kernarg_here<uint32_t>(offsetof(PwDwArgs, bw_magic));
+    const ConvArgs ql = kernarg_here<ConvArgs>(offsetof(PwDwArgs, pw)), dl = kernarg_here<ConvArgs>(offsetof(PwDwArgs, dw));
+    asm volatile("" ::"s"(ql.acc_init), "s"(ql.mult), "s"(ql.bias), "s"(ql.out_zp), "s"(ql.out_zp_f), "s"(ql.clamp_lo), "s"(ql.clamp_hi),
+                 "s"(ql.out_scale), "s"(ql.inv_out_scale), "s"(dl.w), "s"(dl.acc_init), "s"(dl.mult), "s"(dl.bias), "s"(dl.out));
+    asm volatile("" ::"s"(dl.out_zp), "s"(dl.out_zp_f), "s"(dl.clamp_lo), "s"(dl.clamp_hi), "s"(dl.out_scale), "s"(dl.inv_out_scale),
+                 "s"(dl.in_zp), "s"(dl.Ho), "s"(dl.Wo), "s"(dl.C), "s"(dl.sh), "s"(dl.sw), "s"(bw_magic));
+    // constants of the finishing roles, requested BEHIND the fragments (round 6; they were first: "they arrive under the K
     // loop" -- but a wave issues an instruction per ~5.8 cycles, and the nine loads with their address arithmetic stood ~60
     // instructions = 0.17 us in front of the loads the MFMAs wait for)
     // pointwise: wave w finishes channels 8 (w & 3) + 4 half .. +3 of the slice, for every tile (with 8
     // waves: waves 0-3 the even tiles, waves 4-7 the odd ones)
     const int pc = slice * 32 + 8 * fgrp + 4 * fhalf;
-    const int4 p_ai = *reinterpret_cast<const int4 *>(q.acc_init + pc);
-    const float4 p_mu = *reinterpret_cast<const float4 *>(q.mult + pc);
-    const float4 p_bi = *reinterpret_cast<const float4 *>(q.bias + pc);
+    const int4 p_ai = *reinterpret_cast<const int4 *>(ql.acc_init + pc);
+    const float4 p_mu = *reinterpret_cast<const float4 *>(ql.mult + pc);
+    const float4 p_bi = *reinterpret_cast<const float4 *>(ql.bias + pc);
 
-    const DwThreadConsts dwk = dw_load_consts(d, slice * 32, tid);  // depthwise constants
+    const DwThreadConsts dwk = dw_load_consts(dl, slice * 32, tid);  // depthwise constants
+    // the depthwise phase's index arithmetic (dw_patch.h)
+    DwPatchGeom g;
+    g.bh = f.bh, g.bw = f.bw, g.rw = f.rw, g.bw_magic = bw_magic, g.pitch = dw_patch_pitch(f.npx);
+    g.oy0 = oy0, g.ox0 = ox0, g.ry0 = ry0, g.rx0 = rx0, g.n = n, g.ch0 = slice * 32;
+    const DwPrep dwp = dw_patch_prepare(dl, g, tid);
+    // the finishing roles': the patch's pitch and padding value, both layers' clamp bounds and packed zero points (the very
+    // expressions of requant4_i8_t, common.h: computed once, here) and, where the tile rounds are compile-time, every round's
+    // patch slot and in-image mask
+    const int ppitch = g.pitch;
+    const uint32_t zpad = dw_patch_pad(dl);
+    {
+        const float qcl = ql.clamp_lo - ql.out_zp_f, qch = ql.clamp_hi - ql.out_zp_f, dcl = dl.clamp_lo - dl.out_zp_f, dch = dl.clamp_hi - dl.out_zp_f;
+        const uint32_t qzp2 = (uint32_t)(ql.out_zp & 0xffff) * 0x00010001u, dzp2 = (uint32_t)(dl.out_zp & 0xffff) * 0x00010001u;
+        asm volatile("" ::"s"(ppitch), "s"(zpad), "v"(qcl), "v"(qch), "v"(dcl), "v"(dch), "s"(qzp2), "s"(dzp2));
+    }
+    auto in_image = [&](int j) {
+        const int r = (int)(((uint32_t)j * f.rw_magic) >> 20);
+        const int c = j - r * f.rw;
+        return (unsigned)(ry0 + r) < (unsigned)q.H && (unsigned)(rx0 + c) < (unsigned)q.W;
+    };
+    constexpr int NFT = (FIXED && EMT) ? TPW * (4 / (KSV ? KSV : 1)) : 1;  // compile-time tile rounds
+    uint32_t fslot[NFT], fkeep[NFT];  // per tile: the dword slot of this lane's pixel, all ones / zero: inside / outside the image
+    if constexpr (FIXED && EMT) {
+#pragma unroll
+        for (int t = 0; t < NFT; ++t) {
+            const int j = t * 32 + frow;
+            fslot[t] = (uint32_t)dw_patch_slot(j, 2 * fgrp + fhalf, ppitch);
+            fkeep[t] = in_image(j) ? 0xffffffffu : 0u;
+            asm volatile("" ::"v"(fslot[t]), "v"(fkeep[t]));
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
 
     v16i acc[MTW];
     if constexpr (EXACT) {
@@ -201,7 +251,10 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
         }
     }
 
-    if (q.debug & 256) return;  // ablation (tools/pair_bench.py): stop after loads + MFMA
+    // The ablation exits (tools/pair_bench.py) exist in the run-time form only (SHL_MI355X_PWDW_GENERIC=1): a conditional exit is a
+    // block boundary, and the compiler sinks every load and every computation above into the block of its first use behind it.
+    if constexpr (!FIXED)
+        if (q.debug & 256) return;  // ablation: stop after loads + MFMA
     // ---- partial sums -> LDS: part[((tile * ks + kpart) * 4 + group) * 64 + lane] = 4 channels
     v4i *part = reinterpret_cast<v4i *>(smem);
     uint32_t *patch = reinterpret_cast<uint32_t *>(smem + (size_t)mtp * ks * 4096);  // eight dword planes (dw_patch.h)
@@ -219,7 +272,8 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
         }
     }
     __syncthreads();
-    if (q.debug & 512) return;  // ablation: stop after the partial sums met in LDS
+    if constexpr (!FIXED)
+        if (q.debug & 512) return;  // ablation: stop after the partial sums met in LDS
     // ---- finish the pointwise layer: group `wave` of every tile -> int8 patch in LDS
     // Two tiles per round, every partial sum of both requested before the first use: a wave is alone on its SIMD here, and
     // one tile at a time is a chain of LDS latency -> adds -> the requantisation's dependent fmas -> LDS write that nothing
@@ -227,12 +281,12 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
     // per MobileNetV1 pass.  (Four tiles per round through small arrays: 74.7 us -- the code grew more than the chain shrank.)
     {
         // patch pixels outside the image take the depthwise layer's input zero point (dw_patch.h: the reader tests nothing)
-        const int ppitch = dw_patch_pitch(f.npx);
-        const uint32_t zpad = dw_patch_pad(d);
-        auto in_image = [&](int j) {
-            const int r = (int)(((uint32_t)j * f.rw_magic) >> 20);
-            const int c = j - r * f.rw;
-            return (unsigned)(ry0 + r) < (unsigned)q.H && (unsigned)(rx0 + c) < (unsigned)q.W;
+        auto put = [&](int tile, int j, uint32_t pk) {
+            if constexpr (FIXED && EMT) {
+                if (j < f.npx) patch[fslot[tile]] = (pk & fkeep[tile]) | (zpad & ~fkeep[tile]);
+            } else {
+                if (j < f.npx) patch[dw_patch_slot(j, 2 * fgrp + fhalf, ppitch)] = in_image(j) ? pk : zpad;
+            }
         };
         const int tstep = nwaves >> 2;
         for (int tile = FIXED ? 0 : wave >> 2; tile < mt; tile += 2 * tstep) {  // (four waves: wave >> 2 = 0)
@@ -246,27 +300,25 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
                     v0 += part[((tile * ks + k) * 4 + fgrp) * 64 + lane];
                     v1 += part[((tile1 * ks + k) * 4 + fgrp) * 64 + lane];
                 }
-                const uint32_t pk0 = requant4_i8_sel<EPQ>(v0[0] + p_ai.x, v0[1] + p_ai.y, v0[2] + p_ai.z, v0[3] + p_ai.w, p_mu, p_bi, q);
-                const uint32_t pk1 = requant4_i8_sel<EPQ>(v1[0] + p_ai.x, v1[1] + p_ai.y, v1[2] + p_ai.z, v1[3] + p_ai.w, p_mu, p_bi, q);
+                const uint32_t pk0 = requant4_i8_sel<EPQ>(v0[0] + p_ai.x, v0[1] + p_ai.y, v0[2] + p_ai.z, v0[3] + p_ai.w, p_mu, p_bi, ql);
+                const uint32_t pk1 = requant4_i8_sel<EPQ>(v1[0] + p_ai.x, v1[1] + p_ai.y, v1[2] + p_ai.z, v1[3] + p_ai.w, p_mu, p_bi, ql);
                 const int j1 = tile1 * 32 + frow;
-                if (j0 < f.npx) patch[dw_patch_slot(j0, 2 * fgrp + fhalf, ppitch)] = in_image(j0) ? pk0 : zpad;
-                if (j1 < f.npx) patch[dw_patch_slot(j1, 2 * fgrp + fhalf, ppitch)] = in_image(j1) ? pk1 : zpad;
+                put(tile, j0, pk0);
+                put(tile1, j1, pk1);
             } else {  // the odd last tile alone (it used to be computed twice: ~50 instructions of a wave that issues one per ~5.8 cycles)
 #pragma unroll
                 for (int k = 1; k < ks; ++k) v0 += part[((tile * ks + k) * 4 + fgrp) * 64 + lane];
-                const uint32_t pk0 = requant4_i8_sel<EPQ>(v0[0] + p_ai.x, v0[1] + p_ai.y, v0[2] + p_ai.z, v0[3] + p_ai.w, p_mu, p_bi, q);
-                if (j0 < f.npx) patch[dw_patch_slot(j0, 2 * fgrp + fhalf, ppitch)] = in_image(j0) ? pk0 : zpad;
+                const uint32_t pk0 = requant4_i8_sel<EPQ>(v0[0] + p_ai.x, v0[1] + p_ai.y, v0[2] + p_ai.z, v0[3] + p_ai.w, p_mu, p_bi, ql);
+                put(tile, j0, pk0);
             }
         }
     }
     __syncthreads();
 
-    if (q.debug & 1024) return;  // ablation: stop after the pointwise epilogue
+    if constexpr (!FIXED)
+        if (q.debug & 1024) return;  // ablation: stop after the pointwise epilogue
     // ---- depthwise 3x3 on the slice's 32 channels, from the LDS patch (dw_patch.h)
-    DwPatchGeom g;
-    g.bh = f.bh, g.bw = f.bw, g.rw = f.rw, g.bw_magic = f.bw_magic, g.pitch = dw_patch_pitch(f.npx);
-    g.oy0 = oy0, g.ox0 = ox0, g.ry0 = ry0, g.rx0 = rx0, g.n = n, g.ch0 = slice * 32;
-    depthwise_from_patch<EPD>(d, patch, g, dwk, tid, nwaves * 64);
+    depthwise_from_patch<EPD>(dl, patch, g, dwk, dwp, tid, nwaves * 64);
 }
 
 // ---- host side ---------------------------------------------------------------------------------

@@ -68,6 +68,11 @@ __global__ __launch_bounds__(256) void stemdw_fused_kernel(StemDwArgs f)
     const int ntasks = 2 * f.npx;
     const int ppitch = dw_patch_pitch(f.npx);
     const uint32_t zpad = dw_patch_pad(d);
+    // the depthwise phase's index arithmetic, in front of phase 1 (dw_patch.h: left to the compiler it stands behind the last barrier)
+    DwPatchGeom g;
+    g.bh = f.bh, g.bw = f.bw, g.rw = f.rw, g.bw_magic = f.bw_magic, g.pitch = ppitch;
+    g.oy0 = oy0, g.ox0 = ox0, g.ry0 = ry0, g.rx0 = rx0, g.n = n, g.ch0 = 0;
+    const DwPrep dwp = dw_patch_prepare(d, g, tid);
     for (int base = 0; base < ntasks; base += 256) {  // uniform trip count: the barrier below is safe
         const bool valid = base + tid < ntasks;
         const int task = valid ? base + tid : ntasks - 1;
@@ -122,10 +127,7 @@ __global__ __launch_bounds__(256) void stemdw_fused_kernel(StemDwArgs f)
     __syncthreads();
 
     // ---- phase 2: depthwise 3x3 from the patch (dw_patch.h)
-    DwPatchGeom g;
-    g.bh = f.bh, g.bw = f.bw, g.rw = f.rw, g.bw_magic = f.bw_magic, g.pitch = ppitch;
-    g.oy0 = oy0, g.ox0 = ox0, g.ry0 = ry0, g.rx0 = rx0, g.n = n, g.ch0 = 0;
-    depthwise_from_patch<EPD>(d, patch, g, dwk, tid, 256);
+    depthwise_from_patch<EPD>(d, patch, g, dwk, dwp, tid, 256);
 }
 
 static bool stemdw_geometry(const ConvArgs &q, const ConvArgs &d, StemDwArgs &f)

@@ -4,6 +4,8 @@
 
     python tools/pair_bench.py [--batch 1] [--reps 20] [--sweep]
 Every fused result is compared byte for byte with the two-launch result.
+The int8 kernel's ablation exits (SHL_MI355X_DEBUG=256 | 512 | 1024, tools/dev/pair_phases.sh) exist in its run-time form only:
+set SHL_MI355X_PWDW_GENERIC=1 with them.
 """
 import argparse
 import ctypes as C
