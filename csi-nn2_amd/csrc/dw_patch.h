@@ -40,7 +40,9 @@ __device__ __forceinline__ T kernarg_here(size_t off)
 }
 
 struct DwPatchGeom {
-    int bh, bw;         // output rectangle of the workgroup
+    int bh, bw;         // output rectangle the threads decompose their output index by (the launch's largest)
+    int lbh, lbw;       // the part of THIS workgroup's rectangle that lies in the output map (<= bh, bw): rectangles of a launch
+                        // may differ (pwdw_fused.hip: wider border rectangles) and the last ones may stick out of the map
     int rw;             // patch width in pixels
     int pitch;          // plane pitch in dwords (dw_patch_pitch)
     uint32_t bw_magic;  // po / bw == (po * bw_magic) >> 20 for po < 4096
@@ -76,7 +78,7 @@ __device__ __forceinline__ DwThreadConsts dw_load_consts(const ConvArgs &d, int 
 struct DwOutPos {
     uint32_t lds;  // dword index of tap (0, 0) in the patch: plane + (oyl sh) rw + oxl sw
     uint32_t out;  // byte offset of the thread's four channels inside the output image
-    bool live;     // the output pixel exists (the rectangle may stick out of the image)
+    bool live;     // the output pixel exists (inside the workgroup's own rectangle and the map: DwPatchGeom::lbh, lbw)
 };
 
 // What the depthwise phase needs beside the patch and the constants, none of it dependent on loaded data: dw_patch_prepare.
@@ -96,7 +98,7 @@ __device__ __forceinline__ DwOutPos dw_patch_locate(const ConvArgs &d, const DwP
     p.lds = (uint32_t)(cg * g.pitch + (oyl * d.sh) * g.rw + oxl * d.sw);
     // (inside an image 32 bits address every byte: the callers admit images below 2 GiB)
     p.out = (uint32_t)((oy * d.Wo + ox) * d.C + g.ch0 + cg * 4);
-    p.live = oy < d.Ho && ox < d.Wo;
+    p.live = oyl < g.lbh && oxl < g.lbw;
     return p;
 }
 

@@ -11,14 +11,19 @@
 // share it.
 //
 //   workgroup = (32-channel slice) x (bh x bw rectangle of depthwise OUTPUT pixels), 4 waves
-//   1. pointwise: the rectangle's input patch, ((bh-1) s + 3) x ((bw-1) s + 3) pixels of the
-//      pointwise layer, is cut into 32-pixel MFMA tiles.  A wave owns (tile, K part) pairs: K is
+//   1. pointwise: the rectangle's input patch is ((bh-1) s + 3) x ((bw-1) s + 3) pixels of the pointwise layer.  Only the part
+//      of it INSIDE the image -- the workgroup's window -- is computed: patch pixels outside the image are the depthwise layer's
+//      padding, written to LDS once, up front.  The window is cut into 32-pixel MFMA tiles (row j of the workgroup = window
+//      pixel (j / iwm, j % iwm), iwm = the widest window of the launch; a narrower window leaves rows unused).  Rectangles of a launch need not be equal: along an axis the first and the last may be one
+//      pixel wider (choose_rect), because one row / column of their patch is padding -- 14 = 4 + 3 + 3 + 4 gives every one of
+//      the 4 x 4 rectangles a 5 x 5 window, ONE tile, where the uniform 4 x 4 rectangles' 6 x 6 patches took two.
+//      A wave owns (tile, K part) pairs: K is
 //      split KS ways (deep K: one memory round trip instead of KS), tiles are dealt to the 4/KS wave
 //      groups.  Every fragment is requested up front -- weights [32 ch][K] rows and pixel rows are
 //      both contiguous 16-byte pieces per lane -- then v_mfma_i32_32x32x32_i8.
 //   2. partial sums meet in LDS; wave w finishes register group w (channels 8w + 4 half .. +3) of
 //      every tile: + acc_init, pointwise requantisation (+ relu), one dword into the LDS patch
-//      as eight dword planes [channel quad][pixel] (dw_patch.h; pixels outside the image get the depthwise layer's padding value).
+//      as eight dword planes [channel quad][pixel] (dw_patch.h; pixels outside the image hold the depthwise layer's padding value).
 //   3. depthwise: thread = (output pixel, 4 channels): nine dwords from the LDS patch (the padding
 //      value for taps outside the image), byte transposes + v_dot4_i32_i8 against the depthwise
 //      plan's packed weights, depthwise requantisation (+ relu), one dword to HBM.
@@ -29,25 +34,37 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <algorithm>
+#include <vector>
+
 #include "dw_patch.h"
 #include "igemm_common.h"
 
 namespace shl {
 
+// what the kernel reads in the shadow of its fragment loads (beside the two layers): one aligned block, two scalar loads
+struct alignas(32) PwDwLateArgs {
+    uint32_t bw_magic;         // ceil(2^20 / dbw): j / dbw == (j * bw_magic) >> 20 for j < 4096
+    int32_t rw;                // patch width  (dbw - 1) * sw + 3: the LARGEST rectangle's -- one LDS layout per launch
+    int32_t npx;               // patch pixels rh * rw (the largest rectangle's)
+    int32_t dbh, dbw;          // the largest rectangle = bh + max(ey_lo, ey_hi), bw + max(ex_lo, ex_hi): the depthwise phase's index decomposition
+    // (sums the kernel would otherwise form itself: a wave issues one instruction per ~5.8 cycles)
+    int32_t bhe, bwe;          // bh + ey_lo, bw + ex_lo: rectangle t ends where t bh + bhe, t bw + bwe begins
+    int32_t ylast, xlast;      // tiles_y - 1, tiles_x - 1
+    int32_t cy, cx;            // 3 - sh - pt, 3 - sw - pl: output row oye - 1 reads input rows up to, not including, oye sh + cy
+    int32_t reserved;
+};
+
 struct PwDwArgs {
     ConvArgs pw;  // in = the pair's input tensor; out unused
     ConvArgs dw;  // in unused; out = the pair's output tensor
-    int32_t bh, bw;            // depthwise output rectangle of a workgroup
+    int32_t bh, bw;            // depthwise output rectangle of a workgroup (the first / last of an axis: + ey_lo / ey_hi, ex_lo / ex_hi)
     int32_t tiles_x, tiles_y;  // rectangles per image
-    int32_t rw;                // patch width  (bw - 1) * sw + 3
-    int32_t npx;               // patch pixels rh * rw
-    int32_t mt;                // 32-pixel MFMA tiles per patch
+    int32_t mt;                // 32-pixel MFMA tiles per window = ceil(nwin / 32)
     int32_t nwaves;            // waves per workgroup: 4 or 8
     int32_t ks;                // K split: 1, 2, 4 or 8
     int32_t nsw;               // K sub-steps (32 B) per wave
     int32_t nsub;              // K sub-steps in all = C / 32
-    uint32_t rw_magic;         // ceil(2^20 / rw): j / rw == (j * rw_magic) >> 20 for j < 4096
-    uint32_t bw_magic;         // same for bw
     // workgroup id -> (slice, rectangle), XCD aware (hardware hands workgroup L of a 1-D grid to XCD L % 8): the eight
     // XCDs form xg slice groups x 8 / xg rectangle groups, so that an XCD's L2 fetches the activations of 1 / (8 / xg)
     // of the rectangles and the weights of 1 / xg of the slices.  xg = 0: plain 3-D grid (slice, tx, ty).
@@ -62,18 +79,29 @@ struct PwDwArgs {
     int32_t ks_log2;           // log2(ks)
     int32_t mwn;               // wave groups over the tiles = nwaves / ks
     int64_t img_stride;        // bytes of an image of the pointwise input = H W C
+    // rectangles of unequal size: rectangle t of an axis starts at t b + (t > 0 ? e_lo : 0) and is b + (t == 0 ? e_lo : 0) +
+    // (t == last ? e_hi : 0) long; all zero: the uniform grid (the last rectangles may stick out of the map)
+    int32_t ex_lo, ex_hi, ey_lo, ey_hi;  // 0 or 1
+    int32_t iwm;               // the widest window (in-image patch columns) of the launch's rectangles: MFMA row j = window pixel (j / iwm, j % iwm)
+    uint32_t iwm_magic;        // ceil(2^20 / iwm): j / iwm == (j * iwm_magic) >> 20 for j < 4096
+    int32_t nwin;              // MFMA rows that can hold a pixel = highest window x iwm: mt = ceil(nwin / 32)
+    PwDwLateArgs late;   // (behind the fragment loads)
 };
+
+// dwords per thread and tile round with which a compile-time form (256 threads) fills its patch with the padding value: room for
+// 8 planes x 96 dwords per tile, i.e. a patch of up to twice the window's 32 pixels
+constexpr int PWDW_PAD_DWORDS = 3;
 
 // MTW: MFMA tiles per wave (upper bound), NSW: K sub-steps per wave (upper bound), MAXT: threads (the
 // 8-sub-step form needs more than the 256 registers a lane gets with two waves per SIMD).  EXACT: every wave has exactly NSW
 // sub-steps (K / 32 = ks NSW: every MobileNet pair but the first) -- no per-fragment guards, and the first MFMA of a tile takes
 // the constant 0 as its C operand instead of 16 zeroed registers per tile.
 // KSV, TPW (both or neither; four waves): the K split and the tiles per wave as compile-time values -- every wave runs exactly TPW
-// tiles, i.e. the patch is treated as TPW 4 / KSV tiles (tiles past the real mt read the patch's last pixel and park their sums
+// tiles, i.e. the window is treated as TPW 4 / KSV tiles (tiles past the real mt read some pixel of the image and park their sums
 // in LDS slots nothing reads: the host sizes the partial-sum area for the padded count): no tile guards around the loads, the
 // MFMAs and the LDS writes (four scalar instructions per MFMA in the generic form), the sums over the K parts unrolled.
 // 0: run-time values (eight waves, deeper patches).
-// EMT: the patch has exactly TPW 4 / KSV tiles (the finishing loop's trip count is a compile-time value as well: 0.1 us per launch).
+// EMT: the window has exactly TPW 4 / KSV tiles (the finishing loop's trip count is a compile-time value as well: 0.1 us per launch).
 // EPQ / EPD: the two layers' epilogue flavours (common.h; -1: chosen at run time) -- with all four flavours of three requantisation
 // sites inline the kernel is 1 500 instructions, a third of which one launch runs, fetched cold by every workgroup.
 template <int MTW, int NSW, int MAXT, bool EXACT, int KSV = 0, int TPW = 0, bool EMT = false, int EPQ = -1, int EPD = -1>
@@ -81,6 +109,7 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
 {
     static_assert((KSV == 0) == (TPW == 0) && (TPW == 0 || (TPW == MTW && EXACT)), "pwdw_fused: KSV and TPW come together, with MTW = TPW");
     constexpr bool FIXED = TPW != 0;
+    constexpr int NFT_ALL = FIXED ? TPW * (4 / (KSV ? KSV : 1)) : 1;  // tiles the compile-time forms run
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const ConvArgs &q = f.pw;
     const ConvArgs &d = f.dw;
@@ -92,9 +121,10 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
     // the compiler otherwise fetches an argument inside the branch that first reads it -- four dependent s_load / s_waitcnt round
     // trips of ~200 cycles in front of the first fragment load
     asm volatile("" ::"s"(f.xg), "s"(f.xg_log2), "s"(f.spg), "s"(f.spg_magic), "s"(f.tx_magic), "s"(f.nrect), "s"(f.tiles_x), "s"(f.tiles_y));
-    asm volatile("" ::"s"(f.bh), "s"(f.bw), "s"(f.rw), "s"(f.npx), "s"(f.mt), "s"(f.ks), "s"(f.nsw), "s"(f.nsub), "s"(f.rw_magic),
+    asm volatile("" ::"s"(f.bh), "s"(f.bw), "s"(f.mt), "s"(f.ks), "s"(f.nsw), "s"(f.nsub),
                  "s"(f.ks_log2), "s"(f.mwn), "s"(f.img_stride));
     asm volatile("" ::"s"(q.in), "s"(q.w_frag), "s"(q.H), "s"(q.W), "s"(q.C), "s"(d.sh), "s"(d.sw), "s"(d.pt), "s"(d.pl), "s"(d.N));
+    asm volatile("" ::"s"(f.ex_lo), "s"(f.ey_lo), "s"(f.iwm), "s"(f.iwm_magic));
     // (only what stands in front of the fragment loads: with the epilogue's and the depthwise phase's arguments in THIS batch the pass
     // got 0.5 us slower in round 6 -- that trial had put them IN FRONT of the fragment loads.  Nor do those arguments "hide under the fragments'
     // latency where the compiler puts them", as this comment used to say: the compiler fetches each in the block of its first use,
@@ -121,8 +151,6 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
         n = ty / f.tiles_y;
         ty -= n * f.tiles_y;
     }
-    const int oy0 = ty * f.bh, ox0 = tx * f.bw;
-    const int ry0 = oy0 * d.sh - d.pt, rx0 = ox0 * d.sw - d.pl;  // patch origin in the image (may be -pad)
 
     const int nwaves = FIXED ? 4 : f.nwaves;  // 4 or 8
     const int fgrp = wave & 3;
@@ -151,18 +179,26 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
     for (int s = 0; s < NSW; ++s)
         if (s < nsw) fa[s] = *reinterpret_cast<const v4i *>(wp + s * wstep);
     if constexpr (FIXED) __builtin_amdgcn_sched_barrier(0);  // (the weight fragments are requested before anything of the pixel addresses is computed)
+    // The workgroup's rectangle starts at output pixel (oy0, ox0); its patch at (ry0, rx0) of the image (may be -pad); its window
+    // = patch intersected with the image, from (wy0, wx0) to, not including, (wye, wxe).  MFMA row j is window pixel (r, c) =
+    // (j / iwm, j % iwm) with the launch's widest window iwm: one magic from the host.  In front of the pixel loads stands only
+    // what their addresses need -- the origins; where the window ends waits for the shadow.
+    const int oy0 = ty * f.bh + min(ty, f.ey_lo), ox0 = tx * f.bw + min(tx, f.ex_lo);  // (e_lo is 0 or 1: + e_lo behind the first rectangle)
+    const int ry0 = oy0 * d.sh - d.pt, rx0 = ox0 * d.sw - d.pl;
+    const int wy0 = max(ry0, 0), wx0 = max(rx0, 0);
+    auto win_rc = [&](int j, int &r, int &c) {
+        r = (int)(((uint32_t)j * f.iwm_magic) >> 20);
+        c = j - r * f.iwm;
+    };
     v4i fb[MTW][NSW];
+    int lr[MTW], lc[MTW];  // (this wave's rows: with four K parts they are the workgroup's, and the shadow takes them from here)
 #pragma unroll
     for (int i = 0; i < MTW; ++i) {
         const int tile = mw + i * mwn;
         if (FIXED || tile < mt) {
-            int j = tile * 32 + frow;
-            j = j < f.npx ? j : f.npx - 1;
-            const int r = (int)(((uint32_t)j * f.rw_magic) >> 20);
-            const int c = j - r * f.rw;
-            int y = ry0 + r, x = rx0 + c;  // pixels outside the image: any valid address (never used)
-            y = max(0, min(y, q.H - 1));
-            x = max(0, min(x, q.W - 1));
+            win_rc(tile * 32 + frow, lr[i], lc[i]);
+            // rows that hold no pixel of this window (past its width or its height): any valid address, the sums are never used
+            const int y = min(wy0 + lr[i], q.H - 1), x = min(wx0 + lc[i], q.W - 1);
             const char *px = img + (y * q.W + x) * q.C + fhalf * 16 + sub0 * 32;
 #pragma unroll
             for (int s = 0; s < NSW; ++s)
@@ -177,12 +213,14 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
     // every kernel argument of the finishing roles and the depthwise phase in ONE batch of scalar loads, HERE: read through
     // kernarg_here (dw_patch.h) they cannot rise in front of the fragment loads, "used" by an empty asm they cannot sink behind the
     // barriers.  From here on the two layers are ql and dl.
-    const uint32_t bw_magic = kernarg_here<uint32_t>(offsetof(PwDwArgs, bw_magic));
+    const PwDwLateArgs fl = kernarg_here<PwDwLateArgs>(offsetof(PwDwArgs, late));
+    const uint32_t bw_magic = fl.bw_magic;
     const ConvArgs ql = kernarg_here<ConvArgs>(offsetof(PwDwArgs, pw)), dl = kernarg_here<ConvArgs>(offsetof(PwDwArgs, dw));
     asm volatile("" ::"s"(ql.acc_init), "s"(ql.mult), "s"(ql.bias), "s"(ql.out_zp), "s"(ql.out_zp_f), "s"(ql.clamp_lo), "s"(ql.clamp_hi),
                  "s"(ql.out_scale), "s"(ql.inv_out_scale), "s"(dl.w), "s"(dl.acc_init), "s"(dl.mult), "s"(dl.bias), "s"(dl.out));
     asm volatile("" ::"s"(dl.out_zp), "s"(dl.out_zp_f), "s"(dl.clamp_lo), "s"(dl.clamp_hi), "s"(dl.out_scale), "s"(dl.inv_out_scale),
                  "s"(dl.in_zp), "s"(dl.Ho), "s"(dl.Wo), "s"(dl.C), "s"(dl.sh), "s"(dl.sw), "s"(bw_magic));
+    asm volatile("" ::"s"(fl.bhe), "s"(fl.bwe), "s"(fl.cy), "s"(fl.cx), "s"(fl.ylast), "s"(fl.xlast), "s"(fl.dbh), "s"(fl.dbw), "s"(fl.rw), "s"(fl.npx));
     // constants of the finishing roles, requested BEHIND the fragments (round 6; they were first: "they arrive under the K
     // loop" -- but a wave issues an instruction per ~5.8 cycles, and the nine loads with their address arithmetic stood ~60
     // instructions = 0.17 us in front of the loads the MFMAs wait for)
@@ -194,14 +232,18 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
     const float4 p_bi = *reinterpret_cast<const float4 *>(ql.bias + pc);
 
     const DwThreadConsts dwk = dw_load_consts(dl, slice * 32, tid);  // depthwise constants
+    // the rest of the workgroup's geometry.  One past the rectangle's last output row / column: where the next rectangle begins, the
+    // map's edge for the last one (which may be e_hi longer, or stick out of the map in a uniform grid); the rectangle's own
+    // size for the depthwise phase's `live`.
+    const int oye = ty == fl.ylast ? dl.Ho : ty * f.bh + fl.bhe, oxe = tx == fl.xlast ? dl.Wo : tx * f.bw + fl.bwe;
     // the depthwise phase's index arithmetic (dw_patch.h)
     DwPatchGeom g;
-    g.bh = f.bh, g.bw = f.bw, g.rw = f.rw, g.bw_magic = bw_magic, g.pitch = dw_patch_pitch(f.npx);
+    g.bh = fl.dbh, g.bw = fl.dbw, g.lbh = oye - oy0, g.lbw = oxe - ox0, g.rw = fl.rw, g.bw_magic = bw_magic, g.pitch = dw_patch_pitch(fl.npx);
     g.oy0 = oy0, g.ox0 = ox0, g.ry0 = ry0, g.rx0 = rx0, g.n = n, g.ch0 = slice * 32;
     const DwPrep dwp = dw_patch_prepare(dl, g, tid);
     // the finishing roles': the patch's pitch and padding value, both layers' clamp bounds and packed zero points (the very
     // expressions of requant4_i8_t, common.h: computed once, here) and, where the tile rounds are compile-time, every round's
-    // patch slot and in-image mask
+    // patch slot
     const int ppitch = g.pitch;
     const uint32_t zpad = dw_patch_pad(dl);
     {
@@ -209,23 +251,41 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
         const uint32_t qzp2 = (uint32_t)(ql.out_zp & 0xffff) * 0x00010001u, dzp2 = (uint32_t)(dl.out_zp & 0xffff) * 0x00010001u;
         asm volatile("" ::"s"(ppitch), "s"(zpad), "v"(qcl), "v"(qch), "v"(dcl), "v"(dch), "s"(qzp2), "s"(dzp2));
     }
-    auto in_image = [&](int j) {
-        const int r = (int)(((uint32_t)j * f.rw_magic) >> 20);
-        const int c = j - r * f.rw;
-        return (unsigned)(ry0 + r) < (unsigned)q.H && (unsigned)(rx0 + c) < (unsigned)q.W;
-    };
+    __builtin_amdgcn_sched_barrier(0);
+
+    // ---- behind the shadow, in the MFMAs' block: a wave's MFMAs are a dependent chain of 16-pass instructions, and the scalar
+    // and vector instructions below issue between them.  Where the window ends:
+    const int wye = min(oye * dl.sh + fl.cy, q.H), wxe = min(oxe * dl.sw + fl.cx, q.W);
+    // window pixel (r, c) -> whether this workgroup's window has it, and its slot in the patch (the patch keeps the largest
+    // rectangle's layout: rw pixels per row).  Rows without a pixel go to the plane's last dword, which no reader looks at
+    // (dw_patch_pitch: 8 spare dwords per plane).
+    const int wslot0 = (wy0 - ry0) * fl.rw + (wx0 - rx0) + (2 * fgrp + fhalf) * ppitch;
+    auto win_has = [&](int r, int c) { return wy0 + r < wye && wx0 + c < wxe; };
+    auto win_slot = [&](int r, int c) { return (uint32_t)(wslot0 + r * fl.rw + c); };
     constexpr int NFT = (FIXED && EMT) ? TPW * (4 / (KSV ? KSV : 1)) : 1;  // compile-time tile rounds
-    uint32_t fslot[NFT], fkeep[NFT];  // per tile: the dword slot of this lane's pixel, all ones / zero: inside / outside the image
+    uint32_t fslot[NFT];  // per tile: the dword slot of this lane's pixel
     if constexpr (FIXED && EMT) {
+        const uint32_t spare = (uint32_t)((2 * fgrp + fhalf) * ppitch + ppitch - 1);
 #pragma unroll
         for (int t = 0; t < NFT; ++t) {
-            const int j = t * 32 + frow;
-            fslot[t] = (uint32_t)dw_patch_slot(j, 2 * fgrp + fhalf, ppitch);
-            fkeep[t] = in_image(j) ? 0xffffffffu : 0u;
-            asm volatile("" ::"v"(fslot[t]), "v"(fkeep[t]));
+            int r, c;
+            if constexpr (KSV == 4) r = lr[t], c = lc[t];  // (one wave group: tile t is this wave's t-th)
+            else win_rc(t * 32 + frow, r, c);
+            fslot[t] = win_has(r, c) ? win_slot(r, c) : spare;
+            asm volatile("" ::"v"(fslot[t]));
         }
     }
-    __builtin_amdgcn_sched_barrier(0);
+    // the whole patch takes the depthwise layer's padding value (dw_patch.h: the reader tests nothing), HERE: the patch does not
+    // alias the partial sums, and barrier 1 stands between these stores and the window's pixels (put(), below).  The compile-time
+    // forms store without a branch -- a block boundary in the shadow lets the compiler sink the loads above: every thread
+    // PWDW_PAD_DWORDS dwords per tile round, into an area the host sizes for that (it keeps larger patches for the run-time form).
+    uint32_t *patch = reinterpret_cast<uint32_t *>(smem + (size_t)mtp * ks * 4096);  // eight dword planes (dw_patch.h)
+    if constexpr (FIXED) {
+#pragma unroll
+        for (int k = 0; k < PWDW_PAD_DWORDS * NFT_ALL; ++k) patch[tid + 256 * k] = zpad;
+    } else {
+        for (int i = tid; i < 8 * ppitch; i += nwaves * 64) patch[i] = zpad;
+    }
 
     v16i acc[MTW];
     if constexpr (EXACT) {
@@ -257,7 +317,6 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
         if (q.debug & 256) return;  // ablation: stop after loads + MFMA
     // ---- partial sums -> LDS: part[((tile * ks + kpart) * 4 + group) * 64 + lane] = 4 channels
     v4i *part = reinterpret_cast<v4i *>(smem);
-    uint32_t *patch = reinterpret_cast<uint32_t *>(smem + (size_t)mtp * ks * 4096);  // eight dword planes (dw_patch.h)
 #pragma unroll
     for (int i = 0; i < MTW; ++i) {
         const int tile = mw + i * mwn;
@@ -280,12 +339,14 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
     // overlaps (the patch writes also keep the compiler from moving the next tile's reads up): 71.0 - 71.2 -> 70.5 - 70.9 us
     // per MobileNetV1 pass.  (Four tiles per round through small arrays: 74.7 us -- the code grew more than the chain shrank.)
     {
-        // patch pixels outside the image take the depthwise layer's input zero point (dw_patch.h: the reader tests nothing)
+        // the window's pixels only: the rest of the patch holds the padding value since the shadow
         auto put = [&](int tile, int j, uint32_t pk) {
             if constexpr (FIXED && EMT) {
-                if (j < f.npx) patch[fslot[tile]] = (pk & fkeep[tile]) | (zpad & ~fkeep[tile]);
+                patch[fslot[tile]] = pk;
             } else {
-                if (j < f.npx) patch[dw_patch_slot(j, 2 * fgrp + fhalf, ppitch)] = in_image(j) ? pk : zpad;
+                int r, c;
+                win_rc(j, r, c);
+                if (win_has(r, c)) patch[win_slot(r, c)] = pk;
             }
         };
         const int tstep = nwaves >> 2;
@@ -343,7 +404,41 @@ static bool shapes_pair(const ConvArgs &q, const ConvArgs &d)
     return true;
 }
 
-// choose the workgroup rectangle; returns false when nothing fits
+// One axis of a rectangle grid: n rectangles of b output pixels, the first e_lo and the last e_hi wider (0 or 1).  e_lo = e_hi = 0
+// is the uniform grid, whose last rectangle may stick out of the map.
+struct PwDwAxis {
+    int b, n, e_lo, e_hi;
+    int win;  // the largest window along the axis: in-image pixels of a rectangle's patch (what pwdw_fused_kernel computes per workgroup)
+};
+static int axis_window(int in_len, int out_len, int s, int pad, const PwDwAxis &a)
+{
+    int best = 0;
+    for (int t = 0; t < a.n; ++t) {
+        const int o0 = t * a.b + (t > 0 ? a.e_lo : 0);
+        const int len = std::min(a.b + (t == 0 ? a.e_lo : 0) + (t == a.n - 1 ? a.e_hi : 0), out_len - o0);
+        const int r0 = o0 * s - pad;
+        best = std::max(best, std::min(r0 + (len - 1) * s + 3, in_len) - std::max(r0, 0));
+    }
+    return best;
+}
+// the grids of an axis: the uniform ones (rectangle lengths `lens`) and, unless a grid is forced, those whose border rectangles are one
+// longer -- a border rectangle's patch has a row / column of padding, which costs no pointwise work
+static std::vector<PwDwAxis> axis_grids(int in_len, int out_len, int s, int pad, const std::vector<int> &lens, int max_n, bool uniform_only)
+{
+    std::vector<PwDwAxis> v;
+    for (int b : lens) v.push_back({b, (out_len + b - 1) / b, 0, 0, 0});
+    if (!uniform_only)
+        for (int n = 2; n <= max_n && n <= out_len; ++n)
+            for (int e = 1; e <= 3; ++e) {  // (e_lo, e_hi) = (1, 0), (0, 1), (1, 1)
+                const int e_lo = e & 1, e_hi = e >> 1, rest = out_len - e_lo - e_hi;
+                if (rest < n || rest % n) continue;
+                v.push_back({rest / n, n, e_lo, e_hi, 0});
+            }
+    for (PwDwAxis &a : v) a.win = axis_window(in_len, out_len, s, pad, a);
+    return v;
+}
+
+// choose the workgroups' rectangles; returns false when nothing fits
 static bool choose_rect(const ConvArgs &q, const ConvArgs &d, PwDwArgs &f)
 {
     const int nsub = q.C >> 5;
@@ -354,43 +449,64 @@ static bool choose_rect(const ConvArgs &q, const ConvArgs &d, PwDwArgs &f)
     if (nwaves == 8 && nsw > 4) return false;  // the 8-sub-step kernel is built for 4 waves
     const int64_t slices = q.Co >> 5;
     int force_h = 0, force_w = 0;
-    const char *env = getenv("SHL_MI355X_PWDW_TILE");  // "<bh>x<bw>": tuning override (tools/pair_bench.py)
+    const char *env = getenv("SHL_MI355X_PWDW_TILE");  // "<bh>x<bw>": tuning override, a uniform grid (tools/pair_bench.py)
     if (env) sscanf(env, "%dx%d", &force_h, &force_w);
+    std::vector<int> lens_y, lens_x;
+    for (int bh = 1; bh <= d.Ho && bh <= 32; ++bh)
+        if (!force_h || bh == force_h) lens_y.push_back(bh);
+    for (int div = 1; div <= 16; ++div) {
+        const int bw = (d.Wo + div - 1) / div;
+        if (div > 1 && bw == (d.Wo + div - 2) / (div - 1)) continue;  // same width as the previous div
+        if (!force_h || bw == force_w) lens_x.push_back(bw);
+    }
+    const std::vector<PwDwAxis> gy = axis_grids(q.H, d.Ho, d.sh, d.pt, lens_y, 32, force_h != 0);
+    const std::vector<PwDwAxis> gx = axis_grids(q.W, d.Wo, d.sw, d.pl, lens_x, 16, force_h != 0);
     double best = 1e30;
-    int best_h = 0, best_w = 0;
-    for (int bh = 1; bh <= d.Ho && bh <= 32; ++bh) {
-        for (int div = 1; div <= 16; ++div) {
-            const int bw = (d.Wo + div - 1) / div;
-            if (div > 1 && bw == (d.Wo + div - 2) / (div - 1)) continue;  // same width as the previous div
-            if (force_h && (bh != force_h || bw != force_w)) continue;
-            const int rh = (bh - 1) * d.sh + 3, rw = (bw - 1) * d.sw + 3;
-            const int npx = rh * rw;
-            const int mt = (npx + 31) / 32;
-            if (mt > mt_max || rw > 256 || bw > 256 || npx >= 4096 || bh * bw >= 4096) continue;
+    const PwDwAxis *best_y = nullptr, *best_x = nullptr;
+    for (const PwDwAxis &y : gy) {
+        for (const PwDwAxis &x : gx) {
+            const int dbh = y.b + std::max(y.e_lo, y.e_hi), dbw = x.b + std::max(x.e_lo, x.e_hi);
+            const int rh = (dbh - 1) * d.sh + 3, rw = (dbw - 1) * d.sw + 3;
+            const int npx = rh * rw;  // the LDS patch: the largest rectangle's
+            const int nwin = std::max(y.win, 1) * std::max(x.win, 1);  // MFMA rows: highest window x widest window
+            const int mt = (nwin + 31) / 32;
+            if (dbh > 32 || mt > mt_max || rw > 256 || dbw > 256 || npx >= 4096 || dbh * dbw >= 4096) continue;
             if ((size_t)mt * ks * 4096 + dw_patch_bytes(npx) > 96 * 1024) continue;  // partial sums + patch in LDS
-            const int64_t blocks = slices * ((d.Ho + bh - 1) / bh) * ((d.Wo + bw - 1) / bw) * d.N;
+            const int64_t blocks = slices * y.n * x.n * d.N;
             // Measured on MobileNetV1 at batch 1 (tools/pair_bench.py --sweep, profiles/r01_notes.md): what
             // a rectangle costs is the bytes its CU has to pull through its L1 -- (mt pixel tiles + 1
             // weight tile) x K per workgroup, times the workgroups that land on one CU -- plus a little
             // per depthwise pass; among equals, more workgroups (up to one per CU) finish sooner.
+            // mt counts the tiles of the largest WINDOW: padding pixels are neither loaded nor multiplied
+            // (profiles/pwdw_window_notes.md: the per-tile cost re-measured on the 14 x 14 pairs, the weights
+            // of the other terms were not re-fitted).
             const double rounds = (double)((blocks + 255) / 256);
-            const double score = rounds * ((mt + 1) * nsub + 2.0 * ((bh * bw + 31) / 32) + 4.0) -
-                                 (blocks <= 256 ? blocks / 1024.0 : 0.0);
+            // (last, far below a workgroup's worth of the term before it: among grids of equal tiles, the smaller window -- fewer
+            // pixel rows through L1 that no tile needed to grow for)
+            const double score = rounds * ((mt + 1) * nsub + 2.0 * ((dbh * dbw + 31) / 32) + 4.0) -
+                                 (blocks <= 256 ? blocks / 1024.0 : 0.0) + nwin * 1e-7;
             if (score < best) {
                 best = score;
-                best_h = bh;
-                best_w = bw;
+                best_y = &y;
+                best_x = &x;
             }
         }
     }
-    if (!best_h) return false;
-    f.bh = best_h;
-    f.bw = best_w;
-    f.tiles_y = (d.Ho + f.bh - 1) / f.bh;
-    f.tiles_x = (d.Wo + f.bw - 1) / f.bw;
-    f.rw = (f.bw - 1) * d.sw + 3;
-    f.npx = ((f.bh - 1) * d.sh + 3) * f.rw;
-    f.mt = (f.npx + 31) / 32;
+    if (!best_y) return false;
+    f.bh = best_y->b, f.ey_lo = best_y->e_lo, f.ey_hi = best_y->e_hi, f.tiles_y = best_y->n;
+    f.bw = best_x->b, f.ex_lo = best_x->e_lo, f.ex_hi = best_x->e_hi, f.tiles_x = best_x->n;
+    f.late.dbh = f.bh + std::max(f.ey_lo, f.ey_hi);
+    f.late.dbw = f.bw + std::max(f.ex_lo, f.ex_hi);
+    f.late.bhe = f.bh + f.ey_lo, f.late.bwe = f.bw + f.ex_lo;
+    f.late.ylast = f.tiles_y - 1, f.late.xlast = f.tiles_x - 1;
+    f.late.reserved = 0;
+    f.iwm = std::max(best_x->win, 1);
+    f.iwm_magic = ((1u << 20) + f.iwm - 1) / f.iwm;
+    f.late.cy = 3 - d.sh - d.pt, f.late.cx = 3 - d.sw - d.pl;
+    f.late.rw = (f.late.dbw - 1) * d.sw + 3;
+    f.late.npx = ((f.late.dbh - 1) * d.sh + 3) * f.late.rw;
+    f.nwin = std::max(best_y->win, 1) * std::max(best_x->win, 1);
+    f.mt = (f.nwin + 31) / 32;
     f.nwaves = nwaves;
     f.ks = ks;
     f.nsw = nsw;
@@ -398,8 +514,7 @@ static bool choose_rect(const ConvArgs &q, const ConvArgs &d, PwDwArgs &f)
     f.ks_log2 = ks == 8 ? 3 : (ks == 4 ? 2 : (ks == 2 ? 1 : 0));
     f.mwn = nwaves / ks;
     f.img_stride = (int64_t)q.H * q.W * q.C;
-    f.rw_magic = ((1u << 20) + f.rw - 1) / f.rw;
-    f.bw_magic = ((1u << 20) + f.bw - 1) / f.bw;
+    f.late.bw_magic = ((1u << 20) + f.late.dbw - 1) / f.late.dbw;
     // Which XCDs share what.  HBM-side bytes of the launch ~ xg x activations + (8 / xg) x weights (every slice group
     // fetches the rectangles' pixels, every rectangle group the slices' weights; measured on the plain grid: 2.97x
     // the algorithmic bytes over MobileNetV1's twelve pairs, profiles/r03_h_pmc_traffic.json): take the cheapest
@@ -458,6 +573,17 @@ bool pwdw_fusable(const ConvArgs &q, const ConvArgs &d, int pw_is_igemm, int dw_
     return true;
 }
 
+// what launch_pwdw_fused would run for the pair (tests, tools): the rectangle grid, the tiles per workgroup, the K split, the workgroups
+bool pwdw_fused_geometry(const ConvArgs &q, const ConvArgs &d, int32_t out[SHL_PWDW_GEOMETRY_FIELDS])
+{
+    PwDwArgs f;
+    if (!shapes_pair(q, d) || !choose_rect(q, d, f)) return false;
+    const int32_t v[SHL_PWDW_GEOMETRY_FIELDS] = {f.tiles_y, f.tiles_x, f.bh,  f.bw, f.ey_lo, f.ey_hi,
+                                                 f.ex_lo,   f.ex_hi,   f.mt,  f.ks, f.nwin,  (int32_t)((q.Co >> 5) * f.nrect)};
+    for (int i = 0; i < SHL_PWDW_GEOMETRY_FIELDS; ++i) out[i] = v[i];
+    return true;
+}
+
 int launch_pwdw_fused(const ConvArgs &q, const ConvArgs &d, hipStream_t s)
 {
     PwDwArgs f;
@@ -472,12 +598,13 @@ int launch_pwdw_fused(const ConvArgs &q, const ConvArgs &d, hipStream_t s)
         const int rpg = 8 / f.xg;
         grid = dim3((unsigned)(8 * f.spg * ((f.nrect + rpg - 1) / rpg)), 1, 1);
     }
-    size_t lds = (size_t)f.mt * f.ks * 4096 + dw_patch_bytes(f.npx);
+    size_t lds = (size_t)f.mt * f.ks * 4096 + dw_patch_bytes(f.late.npx);
     {
         static const char *pr = getenv("SHL_MI355X_PWDW_PRINT");  // "1": the geometry of every launch (tools/dev)
         if (pr && pr[0] == '1')
-            fprintf(stderr, "pwdw_fused %d->%d @%dx%d s%d: rect %dx%d, npx %d, mt %d, ks %d, nsw %d, nsub %d, mwn %d, xg %d, grid %u\n", q.C, q.Co, d.H, d.W,
-                    d.sh, f.bh, f.bw, f.npx, f.mt, f.ks, f.nsw, f.nsub, f.mwn, f.xg, grid.x * grid.y * grid.z);
+            fprintf(stderr, "pwdw_fused %d->%d @%dx%d s%d: %dx%d rects of %dx%d (+%d/+%d, +%d/+%d at the borders), npx %d, nwin %d, mt %d, ks %d, nsw %d, nsub %d, mwn %d, xg %d, grid %u\n",
+                    q.C, q.Co, d.H, d.W, d.sh, f.tiles_y, f.tiles_x, f.bh, f.bw, f.ey_lo, f.ey_hi, f.ex_lo, f.ex_hi, f.late.npx, f.nwin, f.mt, f.ks, f.nsw, f.nsub,
+                    f.mwn, f.xg, grid.x * grid.y * grid.z);
     }
 #define SHL_PWDW2(NSWV, MAXT, EX)                                                                                    \
     do {                                                                                                       \
@@ -508,8 +635,9 @@ int launch_pwdw_fused(const ConvArgs &q, const ConvArgs &d, hipStream_t s)
     } while (0)
 #define SHL_PWDW_FIXED(NSWV, KSV, TPWV)                                                                                  \
     if (f.nwaves == 4 && f.nsw == NSWV && f.nsub == KSV * NSWV && f.ks == KSV && f.mt <= TPWV * (4 / KSV) &&            \
-        f.mt > (TPWV - 1) * (4 / KSV)) {                                                                                \
-        lds = (size_t)(TPWV * (4 / KSV)) * f.ks * 4096 + dw_patch_bytes(f.npx); /* partial sums of the padded tiles */    \
+        f.mt > (TPWV - 1) * (4 / KSV) && dw_patch_bytes(f.late.npx) <= (size_t)1024 * PWDW_PAD_DWORDS * (TPWV * (4 / KSV))) {                                                                         \
+        /* partial sums of the padded tiles + the area the padding fill covers */                                       \
+        lds = (size_t)(TPWV * (4 / KSV)) * (f.ks * 4096 + 1024 * PWDW_PAD_DWORDS);                                        \
         if (f.mt == TPWV * (4 / KSV))                                                                                   \
             SHL_PWDW_EPI(TPWV, NSWV, KSV, true);                                                                        \
         else                                                                                                            \

@@ -71,6 +71,7 @@ __global__ __launch_bounds__(256) void stemdw_fused_kernel(StemDwArgs f)
     // the depthwise phase's index arithmetic, in front of phase 1 (dw_patch.h: left to the compiler it stands behind the last barrier)
     DwPatchGeom g;
     g.bh = f.bh, g.bw = f.bw, g.rw = f.rw, g.bw_magic = f.bw_magic, g.pitch = ppitch;
+    g.lbh = min(f.bh, d.Ho - oy0), g.lbw = min(f.bw, d.Wo - ox0);  // uniform rectangles; the last ones may stick out of the map
     g.oy0 = oy0, g.ox0 = ox0, g.ry0 = ry0, g.rx0 = rx0, g.n = n, g.ch0 = 0;
     const DwPrep dwp = dw_patch_prepare(d, g, tid);
     for (int base = 0; base < ntasks; base += 256) {  // uniform trip count: the barrier below is safe

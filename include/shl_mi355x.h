@@ -306,6 +306,12 @@ int shl_mi355x_pwdw_fusable(const shl_mi355x_conv_plan *pw, const shl_mi355x_con
 /* which fused kernel would run the pair: 0 none (= not fusable), else the form's number (conv_plan.hip:pwdw_kernel_for: 1 latency
  * form, 3 stem + depthwise, 4 / 5 binary16 NCHW, 6 dwpw_stream, 7 dwpw_resident) -- for tools and tests that name the kernel */
 int shl_mi355x_pwdw_form(const shl_mi355x_conv_plan *pw, const shl_mi355x_conv_plan *dw, int32_t batch);
+/* the geometry the latency form (1) would run the pair with, read-only, for tools and tests: out[0..11] = rectangles per image
+ * along y and x, a rectangle's output rows and columns, the extra rows of the first / last rectangle along y and the extra columns
+ * of the first / last along x (0 or 1: a border rectangle's patch has a row / column of padding, which costs no pointwise work),
+ * 32-pixel MFMA tiles per workgroup, K split, pixels of the largest in-image window, workgroups of the launch.  `count` >= 12.
+ * SHL_MI355X_ENOTSUP when the pair runs another form or none. */
+int shl_mi355x_pwdw_geometry(const shl_mi355x_conv_plan *pw, const shl_mi355x_conv_plan *dw, int32_t batch, int32_t *out, int32_t count);
 int shl_mi355x_pwdw_forward(const shl_mi355x_conv_plan *pw, const shl_mi355x_conv_plan *dw,
                             const void *input_dev, void *output_dev, int32_t batch, void *stream);
 

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Pointwise + depthwise pairs of MobileNetV1: two stand-alone launches vs the fused launch
-(csrc/pwdw_fused.hip), graph-timed, with an optional sweep over the workgroup rectangle.
+(csrc/pwdw_fused.hip), graph-timed, with an optional sweep over the workgroup rectangle (SHL_MI355X_PWDW_TILE forces a UNIFORM
+grid; the grid the library chooses itself -- border rectangles may be one pixel wider -- is printed with the "fused" time).
 
     python tools/pair_bench.py [--batch 1] [--reps 20] [--sweep]
 Every fused result is compared byte for byte with the two-launch result.
@@ -99,6 +100,11 @@ def main():
         t_f, bad = run_variant("auto")
         line = "%-24s + %-24s  separate %6.2f us   fused %6.2f us%s" % (
             wl.layer_name(p["layer"]), wl.layer_name(d["layer"]), t_sep, t_f, "  MISMATCH %d" % bad if bad else "")
+        geo = (C.c_int32 * 12)()
+        if not f16 and hip.shl_mi355x_pwdw_geometry(plan_p, plan_d, a.batch, geo, 12) == 0:  # the grid the library chose
+            ny, nx, bh, bw, ey0, ey1, ex0, ex1, tiles = list(geo)[:9]
+            line += "   [%dx%d rects of %dx%d, borders +%d/+%d rows +%d/+%d columns, %d tile%s]" % (
+                ny, nx, bh, bw, ey0, ey1, ex0, ex1, tiles, "" if tiles == 1 else "s")
         tot_sep += t_sep
         tot_fused += t_f
         if a.sweep and f16:
