@@ -29,9 +29,11 @@ LAYOUT_NHWC, LAYOUT_OHWI, LAYOUT_1HWO = 15, 18, 22
 CSINN_TRUE = 1
 OP_CONV2D, OP_CONV2D_RELU, OP_CONV2D_RELU6 = 28, 29, 30
 OP_DEPTHWISE_CONV2D, OP_FULLYCONNECTED = 35, 71
+OP_AVGPOOL2D, OP_MAXPOOL2D = 14, 98
 
 SHL_NHWC, SHL_NCHW = 0, 1
 SHL_I8, SHL_F16 = 0, 1
+POOL_MAX, POOL_AVG = 0, 1
 ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2
 ALGO_AUTO, ALGO_DIRECT, ALGO_IGEMM, ALGO_DW, ALGO_GEMV, ALGO_STEM = 0, 1, 2, 3, 4, 5
 
@@ -132,6 +134,14 @@ class ConvDesc(C.Structure):
         [("out_scale", C.c_float), ("reserved", C.c_int32 * 4)]
 
 
+class PoolDesc(C.Structure):
+    """struct shl_mi355x_pool_desc (include/shl_mi355x.h)"""
+    _fields_ = [(n, C.c_int32) for n in (
+        "kind", "dtype", "layout", "batch", "c", "in_h", "in_w", "out_h", "out_w", "kernel_h", "kernel_w",
+        "stride_h", "stride_w", "pad_top", "pad_left", "count_include_pad", "in_zp", "out_zp")] + \
+        [("in_scale", C.c_float), ("out_scale", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
 ABI_STRUCTS = {"csinn_quant_info": QuantInfo, "csinn_tensor": Tensor, "csinn_session": Session,
                "csinn_callback": Callback, "csinn_params_base": ParamsBase,
                "csinn_conv2d_params": Conv2dParams, "csinn_fc_params": FcParams,
@@ -222,6 +232,8 @@ def load_hip():
         "shl_mi355x_layout_convert": (C.c_int, [vp, vp, C.c_int64, i32, i32, i32, i32, vp]),
         "shl_mi355x_global_avgpool2d": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, f32, i32, f32, i32, vp]),
         "shl_mi355x_softmax": (C.c_int, [vp, vp, i32, C.c_int64, i32, C.c_int64, f32, i32, f32, i32, vp]),
+        "shl_mi355x_pool2d": (C.c_int, [vp, vp, C.POINTER(PoolDesc), vp]),
+        "shl_mi355x_pool2d_kernel_name": (C.c_char_p, [C.POINTER(PoolDesc)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -258,7 +270,7 @@ _FRONTEND_SIGS = {
     "shl_mem_free": (None, [C.c_void_p]),
     "shl_debug_set_level": (None, [C.c_int]),
 }
-_SISO_OPS = ("csinn_relu", "csinn_relu6", "csinn_global_avgpool2d", "csinn_softmax")
+_SISO_OPS = ("csinn_relu", "csinn_relu6", "csinn_global_avgpool2d", "csinn_softmax", "csinn_maxpool2d", "csinn_avgpool2d")
 _CONV_OPS = ["csinn_conv2d", "csinn_conv2d_relu", "csinn_conv2d_relu6", "csinn_depthwise_conv2d",
              "csinn_depthwise_conv2d_relu", "csinn_fullyconnected"] + list(_SISO_OPS)
 
@@ -412,6 +424,24 @@ def conv_params(fe, keep, api, layout, stride=(1, 1), pad=(0, 0, 0, 0), dilation
     pc.pad_top, pc.pad_left, pc.pad_down, pc.pad_right = pad
     pc.dilation_height, pc.dilation_width = dilation
     pc.conv_extra.fuse_zp2bias = fuse_zp2bias
+    return p
+
+
+def pool_params(fe, keep, api, layout, kernel=(2, 2), stride=(2, 2), pad=(0, 0, 0, 0), ceil_mode=0,
+                count_include_pad=False, sess=None, name=b"pool"):
+    """params block of csinn_maxpool2d / csinn_avgpool2d; pad = (top, left, down, right)"""
+    p = fe.csinn_alloc_params(C.sizeof(PoolParams), sess)
+    pc = C.cast(p, C.POINTER(PoolParams)).contents
+    pc.base.api = api
+    pc.base.layout = layout
+    pc.base.name = keep.add(C.c_char_p(name)).value
+    if sess is not None:
+        pc.base.sess = sess
+    pc.filter_height, pc.filter_width = kernel
+    pc.stride_height, pc.stride_width = stride
+    pc.pad_top, pc.pad_left, pc.pad_down, pc.pad_right = pad
+    pc.ceil_mode = ceil_mode
+    pc.count_include_pad = bool(count_include_pad)
     return p
 
 

@@ -177,6 +177,18 @@ int shl_gref_global_avgpool2d(struct csinn_tensor *input, struct csinn_tensor *o
     return record_siso(input, output, CSINN_OP_GLOBAL_AVGPOOL2D, params);
 }
 
+int shl_gref_maxpool2d(struct csinn_tensor *input, struct csinn_tensor *output,
+                       struct csinn_pool_params *params)
+{
+    return record_siso(input, output, CSINN_OP_MAXPOOL2D, params);
+}
+
+int shl_gref_avgpool2d(struct csinn_tensor *input, struct csinn_tensor *output,
+                       struct csinn_pool_params *params)
+{
+    return record_siso(input, output, CSINN_OP_AVGPOOL2D, params);
+}
+
 int shl_gref_softmax(struct csinn_tensor *input, struct csinn_tensor *output,
                      struct csinn_softmax_params *params)
 {
@@ -192,6 +204,8 @@ int shl_gref_call_layer_func(void *fn, struct shl_node *node)
         case CSINN_OP_RELU:
         case CSINN_OP_RELU6:
         case CSINN_OP_GLOBAL_AVGPOOL2D:
+        case CSINN_OP_MAXPOOL2D:
+        case CSINN_OP_AVGPOOL2D:
         case CSINN_OP_SOFTMAX:
             return f(node->in[0]->data, node->out[0]->data, params);
         case CSINN_OP_ADD:
@@ -243,6 +257,8 @@ static struct csinn_callback *gref_cb_map(int op, int dtype)
         {CSINN_OP_RELU, shl_gref_relu},
         {CSINN_OP_RELU6, shl_gref_relu6},
         {CSINN_OP_GLOBAL_AVGPOOL2D, shl_gref_global_avgpool2d},
+        {CSINN_OP_MAXPOOL2D, shl_gref_maxpool2d},
+        {CSINN_OP_AVGPOOL2D, shl_gref_avgpool2d},
         {CSINN_OP_SOFTMAX, shl_gref_softmax},
         {CSINN_OP_ADD, shl_gref_add},
     };

@@ -31,6 +31,12 @@ const void *shl_mi355x_stage_in(struct shl_mi355x_ctx *ctx, struct csinn_tensor 
 void *shl_mi355x_stage_out_begin(struct shl_mi355x_ctx *ctx, struct csinn_tensor *t, int slot);
 int shl_mi355x_stage_out_end(struct shl_mi355x_ctx *ctx, struct csinn_tensor *t, void *dev);
 
+/* perf callbacks of the windowed pools (pooling.c): single-input signature + the trailing info block */
+int shl_mi355x_maxpool2d_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params,
+                              struct csinn_perf_info *info);
+int shl_mi355x_avgpool2d_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params,
+                              struct csinn_perf_info *info);
+
 float shl_mi355x_half_to_float(uint16_t h);
 
 /* session.c: fold the relu / relu6 layer that is the convolution's only consumer into its plan (convolution.c) */

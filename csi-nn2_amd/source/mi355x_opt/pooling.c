@@ -1,11 +1,14 @@
 /*
  * pooling.c -- global_avgpool2d and softmax callbacks of the MI355X backend: the two operators
  * between MobileNetV1's last pointwise convolution and its output (SURVEY 8f1;
- * example/c906_mobilenetv1_f16.c:1805-1886 of the reference).
+ * example/c906_mobilenetv1_f16.c:1805-1886 of the reference); the windowed maxpool2d / avgpool2d (ResNet's stem
+ * pool, Inception-style average pools); the residual add.
  *
  * exec(input, output, params) with the reference's signatures
- * (source/reference/global_averagepool.c:46-50, softmax.c:68-72).
+ * (source/reference/global_averagepool.c:46-50, maxpool.c:113-124, averagepool.c:127-138, softmax.c:68-72).
  */
+#include <string.h>
+
 #include "mi355x_internal.h"
 
 static int dtype_code(const struct csinn_tensor *t)
@@ -76,6 +79,98 @@ int shl_mi355x_global_avgpool2d_exec(struct csinn_tensor *input, struct csinn_te
         return CSINN_FALSE;
     }
     return shl_mi355x_stage_out_end(ctx, output, out_dev);
+}
+
+/* maxpool2d / avgpool2d (source/reference/maxpool.c:113-124, averagepool.c:127-138): the window geometry comes
+ * from params, the output size from the OUTPUT tensor's dims (ceil_mode, pad_down and pad_right act through it) */
+static int pool2d_desc(const char *op, int kind, struct csinn_tensor *input, struct csinn_tensor *output,
+                       struct csinn_pool_params *params, struct shl_mi355x_pool_desc *desc)
+{
+    int dtype;
+    int rc = check_io(op, input, output, &dtype);
+    if (rc != CSINN_TRUE) return rc;
+    if (input->dim_count != 4 || output->dim_count != 4) {
+        shl_debug_error("mi355x: %s expects a 4-d tensor\n", op);
+        return CSINN_FALSE;
+    }
+    struct shl_mi355x_pool_desc d;
+    memset(&d, 0, sizeof(d));
+    int out_c;
+    if (params->base.layout == CSINN_LAYOUT_NCHW) {
+        d.layout = SHL_MI355X_NCHW;
+        d.c = input->dim[1], d.in_h = input->dim[2], d.in_w = input->dim[3];
+        out_c = output->dim[1], d.out_h = output->dim[2], d.out_w = output->dim[3];
+    } else if (params->base.layout == CSINN_LAYOUT_NHWC) {
+        d.layout = SHL_MI355X_NHWC;
+        d.in_h = input->dim[1], d.in_w = input->dim[2], d.c = input->dim[3];
+        d.out_h = output->dim[1], d.out_w = output->dim[2], out_c = output->dim[3];
+    } else {
+        return CSINN_UNSUPPORT_LAYOUT;
+    }
+    if (output->dim[0] != input->dim[0] || out_c != d.c) {
+        shl_debug_error("mi355x: %s: batch / channels of input and output differ\n", op);
+        return CSINN_FALSE;
+    }
+    d.kind = kind;
+    d.dtype = dtype;
+    d.batch = input->dim[0];
+    d.kernel_h = params->filter_height, d.kernel_w = params->filter_width;
+    d.stride_h = params->stride_height, d.stride_w = params->stride_width;
+    d.pad_top = params->pad_top, d.pad_left = params->pad_left;
+    d.count_include_pad = params->count_include_pad ? 1 : 0;
+    d.in_scale = input->qinfo->scale, d.in_zp = input->qinfo->zero_point;
+    d.out_scale = output->qinfo->scale, d.out_zp = output->qinfo->zero_point;
+    *desc = d;
+    return CSINN_TRUE;
+}
+
+static int pool2d_exec(const char *op, int kind, struct csinn_tensor *input, struct csinn_tensor *output,
+                       struct csinn_pool_params *params)
+{
+    struct shl_mi355x_pool_desc d;
+    int rc = pool2d_desc(op, kind, input, output, params, &d);
+    if (rc != CSINN_TRUE) return rc;
+    struct shl_mi355x_ctx *ctx = shl_mi355x_ctx_of(params->base.sess);
+    const void *in_dev = shl_mi355x_stage_in(ctx, input, 0);
+    void *out_dev = shl_mi355x_stage_out_begin(ctx, output, 1);
+    if (in_dev == NULL || out_dev == NULL) return CSINN_FALSE;
+    int st = shl_mi355x_pool2d(in_dev, out_dev, &d, shl_mi355x_ctx_stream(ctx));
+    if (st != SHL_MI355X_OK) {
+        shl_debug_error("mi355x: %s failed (%d): %s\n", op, st, shl_mi355x_last_error());
+        return CSINN_FALSE;
+    }
+    return shl_mi355x_stage_out_end(ctx, output, out_dev);
+}
+
+int shl_mi355x_maxpool2d_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params)
+{
+    return pool2d_exec("maxpool2d", SHL_MI355X_POOL_MAX, input, output, params);
+}
+
+int shl_mi355x_avgpool2d_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params)
+{
+    return pool2d_exec("avgpool2d", SHL_MI355X_POOL_AVG, input, output, params);
+}
+
+/* perf callbacks (single-input signature): the kernel form the rules choose for this layer */
+int shl_mi355x_maxpool2d_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params,
+                              struct csinn_perf_info *info)
+{
+    struct shl_mi355x_pool_desc d;
+    int rc = pool2d_desc("maxpool2d", SHL_MI355X_POOL_MAX, input, output, params, &d);
+    if (rc != CSINN_TRUE) return rc;
+    info->kernel_name = (char *)shl_mi355x_pool2d_kernel_name(&d);
+    return CSINN_TRUE;
+}
+
+int shl_mi355x_avgpool2d_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params,
+                              struct csinn_perf_info *info)
+{
+    struct shl_mi355x_pool_desc d;
+    int rc = pool2d_desc("avgpool2d", SHL_MI355X_POOL_AVG, input, output, params, &d);
+    if (rc != CSINN_TRUE) return rc;
+    info->kernel_name = (char *)shl_mi355x_pool2d_kernel_name(&d);
+    return CSINN_TRUE;
 }
 
 int shl_mi355x_softmax_exec(struct csinn_tensor *input, struct csinn_tensor *output,

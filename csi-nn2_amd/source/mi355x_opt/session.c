@@ -97,6 +97,7 @@ static int gpu_native(int (*exec)())
     return exec == (int (*)())shl_mi355x_conv2d_exec || exec == (int (*)())shl_mi355x_group_conv2d_exec || exec == (int (*)())shl_mi355x_fullyconnected_exec ||
            exec == (int (*)())shl_mi355x_relu_exec || exec == (int (*)())shl_mi355x_relu6_exec ||
            exec == (int (*)())shl_mi355x_global_avgpool2d_exec || exec == (int (*)())shl_mi355x_softmax_exec ||
+           exec == (int (*)())shl_mi355x_maxpool2d_exec || exec == (int (*)())shl_mi355x_avgpool2d_exec ||
            exec == (int (*)())shl_mi355x_add_exec;
 }
 
@@ -106,6 +107,8 @@ static int op_arity(int type)
         case CSINN_OP_RELU:
         case CSINN_OP_RELU6:
         case CSINN_OP_GLOBAL_AVGPOOL2D:
+        case CSINN_OP_MAXPOOL2D:
+        case CSINN_OP_AVGPOOL2D:
         case CSINN_OP_SOFTMAX:
             return 1;
         case CSINN_OP_ADD:

@@ -585,6 +585,10 @@ void shl_target_init_mi355x(void)
         reg(dts[i], CSINN_OP_RELU, NULL, shl_mi355x_relu_exec, shl_gref_relu);
         reg(dts[i], CSINN_OP_RELU6, NULL, shl_mi355x_relu6_exec, shl_gref_relu6);
         reg(dts[i], CSINN_OP_GLOBAL_AVGPOOL2D, NULL, shl_mi355x_global_avgpool2d_exec, shl_gref_global_avgpool2d);
+        reg(dts[i], CSINN_OP_MAXPOOL2D, NULL, shl_mi355x_maxpool2d_exec, shl_gref_maxpool2d);
+        g_table[g_table_len - 1].cb.perf = shl_mi355x_maxpool2d_perf;
+        reg(dts[i], CSINN_OP_AVGPOOL2D, NULL, shl_mi355x_avgpool2d_exec, shl_gref_avgpool2d);
+        g_table[g_table_len - 1].cb.perf = shl_mi355x_avgpool2d_perf;
         reg(dts[i], CSINN_OP_SOFTMAX, NULL, shl_mi355x_softmax_exec, shl_gref_softmax);
         reg(dts[i], CSINN_OP_ADD, NULL, shl_mi355x_add_exec, shl_gref_add);
     }

@@ -7,6 +7,7 @@
  *   depthwise_conv2d .. source/nn2/depthwise_conv2d.c:26-57, depthwise_conv2d_relu.c
  *   fullyconnected .... source/nn2/fullyconnected.c:26-57
  *   relu / relu6 ...... source/nn2/relu.c, relu6.c
+ *   maxpool2d / avgpool2d  source/nn2/maxpool.c, averagepool.c
  * The only deliberate difference: a missing callback is reported (CSINN_CALLBACK_UNSET and an
  * error message) instead of being dereferenced.
  */
@@ -157,6 +158,29 @@ int csinn_global_avgpool2d_init(struct csinn_tensor *input, struct csinn_tensor 
 }
 int csinn_global_avgpool2d(struct csinn_tensor *input, struct csinn_tensor *output,
                            struct csinn_pool_params *params)
+{
+    return run3(&params->base, input, output, params);
+}
+
+/* source/nn2/maxpool.c, averagepool.c of the reference: same dispatch as the global pool */
+int csinn_maxpool2d_init(struct csinn_tensor *input, struct csinn_tensor *output,
+                         struct csinn_pool_params *params)
+{
+    return map_and_init3(&params->base, CSINN_OP_MAXPOOL2D, input->dtype, input, output, params);
+}
+int csinn_maxpool2d(struct csinn_tensor *input, struct csinn_tensor *output,
+                    struct csinn_pool_params *params)
+{
+    return run3(&params->base, input, output, params);
+}
+
+int csinn_avgpool2d_init(struct csinn_tensor *input, struct csinn_tensor *output,
+                         struct csinn_pool_params *params)
+{
+    return map_and_init3(&params->base, CSINN_OP_AVGPOOL2D, input->dtype, input, output, params);
+}
+int csinn_avgpool2d(struct csinn_tensor *input, struct csinn_tensor *output,
+                    struct csinn_pool_params *params)
 {
     return run3(&params->base, input, output, params);
 }

@@ -61,6 +61,15 @@ int csinn_global_avgpool2d_init(struct csinn_tensor *input, struct csinn_tensor 
                                 struct csinn_pool_params *params);
 int csinn_global_avgpool2d(struct csinn_tensor *input, struct csinn_tensor *output,
                            struct csinn_pool_params *params);
+/* windowed pooling (source/nn2/maxpool.c, averagepool.c of the reference): the output tensor's dims set the output size */
+int csinn_maxpool2d_init(struct csinn_tensor *input, struct csinn_tensor *output,
+                         struct csinn_pool_params *params);
+int csinn_maxpool2d(struct csinn_tensor *input, struct csinn_tensor *output,
+                    struct csinn_pool_params *params);
+int csinn_avgpool2d_init(struct csinn_tensor *input, struct csinn_tensor *output,
+                         struct csinn_pool_params *params);
+int csinn_avgpool2d(struct csinn_tensor *input, struct csinn_tensor *output,
+                    struct csinn_pool_params *params);
 int csinn_softmax_init(struct csinn_tensor *input, struct csinn_tensor *output,
                        struct csinn_softmax_params *params);
 int csinn_softmax(struct csinn_tensor *input, struct csinn_tensor *output,

@@ -116,6 +116,7 @@ enum csinn_op_enum {
     CSINN_OP_CONV2D_RELU = 29,
     CSINN_OP_CONV2D_RELU6 = 30,
     CSINN_OP_ADD = 3,
+    CSINN_OP_AVGPOOL2D = 14,
     CSINN_OP_CONV2D_CHANNEL = 31,
     CSINN_OP_CONV2D_CHANNEL_RELU = 32,
     CSINN_OP_CONV2D_CHANNEL_RELU6 = 33,
@@ -132,6 +133,7 @@ enum csinn_op_enum {
     CSINN_OP_GROUP_CONV2D_CHANNEL_RELU = 46,
     CSINN_OP_FULLYCONNECTED = 71,
     CSINN_OP_GLOBAL_AVGPOOL2D = 74,
+    CSINN_OP_MAXPOOL2D = 98,
     CSINN_OP_RELU = 127,
     CSINN_OP_RELU6 = 129,
     CSINN_OP_SOFTMAX = 159,

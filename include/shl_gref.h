@@ -71,6 +71,10 @@ int shl_gref_add(struct csinn_tensor *input0, struct csinn_tensor *input1, struc
                  struct csinn_diso_params *params);
 int shl_gref_global_avgpool2d(struct csinn_tensor *input, struct csinn_tensor *output,
                               struct csinn_pool_params *params);
+int shl_gref_maxpool2d(struct csinn_tensor *input, struct csinn_tensor *output,
+                       struct csinn_pool_params *params);
+int shl_gref_avgpool2d(struct csinn_tensor *input, struct csinn_tensor *output,
+                       struct csinn_pool_params *params);
 int shl_gref_softmax(struct csinn_tensor *input, struct csinn_tensor *output,
                      struct csinn_softmax_params *params);
 

@@ -340,6 +340,35 @@ int shl_mi355x_global_avgpool2d(const void *input_dev, void *output_dev, int32_t
                                 int32_t batch, int32_t channels, int32_t pixels, float in_scale,
                                 int32_t in_zp, float out_scale, int32_t out_zp, void *stream);
 
+/* windowed max / average pooling of an int8 / binary16 tensor: shl_ref_maxpool2d_quant / shl_ref_avgpool2d_quant
+ * (source/reference/maxpool.c:21-124, averagepool.c:21-138), bit for bit for any scales.  The window of output
+ * (oy, ox) starts at (oy * stride_h - pad_top, ox * stride_w - pad_left) and is clamped to the image; out_h / out_w
+ * are the OUTPUT TENSOR's dims (ceil_mode, pad_down and pad_right act through them only).  avg divides by the number
+ * of in-image taps, or by kernel_h * kernel_w with count_include_pad.  f16: scales and zero points are ignored.
+ * A shape in which some window holds no input element is refused (SHL_MI355X_EINVAL).  Enqueues only: no allocation,
+ * no synchronisation (capturable in a hipGraph). */
+enum shl_mi355x_pool_kind {
+    SHL_MI355X_POOL_MAX = 0,
+    SHL_MI355X_POOL_AVG = 1
+};
+
+struct shl_mi355x_pool_desc {
+    int32_t kind;   /* shl_mi355x_pool_kind */
+    int32_t dtype;  /* SHL_MI355X_I8 / SHL_MI355X_F16 */
+    int32_t layout; /* SHL_MI355X_NHWC / SHL_MI355X_NCHW */
+    int32_t batch, c, in_h, in_w, out_h, out_w;
+    int32_t kernel_h, kernel_w, stride_h, stride_w, pad_top, pad_left;
+    int32_t count_include_pad;
+    int32_t in_zp, out_zp;
+    float in_scale, out_scale;
+    int32_t reserved[4]; /* must be zero */
+};
+
+int shl_mi355x_pool2d(const void *in_dev, void *out_dev, const struct shl_mi355x_pool_desc *d, void *stream);
+/* the kernel form the rules choose for `d` ("pool2d_nhwc_vec", "pool2d_nchw_row", "pool2d_generic"; "" for an
+ * invalid descriptor).  Pure host code: touches no device */
+const char *shl_mi355x_pool2d_kernel_name(const struct shl_mi355x_pool_desc *d);
+
 /* softmax along one axis of a tensor viewed as [outer, count, inner]:
  * shl_ref_softmax_quant (source/reference/softmax.c:21-72): float max, double exp, float running
  * sum in index order.  count <= 8192. */

@@ -99,6 +99,11 @@ int shl_mi355x_add_exec(struct csinn_tensor *input0, struct csinn_tensor *input1
                         struct csinn_diso_params *params);
 int shl_mi355x_global_avgpool2d_exec(struct csinn_tensor *input, struct csinn_tensor *output,
                                      struct csinn_pool_params *params);
+/* windowed pooling: 4-d tensors, the output size is the output tensor's; a window without an in-image tap is refused */
+int shl_mi355x_maxpool2d_exec(struct csinn_tensor *input, struct csinn_tensor *output,
+                              struct csinn_pool_params *params);
+int shl_mi355x_avgpool2d_exec(struct csinn_tensor *input, struct csinn_tensor *output,
+                              struct csinn_pool_params *params);
 int shl_mi355x_softmax_exec(struct csinn_tensor *input, struct csinn_tensor *output,
                             struct csinn_softmax_params *params);
 
