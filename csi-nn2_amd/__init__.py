@@ -30,6 +30,7 @@ CSINN_TRUE = 1
 OP_CONV2D, OP_CONV2D_RELU, OP_CONV2D_RELU6 = 28, 29, 30
 OP_DEPTHWISE_CONV2D, OP_FULLYCONNECTED = 35, 71
 OP_AVGPOOL2D, OP_MAXPOOL2D = 14, 98
+OP_CONCAT = 26
 
 SHL_NHWC, SHL_NCHW = 0, 1
 SHL_I8, SHL_F16 = 0, 1
@@ -125,6 +126,10 @@ class PoolParams(C.Structure):
         "ceil_mode")] + [("count_include_pad", C.c_bool)]
 
 
+class ConcatParams(C.Structure):
+    _fields_ = [("base", ParamsBase), ("inputs_count", C.c_int32), ("axis", C.c_int32)]
+
+
 class ConvDesc(C.Structure):
     """struct shl_mi355x_conv_desc (include/shl_mi355x.h)"""
     _fields_ = [(n, C.c_int32) for n in (
@@ -140,6 +145,12 @@ class PoolDesc(C.Structure):
         "kind", "dtype", "layout", "batch", "c", "in_h", "in_w", "out_h", "out_w", "kernel_h", "kernel_w",
         "stride_h", "stride_w", "pad_top", "pad_left", "count_include_pad", "in_zp", "out_zp")] + \
         [("in_scale", C.c_float), ("out_scale", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+class ConcatDesc(C.Structure):
+    """struct shl_mi355x_concat_desc (include/shl_mi355x.h)"""
+    _fields_ = [("dtype", C.c_int32), ("n_inputs", C.c_int32), ("outer", C.c_int64), ("out_scale", C.c_float),
+                ("out_zp", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
 ABI_STRUCTS = {"csinn_quant_info": QuantInfo, "csinn_tensor": Tensor, "csinn_session": Session,
@@ -234,6 +245,10 @@ def load_hip():
         "shl_mi355x_softmax": (C.c_int, [vp, vp, i32, C.c_int64, i32, C.c_int64, f32, i32, f32, i32, vp]),
         "shl_mi355x_pool2d": (C.c_int, [vp, vp, C.POINTER(PoolDesc), vp]),
         "shl_mi355x_pool2d_kernel_name": (C.c_char_p, [C.POINTER(PoolDesc)]),
+        "shl_mi355x_concat": (C.c_int, [C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(f32), C.POINTER(i32), vp,
+                                        C.POINTER(ConcatDesc), vp]),
+        "shl_mi355x_concat_kernel_name": (C.c_char_p, [C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(f32), C.POINTER(i32),
+                                                       vp, C.POINTER(ConcatDesc)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -304,6 +319,8 @@ def load_frontend(kind="standalone", local=False, path=None):
     for suffix in ("_init", ""):
         fn = getattr(lib, "csinn_add" + suffix)
         fn.restype, fn.argtypes = C.c_int, [tp, tp, tp, C.c_void_p]
+        fn = getattr(lib, "csinn_concat" + suffix)
+        fn.restype, fn.argtypes = C.c_int, [C.POINTER(tp), tp, C.c_void_p]
     lib._typed = True
     lib.kind = kind
     return lib
@@ -443,6 +460,25 @@ def pool_params(fe, keep, api, layout, kernel=(2, 2), stride=(2, 2), pad=(0, 0, 
     pc.ceil_mode = ceil_mode
     pc.count_include_pad = bool(count_include_pad)
     return p
+
+
+def concat_params(fe, keep, api, layout, n, axis, sess=None, name=b"concat"):
+    """params block of csinn_concat: n inputs along `axis` (-1: the last axis)"""
+    p = fe.csinn_alloc_params(C.sizeof(ConcatParams), sess)
+    pc = C.cast(p, C.POINTER(ConcatParams)).contents
+    pc.base.api = api
+    pc.base.layout = layout
+    pc.base.name = keep.add(C.c_char_p(name)).value
+    if sess is not None:
+        pc.base.sess = sess
+    pc.inputs_count = n
+    pc.axis = axis
+    return p
+
+
+def tensor_array(keep, tensors):
+    """struct csinn_tensor *[]: what csinn_concat takes as its inputs"""
+    return keep.add((C.POINTER(Tensor) * len(tensors))(*tensors))
 
 
 def fc_params(fe, keep, api, units, fuse_zp2bias=0, sess=None, name=b"fc"):

@@ -171,6 +171,26 @@ int shl_gref_add(struct csinn_tensor *input0, struct csinn_tensor *input1, struc
     return shl_gref_graph_insert(layer, shl_gref_get_graph(output->sess ? output->sess : input0->sess));
 }
 
+/* params->inputs_count inputs, any of which may be a constant tensor (it becomes a const node), one output */
+int shl_gref_concat(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params)
+{
+    const int n = params->inputs_count;
+    struct shl_node *layer = shl_node_alloc(CSINN_OP_CONCAT, params->base.name, n, 1, params);
+    struct shl_node *produced = shl_node_var_alloc(output->name, output);
+    struct csinn_session *sess = output->sess;
+    for (int i = 0; i < n; i++) {
+        if (input[i]->is_const) {
+            shl_node_add_in(layer, shl_node_const_var_alloc(input[i]->name, input[i]), i);
+        } else {
+            shl_node_add_in(layer, (struct shl_node *)input[i]->data, i);
+            if (sess == NULL) sess = input[i]->sess;
+        }
+    }
+    shl_node_add_out(layer, produced, 0);
+    output->data = produced;
+    return shl_gref_graph_insert(layer, shl_gref_get_graph(sess));
+}
+
 int shl_gref_global_avgpool2d(struct csinn_tensor *input, struct csinn_tensor *output,
                               struct csinn_pool_params *params)
 {
@@ -210,6 +230,13 @@ int shl_gref_call_layer_func(void *fn, struct shl_node *node)
             return f(node->in[0]->data, node->out[0]->data, params);
         case CSINN_OP_ADD:
             return f(node->in[0]->data, node->in[1]->data, node->out[0]->data, params);
+        case CSINN_OP_CONCAT: {
+            struct csinn_tensor **ins = shl_mem_alloc((int64_t)node->in_num * sizeof(*ins));
+            for (int i = 0; i < node->in_num; i++) ins[i] = node->in[i]->data;
+            int rc = f(ins, node->out[0]->data, params);
+            shl_mem_free(ins);
+            return rc;
+        }
         case CSINN_OP_CONV2D:
         case CSINN_OP_CONV2D_RELU:
         case CSINN_OP_CONV2D_RELU6:
@@ -261,6 +288,7 @@ static struct csinn_callback *gref_cb_map(int op, int dtype)
         {CSINN_OP_AVGPOOL2D, shl_gref_avgpool2d},
         {CSINN_OP_SOFTMAX, shl_gref_softmax},
         {CSINN_OP_ADD, shl_gref_add},
+        {CSINN_OP_CONCAT, shl_gref_concat},
     };
     for (unsigned i = 0; i < sizeof(table) / sizeof(table[0]); i++) {
         if (table[i].op == op) {

@@ -30,12 +30,21 @@ void shl_mi355x_ctx_release(struct csinn_session *sess);
 const void *shl_mi355x_stage_in(struct shl_mi355x_ctx *ctx, struct csinn_tensor *t, int slot);
 void *shl_mi355x_stage_out_begin(struct shl_mi355x_ctx *ctx, struct csinn_tensor *t, int slot);
 int shl_mi355x_stage_out_end(struct shl_mi355x_ctx *ctx, struct csinn_tensor *t, void *dev);
+/* n inputs at once (concat): host tensors are packed into staging slot 0 at 256-byte-aligned offsets and uploaded on the
+ * context's stream, DMABUF tensors are used in place, tensors of zero elements get NULL; dev[i]: where tensor i lives.
+ * SHL_MI355X_STAGE_ALIGN is that alignment, for callers that predict a kernel form before anything is staged */
+#define SHL_MI355X_STAGE_ALIGN 256
+int shl_mi355x_stage_in_many(struct shl_mi355x_ctx *ctx, struct csinn_tensor **t, int n, const void **dev);
 
 /* perf callbacks of the windowed pools (pooling.c): single-input signature + the trailing info block */
 int shl_mi355x_maxpool2d_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params,
                               struct csinn_perf_info *info);
 int shl_mi355x_avgpool2d_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params,
                               struct csinn_perf_info *info);
+
+/* ... and of concat: the array-of-inputs signature */
+int shl_mi355x_concat_perf(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params,
+                           struct csinn_perf_info *info);
 
 float shl_mi355x_half_to_float(uint16_t h);
 

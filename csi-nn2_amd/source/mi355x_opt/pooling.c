@@ -2,11 +2,13 @@
  * pooling.c -- global_avgpool2d and softmax callbacks of the MI355X backend: the two operators
  * between MobileNetV1's last pointwise convolution and its output (SURVEY 8f1;
  * example/c906_mobilenetv1_f16.c:1805-1886 of the reference); the windowed maxpool2d / avgpool2d (ResNet's stem
- * pool, Inception-style average pools); the residual add.
+ * pool, Inception-style average pools); the residual add; concat (the end of every Fire module and Inception block).
  *
  * exec(input, output, params) with the reference's signatures
- * (source/reference/global_averagepool.c:46-50, maxpool.c:113-124, averagepool.c:127-138, softmax.c:68-72).
+ * (source/reference/global_averagepool.c:46-50, maxpool.c:113-124, averagepool.c:127-138, softmax.c:68-72,
+ * concat.c:51-76).
  */
+#include <stdlib.h>
 #include <string.h>
 
 #include "mi355x_internal.h"
@@ -236,4 +238,139 @@ int shl_mi355x_add_exec(struct csinn_tensor *input0, struct csinn_tensor *input1
         return CSINN_FALSE;
     }
     return shl_mi355x_stage_out_end(ctx, output, out_dev);
+}
+
+/* concat (source/reference/concat.c:21-76): a variable number of inputs.  The reference trusts the shapes; here a
+ * mismatch is an error, where it would read past a buffer. */
+struct concat_call {
+    struct shl_mi355x_concat_desc desc;
+    int64_t *len;
+    float *scale;
+    int32_t *zp;
+    const void **dev;
+};
+
+static void concat_release(struct concat_call *c)
+{
+    free(c->len);
+    free(c->scale);
+    free(c->zp);
+    free(c->dev);
+}
+
+static int concat_prepare(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params,
+                          struct concat_call *c)
+{
+    memset(c, 0, sizeof(*c));
+    const int n = params->inputs_count;
+    if (input == NULL || n < 1) {
+        shl_debug_error("mi355x: concat needs at least one input\n");
+        return CSINN_FALSE;
+    }
+    const int dims = output->dim_count;
+    /* axis == -1 is the last axis; the reference rewrites params->axis, which a params block shared between threads
+     * or replayed by a graph has no need of */
+    const int axis = params->axis == -1 ? dims - 1 : params->axis;
+    if (dims < 1 || dims > MAX_DIM || axis < 0 || axis >= dims) {
+        shl_debug_error("mi355x: concat: axis %d of a %d-d tensor\n", params->axis, dims);
+        return CSINN_FALSE;
+    }
+    int64_t outer = 1, inner = 1, along = 0;
+    for (int k = 0; k < axis; k++) outer *= output->dim[k];
+    for (int k = axis + 1; k < dims; k++) inner *= output->dim[k];
+    int dtype = -1;
+    for (int i = 0; i < n; i++) {
+        if (input[i] == NULL) {
+            shl_debug_error("mi355x: concat: input %d is NULL\n", i);
+            return CSINN_FALSE;
+        }
+        int rc = check_io("concat", input[i], output, &dtype);
+        if (rc != CSINN_TRUE) return rc;
+        if (input[i]->dim_count != dims) {
+            shl_debug_error("mi355x: concat: input %d is %d-d, the output %d-d\n", i, input[i]->dim_count, dims);
+            return CSINN_FALSE;
+        }
+        for (int k = 0; k < dims; k++)
+            if (input[i]->dim[k] < 0 || (k != axis && input[i]->dim[k] != output->dim[k])) {
+                shl_debug_error("mi355x: concat: dim %d of input %d is %d, the output's %d\n", k, i, input[i]->dim[k],
+                                output->dim[k]);
+                return CSINN_FALSE;
+            }
+        along += input[i]->dim[axis];
+    }
+    if (along != output->dim[axis]) {
+        shl_debug_error("mi355x: concat: the inputs hold %lld along axis %d, the output %d\n", (long long)along, axis,
+                        output->dim[axis]);
+        return CSINN_FALSE;
+    }
+    c->len = calloc((size_t)n, sizeof(*c->len));
+    c->scale = calloc((size_t)n, sizeof(*c->scale));
+    c->zp = calloc((size_t)n, sizeof(*c->zp));
+    c->dev = calloc((size_t)n, sizeof(*c->dev));
+    if (!c->len || !c->scale || !c->zp || !c->dev) {
+        concat_release(c);
+        return CSINN_FALSE;
+    }
+    for (int i = 0; i < n; i++) {
+        c->len[i] = input[i]->dim[axis] * inner;
+        c->scale[i] = input[i]->qinfo->scale;
+        c->zp[i] = input[i]->qinfo->zero_point;
+    }
+    c->desc.dtype = dtype;
+    c->desc.n_inputs = n;
+    c->desc.outer = outer;
+    c->desc.out_scale = output->qinfo->scale;
+    c->desc.out_zp = output->qinfo->zero_point;
+    return CSINN_TRUE;
+}
+
+int shl_mi355x_concat_exec(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params)
+{
+    struct concat_call c;
+    int rc = concat_prepare(input, output, params, &c);
+    if (rc != CSINN_TRUE) return rc;
+    if (csinn_tensor_size(output) == 0) {
+        concat_release(&c);
+        return CSINN_TRUE;
+    }
+    struct shl_mi355x_ctx *ctx = shl_mi355x_ctx_of(params->base.sess);
+    void *out_dev = NULL;
+    if (shl_mi355x_stage_in_many(ctx, input, c.desc.n_inputs, c.dev) == CSINN_TRUE)
+        out_dev = shl_mi355x_stage_out_begin(ctx, output, 1);
+    if (out_dev == NULL) {
+        concat_release(&c);
+        return CSINN_FALSE;
+    }
+    int st = shl_mi355x_concat(c.dev, c.len, c.scale, c.zp, out_dev, &c.desc, shl_mi355x_ctx_stream(ctx));
+    concat_release(&c);
+    if (st != SHL_MI355X_OK) {
+        shl_debug_error("mi355x: concat failed (%d): %s\n", st, shl_mi355x_last_error());
+        return CSINN_FALSE;
+    }
+    return shl_mi355x_stage_out_end(ctx, output, out_dev);
+}
+
+/* the form the rules choose for this layer.  They look at addresses: a DMABUF tensor has its own; host tensors are given
+ * the alignment the staging path will give them (made-up, disjoint addresses: nothing is staged here) */
+int shl_mi355x_concat_perf(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params,
+                           struct csinn_perf_info *info)
+{
+    struct concat_call c;
+    int rc = concat_prepare(input, output, params, &c);
+    if (rc != CSINN_TRUE) return rc;
+    const int es = c.desc.dtype == SHL_MI355X_F16 ? 2 : 1;
+    uintptr_t at = (uintptr_t)1 << 56;
+    for (int i = 0; i < c.desc.n_inputs; i++) {
+        if (input[i]->mtype == CSINN_MEM_TYPE_DMABUF && input[i]->data) {
+            c.dev[i] = input[i]->data;
+            continue;
+        }
+        const uintptr_t bytes = (uintptr_t)(c.len[i] * c.desc.outer * es);
+        c.dev[i] = (const void *)at;
+        at += (bytes + SHL_MI355X_STAGE_ALIGN - 1) / SHL_MI355X_STAGE_ALIGN * SHL_MI355X_STAGE_ALIGN + SHL_MI355X_STAGE_ALIGN;
+    }
+    const void *out = output->mtype == CSINN_MEM_TYPE_DMABUF && output->data ? output->data : (const void *)((uintptr_t)1 << 57);
+    info->kernel_name = (char *)shl_mi355x_concat_kernel_name(c.dev, c.len, c.scale, c.zp, out, &c.desc);
+    concat_release(&c);
+    return CSINN_TRUE;
 }

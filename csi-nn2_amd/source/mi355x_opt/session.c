@@ -98,7 +98,7 @@ static int gpu_native(int (*exec)())
            exec == (int (*)())shl_mi355x_relu_exec || exec == (int (*)())shl_mi355x_relu6_exec ||
            exec == (int (*)())shl_mi355x_global_avgpool2d_exec || exec == (int (*)())shl_mi355x_softmax_exec ||
            exec == (int (*)())shl_mi355x_maxpool2d_exec || exec == (int (*)())shl_mi355x_avgpool2d_exec ||
-           exec == (int (*)())shl_mi355x_add_exec;
+           exec == (int (*)())shl_mi355x_add_exec || exec == (int (*)())shl_mi355x_concat_exec;
 }
 
 static int op_arity(int type)
@@ -127,6 +127,17 @@ static int op_arity(int type)
         default:
             return 0;
     }
+}
+
+/* the number of inputs layer `n` must have; 0: not a layer this file runs.  concat is the one variadic op: as many as its
+ * params say (the exec callback takes them as an array) */
+static int layer_arity(struct shl_node *n)
+{
+    if (n->type == CSINN_OP_CONCAT) {
+        struct csinn_concat_params *p = n->data;
+        return p && p->inputs_count >= 1 ? p->inputs_count : 0;
+    }
+    return op_arity(n->type);
 }
 
 static struct dev_tensor *lookup(struct dev_session *ds, struct shl_node *node)
@@ -324,6 +335,16 @@ static int enqueue_layers(struct dev_session *ds, struct shl_ref_graph *g)
                          in->shadow.dim[0], ds->stream);
             rc = st == SHL_MI355X_OK ? CSINN_TRUE : CSINN_FALSE;
             i = j + folded2;
+        } else if (n->type == CSINN_OP_CONCAT) { /* variadic: an array of shadow tensors */
+            struct csinn_tensor **ins = calloc((size_t)n->in_num, sizeof(*ins));
+            rc = ins ? CSINN_TRUE : CSINN_FALSE;
+            for (int j = 0; rc == CSINN_TRUE && j < n->in_num; j++) {
+                struct dev_tensor *dj = lookup(ds, n->in[j]);
+                if (dj) ins[j] = &dj->shadow;
+                else rc = CSINN_FALSE;
+            }
+            if (rc == CSINN_TRUE) rc = f(ins, &out->shadow, params);
+            free(ins);
         } else if (op_arity(n->type) == 1) {
             rc = f(&in->shadow, &out->shadow, params);
         } else if (op_arity(n->type) == 2) { /* add: the second operand is an activation or a constant */
@@ -413,14 +434,14 @@ int shl_mi355x_session_setup(struct csinn_session *sess)
     for (int i = 0; i < g->layer_index; i++) {
         struct shl_node *n = g->layer[i];
         struct csinn_params_base *params = n->data;
-        const int arity = op_arity(n->type);
+        const int arity = layer_arity(n);
         if (arity == 0 || n->in_num != arity || n->out_num != 1 || params->cb == NULL ||
             !gpu_native(params->cb->exec)) {
             shl_debug_info("mi355x: layer %d (%s, op %d) runs on the host path: session stays host-staged\n", i,
                            n->name ? n->name : "?", n->type);
             return rc;
         }
-        tensors += 2;
+        tensors += 1 + (n->type == CSINN_OP_CONCAT ? n->in_num : 1); /* its output + constants it may bring */
     }
     struct dev_session *ds = calloc(1, sizeof(*ds));
     ds->sess = sess;
@@ -433,21 +454,21 @@ int shl_mi355x_session_setup(struct csinn_session *sess)
     for (int i = 0; ok && i < g->input_num; i++) ok = adopt(ds, g->input[i]) != NULL;
     for (int i = 0; ok && i < g->layer_index; i++) {
         struct shl_node *n = g->layer[i];
-        if (lookup(ds, n->in[0]) == NULL) {
-            shl_debug_error("mi355x: layer %d consumes a tensor that no earlier layer produces\n", i);
-            ok = 0;
-            break;
-        }
-        if (op_arity(n->type) == 2 && lookup(ds, n->in[1]) == NULL) {
-            /* a constant second operand: upload it once, keep it resident */
-            struct csinn_tensor *c = n->in[1]->data;
-            struct dev_tensor *d = c->is_const && c->data ? adopt(ds, n->in[1]) : NULL;
+        /* concat: any input may be a constant; add: the second operand; everything else is produced earlier */
+        const int first_const = n->type == CSINN_OP_CONCAT ? 0 : 1;
+        const int activations = n->type == CSINN_OP_CONCAT ? n->in_num : op_arity(n->type) == 2 ? 2 : 1;
+        for (int j = 0; ok && j < activations; j++) {
+            if (lookup(ds, n->in[j]) != NULL) continue;
+            /* a constant operand: upload it once, keep it resident */
+            struct csinn_tensor *c = n->in[j]->data;
+            struct dev_tensor *d = j >= first_const && c->is_const && c->data ? adopt(ds, n->in[j]) : NULL;
             if (d == NULL || shl_mi355x_upload(d->dev, c->data, d->bytes, ds->stream) != SHL_MI355X_OK) {
-                shl_debug_error("mi355x: layer %d: second operand is neither produced earlier nor constant\n", i);
+                if (j == 0) shl_debug_error("mi355x: layer %d consumes a tensor that no earlier layer produces\n", i);
+                else shl_debug_error("mi355x: layer %d: operand %d is neither produced earlier nor constant\n", i, j);
                 ok = 0;
-                break;
             }
         }
+        if (!ok) break;
         ok = adopt(ds, n->out[0]) != NULL;
     }
     for (int i = 0; ok && i < g->output_num; i++) ok = lookup(ds, g->output[i]) != NULL;

@@ -72,7 +72,7 @@ struct shl_mi355x_ctx {
     struct {
         void *dev;
         size_t bytes;
-    } stage[3]; /* 0: first input, 1: output, 2: second input */
+    } stage[3]; /* 0: first input (concat: all of them, packed), 1: output, 2: second input */
     struct shl_mi355x_ctx *next;
 };
 
@@ -483,6 +483,51 @@ const void *shl_mi355x_stage_in(struct shl_mi355x_ctx *c, struct csinn_tensor *t
     return dev;
 }
 
+/* the inputs of a variadic layer: one staging buffer (slot 0, grown as for a single tensor) holds every host tensor */
+int shl_mi355x_stage_in_many(struct shl_mi355x_ctx *c, struct csinn_tensor **t, int n, const void **dev)
+{
+    size_t total = 0;
+    for (int i = 0; i < n; i++) {
+        dev[i] = NULL;
+        if (csinn_tensor_size(t[i]) == 0) continue;
+        if (t[i]->data == NULL) {
+            shl_debug_error("mi355x: input tensor %d has no data\n", i);
+            return CSINN_FALSE;
+        }
+        if (t[i]->mtype == CSINN_MEM_TYPE_DMABUF) continue;
+        int seen = 0; /* the same tensor given twice travels once */
+        for (int j = 0; j < i && !seen; j++) seen = t[j] == t[i];
+        if (seen) continue;
+        const size_t bytes = (size_t)csinn_tensor_byte_size(t[i]);
+        total += (bytes + SHL_MI355X_STAGE_ALIGN - 1) / SHL_MI355X_STAGE_ALIGN * SHL_MI355X_STAGE_ALIGN;
+    }
+    char *base = NULL;
+    if (total > 0) {
+        if (c == NULL) return CSINN_FALSE;
+        base = stage_buffer(c, 0, total);
+        if (base == NULL) return CSINN_FALSE;
+    }
+    size_t at = 0;
+    for (int i = 0; i < n; i++) {
+        if (csinn_tensor_size(t[i]) == 0) continue;
+        if (t[i]->mtype == CSINN_MEM_TYPE_DMABUF) {
+            dev[i] = t[i]->data;
+            continue;
+        }
+        for (int j = 0; j < i && dev[i] == NULL; j++)
+            if (t[j] == t[i]) dev[i] = dev[j];
+        if (dev[i] != NULL) continue;
+        const size_t bytes = (size_t)csinn_tensor_byte_size(t[i]);
+        if (shl_mi355x_upload(base + at, t[i]->data, bytes, shl_mi355x_ctx_stream(c)) != SHL_MI355X_OK) {
+            shl_debug_error("mi355x: upload failed: %s\n", shl_mi355x_last_error());
+            return CSINN_FALSE;
+        }
+        dev[i] = base + at;
+        at += (bytes + SHL_MI355X_STAGE_ALIGN - 1) / SHL_MI355X_STAGE_ALIGN * SHL_MI355X_STAGE_ALIGN;
+    }
+    return CSINN_TRUE;
+}
+
 void *shl_mi355x_stage_out_begin(struct shl_mi355x_ctx *c, struct csinn_tensor *t, int slot)
 {
     if (t->data == NULL) {
@@ -591,6 +636,8 @@ void shl_target_init_mi355x(void)
         g_table[g_table_len - 1].cb.perf = shl_mi355x_avgpool2d_perf;
         reg(dts[i], CSINN_OP_SOFTMAX, NULL, shl_mi355x_softmax_exec, shl_gref_softmax);
         reg(dts[i], CSINN_OP_ADD, NULL, shl_mi355x_add_exec, shl_gref_add);
+        reg(dts[i], CSINN_OP_CONCAT, NULL, shl_mi355x_concat_exec, shl_gref_concat);
+        g_table[g_table_len - 1].cb.perf = shl_mi355x_concat_perf;
     }
     shl_register_op_callback(CSINN_MI355X, shl_cb_map_mi355x);
     shl_register_runtime_callback(CSINN_MI355X, shl_mi355x_runtime_callback);

@@ -8,6 +8,7 @@
  *   fullyconnected .... source/nn2/fullyconnected.c:26-57
  *   relu / relu6 ...... source/nn2/relu.c, relu6.c
  *   maxpool2d / avgpool2d  source/nn2/maxpool.c, averagepool.c
+ *   concat ............ source/nn2/concat.c
  * The only deliberate difference: a missing callback is reported (CSINN_CALLBACK_UNSET and an
  * error message) instead of being dereferenced.
  */
@@ -216,4 +217,14 @@ int csinn_add(struct csinn_tensor *input0, struct csinn_tensor *input1, struct c
     if (fn == NULL) return CSINN_CALLBACK_UNSET;
     int rc = fn(input0, input1, output, params);
     return rc == CSINN_TRUE ? CSINN_TRUE : rc;
+}
+
+/* source/nn2/concat.c: an array of params->inputs_count inputs; the callbacks are looked up by the OUTPUT's dtype */
+int csinn_concat_init(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params)
+{
+    return map_and_init3(&params->base, CSINN_OP_CONCAT, output->dtype, input, output, params);
+}
+int csinn_concat(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params)
+{
+    return run3(&params->base, input, output, params);
 }

@@ -56,6 +56,10 @@ int csinn_add_init(struct csinn_tensor *input0, struct csinn_tensor *input1, str
                    struct csinn_diso_params *params);
 int csinn_add(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
               struct csinn_diso_params *params);
+/* concat along one axis (source/nn2/concat.c of the reference): `input` is an array of params->inputs_count tensors; the
+ * callbacks are looked up by the OUTPUT's dtype */
+int csinn_concat_init(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params);
+int csinn_concat(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params);
 /* MobileNet tail (source/nn2/global_avgpool2d.c, softmax.c of the reference) */
 int csinn_global_avgpool2d_init(struct csinn_tensor *input, struct csinn_tensor *output,
                                 struct csinn_pool_params *params);

@@ -117,6 +117,7 @@ enum csinn_op_enum {
     CSINN_OP_CONV2D_RELU6 = 30,
     CSINN_OP_ADD = 3,
     CSINN_OP_AVGPOOL2D = 14,
+    CSINN_OP_CONCAT = 26,
     CSINN_OP_CONV2D_CHANNEL = 31,
     CSINN_OP_CONV2D_CHANNEL_RELU = 32,
     CSINN_OP_CONV2D_CHANNEL_RELU6 = 33,
@@ -360,6 +361,13 @@ struct csinn_relu_params { /* 56 B */
 
 struct csinn_softmax_params { /* 48 B */
     struct csinn_params_base base;
+    int32_t axis;
+};
+
+/* concat: a variable number of inputs, handed over as an array of tensor pointers; axis == -1 is the last axis */
+struct csinn_concat_params { /* 48 B */
+    struct csinn_params_base base;
+    int32_t inputs_count;
     int32_t axis;
 };
 

@@ -369,6 +369,33 @@ int shl_mi355x_pool2d(const void *in_dev, void *out_dev, const struct shl_mi355x
  * invalid descriptor).  Pure host code: touches no device */
 const char *shl_mi355x_pool2d_kernel_name(const struct shl_mi355x_pool_desc *d);
 
+/* concat of n_inputs int8 / binary16 tensors along one axis: shl_ref_concat_quant (source/reference/concat.c:21-76), bit
+ * for bit.  The output is viewed as [outer][row], row = sum of len[i]; input i is [outer][len[i]] (len[i] = its axis dim
+ * times the product of the dims behind the axis, in elements) and lands at column sum of len[0..i).  Every input is
+ * dequantised with its own record and requantised with the output's (int8; an input whose record equals the output's is
+ * copied as bytes once that round trip was checked to be the identity); binary16 passes through the reference's
+ * float32 -> binary16 conversion (infinities saturate to +-65504, every NaN becomes 0x7FFF / 0xFFFF), scales and zero
+ * points are ignored.  Inputs of len 0 are skipped; the same buffer may be given more than once; the output must not
+ * overlap an input.  Up to 8 inputs travel in one launch, more in further launches.  Enqueues only: no allocation, no
+ * upload, no synchronisation (capturable in a hipGraph). */
+struct shl_mi355x_concat_desc {
+    int32_t dtype;    /* SHL_MI355X_I8 / SHL_MI355X_F16 */
+    int32_t n_inputs; /* >= 1, no upper bound */
+    int64_t outer;    /* product of the dims in front of the axis */
+    float out_scale;
+    int32_t out_zp;
+    int32_t reserved[4]; /* must be zero */
+};
+
+int shl_mi355x_concat(const void *const *in_dev, const int64_t *len, const float *in_scale, const int32_t *in_zp,
+                      void *out_dev, const struct shl_mi355x_concat_desc *d, void *stream);
+/* the kernel form the rules choose ("concat_vec": 16 bytes per thread, when every len[i] in bytes is a multiple of 16
+ * and every pointer is 16-byte aligned; "concat_generic": one element per thread; "" for invalid arguments).  Pure host
+ * code: looks at the pointers' values only, touches no device */
+const char *shl_mi355x_concat_kernel_name(const void *const *in_dev, const int64_t *len, const float *in_scale,
+                                          const int32_t *in_zp, const void *out_dev,
+                                          const struct shl_mi355x_concat_desc *d);
+
 /* softmax along one axis of a tensor viewed as [outer, count, inner]:
  * shl_ref_softmax_quant (source/reference/softmax.c:21-72): float max, double exp, float running
  * sum in index order.  count <= 8192. */

@@ -97,6 +97,9 @@ int shl_mi355x_relu6_exec(struct csinn_tensor *input, struct csinn_tensor *outpu
                           struct csinn_relu_params *params);
 int shl_mi355x_add_exec(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
                         struct csinn_diso_params *params);
+/* concat along params->axis (-1: the last axis) of params->inputs_count tensors: every non-axis dim must equal the
+ * output's and the axis dims must sum to the output's, else the call is refused; the same tensor may appear twice */
+int shl_mi355x_concat_exec(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params);
 int shl_mi355x_global_avgpool2d_exec(struct csinn_tensor *input, struct csinn_tensor *output,
                                      struct csinn_pool_params *params);
 /* windowed pooling: 4-d tensors, the output size is the output tensor's; a window without an in-image tap is refused */
