@@ -155,24 +155,26 @@ int shl_mi355x_avgpool2d_exec(struct csinn_tensor *input, struct csinn_tensor *o
 }
 
 /* perf callbacks (single-input signature): the kernel form the rules choose for this layer */
-int shl_mi355x_maxpool2d_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params,
-                              struct csinn_perf_info *info)
+static int pool2d_perf(const char *op, int kind, struct csinn_tensor *input, struct csinn_tensor *output,
+                       struct csinn_pool_params *params, struct csinn_perf_info *info)
 {
     struct shl_mi355x_pool_desc d;
-    int rc = pool2d_desc("maxpool2d", SHL_MI355X_POOL_MAX, input, output, params, &d);
+    int rc = pool2d_desc(op, kind, input, output, params, &d);
     if (rc != CSINN_TRUE) return rc;
     info->kernel_name = (char *)shl_mi355x_pool2d_kernel_name(&d);
     return CSINN_TRUE;
 }
 
+int shl_mi355x_maxpool2d_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params,
+                              struct csinn_perf_info *info)
+{
+    return pool2d_perf("maxpool2d", SHL_MI355X_POOL_MAX, input, output, params, info);
+}
+
 int shl_mi355x_avgpool2d_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params,
                               struct csinn_perf_info *info)
 {
-    struct shl_mi355x_pool_desc d;
-    int rc = pool2d_desc("avgpool2d", SHL_MI355X_POOL_AVG, input, output, params, &d);
-    if (rc != CSINN_TRUE) return rc;
-    info->kernel_name = (char *)shl_mi355x_pool2d_kernel_name(&d);
-    return CSINN_TRUE;
+    return pool2d_perf("avgpool2d", SHL_MI355X_POOL_AVG, input, output, params, info);
 }
 
 int shl_mi355x_softmax_exec(struct csinn_tensor *input, struct csinn_tensor *output,

@@ -34,16 +34,31 @@ struct dev_tensor {
     int probe_dev;
 };
 
+/* one unit the session enqueues: a layer, or two layers that run as one launch.  A relu / relu6 layer folded into the
+ * convolution in front of it is no step and no layer of a step: the convolution's step writes the activation's output */
+enum step_kind {
+    STEP_LAYER,     /* layer a, through its exec callback */
+    STEP_PWDW,      /* a pointwise and a depthwise layer, in either order (shl_mi355x_pwdw_forward) */
+    STEP_POOL_CONV, /* global_avgpool2d a + the convolution / fullyconnected layer b on the pooled map */
+    STEP_CONV_POOL, /* 1x1 convolution a + global_avgpool2d b */
+};
+
+struct step {
+    enum step_kind kind;
+    int a, b;             /* layer indices; b = -1 for STEP_LAYER */
+    struct shl_node *out; /* the tensor node the step finally writes */
+};
+
 struct dev_session {
     struct csinn_session *sess;
     struct dev_tensor *t;
-    int nt;
+    int nt, cap; /* entries of t in use / allocated */
     void *stream;
     void *prev_stream; /* the session's stream before it became device resident */
     int prev_own;      /* ... and whether that was a stream of its own (else: the process default) */
     void *graph_exec;
-    unsigned char *fused;  /* per layer: 2 = runs fused with the depthwise layer behind it (pointwise + depthwise) */
-    unsigned char *folded; /* per layer: 1 = the relu / relu6 layer behind it runs in this convolution's epilogue */
+    struct step *steps; /* what enqueue_layers runs, in order (plan_fusion); kept for the re-capture after a rebind */
+    int nsteps;
     int nfused, nfolded;
     int npool; /* global_avgpool2d layers that run inside their consumer's launch */
     struct dev_session *next;
@@ -72,8 +87,7 @@ static void free_session(struct dev_session *ds)
         shl_mi355x_stream_destroy(ds->stream);
     }
     free(ds->t);
-    free(ds->fused);
-    free(ds->folded);
+    free(ds->steps);
     free(ds);
 }
 
@@ -91,53 +105,62 @@ static void drop_session(struct csinn_session *sess)
     }
 }
 
-/* is `exec` one of the callbacks that run on the GPU and honour DMABUF tensors? */
-static int gpu_native(int (*exec)())
+/* how an exec callback is called.  The value is the number of inputs such a layer has in the graph (kernel and bias
+ * included); 0: as many as its params block says */
+enum call_shape {
+    CALL_ARRAY = 0, /* exec(inputs[], output, params) */
+    CALL_SISO = 1,  /* exec(input, output, params) */
+    CALL_DISO = 2,  /* exec(input0, input1, output, params) */
+    CALL_CONV = 3,  /* exec(input, output, kernel, bias, params) */
+};
+
+/* All a session knows about an operator it runs on the device, one row per op id.  A layer qualifies when its op has a
+ * row and its callback is the row's: the one setup.c registers, which runs on the GPU and honours DMABUF tensors.  (The
+ * per-channel op ids have no row: their sessions stay host-staged.) */
+struct session_op {
+    int type;
+    void *exec;
+    enum call_shape call;
+    int activations; /* the leading inputs that are activations; 0: all of them */
+    int first_const; /* of those, the ones from this index on may be constants instead: uploaded once, kept resident */
+};
+
+static const struct session_op g_ops[] = {
+    {CSINN_OP_CONV2D, shl_mi355x_conv2d_exec, CALL_CONV, 1, 1},
+    {CSINN_OP_CONV2D_RELU, shl_mi355x_conv2d_exec, CALL_CONV, 1, 1},
+    {CSINN_OP_CONV2D_RELU6, shl_mi355x_conv2d_exec, CALL_CONV, 1, 1},
+    {CSINN_OP_DEPTHWISE_CONV2D, shl_mi355x_conv2d_exec, CALL_CONV, 1, 1},
+    {CSINN_OP_DEPTHWISE_CONV2D_RELU, shl_mi355x_conv2d_exec, CALL_CONV, 1, 1},
+    {CSINN_OP_DEPTHWISE_CONV2D_RELU6, shl_mi355x_conv2d_exec, CALL_CONV, 1, 1},
+    {CSINN_OP_GROUP_CONV2D, shl_mi355x_group_conv2d_exec, CALL_CONV, 1, 1},
+    {CSINN_OP_GROUP_CONV2D_RELU, shl_mi355x_group_conv2d_exec, CALL_CONV, 1, 1},
+    {CSINN_OP_GROUP_CONV2D_RELU6, shl_mi355x_group_conv2d_exec, CALL_CONV, 1, 1},
+    {CSINN_OP_FULLYCONNECTED, shl_mi355x_fullyconnected_exec, CALL_CONV, 1, 1},
+    {CSINN_OP_RELU, shl_mi355x_relu_exec, CALL_SISO, 1, 1},
+    {CSINN_OP_RELU6, shl_mi355x_relu6_exec, CALL_SISO, 1, 1},
+    {CSINN_OP_GLOBAL_AVGPOOL2D, shl_mi355x_global_avgpool2d_exec, CALL_SISO, 1, 1},
+    {CSINN_OP_MAXPOOL2D, shl_mi355x_maxpool2d_exec, CALL_SISO, 1, 1},
+    {CSINN_OP_AVGPOOL2D, shl_mi355x_avgpool2d_exec, CALL_SISO, 1, 1},
+    {CSINN_OP_SOFTMAX, shl_mi355x_softmax_exec, CALL_SISO, 1, 1},
+    {CSINN_OP_ADD, shl_mi355x_add_exec, CALL_DISO, 2, 1},        /* the second operand may be a constant */
+    {CSINN_OP_CONCAT, shl_mi355x_concat_exec, CALL_ARRAY, 0, 0}, /* any input may be */
+};
+
+/* the row of layer `n`; NULL: not a layer this file runs */
+static const struct session_op *session_op(struct shl_node *n)
 {
-    return exec == (int (*)())shl_mi355x_conv2d_exec || exec == (int (*)())shl_mi355x_group_conv2d_exec || exec == (int (*)())shl_mi355x_fullyconnected_exec ||
-           exec == (int (*)())shl_mi355x_relu_exec || exec == (int (*)())shl_mi355x_relu6_exec ||
-           exec == (int (*)())shl_mi355x_global_avgpool2d_exec || exec == (int (*)())shl_mi355x_softmax_exec ||
-           exec == (int (*)())shl_mi355x_maxpool2d_exec || exec == (int (*)())shl_mi355x_avgpool2d_exec ||
-           exec == (int (*)())shl_mi355x_add_exec || exec == (int (*)())shl_mi355x_concat_exec;
+    struct csinn_params_base *params = n->data;
+    for (size_t i = 0; i < sizeof(g_ops) / sizeof(g_ops[0]); i++)
+        if (g_ops[i].type == n->type) return params->cb && (void *)params->cb->exec == g_ops[i].exec ? &g_ops[i] : NULL;
+    return NULL;
 }
 
-static int op_arity(int type)
+/* the number of inputs layer `n` must have; 0: none will do */
+static int inputs_of(const struct session_op *op, struct shl_node *n)
 {
-    switch (type) {
-        case CSINN_OP_RELU:
-        case CSINN_OP_RELU6:
-        case CSINN_OP_GLOBAL_AVGPOOL2D:
-        case CSINN_OP_MAXPOOL2D:
-        case CSINN_OP_AVGPOOL2D:
-        case CSINN_OP_SOFTMAX:
-            return 1;
-        case CSINN_OP_ADD:
-            return 2;
-        case CSINN_OP_CONV2D:
-        case CSINN_OP_CONV2D_RELU:
-        case CSINN_OP_CONV2D_RELU6:
-        case CSINN_OP_DEPTHWISE_CONV2D:
-        case CSINN_OP_DEPTHWISE_CONV2D_RELU:
-        case CSINN_OP_DEPTHWISE_CONV2D_RELU6:
-        case CSINN_OP_GROUP_CONV2D:
-        case CSINN_OP_GROUP_CONV2D_RELU:
-        case CSINN_OP_GROUP_CONV2D_RELU6:
-        case CSINN_OP_FULLYCONNECTED:
-            return 3;
-        default:
-            return 0;
-    }
-}
-
-/* the number of inputs layer `n` must have; 0: not a layer this file runs.  concat is the one variadic op: as many as its
- * params say (the exec callback takes them as an array) */
-static int layer_arity(struct shl_node *n)
-{
-    if (n->type == CSINN_OP_CONCAT) {
-        struct csinn_concat_params *p = n->data;
-        return p && p->inputs_count >= 1 ? p->inputs_count : 0;
-    }
-    return op_arity(n->type);
+    if (op->call != CALL_ARRAY) return op->call;
+    struct csinn_concat_params *p = n->data;
+    return p->inputs_count >= 1 ? p->inputs_count : 0;
 }
 
 static struct dev_tensor *lookup(struct dev_session *ds, struct shl_node *node)
@@ -151,6 +174,10 @@ static struct dev_tensor *adopt(struct dev_session *ds, struct shl_node *node)
 {
     struct dev_tensor *d = lookup(ds, node);
     if (d) return d;
+    if (ds->nt >= ds->cap) {
+        shl_debug_error("mi355x: the session's tensor table is full (%d entries)\n", ds->cap);
+        return NULL;
+    }
     d = &ds->t[ds->nt++];
     d->node = node;
     struct csinn_tensor *t = node->data;
@@ -184,160 +211,122 @@ static int consumers_of(struct shl_ref_graph *g, struct shl_node *tensor)
     return consumers;
 }
 
-/* the tensor node layer i finally writes: its own output, or the output of the activation layer folded into it */
-static struct shl_node *final_out(struct dev_session *ds, struct shl_ref_graph *g, int i)
+/* can steps `s` and `next` (adjacent, each still one layer) run as one launch, and as which?  STEP_LAYER: no */
+static enum step_kind merged_kind(struct shl_ref_graph *g, const struct step *s, const struct step *next)
 {
-    return ds->folded[i] ? g->layer[i + 1]->out[0] : g->layer[i]->out[0];
+    struct shl_node *a = g->layer[s->a], *b = g->layer[next->a], *mid = s->out;
+    if (b->in[0] != mid || consumers_of(g, mid) != 1) return STEP_LAYER;
+    /* global_avgpool2d -> the convolution / fullyconnected layer on the pooled map: one launch (csrc/conv_gemv.hip) */
+    if (a->type == CSINN_OP_GLOBAL_AVGPOOL2D && (is_conv_op(b->type) || b->type == CSINN_OP_FULLYCONNECTED)) {
+        struct csinn_tensor *pin = a->in[0]->data, *pmid = mid->data;
+        struct csinn_pool_params *pp = a->data;
+        shl_mi355x_conv_plan *pb = shl_mi355x_registry_get(b->data);
+        const int nhwc = pp->base.layout == CSINN_LAYOUT_NHWC;
+        if (pb && nhwc && pin->dim_count == 4 && pin->dtype == CSINN_DTYPE_INT8 && pin->qinfo && pmid->qinfo &&
+            pin->quant_channel <= 1 && pmid->quant_channel <= 1 &&
+            shl_mi355x_pool_conv_fusable(pb, pin->dim[0], pin->dim[1] * pin->dim[2]))
+            return STEP_POOL_CONV;
+    }
+    /* 1x1 convolution -> global_avgpool2d, the pooled tensor being all anything reads of it: one launch
+     * (csrc/conv1x1_latency.hip: the workgroup of a channel slice holds the whole map) */
+    if (is_conv_op(a->type) && b->type == CSINN_OP_GLOBAL_AVGPOOL2D) {
+        struct csinn_tensor *cin = a->in[0]->data, *pmid = mid->data, *pout = b->out[0]->data;
+        struct csinn_pool_params *pp = b->data;
+        shl_mi355x_conv_plan *pa = shl_mi355x_registry_get(a->data);
+        if (pa && pp->base.layout == CSINN_LAYOUT_NHWC && pmid->dim_count == 4 && pmid->dtype == CSINN_DTYPE_INT8 && pmid->qinfo &&
+            pout->qinfo && pmid->quant_channel <= 1 && pout->quant_channel <= 1 &&
+            shl_mi355x_conv_pool_fusable(pa, cin->dim[0]))
+            return STEP_CONV_POOL;
+    }
+    /* pointwise -> depthwise (latency form, small batches) or depthwise -> pointwise (bandwidth form, large
+     * batches: csrc/dwpw_stream.hip); shl_mi355x_pwdw_fusable tells the orders apart by the plans */
+    if ((is_conv_op(a->type) && is_dw_op(b->type)) || (is_dw_op(a->type) && is_conv_op(b->type))) {
+        shl_mi355x_conv_plan *pa = shl_mi355x_registry_get(a->data), *pb = shl_mi355x_registry_get(b->data);
+        struct csinn_tensor *in = a->in[0]->data;
+        if (pa && pb && shl_mi355x_pwdw_fusable(pa, pb, in->dim[0])) return STEP_PWDW;
+    }
+    return STEP_LAYER;
 }
 
 /* Graph-level rewrites; the intermediate tensors then never exist in HBM:
  *   conv / depthwise (no activation) -> relu | relu6, the convolution's only consumer, same output record
- *        the activation moves into the convolution's epilogue (folded[i] = 1, the relu layer is skipped): what a
- *        converter emits for a RISC-V target -- example/c906_mobilenetv1_f16.c is 28 csinn_conv2d + 27 csinn_relu --
- *        runs as 28 launches, not 55
- *   1x1 convolution -> depthwise 3x3   one launch of csrc/pwdw_fused.hip (int8 NHWC) / pwdw_f16_nchw.hip (fused[i] = 2)
+ *        the activation moves into the convolution's epilogue (the relu layer gets no step, the convolution's step writes
+ *        the relu's output): what a converter emits for a RISC-V target -- example/c906_mobilenetv1_f16.c is
+ *        28 csinn_conv2d + 27 csinn_relu -- runs as 28 launches, not 55
+ *   1x1 convolution -> depthwise 3x3   one launch of csrc/pwdw_fused.hip (int8 NHWC) / pwdw_f16_nchw.hip (STEP_PWDW)
  *   depthwise 3x3 -> 1x1 convolution   one launch of csrc/dwpw_stream.hip at throughput batches (32 / 64 / 128 / 256 channels:
  *        the requantised depthwise tile is the pointwise MFMA operand); the latency form of this pairing recomputed the
- *        depthwise tile in every channel slice and is parked (attic/README.md) */
-static void plan_fusion(struct dev_session *ds, struct shl_ref_graph *g)
+ *        depthwise tile in every channel slice and is parked (attic/README.md)
+ * Fills ds->steps. */
+static int plan_fusion(struct dev_session *ds, struct shl_ref_graph *g)
 {
-    ds->fused = calloc((size_t)g->layer_index + 1, 1);
-    ds->folded = calloc((size_t)g->layer_index + 1, 1);
-    static const char *off = NULL;
-    off = getenv("SHL_MI355X_NO_FUSION");
-    for (int i = 0; !(off && off[0] == '1') && i + 1 < g->layer_index; i++) {
-        struct shl_node *a = g->layer[i], *b = g->layer[i + 1];
+    struct step *steps = ds->steps = calloc((size_t)g->layer_index, sizeof(*steps));
+    if (steps == NULL) return 0;
+    const char *off = getenv("SHL_MI355X_NO_FUSION");
+    const int fold = !(off && off[0] == '1');
+    int ns = 0;
+    /* one step per layer; an activation that folds joins the convolution's step */
+    for (int i = 0; i < g->layer_index; i++) {
+        struct shl_node *a = g->layer[i], *b = i + 1 < g->layer_index ? g->layer[i + 1] : NULL;
+        struct step *s = &steps[ns++];
+        *s = (struct step){STEP_LAYER, i, -1, a->out[0]};
         const int plain = a->type == CSINN_OP_CONV2D || a->type == CSINN_OP_DEPTHWISE_CONV2D;
-        if (!plain || (b->type != CSINN_OP_RELU && b->type != CSINN_OP_RELU6)) continue;
+        if (!fold || !plain || b == NULL || (b->type != CSINN_OP_RELU && b->type != CSINN_OP_RELU6)) continue;
         if (b->in[0] != a->out[0] || consumers_of(g, a->out[0]) != 1) continue;
         if (shl_mi355x_conv2d_fold_activation(a->in[0]->data, a->out[0]->data, b->out[0]->data, a->in[1]->data,
                                               a->in[2]->data, a->data, b->type == CSINN_OP_RELU6) == CSINN_TRUE) {
-            ds->folded[i] = 1;
+            s->out = b->out[0];
             ds->nfolded++;
             i++; /* the activation layer is taken */
         }
     }
     /* a depthwise layer whose output does not feed ONE pointwise layer that the bandwidth form takes keeps its latency pair
      * (the plan pair test below cannot see a layer's consumer: ADVICE r05 -- dw 32 -> pw 16 of MobileNetV2, two consumers, ...) */
-    for (int i = 0; i < g->layer_index; i++) {
-        struct shl_node *a = g->layer[i];
+    for (int k = 0; k < ns; k++) {
+        struct shl_node *a = g->layer[steps[k].a], *b = k + 1 < ns ? g->layer[steps[k + 1].a] : NULL;
         if (!is_dw_op(a->type)) continue;
         shl_mi355x_conv_plan *pa = shl_mi355x_registry_get(a->data);
         if (pa == NULL) continue;
-        const int j = i + 1 + ds->folded[i];
-        struct shl_node *mid = final_out(ds, g, i);
         struct csinn_tensor *in = a->in[0]->data;
         int streams = 0;
-        if (j < g->layer_index && g->layer[j]->in[0] == mid && is_conv_op(g->layer[j]->type) && consumers_of(g, mid) == 1) {
-            shl_mi355x_conv_plan *pb = shl_mi355x_registry_get(g->layer[j]->data);
+        if (b && b->in[0] == steps[k].out && is_conv_op(b->type) && consumers_of(g, steps[k].out) == 1) {
+            shl_mi355x_conv_plan *pb = shl_mi355x_registry_get(b->data);
             streams = pb != NULL && shl_mi355x_pwdw_fusable(pa, pb, in->dim[0]);
         }
         shl_mi355x_conv_plan_set_no_stream_consumer(pa, !streams);
     }
-    for (int i = 0; i + 1 < g->layer_index; i++) {
-        const int j = i + 1 + ds->folded[i]; /* the next layer that still runs */
-        if (j >= g->layer_index) break;
-        struct shl_node *a = g->layer[i], *b = g->layer[j];
-        struct shl_node *mid = final_out(ds, g, i);
-        if (b->in[0] != mid) {
-            i = j - 1;
-            continue;
+    /* merge adjacent steps greedily from the front; a merged step is not the first half of another merge */
+    for (int k = 0; k < ns; k++) {
+        struct step s = steps[k];
+        const enum step_kind kind = k + 1 < ns ? merged_kind(g, &s, &steps[k + 1]) : STEP_LAYER;
+        if (kind != STEP_LAYER) {
+            k++; /* the second step is taken */
+            s = (struct step){kind, s.a, steps[k].a, steps[k].out};
+            if (kind == STEP_PWDW) ds->nfused++;
+            else ds->npool++;
         }
-        /* global_avgpool2d -> the convolution / fullyconnected layer on the pooled map: one launch (csrc/conv_gemv.hip) */
-        if (a->type == CSINN_OP_GLOBAL_AVGPOOL2D && (is_conv_op(b->type) || b->type == CSINN_OP_FULLYCONNECTED) &&
-            consumers_of(g, mid) == 1) {
-            struct csinn_tensor *pin = a->in[0]->data, *pmid = mid->data;
-            struct csinn_pool_params *pp = a->data;
-            shl_mi355x_conv_plan *pb = shl_mi355x_registry_get(b->data);
-            const int nhwc = pp->base.layout == CSINN_LAYOUT_NHWC;
-            if (pb && nhwc && pin->dim_count == 4 && pin->dtype == CSINN_DTYPE_INT8 && pin->qinfo && pmid->qinfo &&
-                pin->quant_channel <= 1 && pmid->quant_channel <= 1 &&
-                shl_mi355x_pool_conv_fusable(pb, pin->dim[0], pin->dim[1] * pin->dim[2])) {
-                ds->fused[i] = 3;
-                ds->npool++;
-                i = j + ds->folded[j];
-                continue;
-            }
-        }
-        /* 1x1 convolution -> global_avgpool2d, the pooled tensor being all anything reads of it: one launch
-         * (csrc/conv1x1_latency.hip: the workgroup of a channel slice holds the whole map) */
-        if (is_conv_op(a->type) && b->type == CSINN_OP_GLOBAL_AVGPOOL2D && consumers_of(g, mid) == 1) {
-            struct csinn_tensor *cin = a->in[0]->data, *pmid = mid->data, *pout = b->out[0]->data;
-            struct csinn_pool_params *pp = b->data;
-            shl_mi355x_conv_plan *pa = shl_mi355x_registry_get(a->data);
-            if (pa && pp->base.layout == CSINN_LAYOUT_NHWC && pmid->dim_count == 4 && pmid->dtype == CSINN_DTYPE_INT8 && pmid->qinfo &&
-                pout->qinfo && pmid->quant_channel <= 1 && pout->quant_channel <= 1 &&
-                shl_mi355x_conv_pool_fusable(pa, cin->dim[0])) {
-                ds->fused[i] = 4;
-                ds->npool++;
-                i = j;
-                continue;
-            }
-        }
-        /* pointwise -> depthwise (latency form, small batches) or depthwise -> pointwise (bandwidth form, large
-         * batches: csrc/dwpw_stream.hip); shl_mi355x_pwdw_fusable tells the orders apart by the plans */
-        const int pw_dw = (is_conv_op(a->type) && is_dw_op(b->type)) || (is_dw_op(a->type) && is_conv_op(b->type));
-        if (!pw_dw || consumers_of(g, mid) != 1) {
-            i = j - 1;
-            continue;
-        }
-        shl_mi355x_conv_plan *pa = shl_mi355x_registry_get(a->data), *pb = shl_mi355x_registry_get(b->data);
-        struct csinn_tensor *in = a->in[0]->data;
-        if (pa && pb && shl_mi355x_pwdw_fusable(pa, pb, in->dim[0])) {
-            ds->fused[i] = 2;
-            ds->nfused++;
-            i = j + ds->folded[j]; /* the depthwise layer (and its activation) is taken */
-        } else {
-            i = j - 1;
-        }
+        steps[ds->nsteps++] = s;
     }
+    return 1;
 }
 
-/* enqueue every layer on the session stream, tensors resident in HBM */
-static int enqueue_layers(struct dev_session *ds, struct shl_ref_graph *g)
+/* layer `n` through its exec callback, writing `out` */
+static int run_layer(struct dev_session *ds, struct shl_node *n, struct dev_tensor *out)
 {
-    for (int i = 0; i < g->layer_index; i++) {
-        struct shl_node *n = g->layer[i];
-        struct csinn_params_base *params = n->data;
-        const int first = i;
-        const int folded = ds->folded && ds->folded[i];
-        struct dev_tensor *in = lookup(ds, n->in[0]);
-        struct dev_tensor *out = lookup(ds, folded ? g->layer[i + 1]->out[0] : n->out[0]);
-        int (*f)() = params->cb->exec;
-        int rc;
-        if (ds->fused && ds->fused[i] == 3) { /* global_avgpool2d + the layer on the pooled map */
-            const int j = i + 1;
-            struct shl_node *nx = g->layer[j];
-            const int folded2 = ds->folded && ds->folded[j];
-            struct dev_tensor *out2 = lookup(ds, folded2 ? g->layer[j + 1]->out[0] : nx->out[0]);
-            struct csinn_tensor *pin = n->in[0]->data, *pmid = n->out[0]->data;
-            int st = shl_mi355x_pool_conv_forward(shl_mi355x_registry_get(nx->data), in->dev, out2->dev, in->shadow.dim[0],
-                                                  pin->dim[1] * pin->dim[2], pin->qinfo->scale, pin->qinfo->zero_point,
-                                                  pmid->qinfo->scale, pmid->qinfo->zero_point, ds->stream);
-            rc = st == SHL_MI355X_OK ? CSINN_TRUE : CSINN_FALSE;
-            i = j + folded2;
-        } else if (ds->fused && ds->fused[i] == 4) { /* 1x1 convolution (+ folded activation) + global_avgpool2d */
-            const int j = i + 1 + folded;
-            struct shl_node *nx = g->layer[j];
-            struct dev_tensor *out2 = lookup(ds, nx->out[0]);
-            struct csinn_tensor *pmid = nx->in[0]->data, *pout = nx->out[0]->data;
-            int st = shl_mi355x_conv_pool_forward(shl_mi355x_registry_get(n->data), in->dev, NULL, out2->dev, in->shadow.dim[0],
-                                                  pmid->qinfo->scale, pmid->qinfo->zero_point, pout->qinfo->scale,
-                                                  pout->qinfo->zero_point, ds->stream);
-            rc = st == SHL_MI355X_OK ? CSINN_TRUE : CSINN_FALSE;
-            i = j;
-        } else if (ds->fused && ds->fused[i]) {
-            const int j = i + 1 + folded;
-            struct shl_node *nx = g->layer[j];
-            const int folded2 = ds->folded && ds->folded[j];
-            struct dev_tensor *out2 = lookup(ds, folded2 ? g->layer[j + 1]->out[0] : nx->out[0]);
-            int st = shl_mi355x_pwdw_forward(shl_mi355x_registry_get(n->data), shl_mi355x_registry_get(nx->data), in->dev, out2->dev,
-                         in->shadow.dim[0], ds->stream);
-            rc = st == SHL_MI355X_OK ? CSINN_TRUE : CSINN_FALSE;
-            i = j + folded2;
-        } else if (n->type == CSINN_OP_CONCAT) { /* variadic: an array of shadow tensors */
+    struct csinn_params_base *params = n->data;
+    int (*f)() = params->cb->exec;
+    struct dev_tensor *in = lookup(ds, n->in[0]), *in1;
+    switch (session_op(n)->call) {
+        case CALL_SISO:
+            return f(&in->shadow, &out->shadow, params);
+        case CALL_DISO: /* add: the second operand is an activation or a resident constant */
+            in1 = lookup(ds, n->in[1]);
+            return in1 ? f(&in->shadow, &in1->shadow, &out->shadow, params) : CSINN_FALSE;
+        case CALL_CONV:
+            return f(&in->shadow, &out->shadow, n->in[1]->data, n->in[2]->data, params);
+        default: { /* CALL_ARRAY: an array of shadow tensors */
             struct csinn_tensor **ins = calloc((size_t)n->in_num, sizeof(*ins));
-            rc = ins ? CSINN_TRUE : CSINN_FALSE;
+            int rc = ins ? CSINN_TRUE : CSINN_FALSE;
             for (int j = 0; rc == CSINN_TRUE && j < n->in_num; j++) {
                 struct dev_tensor *dj = lookup(ds, n->in[j]);
                 if (dj) ins[j] = &dj->shadow;
@@ -345,18 +334,46 @@ static int enqueue_layers(struct dev_session *ds, struct shl_ref_graph *g)
             }
             if (rc == CSINN_TRUE) rc = f(ins, &out->shadow, params);
             free(ins);
-        } else if (op_arity(n->type) == 1) {
-            rc = f(&in->shadow, &out->shadow, params);
-        } else if (op_arity(n->type) == 2) { /* add: the second operand is an activation or a constant */
-            struct dev_tensor *in1 = lookup(ds, n->in[1]);
-            rc = f(&in->shadow, in1 ? (void *)&in1->shadow : n->in[1]->data, &out->shadow, params);
-        } else {
-            rc = f(&in->shadow, &out->shadow, n->in[1]->data, n->in[2]->data, params);
-            i += folded; /* the activation layer ran inside the convolution */
+            return rc;
+        }
+    }
+}
+
+static int status_of(int st) { return st == SHL_MI355X_OK ? CSINN_TRUE : CSINN_FALSE; }
+
+/* enqueue every step on the session stream, tensors resident in HBM */
+static int enqueue_layers(struct dev_session *ds, struct shl_ref_graph *g)
+{
+    for (int k = 0; k < ds->nsteps; k++) {
+        const struct step *s = &ds->steps[k];
+        struct shl_node *n = g->layer[s->a], *nx = s->b >= 0 ? g->layer[s->b] : NULL;
+        struct dev_tensor *in = lookup(ds, n->in[0]), *out = lookup(ds, s->out);
+        const int batch = in->shadow.dim[0];
+        int rc;
+        switch (s->kind) {
+            case STEP_POOL_CONV: {
+                struct csinn_tensor *pin = n->in[0]->data, *pmid = n->out[0]->data;
+                rc = status_of(shl_mi355x_pool_conv_forward(shl_mi355x_registry_get(nx->data), in->dev, out->dev, batch,
+                                                            pin->dim[1] * pin->dim[2], pin->qinfo->scale, pin->qinfo->zero_point,
+                                                            pmid->qinfo->scale, pmid->qinfo->zero_point, ds->stream));
+                break;
+            }
+            case STEP_CONV_POOL: { /* the pool reads what the convolution (+ folded activation) would have written */
+                struct csinn_tensor *pmid = nx->in[0]->data, *pout = nx->out[0]->data;
+                rc = status_of(shl_mi355x_conv_pool_forward(shl_mi355x_registry_get(n->data), in->dev, NULL, out->dev, batch,
+                                                            pmid->qinfo->scale, pmid->qinfo->zero_point, pout->qinfo->scale,
+                                                            pout->qinfo->zero_point, ds->stream));
+                break;
+            }
+            case STEP_PWDW:
+                rc = status_of(shl_mi355x_pwdw_forward(shl_mi355x_registry_get(n->data), shl_mi355x_registry_get(nx->data), in->dev,
+                                                       out->dev, batch, ds->stream));
+                break;
+            default:
+                rc = run_layer(ds, n, out);
         }
         if (rc != CSINN_TRUE) {
-            shl_debug_error("mi355x: layer %d (%s) failed while building the device graph\n", first,
-                            n->name ? n->name : "?");
+            shl_debug_error("mi355x: layer %d (%s) failed while building the device graph\n", s->a, n->name ? n->name : "?");
             return CSINN_FALSE;
         }
     }
@@ -433,19 +450,19 @@ int shl_mi355x_session_setup(struct csinn_session *sess)
     int tensors = g->input_num;
     for (int i = 0; i < g->layer_index; i++) {
         struct shl_node *n = g->layer[i];
-        struct csinn_params_base *params = n->data;
-        const int arity = layer_arity(n);
-        if (arity == 0 || n->in_num != arity || n->out_num != 1 || params->cb == NULL ||
-            !gpu_native(params->cb->exec)) {
+        const struct session_op *op = session_op(n);
+        const int inputs = op ? inputs_of(op, n) : 0;
+        if (inputs == 0 || n->in_num != inputs || n->out_num != 1) {
             shl_debug_info("mi355x: layer %d (%s, op %d) runs on the host path: session stays host-staged\n", i,
                            n->name ? n->name : "?", n->type);
             return rc;
         }
-        tensors += 1 + (n->type == CSINN_OP_CONCAT ? n->in_num : 1); /* its output + constants it may bring */
+        tensors += 1 + (op->activations ? op->activations : inputs) - op->first_const; /* its output + constants it may bring */
     }
     struct dev_session *ds = calloc(1, sizeof(*ds));
     ds->sess = sess;
-    ds->t = calloc((size_t)tensors + 1, sizeof(struct dev_tensor));
+    ds->t = calloc((size_t)tensors, sizeof(struct dev_tensor));
+    ds->cap = ds->t ? tensors : 0;
     ds->stream = shl_mi355x_stream_create();
     int ok = ds->stream != NULL;
     ds->prev_own = shl_mi355x_session_has_own_stream(sess);
@@ -454,14 +471,13 @@ int shl_mi355x_session_setup(struct csinn_session *sess)
     for (int i = 0; ok && i < g->input_num; i++) ok = adopt(ds, g->input[i]) != NULL;
     for (int i = 0; ok && i < g->layer_index; i++) {
         struct shl_node *n = g->layer[i];
-        /* concat: any input may be a constant; add: the second operand; everything else is produced earlier */
-        const int first_const = n->type == CSINN_OP_CONCAT ? 0 : 1;
-        const int activations = n->type == CSINN_OP_CONCAT ? n->in_num : op_arity(n->type) == 2 ? 2 : 1;
+        const struct session_op *op = session_op(n);
+        const int activations = op->activations ? op->activations : n->in_num;
         for (int j = 0; ok && j < activations; j++) {
             if (lookup(ds, n->in[j]) != NULL) continue;
             /* a constant operand: upload it once, keep it resident */
             struct csinn_tensor *c = n->in[j]->data;
-            struct dev_tensor *d = j >= first_const && c->is_const && c->data ? adopt(ds, n->in[j]) : NULL;
+            struct dev_tensor *d = j >= op->first_const && c->is_const && c->data ? adopt(ds, n->in[j]) : NULL;
             if (d == NULL || shl_mi355x_upload(d->dev, c->data, d->bytes, ds->stream) != SHL_MI355X_OK) {
                 if (j == 0) shl_debug_error("mi355x: layer %d consumes a tensor that no earlier layer produces\n", i);
                 else shl_debug_error("mi355x: layer %d: operand %d is neither produced earlier nor constant\n", i, j);
@@ -472,7 +488,7 @@ int shl_mi355x_session_setup(struct csinn_session *sess)
         ok = adopt(ds, n->out[0]) != NULL;
     }
     for (int i = 0; ok && i < g->output_num; i++) ok = lookup(ds, g->output[i]) != NULL;
-    if (ok) plan_fusion(ds, g);
+    if (ok) ok = plan_fusion(ds, g);
     if (ok) ok = capture(ds, g) == CSINN_TRUE; /* the whole model as one hipGraph */
     if (!ok) {
         shl_debug_error("mi355x: device-resident session setup failed (%s); keeping the host path\n",
@@ -567,13 +583,14 @@ void shl_mi355x_session_deinit(struct csinn_session *sess)
     if (gref_deinit) gref_deinit(sess);
 }
 
-/* number of depthwise + pointwise pairs that run as one launch in `sess` */
+/* number of global_avgpool2d layers of `sess` that run inside the launch of the layer in front of or behind them */
 int shl_mi355x_session_fused_pools(struct csinn_session *sess)
 {
     struct dev_session *ds = find_session(sess);
     return ds ? ds->npool : 0;
 }
 
+/* number of depthwise + pointwise pairs that run as one launch in `sess` */
 int shl_mi355x_session_fused_pairs(struct csinn_session *sess)
 {
     struct dev_session *ds = find_session(sess);
@@ -587,7 +604,8 @@ int shl_mi355x_session_folded_activations(struct csinn_session *sess)
     return ds ? ds->nfolded : 0;
 }
 
-/* 1 when `sess` executes as one device-resident hipGraph, 0 when host-staged */
+/* 2 when `sess` executes as one device-resident hipGraph, 1 when device-resident with every run enqueueing its layers
+ * anew (no graph could be captured), 0 when host-staged */
 int shl_mi355x_session_is_device_resident(struct csinn_session *sess)
 {
     struct dev_session *ds = find_session(sess);

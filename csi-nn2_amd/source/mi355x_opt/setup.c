@@ -30,7 +30,7 @@ static int conv_perf(struct csinn_tensor *input, struct csinn_tensor *output,
     return CSINN_TRUE;
 }
 
-static void reg(int dtype, int op, void *init, void *exec, void *est)
+static void reg(int dtype, int op, void *init, void *exec, void *est, void *perf)
 {
     if (g_table_len >= MI355X_CB_MAX) {
         shl_debug_error("mi355x: callback table full\n");
@@ -41,7 +41,7 @@ static void reg(int dtype, int op, void *init, void *exec, void *est)
     g_table[g_table_len].cb.exec = exec;
     g_table[g_table_len].cb.est = est;
     g_table[g_table_len].cb.caps = conv_caps;
-    g_table[g_table_len].cb.perf = conv_perf;
+    g_table[g_table_len].cb.perf = perf;
     g_table_len++;
 }
 
@@ -587,57 +587,54 @@ void shl_target_init_mi355x(void)
     const int dts[2] = {CSINN_DTYPE_INT8, CSINN_DTYPE_FLOAT16};
     for (int i = 0; i < 2; i++) {
         const int dt = dts[i];
-        reg(dt, CSINN_OP_CONV2D, shl_mi355x_conv2d_init, shl_mi355x_conv2d_exec, shl_gref_conv2d);
+        reg(dt, CSINN_OP_CONV2D, shl_mi355x_conv2d_init, shl_mi355x_conv2d_exec, shl_gref_conv2d, conv_perf);
         reg(dt, CSINN_OP_CONV2D_RELU, shl_mi355x_conv2d_relu_init, shl_mi355x_conv2d_exec,
-            shl_gref_conv2d_relu);
+            shl_gref_conv2d_relu, conv_perf);
         reg(dt, CSINN_OP_CONV2D_RELU6, shl_mi355x_conv2d_relu6_init, shl_mi355x_conv2d_exec,
-            shl_gref_conv2d_relu6);
+            shl_gref_conv2d_relu6, conv_perf);
         reg(dt, CSINN_OP_DEPTHWISE_CONV2D, shl_mi355x_conv2d_init, shl_mi355x_conv2d_exec,
-            shl_gref_depthwise_conv2d);
+            shl_gref_depthwise_conv2d, conv_perf);
         reg(dt, CSINN_OP_DEPTHWISE_CONV2D_RELU, shl_mi355x_conv2d_relu_init, shl_mi355x_conv2d_exec,
-            shl_gref_depthwise_conv2d_relu);
+            shl_gref_depthwise_conv2d_relu, conv_perf);
         reg(dt, CSINN_OP_DEPTHWISE_CONV2D_RELU6, shl_mi355x_conv2d_relu6_init,
-            shl_mi355x_conv2d_exec, shl_gref_depthwise_conv2d_relu6);
-        reg(dt, CSINN_OP_GROUP_CONV2D, shl_mi355x_conv2d_init, shl_mi355x_group_conv2d_exec, shl_gref_group_conv2d);
+            shl_mi355x_conv2d_exec, shl_gref_depthwise_conv2d_relu6, conv_perf);
+        reg(dt, CSINN_OP_GROUP_CONV2D, shl_mi355x_conv2d_init, shl_mi355x_group_conv2d_exec, shl_gref_group_conv2d, conv_perf);
         reg(dt, CSINN_OP_GROUP_CONV2D_RELU, shl_mi355x_conv2d_relu_init, shl_mi355x_group_conv2d_exec,
-            shl_gref_group_conv2d_relu);
+            shl_gref_group_conv2d_relu, conv_perf);
         /* the reference's gref has no est for this op id (no shl_gref_group_conv2d_relu6 symbol) */
         if (shl_gref_group_conv2d_relu6)
             reg(dt, CSINN_OP_GROUP_CONV2D_RELU6, shl_mi355x_conv2d_relu6_init, shl_mi355x_group_conv2d_exec,
-                shl_gref_group_conv2d_relu6);
+                shl_gref_group_conv2d_relu6, conv_perf);
         reg(dt, CSINN_OP_FULLYCONNECTED, shl_mi355x_fullyconnected_init,
-            shl_mi355x_fullyconnected_exec, shl_gref_fullyconnected);
+            shl_mi355x_fullyconnected_exec, shl_gref_fullyconnected, conv_perf);
     }
     /* the per-channel op ids exist for int8 only (reference/setup.c:786-808 registers them for every dtype,
      * convolution_channel.c implements u8 / i8) */
     reg(CSINN_DTYPE_INT8, CSINN_OP_CONV2D_CHANNEL, shl_mi355x_conv2d_channel_init, shl_mi355x_conv2d_channel_exec,
-        shl_gref_conv2d);
+        shl_gref_conv2d, conv_perf);
     reg(CSINN_DTYPE_INT8, CSINN_OP_CONV2D_CHANNEL_RELU, shl_mi355x_conv2d_channel_relu_init,
-        shl_mi355x_conv2d_channel_relu_exec, shl_gref_conv2d_relu);
+        shl_mi355x_conv2d_channel_relu_exec, shl_gref_conv2d_relu, conv_perf);
     reg(CSINN_DTYPE_INT8, CSINN_OP_CONV2D_CHANNEL_RELU6, shl_mi355x_conv2d_channel_relu6_init,
-        shl_mi355x_conv2d_channel_relu6_exec, shl_gref_conv2d_relu6);
+        shl_mi355x_conv2d_channel_relu6_exec, shl_gref_conv2d_relu6, conv_perf);
     reg(CSINN_DTYPE_INT8, CSINN_OP_GROUP_CONV2D_CHANNEL, shl_mi355x_group_conv2d_channel_init,
-        shl_mi355x_group_conv2d_channel_exec, shl_gref_group_conv2d);
+        shl_mi355x_group_conv2d_channel_exec, shl_gref_group_conv2d, conv_perf);
     reg(CSINN_DTYPE_INT8, CSINN_OP_GROUP_CONV2D_CHANNEL_RELU, shl_mi355x_group_conv2d_channel_relu_init,
-        shl_mi355x_group_conv2d_channel_relu_exec, shl_gref_group_conv2d_relu);
+        shl_mi355x_group_conv2d_channel_relu_exec, shl_gref_group_conv2d_relu, conv_perf);
     reg(CSINN_DTYPE_INT8, CSINN_OP_DEPTHWISE_CONV2D_CHANNEL, shl_mi355x_depthwise_conv2d_channel_init,
-        shl_mi355x_depthwise_conv2d_channel_exec, shl_gref_depthwise_conv2d);
+        shl_mi355x_depthwise_conv2d_channel_exec, shl_gref_depthwise_conv2d, conv_perf);
     reg(CSINN_DTYPE_INT8, CSINN_OP_DEPTHWISE_CONV2D_CHANNEL_RELU, shl_mi355x_depthwise_conv2d_channel_relu_init,
-        shl_mi355x_depthwise_conv2d_channel_relu_exec, shl_gref_depthwise_conv2d_relu);
+        shl_mi355x_depthwise_conv2d_channel_relu_exec, shl_gref_depthwise_conv2d_relu, conv_perf);
     reg(CSINN_DTYPE_INT8, CSINN_OP_DEPTHWISE_CONV2D_CHANNEL_RELU6, shl_mi355x_depthwise_conv2d_channel_relu6_init,
-        shl_mi355x_depthwise_conv2d_channel_relu6_exec, shl_gref_depthwise_conv2d_relu6);
+        shl_mi355x_depthwise_conv2d_channel_relu6_exec, shl_gref_depthwise_conv2d_relu6, conv_perf);
     for (int i = 0; i < 2; i++) {
-        reg(dts[i], CSINN_OP_RELU, NULL, shl_mi355x_relu_exec, shl_gref_relu);
-        reg(dts[i], CSINN_OP_RELU6, NULL, shl_mi355x_relu6_exec, shl_gref_relu6);
-        reg(dts[i], CSINN_OP_GLOBAL_AVGPOOL2D, NULL, shl_mi355x_global_avgpool2d_exec, shl_gref_global_avgpool2d);
-        reg(dts[i], CSINN_OP_MAXPOOL2D, NULL, shl_mi355x_maxpool2d_exec, shl_gref_maxpool2d);
-        g_table[g_table_len - 1].cb.perf = shl_mi355x_maxpool2d_perf;
-        reg(dts[i], CSINN_OP_AVGPOOL2D, NULL, shl_mi355x_avgpool2d_exec, shl_gref_avgpool2d);
-        g_table[g_table_len - 1].cb.perf = shl_mi355x_avgpool2d_perf;
-        reg(dts[i], CSINN_OP_SOFTMAX, NULL, shl_mi355x_softmax_exec, shl_gref_softmax);
-        reg(dts[i], CSINN_OP_ADD, NULL, shl_mi355x_add_exec, shl_gref_add);
-        reg(dts[i], CSINN_OP_CONCAT, NULL, shl_mi355x_concat_exec, shl_gref_concat);
-        g_table[g_table_len - 1].cb.perf = shl_mi355x_concat_perf;
+        reg(dts[i], CSINN_OP_RELU, NULL, shl_mi355x_relu_exec, shl_gref_relu, conv_perf);
+        reg(dts[i], CSINN_OP_RELU6, NULL, shl_mi355x_relu6_exec, shl_gref_relu6, conv_perf);
+        reg(dts[i], CSINN_OP_GLOBAL_AVGPOOL2D, NULL, shl_mi355x_global_avgpool2d_exec, shl_gref_global_avgpool2d, conv_perf);
+        reg(dts[i], CSINN_OP_MAXPOOL2D, NULL, shl_mi355x_maxpool2d_exec, shl_gref_maxpool2d, shl_mi355x_maxpool2d_perf);
+        reg(dts[i], CSINN_OP_AVGPOOL2D, NULL, shl_mi355x_avgpool2d_exec, shl_gref_avgpool2d, shl_mi355x_avgpool2d_perf);
+        reg(dts[i], CSINN_OP_SOFTMAX, NULL, shl_mi355x_softmax_exec, shl_gref_softmax, conv_perf);
+        reg(dts[i], CSINN_OP_ADD, NULL, shl_mi355x_add_exec, shl_gref_add, conv_perf);
+        reg(dts[i], CSINN_OP_CONCAT, NULL, shl_mi355x_concat_exec, shl_gref_concat, shl_mi355x_concat_perf);
     }
     shl_register_op_callback(CSINN_MI355X, shl_cb_map_mi355x);
     shl_register_runtime_callback(CSINN_MI355X, shl_mi355x_runtime_callback);
