@@ -31,10 +31,12 @@ OP_CONV2D, OP_CONV2D_RELU, OP_CONV2D_RELU6 = 28, 29, 30
 OP_DEPTHWISE_CONV2D, OP_FULLYCONNECTED = 35, 71
 OP_AVGPOOL2D, OP_MAXPOOL2D = 14, 98
 OP_CONCAT = 26
+OP_SIGMOID, OP_HARD_SIGMOID, OP_SILU, OP_LEAKY_RELU, OP_MUL = 154, 78, 190, 84, 107
 
 SHL_NHWC, SHL_NCHW = 0, 1
 SHL_I8, SHL_F16 = 0, 1
 POOL_MAX, POOL_AVG = 0, 1
+UNARY_SIGMOID, UNARY_HARD_SIGMOID, UNARY_SILU, UNARY_LEAKY_RELU = 0, 1, 2, 3
 ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2
 ALGO_AUTO, ALGO_DIRECT, ALGO_IGEMM, ALGO_DW, ALGO_GEMV, ALGO_STEM = 0, 1, 2, 3, 4, 5
 
@@ -115,6 +117,10 @@ class DisoParams(C.Structure):
     _fields_ = [("base", ParamsBase)]
 
 
+class SigmoidParams(C.Structure):
+    _fields_ = [("base", ParamsBase)]
+
+
 class SoftmaxParams(C.Structure):
     _fields_ = [("base", ParamsBase), ("axis", C.c_int32)]
 
@@ -151,6 +157,14 @@ class ConcatDesc(C.Structure):
     """struct shl_mi355x_concat_desc (include/shl_mi355x.h)"""
     _fields_ = [("dtype", C.c_int32), ("n_inputs", C.c_int32), ("outer", C.c_int64), ("out_scale", C.c_float),
                 ("out_zp", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class MulDesc(C.Structure):
+    """struct shl_mi355x_mul_desc (include/shl_mi355x.h)"""
+    _fields_ = [("dtype", C.c_int32), ("ngroups", C.c_int32), ("dim", C.c_int64 * 4), ("b_stride", C.c_int64 * 4),
+                ("a_scale", C.c_float), ("b_scale", C.c_float), ("out_scale", C.c_float),
+                ("a_zp", C.c_int32), ("b_zp", C.c_int32), ("out_zp", C.c_int32), ("a_is_second", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
 
 
 ABI_STRUCTS = {"csinn_quant_info": QuantInfo, "csinn_tensor": Tensor, "csinn_session": Session,
@@ -249,6 +263,11 @@ def load_hip():
                                         C.POINTER(ConcatDesc), vp]),
         "shl_mi355x_concat_kernel_name": (C.c_char_p, [C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(f32), C.POINTER(i32),
                                                        vp, C.POINTER(ConcatDesc)]),
+        "shl_mi355x_unary_lut_i8": (C.c_int, [vp, vp, sz, vp, vp]),
+        "shl_mi355x_unary_lut_i8_kernel_name": (C.c_char_p, [vp, vp]),
+        "shl_mi355x_unary_f16": (C.c_int, [vp, vp, sz, i32, f32, vp]),
+        "shl_mi355x_mul": (C.c_int, [vp, vp, vp, C.POINTER(MulDesc), vp]),
+        "shl_mi355x_mul_kernel_name": (C.c_char_p, [C.POINTER(MulDesc), vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -285,7 +304,8 @@ _FRONTEND_SIGS = {
     "shl_mem_free": (None, [C.c_void_p]),
     "shl_debug_set_level": (None, [C.c_int]),
 }
-_SISO_OPS = ("csinn_relu", "csinn_relu6", "csinn_global_avgpool2d", "csinn_softmax", "csinn_maxpool2d", "csinn_avgpool2d")
+_SISO_OPS = ("csinn_relu", "csinn_relu6", "csinn_global_avgpool2d", "csinn_softmax", "csinn_maxpool2d", "csinn_avgpool2d",
+             "csinn_sigmoid", "csinn_hard_sigmoid", "csinn_silu", "csinn_leaky_relu")
 _CONV_OPS = ["csinn_conv2d", "csinn_conv2d_relu", "csinn_conv2d_relu6", "csinn_depthwise_conv2d",
              "csinn_depthwise_conv2d_relu", "csinn_fullyconnected"] + list(_SISO_OPS)
 
@@ -317,8 +337,9 @@ def load_frontend(kind="standalone", local=False, path=None):
             fn.restype = C.c_int
             fn.argtypes = [tp, tp] + ([C.c_void_p] if nargs == 3 else [tp, tp, C.c_void_p])
     for suffix in ("_init", ""):
-        fn = getattr(lib, "csinn_add" + suffix)
-        fn.restype, fn.argtypes = C.c_int, [tp, tp, tp, C.c_void_p]
+        for op in ("csinn_add", "csinn_mul"):
+            fn = getattr(lib, op + suffix)
+            fn.restype, fn.argtypes = C.c_int, [tp, tp, tp, C.c_void_p]
         fn = getattr(lib, "csinn_concat" + suffix)
         fn.restype, fn.argtypes = C.c_int, [C.POINTER(tp), tp, C.c_void_p]
     lib._typed = True
@@ -356,6 +377,12 @@ def load_backend(frontend):
         opt.shl_mi355x_bcast_const_blocks.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32,
                                                       C.POINTER(Session)]
         opt.shl_mi355x_params_adopt_blocks.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(Session)]
+        table = C.POINTER(C.c_uint8)
+        for op in ("sigmoid", "hard_sigmoid", "silu"):
+            fn = getattr(opt, "shl_mi355x_%s_table_i8" % op)
+            fn.restype, fn.argtypes = None, [C.c_float, C.c_int32, C.c_float, C.c_int32, table]
+        opt.shl_mi355x_leaky_relu_table_i8.restype = None
+        opt.shl_mi355x_leaky_relu_table_i8.argtypes = [C.c_float, C.c_int32, C.c_float, C.c_int32, C.c_float, table]
         opt._typed = True
     # the dispatch tables exist after the first csinn_alloc_session (source/nn2/setup.c:77-84)
     s = frontend.csinn_alloc_session()
@@ -494,10 +521,12 @@ def fc_params(fe, keep, api, units, fuse_zp2bias=0, sess=None, name=b"fc"):
     return p
 
 
-def siso_params(fe, keep, api, kind, layout=LAYOUT_NHWC, axis=1, sess=None, name=b"siso"):
-    """params block of a single-input single-output op: kind in relu | relu6 | pool | softmax"""
+def siso_params(fe, keep, api, kind, layout=LAYOUT_NHWC, axis=1, sess=None, name=b"siso", n=0.0):
+    """params block of a single-input single-output op: kind in relu | relu6 | pool | softmax | sigmoid | hard_sigmoid |
+    silu | leaky_relu (n: its slope), or of add / mul"""
     ctype = {"relu": ReluParams, "relu6": ReluParams, "pool": PoolParams, "softmax": SoftmaxParams,
-             "add": DisoParams}[kind]
+             "add": DisoParams, "mul": DisoParams, "sigmoid": SigmoidParams, "hard_sigmoid": SigmoidParams,
+             "silu": SigmoidParams, "leaky_relu": ReluParams}[kind]
     p = fe.csinn_alloc_params(C.sizeof(ctype), sess)
     pc = C.cast(p, C.POINTER(ctype)).contents
     pc.base.api = api
@@ -509,6 +538,8 @@ def siso_params(fe, keep, api, kind, layout=LAYOUT_NHWC, axis=1, sess=None, name
         pc.axis = axis
     if kind == "relu6":
         pc.n = 6.0
+    if kind == "leaky_relu":
+        pc.n = n
     return p
 
 

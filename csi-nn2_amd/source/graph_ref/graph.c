@@ -152,12 +152,34 @@ int shl_gref_relu6(struct csinn_tensor *input, struct csinn_tensor *output,
     return record_siso(input, output, CSINN_OP_RELU6, params);
 }
 
+/* sigmoid family and leaky_relu (source/graph_ref/sigmoid.c, hard_sigmoid.c, silu.c, leaky_relu.c of the reference):
+ * one input, one output */
+int shl_gref_sigmoid(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params)
+{
+    return record_siso(input, output, CSINN_OP_SIGMOID, params);
+}
+
+int shl_gref_hard_sigmoid(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params)
+{
+    return record_siso(input, output, CSINN_OP_HARD_SIGMOID, params);
+}
+
+int shl_gref_silu(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params)
+{
+    return record_siso(input, output, CSINN_OP_SILU, params);
+}
+
+int shl_gref_leaky_relu(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_relu_params *params)
+{
+    return record_siso(input, output, CSINN_OP_LEAKY_RELU, params);
+}
+
 /* two activation inputs (either may also be a constant tensor), one output
  * (shl_gref_diso_op, source/graph_ref/utils.c of the reference) */
-int shl_gref_add(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
-                 struct csinn_diso_params *params)
+static int record_diso(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output, int op,
+                       struct csinn_diso_params *params)
 {
-    struct shl_node *layer = shl_node_alloc(CSINN_OP_ADD, params->base.name, 2, 1, params);
+    struct shl_node *layer = shl_node_alloc(op, params->base.name, 2, 1, params);
     struct shl_node *produced = shl_node_var_alloc(output->name, output);
     struct csinn_tensor *ins[2] = {input0, input1};
     for (int i = 0; i < 2; i++) {
@@ -169,6 +191,18 @@ int shl_gref_add(struct csinn_tensor *input0, struct csinn_tensor *input1, struc
     shl_node_add_out(layer, produced, 0);
     output->data = produced;
     return shl_gref_graph_insert(layer, shl_gref_get_graph(output->sess ? output->sess : input0->sess));
+}
+
+int shl_gref_add(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
+                 struct csinn_diso_params *params)
+{
+    return record_diso(input0, input1, output, CSINN_OP_ADD, params);
+}
+
+int shl_gref_mul(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
+                 struct csinn_diso_params *params)
+{
+    return record_diso(input0, input1, output, CSINN_OP_MUL, params);
 }
 
 /* params->inputs_count inputs, any of which may be a constant tensor (it becomes a const node), one output */
@@ -227,8 +261,13 @@ int shl_gref_call_layer_func(void *fn, struct shl_node *node)
         case CSINN_OP_MAXPOOL2D:
         case CSINN_OP_AVGPOOL2D:
         case CSINN_OP_SOFTMAX:
+        case CSINN_OP_SIGMOID:
+        case CSINN_OP_HARD_SIGMOID:
+        case CSINN_OP_SILU:
+        case CSINN_OP_LEAKY_RELU:
             return f(node->in[0]->data, node->out[0]->data, params);
         case CSINN_OP_ADD:
+        case CSINN_OP_MUL:
             return f(node->in[0]->data, node->in[1]->data, node->out[0]->data, params);
         case CSINN_OP_CONCAT: {
             struct csinn_tensor **ins = shl_mem_alloc((int64_t)node->in_num * sizeof(*ins));
@@ -289,6 +328,11 @@ static struct csinn_callback *gref_cb_map(int op, int dtype)
         {CSINN_OP_SOFTMAX, shl_gref_softmax},
         {CSINN_OP_ADD, shl_gref_add},
         {CSINN_OP_CONCAT, shl_gref_concat},
+        {CSINN_OP_SIGMOID, shl_gref_sigmoid},
+        {CSINN_OP_HARD_SIGMOID, shl_gref_hard_sigmoid},
+        {CSINN_OP_SILU, shl_gref_silu},
+        {CSINN_OP_LEAKY_RELU, shl_gref_leaky_relu},
+        {CSINN_OP_MUL, shl_gref_mul},
     };
     for (unsigned i = 0; i < sizeof(table) / sizeof(table[0]); i++) {
         if (table[i].op == op) {

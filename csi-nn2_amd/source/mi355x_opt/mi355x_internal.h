@@ -46,6 +46,18 @@ int shl_mi355x_avgpool2d_perf(struct csinn_tensor *input, struct csinn_tensor *o
 int shl_mi355x_concat_perf(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params,
                            struct csinn_perf_info *info);
 
+/* ... and of the elementwise layers (eltwise.c): the kernel form the rules choose */
+int shl_mi355x_sigmoid_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params,
+                            struct csinn_perf_info *info);
+int shl_mi355x_hard_sigmoid_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params,
+                                 struct csinn_perf_info *info);
+int shl_mi355x_silu_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params,
+                         struct csinn_perf_info *info);
+int shl_mi355x_leaky_relu_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_relu_params *params,
+                               struct csinn_perf_info *info);
+int shl_mi355x_mul_perf(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
+                        struct csinn_diso_params *params, struct csinn_perf_info *info);
+
 float shl_mi355x_half_to_float(uint16_t h);
 
 /* session.c: fold the relu / relu6 layer that is the convolution's only consumer into its plan (convolution.c) */

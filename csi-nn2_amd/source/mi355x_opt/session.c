@@ -143,6 +143,11 @@ static const struct session_op g_ops[] = {
     {CSINN_OP_AVGPOOL2D, shl_mi355x_avgpool2d_exec, CALL_SISO, 1, 1},
     {CSINN_OP_SOFTMAX, shl_mi355x_softmax_exec, CALL_SISO, 1, 1},
     {CSINN_OP_ADD, shl_mi355x_add_exec, CALL_DISO, 2, 1},        /* the second operand may be a constant */
+    {CSINN_OP_MUL, shl_mi355x_mul_exec, CALL_DISO, 2, 1},        /* ... and may be broadcast (an SE gate, a per-channel scale) */
+    {CSINN_OP_SIGMOID, shl_mi355x_sigmoid_exec, CALL_SISO, 1, 1},
+    {CSINN_OP_HARD_SIGMOID, shl_mi355x_hard_sigmoid_exec, CALL_SISO, 1, 1},
+    {CSINN_OP_SILU, shl_mi355x_silu_exec, CALL_SISO, 1, 1},
+    {CSINN_OP_LEAKY_RELU, shl_mi355x_leaky_relu_exec, CALL_SISO, 1, 1},
     {CSINN_OP_CONCAT, shl_mi355x_concat_exec, CALL_ARRAY, 0, 0}, /* any input may be */
 };
 

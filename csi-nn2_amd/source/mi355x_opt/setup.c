@@ -634,6 +634,11 @@ void shl_target_init_mi355x(void)
         reg(dts[i], CSINN_OP_AVGPOOL2D, NULL, shl_mi355x_avgpool2d_exec, shl_gref_avgpool2d, shl_mi355x_avgpool2d_perf);
         reg(dts[i], CSINN_OP_SOFTMAX, NULL, shl_mi355x_softmax_exec, shl_gref_softmax, conv_perf);
         reg(dts[i], CSINN_OP_ADD, NULL, shl_mi355x_add_exec, shl_gref_add, conv_perf);
+        reg(dts[i], CSINN_OP_MUL, NULL, shl_mi355x_mul_exec, shl_gref_mul, shl_mi355x_mul_perf);
+        reg(dts[i], CSINN_OP_SIGMOID, NULL, shl_mi355x_sigmoid_exec, shl_gref_sigmoid, shl_mi355x_sigmoid_perf);
+        reg(dts[i], CSINN_OP_HARD_SIGMOID, NULL, shl_mi355x_hard_sigmoid_exec, shl_gref_hard_sigmoid, shl_mi355x_hard_sigmoid_perf);
+        reg(dts[i], CSINN_OP_SILU, NULL, shl_mi355x_silu_exec, shl_gref_silu, shl_mi355x_silu_perf);
+        reg(dts[i], CSINN_OP_LEAKY_RELU, NULL, shl_mi355x_leaky_relu_exec, shl_gref_leaky_relu, shl_mi355x_leaky_relu_perf);
         reg(dts[i], CSINN_OP_CONCAT, NULL, shl_mi355x_concat_exec, shl_gref_concat, shl_mi355x_concat_perf);
     }
     shl_register_op_callback(CSINN_MI355X, shl_cb_map_mi355x);

@@ -9,6 +9,7 @@
  *   relu / relu6 ...... source/nn2/relu.c, relu6.c
  *   maxpool2d / avgpool2d  source/nn2/maxpool.c, averagepool.c
  *   concat ............ source/nn2/concat.c
+ *   sigmoid / hard_sigmoid / silu / leaky_relu / mul  source/nn2/sigmoid.c, hard_sigmoid.c, silu.c, leaky_relu.c, mul.c
  * The only deliberate difference: a missing callback is reported (CSINN_CALLBACK_UNSET and an
  * error message) instead of being dereferenced.
  */
@@ -197,26 +198,85 @@ int csinn_softmax(struct csinn_tensor *input, struct csinn_tensor *output,
     return run3(&params->base, input, output, params);
 }
 
-/* source/nn2/add.c:26-55: two inputs, one output */
-int csinn_add_init(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
-                   struct csinn_diso_params *params)
+/* source/nn2/sigmoid.c, hard_sigmoid.c, silu.c, leaky_relu.c of the reference: one input, one output */
+int csinn_sigmoid_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params)
 {
-    int rc = shl_op_callback_map(&params->base, CSINN_OP_ADD, input0->dtype);
+    return map_and_init3(&params->base, CSINN_OP_SIGMOID, input->dtype, input, output, params);
+}
+int csinn_sigmoid(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params)
+{
+    return run3(&params->base, input, output, params);
+}
+
+int csinn_hard_sigmoid_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params)
+{
+    return map_and_init3(&params->base, CSINN_OP_HARD_SIGMOID, input->dtype, input, output, params);
+}
+int csinn_hard_sigmoid(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params)
+{
+    return run3(&params->base, input, output, params);
+}
+
+int csinn_silu_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params)
+{
+    return map_and_init3(&params->base, CSINN_OP_SILU, input->dtype, input, output, params);
+}
+int csinn_silu(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params)
+{
+    return run3(&params->base, input, output, params);
+}
+
+int csinn_leaky_relu_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_relu_params *params)
+{
+    return map_and_init3(&params->base, CSINN_OP_LEAKY_RELU, input->dtype, input, output, params);
+}
+int csinn_leaky_relu(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_relu_params *params)
+{
+    return run3(&params->base, input, output, params);
+}
+
+/* source/nn2/add.c:26-55, mul.c: two inputs, one output; the callbacks are looked up by the FIRST input's dtype */
+static int map_and_init4(struct csinn_params_base *base, int op, struct csinn_tensor *input0, struct csinn_tensor *input1,
+                         struct csinn_tensor *output, void *params)
+{
+    int rc = shl_op_callback_map(base, op, input0->dtype);
     if (rc != CSINN_TRUE) return rc;
-    int (*init)() = shl_get_init_cb(&params->base);
+    int (*init)() = shl_get_init_cb(base);
     if (init != NULL) {
         rc = init(input0, input1, output, params);
         if (rc != CSINN_TRUE) return rc;
     }
     return CSINN_TRUE;
 }
+
+static int run4(struct csinn_params_base *base, void *a, void *b, void *c, void *params)
+{
+    int (*fn)() = shl_get_p0_cb(base);
+    if (fn == NULL) return CSINN_CALLBACK_UNSET;
+    int rc = fn(a, b, c, params);
+    return rc == CSINN_TRUE ? CSINN_TRUE : rc;
+}
+
+int csinn_add_init(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
+                   struct csinn_diso_params *params)
+{
+    return map_and_init4(&params->base, CSINN_OP_ADD, input0, input1, output, params);
+}
 int csinn_add(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
               struct csinn_diso_params *params)
 {
-    int (*fn)() = shl_get_p0_cb(&params->base);
-    if (fn == NULL) return CSINN_CALLBACK_UNSET;
-    int rc = fn(input0, input1, output, params);
-    return rc == CSINN_TRUE ? CSINN_TRUE : rc;
+    return run4(&params->base, input0, input1, output, params);
+}
+
+int csinn_mul_init(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
+                   struct csinn_diso_params *params)
+{
+    return map_and_init4(&params->base, CSINN_OP_MUL, input0, input1, output, params);
+}
+int csinn_mul(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
+              struct csinn_diso_params *params)
+{
+    return run4(&params->base, input0, input1, output, params);
 }
 
 /* source/nn2/concat.c: an array of params->inputs_count inputs; the callbacks are looked up by the OUTPUT's dtype */

@@ -56,6 +56,21 @@ int csinn_add_init(struct csinn_tensor *input0, struct csinn_tensor *input1, str
                    struct csinn_diso_params *params);
 int csinn_add(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
               struct csinn_diso_params *params);
+/* sigmoid family and leaky_relu (source/nn2/sigmoid.c, hard_sigmoid.c, silu.c, leaky_relu.c of the reference);
+ * leaky_relu's slope is params->n */
+int csinn_sigmoid_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params);
+int csinn_sigmoid(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params);
+int csinn_hard_sigmoid_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params);
+int csinn_hard_sigmoid(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params);
+int csinn_silu_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params);
+int csinn_silu(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params);
+int csinn_leaky_relu_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_relu_params *params);
+int csinn_leaky_relu(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_relu_params *params);
+/* elementwise product with broadcasting of either operand (source/nn2/mul.c) */
+int csinn_mul_init(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
+                   struct csinn_diso_params *params);
+int csinn_mul(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
+              struct csinn_diso_params *params);
 /* concat along one axis (source/nn2/concat.c of the reference): `input` is an array of params->inputs_count tensors; the
  * callbacks are looked up by the OUTPUT's dtype */
 int csinn_concat_init(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params);

@@ -134,10 +134,15 @@ enum csinn_op_enum {
     CSINN_OP_GROUP_CONV2D_CHANNEL_RELU = 46,
     CSINN_OP_FULLYCONNECTED = 71,
     CSINN_OP_GLOBAL_AVGPOOL2D = 74,
+    CSINN_OP_HARD_SIGMOID = 78,
+    CSINN_OP_LEAKY_RELU = 84,
     CSINN_OP_MAXPOOL2D = 98,
+    CSINN_OP_MUL = 107,
     CSINN_OP_RELU = 127,
     CSINN_OP_RELU6 = 129,
+    CSINN_OP_SIGMOID = 154,
     CSINN_OP_SOFTMAX = 159,
+    CSINN_OP_SILU = 190,
     CSINN_OP_SIZE = 194,
     CSINN_OP_AND_UTILS_SIZE = 198
 };
@@ -349,6 +354,11 @@ struct csinn_siso_params {
 
 /* two inputs, one output: add (csinn_data_structure.h:791-793 of the reference) */
 struct csinn_diso_params {
+    struct csinn_params_base base;
+};
+
+/* sigmoid, hard_sigmoid and silu: nothing beyond the base */
+struct csinn_sigmoid_params { /* 40 B */
     struct csinn_params_base base;
 };
 

@@ -69,6 +69,12 @@ int shl_gref_relu6(struct csinn_tensor *input, struct csinn_tensor *output,
                    struct csinn_relu_params *params);
 int shl_gref_add(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
                  struct csinn_diso_params *params);
+int shl_gref_mul(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
+                 struct csinn_diso_params *params);
+int shl_gref_sigmoid(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params);
+int shl_gref_hard_sigmoid(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params);
+int shl_gref_silu(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params);
+int shl_gref_leaky_relu(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_relu_params *params);
 int shl_gref_concat(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params);
 int shl_gref_global_avgpool2d(struct csinn_tensor *input, struct csinn_tensor *output,
                               struct csinn_pool_params *params);

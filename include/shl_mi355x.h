@@ -396,6 +396,60 @@ const char *shl_mi355x_concat_kernel_name(const void *const *in_dev, const int64
                                           const int32_t *in_zp, const void *out_dev,
                                           const struct shl_mi355x_concat_desc *d);
 
+/* int8 unary operator by table: out[i] = table[(uint8_t)in[i]].  Serves sigmoid / hard_sigmoid / silu / leaky_relu (and any
+ * other int8 -> int8 function of one element): with one quantisation record per tensor the reference's
+ * dequantise -> f -> requantise (shl_ref_siso_callback_base, source/reference/utils.c:609-621) has 256 possible results,
+ * which the backend computes on the host (shl_mi355x_*_table_i8, shl_mi355x_backend.h).  `table` is HOST memory, 256
+ * bytes, read during the call: it travels by value in the kernel arguments (no allocation, nothing to keep alive; a
+ * captured graph holds its own copy).  16 bytes per lane when both pointers are 16-byte aligned, one byte per thread
+ * otherwise; any count.  Enqueues only. */
+int shl_mi355x_unary_lut_i8(const int8_t *input_dev, int8_t *output_dev, size_t count, const uint8_t *table, void *stream);
+/* "unary_lut_i8_vec" / "unary_lut_i8_byte": the form those pointers get.  Pure host code */
+const char *shl_mi355x_unary_lut_i8_kernel_name(const void *input_dev, const void *output_dev);
+
+/* binary16 unary operators, qinfo scale 1: f16 -> f32, the reference's formula in the reference's precision
+ * (source/reference/sigmoid.c:33, hard_sigmoid.c:31-37, silu.c:33, leaky_relu.c:33: double exp, one rounding to float;
+ * hard_sigmoid's 0.2 x + 0.5 as the one fused multiply-add the reference's build makes of it),
+ * the reference's float -> binary16 rounding.  `alpha`: leaky_relu's slope (params->n), ignored by the others. */
+enum shl_mi355x_unary_kind {
+    SHL_MI355X_UNARY_SIGMOID = 0,
+    SHL_MI355X_UNARY_HARD_SIGMOID = 1,
+    SHL_MI355X_UNARY_SILU = 2,
+    SHL_MI355X_UNARY_LEAKY_RELU = 3
+};
+int shl_mi355x_unary_f16(const uint16_t *input_dev, uint16_t *output_dev, size_t count, int32_t kind, float alpha,
+                         void *stream);
+
+/* elementwise product with one broadcast operand: shl_ref_mul_quant (source/reference/mul.c:21-40): both operands
+ * dequantised, one fp32 product, requantised; bit for bit.  `a` has the output's shape; `b` is broadcast to it by the
+ * reference's rule (shl_ref_broadcast_to_shape_f32, utils.c:692-785: ranks right-aligned, every dim of b equals the
+ * output's or is 1).  The caller collapses the output's dims to at most 4 groups of neighbouring dims along which b
+ * either varies or is broadcast: dim[g] is group g's size (outermost first), b_stride[g] what one step along it moves in
+ * b, in elements (0: broadcast).  [N,H,W,C] x [N,1,1,C]: dim {N, H W, C}, b_stride {C, 0, 1}; [N,C,H,W] x [1,C,1,1]:
+ * dim {N, C, H W}, b_stride {0, 1, 0}; same shape: dim {count}, b_stride {1}; a scalar: dim {count}, b_stride {0}.
+ * f16: scales and zero points are ignored; a NaN comes out as 0x7FFF with the sign x86 gives it.  The output must not
+ * overlap an operand.  Enqueues only: no allocation, no
+ * upload, no synchronisation (capturable in a hipGraph). */
+struct shl_mi355x_mul_desc {
+    int32_t dtype;   /* SHL_MI355X_I8 / SHL_MI355X_F16 */
+    int32_t ngroups; /* 1 .. 4 */
+    int64_t dim[4];
+    int64_t b_stride[4];
+    float a_scale, b_scale, out_scale;
+    int32_t a_zp, b_zp, out_zp;
+    int32_t a_is_second; /* a is the layer's SECOND input, b its first (the product commutes; of two binary16 NaNs the
+                            reference hands on its second input's) */
+    int32_t reserved[4]; /* must be zero */
+};
+
+int shl_mi355x_mul(const void *a_dev, const void *b_dev, void *out_dev, const struct shl_mi355x_mul_desc *d, void *stream);
+/* the kernel form the rules choose: "mul_vec" (16 bytes per lane: b same-shape, a scalar, or varying only along an
+ * unbroadcast innermost group of whole 16-byte pieces; a, out and a non-scalar b 16-byte aligned), "mul_row" (the
+ * innermost group is broadcast: one b value per run; a and out 16-byte aligned), "mul_generic" (one output per thread;
+ * SHL_MI355X_MUL_FORM=generic forces it); "" for invalid arguments.  Pure host code: looks at the pointers' values only */
+const char *shl_mi355x_mul_kernel_name(const struct shl_mi355x_mul_desc *d, const void *a_dev, const void *b_dev,
+                                       const void *out_dev);
+
 /* softmax along one axis of a tensor viewed as [outer, count, inner]:
  * shl_ref_softmax_quant (source/reference/softmax.c:21-72): float max, double exp, float running
  * sum in index order.  count <= 8192. */

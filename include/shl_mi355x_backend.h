@@ -100,6 +100,22 @@ int shl_mi355x_add_exec(struct csinn_tensor *input0, struct csinn_tensor *input1
 /* concat along params->axis (-1: the last axis) of params->inputs_count tensors: every non-axis dim must equal the
  * output's and the axis dims must sum to the output's, else the call is refused; the same tensor may appear twice */
 int shl_mi355x_concat_exec(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params);
+/* sigmoid / hard_sigmoid / silu / leaky_relu (source/mi355x_opt/eltwise.c): int8 through a 256-entry table built on the
+ * host, binary16 through the formula kernel; input and output hold the same number of elements */
+int shl_mi355x_sigmoid_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params);
+int shl_mi355x_hard_sigmoid_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params);
+int shl_mi355x_silu_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params);
+int shl_mi355x_leaky_relu_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_relu_params *params);
+/* the 256 results of the int8 operator for the two records, as the reference computes them: table[(uint8_t)q] =
+ * float_to_int8(f(int8_to_float(q, in record)), out record).  Pure host code.  `n`: leaky_relu's slope */
+void shl_mi355x_sigmoid_table_i8(float in_scale, int32_t in_zp, float out_scale, int32_t out_zp, uint8_t table[256]);
+void shl_mi355x_hard_sigmoid_table_i8(float in_scale, int32_t in_zp, float out_scale, int32_t out_zp, uint8_t table[256]);
+void shl_mi355x_silu_table_i8(float in_scale, int32_t in_zp, float out_scale, int32_t out_zp, uint8_t table[256]);
+void shl_mi355x_leaky_relu_table_i8(float in_scale, int32_t in_zp, float out_scale, int32_t out_zp, float n, uint8_t table[256]);
+/* elementwise product; one operand has the output's shape, the other is broadcast to it by the reference's rule (either
+ * order).  Both operands needing a broadcast, or shapes that break the rule, are refused */
+int shl_mi355x_mul_exec(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
+                        struct csinn_diso_params *params);
 int shl_mi355x_global_avgpool2d_exec(struct csinn_tensor *input, struct csinn_tensor *output,
                                      struct csinn_pool_params *params);
 /* windowed pooling: 4-d tensors, the output size is the output tensor's; a window without an in-image tap is refused */
