@@ -32,6 +32,8 @@ OP_DEPTHWISE_CONV2D, OP_FULLYCONNECTED = 35, 71
 OP_AVGPOOL2D, OP_MAXPOOL2D = 14, 98
 OP_CONCAT = 26
 OP_SIGMOID, OP_HARD_SIGMOID, OP_SILU, OP_LEAKY_RELU, OP_MUL = 154, 78, 190, 84, 107
+OP_RESIZE = 133
+RESIZE_BILINEAR, RESIZE_NEAREST_NEIGHBOR, RESIZE_NEAREST_BICUBIC = 0, 1, 2  # enum csinn_resize_enum
 
 SHL_NHWC, SHL_NCHW = 0, 1
 SHL_I8, SHL_F16 = 0, 1
@@ -121,6 +123,10 @@ class SigmoidParams(C.Structure):
     _fields_ = [("base", ParamsBase)]
 
 
+class ResizeParams(C.Structure):
+    _fields_ = [("base", ParamsBase), ("resize_mode", C.c_int32), ("align_corners", C.c_bool)]
+
+
 class SoftmaxParams(C.Structure):
     _fields_ = [("base", ParamsBase), ("axis", C.c_int32)]
 
@@ -157,6 +163,13 @@ class ConcatDesc(C.Structure):
     """struct shl_mi355x_concat_desc (include/shl_mi355x.h)"""
     _fields_ = [("dtype", C.c_int32), ("n_inputs", C.c_int32), ("outer", C.c_int64), ("out_scale", C.c_float),
                 ("out_zp", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class ResizeDesc(C.Structure):
+    """struct shl_mi355x_resize_desc (include/shl_mi355x.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("dtype", "layout", "n", "c", "in_h", "in_w", "out_h", "out_w", "mode", "align_corners")] + \
+        [("height_scale", C.c_float), ("width_scale", C.c_float), ("in_scale", C.c_float), ("out_scale", C.c_float),
+         ("in_zp", C.c_int32), ("out_zp", C.c_int32), ("table", C.c_uint8 * 256), ("reserved", C.c_int32 * 4)]
 
 
 class MulDesc(C.Structure):
@@ -268,6 +281,8 @@ def load_hip():
         "shl_mi355x_unary_f16": (C.c_int, [vp, vp, sz, i32, f32, vp]),
         "shl_mi355x_mul": (C.c_int, [vp, vp, vp, C.POINTER(MulDesc), vp]),
         "shl_mi355x_mul_kernel_name": (C.c_char_p, [C.POINTER(MulDesc), vp, vp, vp]),
+        "shl_mi355x_resize": (C.c_int, [vp, vp, C.POINTER(ResizeDesc), vp]),
+        "shl_mi355x_resize_kernel_name": (C.c_char_p, [C.POINTER(ResizeDesc), vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -305,7 +320,7 @@ _FRONTEND_SIGS = {
     "shl_debug_set_level": (None, [C.c_int]),
 }
 _SISO_OPS = ("csinn_relu", "csinn_relu6", "csinn_global_avgpool2d", "csinn_softmax", "csinn_maxpool2d", "csinn_avgpool2d",
-             "csinn_sigmoid", "csinn_hard_sigmoid", "csinn_silu", "csinn_leaky_relu")
+             "csinn_sigmoid", "csinn_hard_sigmoid", "csinn_silu", "csinn_leaky_relu", "csinn_resize")
 _CONV_OPS = ["csinn_conv2d", "csinn_conv2d_relu", "csinn_conv2d_relu6", "csinn_depthwise_conv2d",
              "csinn_depthwise_conv2d_relu", "csinn_fullyconnected"] + list(_SISO_OPS)
 
@@ -381,6 +396,10 @@ def load_backend(frontend):
         for op in ("sigmoid", "hard_sigmoid", "silu"):
             fn = getattr(opt, "shl_mi355x_%s_table_i8" % op)
             fn.restype, fn.argtypes = None, [C.c_float, C.c_int32, C.c_float, C.c_int32, table]
+        opt.shl_mi355x_resize_table_i8.restype = None
+        opt.shl_mi355x_resize_table_i8.argtypes = [C.c_float, C.c_int32, C.c_float, C.c_int32, table]
+        opt.shl_mi355x_resize_scale.restype = C.c_float
+        opt.shl_mi355x_resize_scale.argtypes = [C.c_int32, C.c_int32, C.c_int]
         opt.shl_mi355x_leaky_relu_table_i8.restype = None
         opt.shl_mi355x_leaky_relu_table_i8.argtypes = [C.c_float, C.c_int32, C.c_float, C.c_int32, C.c_float, table]
         opt._typed = True
@@ -506,6 +525,20 @@ def concat_params(fe, keep, api, layout, n, axis, sess=None, name=b"concat"):
 def tensor_array(keep, tensors):
     """struct csinn_tensor *[]: what csinn_concat takes as its inputs"""
     return keep.add((C.POINTER(Tensor) * len(tensors))(*tensors))
+
+
+def resize_params(fe, keep, api, layout, mode=RESIZE_NEAREST_NEIGHBOR, align_corners=False, sess=None, name=b"resize"):
+    """params block of csinn_resize: the output size is the output tensor's"""
+    p = fe.csinn_alloc_params(C.sizeof(ResizeParams), sess)
+    pc = C.cast(p, C.POINTER(ResizeParams)).contents
+    pc.base.api = api
+    pc.base.layout = layout
+    pc.base.name = keep.add(C.c_char_p(name)).value
+    if sess is not None:
+        pc.base.sess = sess
+    pc.resize_mode = mode
+    pc.align_corners = bool(align_corners)
+    return p
 
 
 def fc_params(fe, keep, api, units, fuse_zp2bias=0, sess=None, name=b"fc"):

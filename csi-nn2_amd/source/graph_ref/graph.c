@@ -174,6 +174,12 @@ int shl_gref_leaky_relu(struct csinn_tensor *input, struct csinn_tensor *output,
     return record_siso(input, output, CSINN_OP_LEAKY_RELU, params);
 }
 
+/* resize (source/graph_ref/resize.c of the reference): one input, one output, whose dims the caller has set */
+int shl_gref_resize(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_resize_params *params)
+{
+    return record_siso(input, output, CSINN_OP_RESIZE, params);
+}
+
 /* two activation inputs (either may also be a constant tensor), one output
  * (shl_gref_diso_op, source/graph_ref/utils.c of the reference) */
 static int record_diso(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output, int op,
@@ -265,6 +271,7 @@ int shl_gref_call_layer_func(void *fn, struct shl_node *node)
         case CSINN_OP_HARD_SIGMOID:
         case CSINN_OP_SILU:
         case CSINN_OP_LEAKY_RELU:
+        case CSINN_OP_RESIZE:
             return f(node->in[0]->data, node->out[0]->data, params);
         case CSINN_OP_ADD:
         case CSINN_OP_MUL:
@@ -333,6 +340,7 @@ static struct csinn_callback *gref_cb_map(int op, int dtype)
         {CSINN_OP_SILU, shl_gref_silu},
         {CSINN_OP_LEAKY_RELU, shl_gref_leaky_relu},
         {CSINN_OP_MUL, shl_gref_mul},
+        {CSINN_OP_RESIZE, shl_gref_resize},
     };
     for (unsigned i = 0; i < sizeof(table) / sizeof(table[0]); i++) {
         if (table[i].op == op) {

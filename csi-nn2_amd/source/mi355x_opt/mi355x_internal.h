@@ -58,6 +58,10 @@ int shl_mi355x_leaky_relu_perf(struct csinn_tensor *input, struct csinn_tensor *
 int shl_mi355x_mul_perf(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
                         struct csinn_diso_params *params, struct csinn_perf_info *info);
 
+/* ... and of resize (resize.c) */
+int shl_mi355x_resize_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_resize_params *params,
+                           struct csinn_perf_info *info);
+
 float shl_mi355x_half_to_float(uint16_t h);
 
 /* session.c: fold the relu / relu6 layer that is the convolution's only consumer into its plan (convolution.c) */

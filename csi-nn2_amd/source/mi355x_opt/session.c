@@ -148,6 +148,7 @@ static const struct session_op g_ops[] = {
     {CSINN_OP_HARD_SIGMOID, shl_mi355x_hard_sigmoid_exec, CALL_SISO, 1, 1},
     {CSINN_OP_SILU, shl_mi355x_silu_exec, CALL_SISO, 1, 1},
     {CSINN_OP_LEAKY_RELU, shl_mi355x_leaky_relu_exec, CALL_SISO, 1, 1},
+    {CSINN_OP_RESIZE, shl_mi355x_resize_exec, CALL_SISO, 1, 1},  /* an FPN top-down path, a U-Net decoder, a YOLO neck */
     {CSINN_OP_CONCAT, shl_mi355x_concat_exec, CALL_ARRAY, 0, 0}, /* any input may be */
 };
 

@@ -639,6 +639,7 @@ void shl_target_init_mi355x(void)
         reg(dts[i], CSINN_OP_HARD_SIGMOID, NULL, shl_mi355x_hard_sigmoid_exec, shl_gref_hard_sigmoid, shl_mi355x_hard_sigmoid_perf);
         reg(dts[i], CSINN_OP_SILU, NULL, shl_mi355x_silu_exec, shl_gref_silu, shl_mi355x_silu_perf);
         reg(dts[i], CSINN_OP_LEAKY_RELU, NULL, shl_mi355x_leaky_relu_exec, shl_gref_leaky_relu, shl_mi355x_leaky_relu_perf);
+        reg(dts[i], CSINN_OP_RESIZE, NULL, shl_mi355x_resize_exec, shl_gref_resize, shl_mi355x_resize_perf);
         reg(dts[i], CSINN_OP_CONCAT, NULL, shl_mi355x_concat_exec, shl_gref_concat, shl_mi355x_concat_perf);
     }
     shl_register_op_callback(CSINN_MI355X, shl_cb_map_mi355x);

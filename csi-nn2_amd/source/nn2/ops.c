@@ -9,6 +9,7 @@
  *   relu / relu6 ...... source/nn2/relu.c, relu6.c
  *   maxpool2d / avgpool2d  source/nn2/maxpool.c, averagepool.c
  *   concat ............ source/nn2/concat.c
+ *   resize ............ source/nn2/resize.c
  *   sigmoid / hard_sigmoid / silu / leaky_relu / mul  source/nn2/sigmoid.c, hard_sigmoid.c, silu.c, leaky_relu.c, mul.c
  * The only deliberate difference: a missing callback is reported (CSINN_CALLBACK_UNSET and an
  * error message) instead of being dereferenced.
@@ -277,6 +278,16 @@ int csinn_mul(struct csinn_tensor *input0, struct csinn_tensor *input1, struct c
               struct csinn_diso_params *params)
 {
     return run4(&params->base, input0, input1, output, params);
+}
+
+/* source/nn2/resize.c of the reference: one input, one output */
+int csinn_resize_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_resize_params *params)
+{
+    return map_and_init3(&params->base, CSINN_OP_RESIZE, input->dtype, input, output, params);
+}
+int csinn_resize(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_resize_params *params)
+{
+    return run3(&params->base, input, output, params);
 }
 
 /* source/nn2/concat.c: an array of params->inputs_count inputs; the callbacks are looked up by the OUTPUT's dtype */

@@ -71,6 +71,9 @@ int csinn_mul_init(struct csinn_tensor *input0, struct csinn_tensor *input1, str
                    struct csinn_diso_params *params);
 int csinn_mul(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
               struct csinn_diso_params *params);
+/* nearest-neighbour / bilinear resize to the output tensor's height and width (source/nn2/resize.c of the reference) */
+int csinn_resize_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_resize_params *params);
+int csinn_resize(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_resize_params *params);
 /* concat along one axis (source/nn2/concat.c of the reference): `input` is an array of params->inputs_count tensors; the
  * callbacks are looked up by the OUTPUT's dtype */
 int csinn_concat_init(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params);

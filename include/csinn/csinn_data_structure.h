@@ -140,6 +140,7 @@ enum csinn_op_enum {
     CSINN_OP_MUL = 107,
     CSINN_OP_RELU = 127,
     CSINN_OP_RELU6 = 129,
+    CSINN_OP_RESIZE = 133,
     CSINN_OP_SIGMOID = 154,
     CSINN_OP_SOFTMAX = 159,
     CSINN_OP_SILU = 190,
@@ -372,6 +373,19 @@ struct csinn_relu_params { /* 56 B */
 struct csinn_softmax_params { /* 48 B */
     struct csinn_params_base base;
     int32_t axis;
+};
+
+/* resize of a 4-d tensor to the output tensor's height and width */
+enum csinn_resize_enum {
+    CSINN_RESIZE_BILINEAR = 0,
+    CSINN_RESIZE_NEAREST_NEIGHBOR = 1,
+    CSINN_RESIZE_NEAREST_BICUBIC = 2
+};
+
+struct csinn_resize_params { /* 45 B, padded to 48 */
+    struct csinn_params_base base;
+    enum csinn_resize_enum resize_mode;
+    bool align_corners; /* the corner pixels of input and output coincide: scale (in - 1) / (out - 1) */
 };
 
 /* concat: a variable number of inputs, handed over as an array of tensor pointers; axis == -1 is the last axis */

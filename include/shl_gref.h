@@ -75,6 +75,7 @@ int shl_gref_sigmoid(struct csinn_tensor *input, struct csinn_tensor *output, st
 int shl_gref_hard_sigmoid(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params);
 int shl_gref_silu(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params);
 int shl_gref_leaky_relu(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_relu_params *params);
+int shl_gref_resize(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_resize_params *params);
 int shl_gref_concat(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params);
 int shl_gref_global_avgpool2d(struct csinn_tensor *input, struct csinn_tensor *output,
                               struct csinn_pool_params *params);

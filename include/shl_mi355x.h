@@ -396,6 +396,46 @@ const char *shl_mi355x_concat_kernel_name(const void *const *in_dev, const int64
                                           const int32_t *in_zp, const void *out_dev,
                                           const struct shl_mi355x_concat_desc *d);
 
+/* nearest-neighbour / bilinear resize of a 4-d int8 / binary16 tensor: shl_ref_resize_quant
+ * (source/reference/resize.c:464-468), bit for bit.  height_scale / width_scale are the reference's own floats, computed by
+ * the CALLER as ONE float division each: (float)in / out, with align_corners (float)(in - 1) / (out - 1)
+ * (shl_mi355x_resize_scale, shl_mi355x_backend.h, does it); the source coordinate of output row y is the float product
+ * y * height_scale.  Nearest: min((int)floor(.), in - 1), with align_corners (int)round(.); a gather, every element
+ * dequantised and requantised -- int8 through `table` (table[(uint8_t)q] = the output byte of input byte q:
+ * shl_mi355x_resize_table_i8 builds it; not read when the records are equal and that round trip is the identity),
+ * binary16 through the reference's float32 -> binary16 conversion (infinities saturate to +-65504, every NaN becomes
+ * 0x7FFF / 0xFFFF).  Bilinear: four taps (y0 = floor(.), y1 = min(y0 + 1, in - 1), the same along x), the products
+ * v w_y w_x summed in the reference's order with its build's fused multiply-adds, no tap skipped at weight zero.  f16:
+ * scales and zero points are ignored.  Every image of a batch is computed on its own (the reference's NCHW nearest
+ * routines are not, resize.c:179).  align_corners with an output extent of 1 and bicubic are refused
+ * (SHL_MI355X_EINVAL), and so is an output that overlaps the input.  Enqueues only: no allocation, no upload, no
+ * synchronisation (capturable in a hipGraph). */
+enum shl_mi355x_resize_mode {
+    SHL_MI355X_RESIZE_BILINEAR = 0, /* the values of enum csinn_resize_enum */
+    SHL_MI355X_RESIZE_NEAREST = 1,
+    SHL_MI355X_RESIZE_BICUBIC = 2 /* refused */
+};
+
+struct shl_mi355x_resize_desc {
+    int32_t dtype;  /* SHL_MI355X_I8 / SHL_MI355X_F16 */
+    int32_t layout; /* SHL_MI355X_NHWC / SHL_MI355X_NCHW */
+    int32_t n, c, in_h, in_w, out_h, out_w;
+    int32_t mode;          /* shl_mi355x_resize_mode */
+    int32_t align_corners; /* 0 / 1 */
+    float height_scale, width_scale;
+    float in_scale, out_scale;
+    int32_t in_zp, out_zp;
+    uint8_t table[256];  /* int8 nearest only */
+    int32_t reserved[4]; /* must be zero */
+};
+
+int shl_mi355x_resize(const void *in_dev, void *out_dev, const struct shl_mi355x_resize_desc *d, void *stream);
+/* the kernel form the rules choose: "resize_nhwc_vec" (NHWC, C * element size a multiple of 16, both pointers 16-byte
+ * aligned: 16 bytes of a pixel's channels per thread), "resize_nchw_row" (NCHW, the output pointer 4-byte aligned: whole
+ * dwords of an output row per thread), "resize_generic" (one output per thread; SHL_MI355X_RESIZE_FORM=generic forces it);
+ * "" for invalid arguments.  Pure host code: looks at the pointers' values only, touches no device */
+const char *shl_mi355x_resize_kernel_name(const struct shl_mi355x_resize_desc *d, const void *in_dev, const void *out_dev);
+
 /* int8 unary operator by table: out[i] = table[(uint8_t)in[i]].  Serves sigmoid / hard_sigmoid / silu / leaky_relu (and any
  * other int8 -> int8 function of one element): with one quantisation record per tensor the reference's
  * dequantise -> f -> requantise (shl_ref_siso_callback_base, source/reference/utils.c:609-621) has 256 possible results,

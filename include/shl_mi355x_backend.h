@@ -100,6 +100,15 @@ int shl_mi355x_add_exec(struct csinn_tensor *input0, struct csinn_tensor *input1
 /* concat along params->axis (-1: the last axis) of params->inputs_count tensors: every non-axis dim must equal the
  * output's and the axis dims must sum to the output's, else the call is refused; the same tensor may appear twice */
 int shl_mi355x_concat_exec(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params);
+/* resize (source/mi355x_opt/resize.c): 4-d tensors, nearest-neighbour or bilinear, to the output tensor's height and
+ * width; batch and channels of input and output must agree; bicubic, and align_corners with an output extent of 1 (the
+ * reference divides by zero), are refused */
+int shl_mi355x_resize_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_resize_params *params);
+/* the reference's scale of one axis: ONE float division, (float)in / out or, with align_corners, (float)(in - 1) / (out - 1) */
+float shl_mi355x_resize_scale(int32_t in, int32_t out, int align_corners);
+/* the 256 results of the int8 nearest-neighbour gather for the two records: table[(uint8_t)q] =
+ * float_to_int8(int8_to_float(q, in record), out record).  Pure host code */
+void shl_mi355x_resize_table_i8(float in_scale, int32_t in_zp, float out_scale, int32_t out_zp, uint8_t table[256]);
 /* sigmoid / hard_sigmoid / silu / leaky_relu (source/mi355x_opt/eltwise.c): int8 through a 256-entry table built on the
  * host, binary16 through the formula kernel; input and output hold the same number of elements */
 int shl_mi355x_sigmoid_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params);
