@@ -33,6 +33,8 @@ OP_AVGPOOL2D, OP_MAXPOOL2D = 14, 98
 OP_CONCAT = 26
 OP_SIGMOID, OP_HARD_SIGMOID, OP_SILU, OP_LEAKY_RELU, OP_MUL = 154, 78, 190, 84, 107
 OP_RESIZE = 133
+OP_DECONV2D, OP_DEPTHWISE_DECONV2D, OP_GROUP_DECONV2D = 54, 55, 56
+LAYOUT_IOHW = 31
 RESIZE_BILINEAR, RESIZE_NEAREST_NEIGHBOR, RESIZE_NEAREST_BICUBIC = 0, 1, 2  # enum csinn_resize_enum
 
 SHL_NHWC, SHL_NCHW = 0, 1
@@ -41,6 +43,7 @@ POOL_MAX, POOL_AVG = 0, 1
 UNARY_SIGMOID, UNARY_HARD_SIGMOID, UNARY_SILU, UNARY_LEAKY_RELU = 0, 1, 2, 3
 ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2
 ALGO_AUTO, ALGO_DIRECT, ALGO_IGEMM, ALGO_DW, ALGO_GEMV, ALGO_STEM = 0, 1, 2, 3, 4, 5
+ALGO_DECONV_GATHER, ALGO_DECONV_PHASE = 8, 9
 
 
 class MI355XError(RuntimeError):
@@ -237,6 +240,9 @@ def load_hip():
         "shl_mi355x_conv_plan_create": (C.c_int, [C.POINTER(ConvDesc), vp, vp, vp, vp, C.POINTER(vp)]),
         "shl_mi355x_conv_plan_create_wzp": (C.c_int, [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, C.POINTER(vp)]),
         "shl_mi355x_conv_plan_create_dw_channel": (C.c_int, [C.POINTER(ConvDesc), vp, vp, vp, vp, f32, f32, vp, C.POINTER(vp)]),
+        "shl_mi355x_deconv_plan_create": (C.c_int, [C.POINTER(ConvDesc), vp, vp, vp, vp, C.POINTER(vp)]),
+        "shl_mi355x_deconv_kernel_name": (C.c_char_p, [C.POINTER(ConvDesc)]),
+        "shl_mi355x_deconv_geometry": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(i32), i32]),
         "shl_mi355x_debug_trace": (C.c_int, [vp, i32]),
         "shl_mi355x_debug_div_check": (C.c_int, [vp, i32, vp, vp]),
         "shl_mi355x_debug_f16_round_check": (C.c_int, [vp]),
@@ -322,7 +328,7 @@ _FRONTEND_SIGS = {
 _SISO_OPS = ("csinn_relu", "csinn_relu6", "csinn_global_avgpool2d", "csinn_softmax", "csinn_maxpool2d", "csinn_avgpool2d",
              "csinn_sigmoid", "csinn_hard_sigmoid", "csinn_silu", "csinn_leaky_relu", "csinn_resize")
 _CONV_OPS = ["csinn_conv2d", "csinn_conv2d_relu", "csinn_conv2d_relu6", "csinn_depthwise_conv2d",
-             "csinn_depthwise_conv2d_relu", "csinn_fullyconnected"] + list(_SISO_OPS)
+             "csinn_depthwise_conv2d_relu", "csinn_fullyconnected", "csinn_deconv2d"] + list(_SISO_OPS)
 
 
 def load_frontend(kind="standalone", local=False, path=None):
@@ -487,6 +493,16 @@ def conv_params(fe, keep, api, layout, stride=(1, 1), pad=(0, 0, 0, 0), dilation
     pc.pad_top, pc.pad_left, pc.pad_down, pc.pad_right = pad
     pc.dilation_height, pc.dilation_width = dilation
     pc.conv_extra.fuse_zp2bias = fuse_zp2bias
+    return p
+
+
+def deconv_params(fe, keep, api, layout, stride=(2, 2), pad=(0, 0, 0, 0), out_pad=(0, 0), group=1, dilation=(1, 1), sess=None,
+                  name=b"deconv"):
+    """params block of csinn_deconv2d (a csinn_conv2d_params); pad = (top, left, down, right), out_pad = (height, width):
+    the output size is the output tensor's, which the caller makes out_pad larger"""
+    p = conv_params(fe, keep, api, layout, stride, pad, dilation, group, 0, sess, name)
+    pc = C.cast(p, C.POINTER(Conv2dParams)).contents
+    pc.out_pad_height, pc.out_pad_width = out_pad
     return p
 
 

@@ -614,6 +614,17 @@ void patch_pack_weights(const shl_mi355x_conv_desc &d, int geom, const int8_t *s
 bool patch_setup(ConvArgs &a);                                      // fills pt_rows .. pt_spr for a.N; false: does not fit
 bool patch_auto(const ConvArgs &a, bool vs_wave = false);                                 // the automatic choice takes it (enough tiles)
 int launch_conv_igemm_patch(const ConvArgs &a, hipStream_t s);
+// transposed convolution (deconv.hip): one output per thread ("gather") or one ordinary small convolution per output phase on MFMA
+enum { DECONV_GATHER = 0, DECONV_PHASE = 1 };
+const char *deconv_invalid(const shl_mi355x_conv_desc *d, int *status);  // NULL: a deconvolution the library runs
+int deconv_form(const shl_mi355x_conv_desc &d, bool epilogue_ok, const char **why);  // the one place that chooses; -1: a forced form refused
+const char *deconv_form_name(int form, int dtype);
+int deconv_phases(const shl_mi355x_conv_desc &d);
+size_t deconv_phase_weight_bytes(const shl_mi355x_conv_desc &d);
+size_t deconv_phase_acc_bytes(const shl_mi355x_conv_desc &d);
+void deconv_pack_phase(const shl_mi355x_conv_desc &d, const char *ohwi, char *dst, int32_t *acc);
+int launch_deconv_gather(const ConvArgs &a, int dtype, int layout, hipStream_t s);
+int launch_deconv_phase(const ConvArgs &a, const shl_mi355x_conv_desc &d, hipStream_t s);
 // [N][R][S] -> [N][S][R] for 1- or 2-byte elements (layout.hip)
 int launch_transpose(const void *src, void *dst, int64_t n, int R, int S, int esize, hipStream_t s, int to_nhwc);
 

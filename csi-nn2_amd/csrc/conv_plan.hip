@@ -65,6 +65,12 @@ static int esize_of(const shl_mi355x_conv_desc &d) { return d.dtype == SHL_MI355
 
 static bool is_depthwise(const shl_mi355x_conv_desc &d) { return d.group > 1 && d.group == d.in_c; }
 
+// a transposed convolution's plan (deconv.hip): no partner of any pair or pool fusion
+static bool is_deconv(const shl_mi355x_conv_plan *p)
+{
+    return p->algo == SHL_MI355X_ALGO_DECONV_GATHER || p->algo == SHL_MI355X_ALGO_DECONV_PHASE;
+}
+
 static int validate(const shl_mi355x_conv_desc &d)
 {
     if (d.layout != SHL_MI355X_NHWC && d.layout != SHL_MI355X_NCHW) return SHL_MI355X_EINVAL;
@@ -149,6 +155,55 @@ static bool fma_division_ok(const shl_mi355x_conv_desc &d, const float *mult_hos
         if (!(bound <= 0x1p60f)) return false;  // also NaN
     }
     return true;
+}
+
+// The int8 epilogue a plan's tables admit, derived once for every kind of plan (convolution, transposed convolution): a power of
+// two output scale folded into the tables, or div_by_scale for a converter's scale; neither: only the kernels that carry the
+// hardware's division run the layer.
+static void derive_division(const shl_mi355x_conv_desc &d, const float *mult_host, const float *bias_host, bool *div_exact, bool *div_fma)
+{
+    *div_exact = pow2_fold_ok(d, mult_host, bias_host);
+    *div_fma = !*div_exact && fma_division_ok(d, mult_host, bias_host);
+}
+
+// ... and what the plan keeps of it: the flags, 1 / s, the clamp that stands for saturation + activation
+static void plan_set_epilogue(shl_mi355x_conv_plan *p, bool div_exact, bool div_fma)
+{
+    const shl_mi355x_conv_desc &d = p->desc;
+    p->inv_out_scale = 1.0f / d.out_scale;
+    if (d.dtype == SHL_MI355X_I8) {
+        p->div_exact = div_exact;
+        p->div_fma = div_fma;
+        p->clamp_lo = -128.0f;
+        p->clamp_hi = 127.0f;
+        p->act_clamp = d.act != SHL_MI355X_ACT_NONE && derive_act_clamp(d, &p->clamp_lo, &p->clamp_hi);
+    }
+}
+
+// the flags record, the pad page and the multiplier / bias tables of the host image of a plan's block
+static void plan_write_common(const shl_mi355x_conv_plan *p, char *host, bool tables, const float *mult_host, const float *bias_host)
+{
+    const shl_mi355x_conv_desc &d = p->desc;
+    PlanFlags f = {};
+    f.magic = PLAN_FLAGS_MAGIC;
+    f.div_exact = p->div_exact, f.div_fma = p->div_fma, f.act_clamp = p->act_clamp;
+    f.clamp_lo = p->clamp_lo, f.clamp_hi = p->clamp_hi, f.inv_out_scale = p->inv_out_scale;
+    f.pt_geom = p->pt_geom;
+    f.algo = p->algo, f.kstride = p->kstride, f.block_bytes = p->block_bytes;
+    memcpy(host + p->off_flags, &f, sizeof(f));
+    // padding value: the input zero point (int8) / 0.0 (f16)
+    memset(host + p->off_pad, d.dtype == SHL_MI355X_I8 ? (d.in_zp & 0xFF) : 0, PAD_PAGE_BYTES);
+    if (!tables) return;
+    float *mult = reinterpret_cast<float *>(host + p->off_mult);
+    float *bias = reinterpret_cast<float *>(host + p->off_bias);
+    for (int oc = 0; oc < d.out_c; ++oc) {
+        mult[oc] = mult_host ? mult_host[oc] : 1.0f;
+        bias[oc] = bias_host ? bias_host[oc] : 0.0f;
+        if (p->div_exact) {  // see pow2_fold_ok
+            mult[oc] *= p->inv_out_scale;
+            bias[oc] *= p->inv_out_scale;
+        }
+    }
 }
 
 static int choose_algo(const shl_mi355x_conv_desc &d)
@@ -382,8 +437,8 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
     }
     // int8 output scales: a power of two, or a converter's scale in the range div_by_scale handles -- anything else
     // (out_scale or multipliers beyond 2^+-40) keeps the hardware's division, which only the direct kernel carries
-    const bool i8_div_exact = pow2_fold_ok(d, mult_host, bias_host);
-    const bool i8_div_fma = !i8_div_exact && fma_division_ok(d, mult_host, bias_host);
+    bool i8_div_exact, i8_div_fma;
+    derive_division(d, mult_host, bias_host, &i8_div_exact, &i8_div_fma);
     const bool fast_epilogue_ok = d.dtype != SHL_MI355X_I8 || i8_div_exact || i8_div_fma;
     // asymmetric int8 weights (a non-zero kernel zero point in any record): sum (q - zp_in) (w - zp_k[oc]) over the
     // in-image taps, which only the one-output-per-thread kernels compute (the MFMA / depthwise kernels fold zp_in into
@@ -564,14 +619,7 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
     }
     p->off_flags = align_up(p->block_bytes, 256);
     p->block_bytes = p->off_flags + sizeof(PlanFlags);
-    p->inv_out_scale = 1.0f / d.out_scale;
-    if (d.dtype == SHL_MI355X_I8) {
-        p->div_exact = i8_div_exact;
-        p->div_fma = i8_div_fma;
-        p->clamp_lo = -128.0f;
-        p->clamp_hi = 127.0f;
-        p->act_clamp = d.act != SHL_MI355X_ACT_NONE && derive_act_clamp(d, &p->clamp_lo, &p->clamp_hi);
-    }
+    plan_set_epilogue(p, i8_div_exact, i8_div_fma);
 
     hipError_t e = hipMalloc((void **)&p->block, p->block_bytes);
     if (e != hipSuccess) {
@@ -580,17 +628,7 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
     }
 
     std::vector<char> host(p->block_bytes, 0);
-    {
-        PlanFlags f = {};
-        f.magic = PLAN_FLAGS_MAGIC;
-        f.div_exact = p->div_exact, f.div_fma = p->div_fma, f.act_clamp = p->act_clamp;
-        f.clamp_lo = p->clamp_lo, f.clamp_hi = p->clamp_hi, f.inv_out_scale = p->inv_out_scale;
-        f.pt_geom = p->pt_geom;
-        f.algo = algo, f.kstride = p->kstride, f.block_bytes = p->block_bytes;
-        memcpy(host.data() + p->off_flags, &f, sizeof(f));
-    }
-    // padding value: the input zero point (int8) / 0.0 (f16)
-    memset(host.data() + p->off_pad, d.dtype == SHL_MI355X_I8 ? (d.in_zp & 0xFF) : 0, PAD_PAGE_BYTES);
+    plan_write_common(p, host.data(), kernel_host != nullptr, mult_host, bias_host);
     if (kernel_host) {
         const char *src = static_cast<const char *>(kernel_host);
         if (algo == SHL_MI355X_ALGO_IGEMM) {
@@ -615,17 +653,7 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
         else
             memcpy(host.data() + p->off_w, src, raw_w);
         int32_t *acc = reinterpret_cast<int32_t *>(host.data() + p->off_acc);
-        float *mult = reinterpret_cast<float *>(host.data() + p->off_mult);
-        float *bias = reinterpret_cast<float *>(host.data() + p->off_bias);
-        for (int oc = 0; oc < d.out_c; ++oc) {
-            mult[oc] = mult_host ? mult_host[oc] : 1.0f;
-            bias[oc] = bias_host ? bias_host[oc] : 0.0f;
-            if (p->div_exact) {  // see pow2_fold_ok
-                mult[oc] *= p->inv_out_scale;
-                bias[oc] *= p->inv_out_scale;
-            }
-            acc[oc] = w_asym ? kernel_zp[oc] : 0;  // DIRECT / GROUP: the kernel's zero point per output channel
-        }
+        for (int oc = 0; oc < d.out_c; ++oc) acc[oc] = w_asym ? kernel_zp[oc] : 0;  // DIRECT / GROUP: the kernel's zero point per output channel
         if (algo == SHL_MI355X_ALGO_STEM) {
             // padding is materialised as zp_in here too
             const int8_t *w8 = reinterpret_cast<const int8_t *>(src);
@@ -709,6 +737,80 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
         }
     }
     if (algo == SHL_MI355X_ALGO_IGEMM && kernel_host) tune_plan(p, (hipStream_t)stream, rules_need_pix_tab);
+    *plan_out = p;
+    return SHL_MI355X_OK;
+}
+
+/* transposed convolution (deconv.hip): desc->in_* / out_* are the deconvolution's own, group is 1 or in_c */
+int shl_mi355x_deconv_plan_create(const struct shl_mi355x_conv_desc *desc, const void *kernel_host, const float *mult_host,
+                                  const float *bias_host, void *stream, shl_mi355x_conv_plan **plan_out)
+{
+    if (!desc || !plan_out) {
+        set_error("deconv_plan_create: NULL argument");
+        return SHL_MI355X_EINVAL;
+    }
+    *plan_out = nullptr;
+    int st;
+    const char *why = deconv_invalid(desc, &st);
+    if (why) {
+        set_error("deconv_plan_create: %s", why);
+        return st;
+    }
+    const shl_mi355x_conv_desc &d = *desc;
+    if (d.dtype == SHL_MI355X_I8 && kernel_host && !mult_host) {
+        set_error("deconv_plan_create: int8 needs the per-channel multiplier table");
+        return SHL_MI355X_EINVAL;
+    }
+    bool div_exact, div_fma;
+    derive_division(d, mult_host, bias_host, &div_exact, &div_fma);
+    const int form = deconv_form(d, d.dtype != SHL_MI355X_I8 || div_exact || div_fma, &why);
+    if (form < 0) {
+        set_error("deconv_plan_create: %s", why);
+        return SHL_MI355X_ENOTSUP;
+    }
+    shl_mi355x_conv_plan *p = (shl_mi355x_conv_plan *)calloc(1, sizeof(*p));
+    if (!p) return SHL_MI355X_ENOMEM;
+    p->desc = d;
+    p->algo = form == DECONV_PHASE ? SHL_MI355X_ALGO_DECONV_PHASE : SHL_MI355X_ALGO_DECONV_GATHER;
+    p->kernel_name = deconv_form_name(form, d.dtype);
+    const int es = esize_of(d);
+    const size_t raw_w = (size_t)d.out_c * (d.in_c / d.group) * d.kernel_h * d.kernel_w * es;
+    const size_t tab_bytes = align_up((size_t)d.out_c, 128) * 4;
+    // gather: the kernel tensor as it is, no accumulator table; phase: the fragment-ordered copy and acc_init per phase
+    p->off_w = 0;
+    p->off_acc = align_up(form == DECONV_PHASE ? 0 : raw_w, 256);
+    p->off_mult = p->off_acc + (form == DECONV_PHASE ? align_up(deconv_phase_acc_bytes(d), 256) : tab_bytes);
+    p->off_bias = p->off_mult + tab_bytes;
+    p->off_pad = p->off_bias + tab_bytes;
+    p->block_bytes = p->off_pad + PAD_PAGE_BYTES;
+    if (form == DECONV_PHASE) {
+        p->off_wfrag = p->block_bytes;
+        p->block_bytes += deconv_phase_weight_bytes(d);
+    }
+    p->off_flags = align_up(p->block_bytes, 256);
+    p->block_bytes = p->off_flags + sizeof(PlanFlags);
+    plan_set_epilogue(p, div_exact, div_fma);
+    std::vector<char> host(p->block_bytes, 0);
+    plan_write_common(p, host.data(), kernel_host != nullptr, mult_host, bias_host);
+    if (kernel_host) {
+        if (form == DECONV_PHASE)
+            deconv_pack_phase(d, static_cast<const char *>(kernel_host), host.data() + p->off_wfrag,
+                              reinterpret_cast<int32_t *>(host.data() + p->off_acc));
+        else
+            memcpy(host.data() + p->off_w, kernel_host, raw_w);
+    }
+    hipError_t e = hipMalloc((void **)&p->block, p->block_bytes);
+    if (e != hipSuccess) {
+        free(p);
+        return hip_fail(e, "hipMalloc(plan block)");
+    }
+    e = hipMemcpyAsync(p->block, host.data(), p->block_bytes, hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) {
+        (void)hipFree(p->block);
+        free(p);
+        return hip_fail(e, "upload(plan block)");
+    }
     *plan_out = p;
     return SHL_MI355X_OK;
 }
@@ -976,6 +1078,10 @@ static int conv_forward_impl(const shl_mi355x_conv_plan *plan, const void *input
             return launch_dwconv_channel(a, s);
         case SHL_MI355X_ALGO_GROUP:
             return launch_conv_group_direct(a, d.dtype, d.layout, s);
+        case SHL_MI355X_ALGO_DECONV_GATHER:
+            return launch_deconv_gather(a, d.dtype, d.layout, s);
+        case SHL_MI355X_ALGO_DECONV_PHASE:
+            return launch_deconv_phase(a, d, s);
         default:
             return launch_conv_direct(a, d.dtype, d.layout,
                                       is_depthwise(d) && d.layout == SHL_MI355X_NHWC, s);
@@ -1107,7 +1213,7 @@ int shl_mi355x_conv_pool_forward(const shl_mi355x_conv_plan *plan, const void *i
 /* pointwise 1x1 + the depthwise 3x3 consuming it, fused into one launch */
 int shl_mi355x_pwdw_form(const shl_mi355x_conv_plan *pw, const shl_mi355x_conv_plan *dw, int32_t batch)
 {
-    if (!dw || !pw) return 0;
+    if (!dw || !pw || is_deconv(pw) || is_deconv(dw)) return 0;
     static const char *off = getenv("SHL_MI355X_NO_FUSION");
     static const char *sel = getenv("SHL_MI355X_PWDW");  // "0": keep pointwise and depthwise launches apart
     if ((off && off[0] == '1') || (sel && sel[0] == '0')) return 0;

@@ -132,6 +132,34 @@ EST_CONV(shl_gref_depthwise_conv2d_relu6, CSINN_OP_DEPTHWISE_CONV2D_RELU6)
 EST_CONV(shl_gref_group_conv2d, CSINN_OP_GROUP_CONV2D)
 EST_CONV(shl_gref_group_conv2d_relu, CSINN_OP_GROUP_CONV2D_RELU)
 EST_CONV(shl_gref_group_conv2d_relu6, CSINN_OP_GROUP_CONV2D_RELU6)
+EST_CONV(shl_gref_deconv2d, CSINN_OP_DECONV2D)
+EST_CONV(shl_gref_depthwise_deconv2d, CSINN_OP_DEPTHWISE_DECONV2D)
+EST_CONV(shl_gref_group_deconv2d, CSINN_OP_GROUP_DECONV2D)
+
+/* the output shape of a transposed convolution (source/graph_ref/deconvolution.c:29-68 of the reference):
+ * out = (in - 1) * stride - (pad_a + pad_b) + dilation * (K - 1) + 1; channels from the kernel tensor */
+int shl_gref_deconv2d_infer_shape(CSINN_CONV_ARGS)
+{
+    (void)bias;
+    int c, h, w, kernel_oc;
+    if (input->layout == CSINN_LAYOUT_NCHW) {
+        c = 1, h = 2, w = 3;
+        kernel_oc = params->group == input->dim[c] ? kernel->dim[0] : kernel->dim[1];
+    } else if (input->layout == CSINN_LAYOUT_NHWC) {
+        h = 1, w = 2, c = 3;
+        kernel_oc = params->group == input->dim[c] ? kernel->dim[3] : kernel->dim[0];
+    } else {
+        return CSINN_UNSUPPORT_LAYOUT;
+    }
+    output->dim_count = 4;
+    output->dim[0] = input->dim[0];
+    output->dim[c] = kernel_oc;
+    output->dim[h] = (input->dim[h] - 1) * params->stride_height - (params->pad_top + params->pad_down) +
+                     params->dilation_height * (kernel->dim[h] - 1) + 1;
+    output->dim[w] = (input->dim[w] - 1) * params->stride_width - (params->pad_left + params->pad_right) +
+                     params->dilation_width * (kernel->dim[w] - 1) + 1;
+    return CSINN_TRUE;
+}
 
 int shl_gref_fullyconnected(struct csinn_tensor *input, struct csinn_tensor *output,
                             struct csinn_tensor *weights, struct csinn_tensor *bias,
@@ -292,6 +320,9 @@ int shl_gref_call_layer_func(void *fn, struct shl_node *node)
         case CSINN_OP_GROUP_CONV2D:
         case CSINN_OP_GROUP_CONV2D_RELU:
         case CSINN_OP_GROUP_CONV2D_RELU6:
+        case CSINN_OP_DECONV2D:
+        case CSINN_OP_DEPTHWISE_DECONV2D:
+        case CSINN_OP_GROUP_DECONV2D:
         case CSINN_OP_FULLYCONNECTED:
             return f(node->in[0]->data, node->out[0]->data, node->in[1]->data, node->in[2]->data,
                      params);
@@ -311,7 +342,7 @@ struct csinn_callback *shl_gref_best_callback(struct shl_node *node)
     return params->cb;
 }
 
-static struct csinn_callback g_est_only[24];
+static struct csinn_callback g_est_only[32];
 
 static struct csinn_callback *gref_cb_map(int op, int dtype)
 {
@@ -326,6 +357,9 @@ static struct csinn_callback *gref_cb_map(int op, int dtype)
         {CSINN_OP_GROUP_CONV2D, shl_gref_group_conv2d},
         {CSINN_OP_GROUP_CONV2D_RELU, shl_gref_group_conv2d_relu},
         {CSINN_OP_GROUP_CONV2D_RELU6, shl_gref_group_conv2d_relu6},
+        {CSINN_OP_DECONV2D, shl_gref_deconv2d},
+        {CSINN_OP_DEPTHWISE_DECONV2D, shl_gref_depthwise_deconv2d},
+        {CSINN_OP_GROUP_DECONV2D, shl_gref_group_deconv2d},
         {CSINN_OP_FULLYCONNECTED, shl_gref_fullyconnected},
         {CSINN_OP_RELU, shl_gref_relu},
         {CSINN_OP_RELU6, shl_gref_relu6},
@@ -342,6 +376,7 @@ static struct csinn_callback *gref_cb_map(int op, int dtype)
         {CSINN_OP_MUL, shl_gref_mul},
         {CSINN_OP_RESIZE, shl_gref_resize},
     };
+    _Static_assert(sizeof(table) / sizeof(table[0]) <= sizeof(g_est_only) / sizeof(g_est_only[0]), "one callback block per table row");
     for (unsigned i = 0; i < sizeof(table) / sizeof(table[0]); i++) {
         if (table[i].op == op) {
             g_est_only[i].est = table[i].est;

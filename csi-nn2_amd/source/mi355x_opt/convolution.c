@@ -24,8 +24,8 @@
 #include "mi355x_internal.h"
 
 int shl_mi355x_group_conv2d_exec(CSINN_CONV_ARGS);
-static int run_plan(struct csinn_params_base *base, struct csinn_tensor *input, struct csinn_tensor *output, int batch,
-                    const char *what);
+#define run_plan shl_mi355x_run_plan
+#define build_tables shl_mi355x_conv_build_tables
 
 /* ------------------------------------------------------------------------ descriptor */
 
@@ -47,7 +47,7 @@ static int scale_is_one(float s) { return fabsf(s - 1.0f) <= 1.1920929e-07f; }
 
 /* fp32 image of the bias as the reference computes it, and the per-channel multipliers.
  * Returns CSINN_TRUE or a negative status. */
-static int build_tables(const struct shl_mi355x_conv_desc *d, struct csinn_tensor *input,
+int build_tables(const struct shl_mi355x_conv_desc *d, struct csinn_tensor *input,
                         struct csinn_tensor *kernel, struct csinn_tensor *bias, int fuse_zp2bias,
                         int dw_weights_last, float *mult, float *bias_f, int32_t *kzp)
 {
@@ -283,6 +283,13 @@ int shl_mi355x_conv2d_fold_activation(struct csinn_tensor *input, struct csinn_t
                                       struct csinn_conv2d_params *params, int relu6)
 {
     if (shl_mi355x_registry_get(params) == NULL) return CSINN_FALSE; /* grouped / never initialised */
+    if (!shl_mi355x_activation_folds(conv_output, output)) return CSINN_FALSE;
+    return conv_init_common(input, output, kernel, bias, params, relu6 ? SHL_MI355X_ACT_RELU6 : SHL_MI355X_ACT_RELU);
+}
+
+/* the conditions under which a relu / relu6 layer is its producer's fused activation: same tensor, same record */
+int shl_mi355x_activation_folds(struct csinn_tensor *conv_output, struct csinn_tensor *output)
+{
     if (conv_output->qinfo == NULL || output->qinfo == NULL || conv_output->quant_channel > 1 || output->quant_channel > 1)
         return CSINN_FALSE;
     if (conv_output->dtype != output->dtype || conv_output->dim_count != output->dim_count) return CSINN_FALSE;
@@ -291,11 +298,11 @@ int shl_mi355x_conv2d_fold_activation(struct csinn_tensor *input, struct csinn_t
     if (conv_output->qinfo->scale != output->qinfo->scale) return CSINN_FALSE;
     if (output->dtype == CSINN_DTYPE_INT8 && conv_output->qinfo->zero_point != output->qinfo->zero_point) return CSINN_FALSE;
     if (output->dtype == CSINN_DTYPE_FLOAT16 && !scale_is_one(output->qinfo->scale)) return CSINN_FALSE;
-    return conv_init_common(input, output, kernel, bias, params, relu6 ? SHL_MI355X_ACT_RELU6 : SHL_MI355X_ACT_RELU);
+    return CSINN_TRUE;
 }
 
-static int run_plan(struct csinn_params_base *base, struct csinn_tensor *input, struct csinn_tensor *output,
-                    int batch, const char *what)
+int run_plan(struct csinn_params_base *base, struct csinn_tensor *input, struct csinn_tensor *output,
+             int batch, const char *what)
 {
     shl_mi355x_conv_plan *plan = shl_mi355x_registry_get(base);
     if (plan == NULL) {

@@ -70,5 +70,22 @@ int shl_mi355x_conv2d_fold_activation(struct csinn_tensor *input, struct csinn_t
                                       struct csinn_conv2d_params *params, int relu6);
 int shl_mi355x_conv2d_relu_init(CSINN_CONV_ARGS);
 int shl_mi355x_conv2d_relu6_init(CSINN_CONV_ARGS);
+/* ... the conditions of that fold (same dims, same record; binary16: scale 1), and the same fold for a transposed convolution
+ * (deconvolution.c) */
+int shl_mi355x_activation_folds(struct csinn_tensor *conv_output, struct csinn_tensor *output);
+int shl_mi355x_deconv2d_fold_activation(struct csinn_tensor *input, struct csinn_tensor *deconv_output,
+                                        struct csinn_tensor *output, struct csinn_tensor *kernel, struct csinn_tensor *bias,
+                                        struct csinn_conv2d_params *params, int relu6);
+
+/* convolution.c, shared with deconvolution.c: the per-output-channel fp32 tables of the numerical contract from the tensors'
+ * records (dw_weights_last: the kernel's channel is its LAST dim), and exec of the plan registered under `base` (host
+ * staging, DMABUF tensors, SHL_MI355X_TRACE_EXEC) */
+int shl_mi355x_conv_build_tables(const struct shl_mi355x_conv_desc *d, struct csinn_tensor *input, struct csinn_tensor *kernel,
+                                 struct csinn_tensor *bias, int fuse_zp2bias, int dw_weights_last, float *mult, float *bias_f,
+                                 int32_t *kzp);
+int shl_mi355x_run_plan(struct csinn_params_base *base, struct csinn_tensor *input, struct csinn_tensor *output, int batch,
+                        const char *what);
+int shl_mi355x_deconv2d_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_tensor *kernel,
+                             struct csinn_tensor *bias, struct csinn_conv2d_params *params, struct csinn_perf_info *info);
 
 #endif /* MI355X_INTERNAL_H_ */

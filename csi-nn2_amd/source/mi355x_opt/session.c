@@ -135,6 +135,8 @@ static const struct session_op g_ops[] = {
     {CSINN_OP_GROUP_CONV2D, shl_mi355x_group_conv2d_exec, CALL_CONV, 1, 1},
     {CSINN_OP_GROUP_CONV2D_RELU, shl_mi355x_group_conv2d_exec, CALL_CONV, 1, 1},
     {CSINN_OP_GROUP_CONV2D_RELU6, shl_mi355x_group_conv2d_exec, CALL_CONV, 1, 1},
+    {CSINN_OP_DECONV2D, shl_mi355x_deconv2d_exec, CALL_CONV, 1, 1}, /* the learned upsampling of a decoder */
+    {CSINN_OP_DEPTHWISE_DECONV2D, shl_mi355x_deconv2d_exec, CALL_CONV, 1, 1},
     {CSINN_OP_FULLYCONNECTED, shl_mi355x_fullyconnected_exec, CALL_CONV, 1, 1},
     {CSINN_OP_RELU, shl_mi355x_relu_exec, CALL_SISO, 1, 1},
     {CSINN_OP_RELU6, shl_mi355x_relu6_exec, CALL_SISO, 1, 1},
@@ -255,7 +257,7 @@ static enum step_kind merged_kind(struct shl_ref_graph *g, const struct step *s,
 }
 
 /* Graph-level rewrites; the intermediate tensors then never exist in HBM:
- *   conv / depthwise (no activation) -> relu | relu6, the convolution's only consumer, same output record
+ *   conv / depthwise / deconv2d (no activation) -> relu | relu6, the convolution's only consumer, same output record
  *        the activation moves into the convolution's epilogue (the relu layer gets no step, the convolution's step writes
  *        the relu's output): what a converter emits for a RISC-V target -- example/c906_mobilenetv1_f16.c is
  *        28 csinn_conv2d + 27 csinn_relu -- runs as 28 launches, not 55
@@ -277,10 +279,14 @@ static int plan_fusion(struct dev_session *ds, struct shl_ref_graph *g)
         struct step *s = &steps[ns++];
         *s = (struct step){STEP_LAYER, i, -1, a->out[0]};
         const int plain = a->type == CSINN_OP_CONV2D || a->type == CSINN_OP_DEPTHWISE_CONV2D;
-        if (!fold || !plain || b == NULL || (b->type != CSINN_OP_RELU && b->type != CSINN_OP_RELU6)) continue;
+        const int deconv = a->type == CSINN_OP_DECONV2D || a->type == CSINN_OP_DEPTHWISE_DECONV2D;
+        if (!fold || !(plain || deconv) || b == NULL || (b->type != CSINN_OP_RELU && b->type != CSINN_OP_RELU6)) continue;
         if (b->in[0] != a->out[0] || consumers_of(g, a->out[0]) != 1) continue;
-        if (shl_mi355x_conv2d_fold_activation(a->in[0]->data, a->out[0]->data, b->out[0]->data, a->in[1]->data,
-                                              a->in[2]->data, a->data, b->type == CSINN_OP_RELU6) == CSINN_TRUE) {
+        int (*const fold_activation)(struct csinn_tensor *, struct csinn_tensor *, struct csinn_tensor *, struct csinn_tensor *,
+                                     struct csinn_tensor *, struct csinn_conv2d_params *, int) =
+            deconv ? shl_mi355x_deconv2d_fold_activation : shl_mi355x_conv2d_fold_activation;
+        if (fold_activation(a->in[0]->data, a->out[0]->data, b->out[0]->data, a->in[1]->data, a->in[2]->data, a->data,
+                            b->type == CSINN_OP_RELU6) == CSINN_TRUE) {
             s->out = b->out[0];
             ds->nfolded++;
             i++; /* the activation layer is taken */

@@ -12,7 +12,7 @@
 #include "mi355x_internal.h"
 
 /* ------------------------------------------------------------------------ callback table */
-#define MI355X_CB_MAX 64
+#define MI355X_CB_MAX 96
 static struct {
     int key; /* op * CSINN_DTYPE_SIZE + dtype */
     struct csinn_callback cb;
@@ -605,6 +605,11 @@ void shl_target_init_mi355x(void)
         if (shl_gref_group_conv2d_relu6)
             reg(dt, CSINN_OP_GROUP_CONV2D_RELU6, shl_mi355x_conv2d_relu6_init, shl_mi355x_group_conv2d_exec,
                 shl_gref_group_conv2d_relu6, conv_perf);
+        reg(dt, CSINN_OP_DECONV2D, shl_mi355x_deconv2d_init, shl_mi355x_deconv2d_exec, shl_gref_deconv2d, shl_mi355x_deconv2d_perf);
+        reg(dt, CSINN_OP_DEPTHWISE_DECONV2D, shl_mi355x_deconv2d_init, shl_mi355x_deconv2d_exec, shl_gref_depthwise_deconv2d,
+            shl_mi355x_deconv2d_perf);
+        /* (refused at init with a message: next to libshl the layer then runs on the reference's kernel) */
+        reg(dt, CSINN_OP_GROUP_DECONV2D, shl_mi355x_deconv2d_init, shl_mi355x_deconv2d_exec, shl_gref_group_deconv2d, shl_mi355x_deconv2d_perf);
         reg(dt, CSINN_OP_FULLYCONNECTED, shl_mi355x_fullyconnected_init,
             shl_mi355x_fullyconnected_exec, shl_gref_fullyconnected, conv_perf);
     }

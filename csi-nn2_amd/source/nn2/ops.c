@@ -10,6 +10,7 @@
  *   maxpool2d / avgpool2d  source/nn2/maxpool.c, averagepool.c
  *   concat ............ source/nn2/concat.c
  *   resize ............ source/nn2/resize.c
+ *   deconv2d .......... source/nn2/deconvolution.c
  *   sigmoid / hard_sigmoid / silu / leaky_relu / mul  source/nn2/sigmoid.c, hard_sigmoid.c, silu.c, leaky_relu.c, mul.c
  * The only deliberate difference: a missing callback is reported (CSINN_CALLBACK_UNSET and an
  * error message) instead of being dereferenced.
@@ -279,6 +280,23 @@ int csinn_mul(struct csinn_tensor *input0, struct csinn_tensor *input1, struct c
 {
     return run4(&params->base, input0, input1, output, params);
 }
+
+/* source/nn2/deconvolution.c:26-46 of the reference: the op id by the group count alone, and the init callback's status
+ * is dropped -- a layer whose init refused it is left with a callback that fails at csinn_deconv2d */
+int csinn_deconv2d_init(CSINN_CONV_ARGS)
+{
+    const int nchw = params->base.layout == CSINN_LAYOUT_NCHW, nhwc = params->base.layout == CSINN_LAYOUT_NHWC;
+    int op;
+    if (params->group == 1) op = CSINN_OP_DECONV2D;
+    else if ((nchw && params->group == input->dim[1]) || (nhwc && params->group == input->dim[3])) op = CSINN_OP_DEPTHWISE_DECONV2D;
+    else if ((nchw && params->group == output->dim[1]) || (nhwc && params->group == output->dim[3])) op = CSINN_OP_GROUP_DECONV2D;
+    else return CSINN_FALSE;
+    if (shl_op_callback_map(&params->base, op, input->dtype) != CSINN_TRUE) return CSINN_TRUE; /* (csinn_deconv2d reports it) */
+    int (*init)() = shl_get_init_cb(&params->base);
+    if (init != NULL) init(input, output, kernel, bias, params);
+    return CSINN_TRUE;
+}
+int csinn_deconv2d(CSINN_CONV_ARGS) { return run5(&params->base, input, output, kernel, bias, params); }
 
 /* source/nn2/resize.c of the reference: one input, one output */
 int csinn_resize_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_resize_params *params)

@@ -71,6 +71,12 @@ int csinn_mul_init(struct csinn_tensor *input0, struct csinn_tensor *input1, str
                    struct csinn_diso_params *params);
 int csinn_mul(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
               struct csinn_diso_params *params);
+/* transposed convolution (source/nn2/deconvolution.c of the reference): group == 1 is CSINN_OP_DECONV2D, group == Cin
+ * CSINN_OP_DEPTHWISE_DECONV2D, group == Cout CSINN_OP_GROUP_DECONV2D, anything else CSINN_FALSE; kernel [O,Kh,Kw,I] (NHWC) /
+ * [I,O,Kh,Kw] (NCHW), depthwise [1,Kh,Kw,C] / [C,1,Kh,Kw]; the output size is the output tensor's.  As in the reference the
+ * init callback's status is not returned: a layer the backend refused fails at csinn_deconv2d */
+int csinn_deconv2d_init(CSINN_CONV_ARGS);
+int csinn_deconv2d(CSINN_CONV_ARGS);
 /* nearest-neighbour / bilinear resize to the output tensor's height and width (source/nn2/resize.c of the reference) */
 int csinn_resize_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_resize_params *params);
 int csinn_resize(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_resize_params *params);

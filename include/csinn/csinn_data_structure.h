@@ -132,6 +132,9 @@ enum csinn_op_enum {
     CSINN_OP_GROUP_CONV2D_RELU6 = 44,
     CSINN_OP_GROUP_CONV2D_CHANNEL = 45,
     CSINN_OP_GROUP_CONV2D_CHANNEL_RELU = 46,
+    CSINN_OP_DECONV2D = 54, /* transposed convolution: group == 1 / == Cin / == Cout (csinn_deconv2d_init) */
+    CSINN_OP_DEPTHWISE_DECONV2D = 55,
+    CSINN_OP_GROUP_DECONV2D = 56,
     CSINN_OP_FULLYCONNECTED = 71,
     CSINN_OP_GLOBAL_AVGPOOL2D = 74,
     CSINN_OP_HARD_SIGMOID = 78,
@@ -199,7 +202,8 @@ enum csinn_layout_enum {
     CSINN_LAYOUT_OWI = 17,
     CSINN_LAYOUT_OHWI = 18,
     CSINN_LAYOUT_ODHWI = 21,
-    CSINN_LAYOUT_1HWO = 22 /* depthwise kernel [1,Kh,Kw,Cout] */
+    CSINN_LAYOUT_1HWO = 22, /* depthwise kernel [1,Kh,Kw,Cout] */
+    CSINN_LAYOUT_IOHW = 31  /* deconv2d kernel of an NCHW model [Cin,Cout,Kh,Kw] */
 };
 
 enum csinn_status_enum {

@@ -71,7 +71,10 @@ enum shl_mi355x_algo {
      *   NHWC  the buffers are G consecutive tensors [N, H, W, C/G] -> [N, Ho, Wo, Cout/G] (NOT channel-interleaved
      *         groups): restated literally, identical results are the contract.
      * Never chosen by ALGO_AUTO: a descriptor with group > 1 alone cannot say which of the two the caller means */
-    SHL_MI355X_ALGO_GROUP = 7
+    SHL_MI355X_ALGO_GROUP = 7,
+    /* transposed convolution (shl_mi355x_deconv_plan_create; never chosen for a convolution descriptor) */
+    SHL_MI355X_ALGO_DECONV_GATHER = 8, /* one output element per thread, any shape (VALU) */
+    SHL_MI355X_ALGO_DECONV_PHASE = 9   /* one ordinary small convolution per output phase on MFMA, no LDS */
 };
 
 /* ------------------------------------------------------------------------------------
@@ -236,6 +239,40 @@ int shl_mi355x_conv_plan_create_dw_channel(const struct shl_mi355x_conv_desc *de
                                            const float *kernel_scale, const int32_t *kernel_zp,
                                            const int32_t *bias_i32, float in_scale, float out_scale_ms,
                                            void *stream, shl_mi355x_conv_plan **plan_out);
+
+/*
+ * Plan for a transposed convolution: CSINN_OP_DECONV2D / CSINN_OP_DEPTHWISE_DECONV2D, shl_ref_deconv2d_quant /
+ * shl_ref_depthwise_deconv2d_quant (source/reference/deconvolution.c:21-175, 334-369).
+ *   out[n, iy*stride_h - pad_top + ky, ix*stride_w - pad_left + kx, oc] += in[n, iy, ix, ic] * w[oc, ky, kx, ic]
+ * with the epilogue of shl_mi355x_conv_forward (int8: exact int32 sum of (q - in_zp) * w, then mult / bias / requantise /
+ * relu; binary16: fp32 sum in the reference's order, its own rounding).  desc->in_* and out_* are the deconvolution's own
+ * input and output; the output extents are free (output_padding is a larger output, positions that no tap reaches hold
+ * the bias alone) up to the typo guard
+ *       out_h <= (in_h - 1) * stride_h + kernel_h + stride_h      (and the same in w)
+ * -- no padding lets the operator reach further than (in - 1) * stride + kernel, one more stride is room for any
+ * output_padding; larger is SHL_MI355X_EINVAL, as are non-positive extents.  group is 1 or in_c (depthwise: out_c == in_c),
+ * dilation must be 1, desc->algo is ignored: anything else is SHL_MI355X_ENOTSUP.  Every refusal happens before the first
+ * device call.
+ *   kernel_host   group 1: [O, Kh, Kw, I] (NHWC) / [I, O, Kh, Kw] (NCHW); depthwise: [1, Kh, Kw, C] / [C, 1, Kh, Kw]
+ *   mult_host     int8: out_c floats s_in * s_kernel[oc];  bias_host: out_c floats or NULL -- as for shl_mi355x_conv_plan_create
+ * Two kernel forms (csrc/deconv.hip): "deconv_phase_*" (MFMA; NHWC, group 1, in_c * element size a multiple
+ * of 32, int8 tables in the range of the fast epilogue) and "deconv_gather_*" (everything).  SHL_MI355X_DECONV_FORM=gather
+ * | phase forces one; a forced phase form on a layer it does not take is SHL_MI355X_ENOTSUP.
+ * The plan runs through shl_mi355x_conv_forward / _destroy / _algo / _kernel_name / _bytes / _const_block / _adopt_block
+ * like any other and is independent of the batch; the pool and pair fusion queries answer 0 for it.
+ */
+int shl_mi355x_deconv_plan_create(const struct shl_mi355x_conv_desc *desc, const void *kernel_host, const float *mult_host,
+                                  const float *bias_host, void *stream, shl_mi355x_conv_plan **plan_out);
+/* the kernel the rules (and the switch) choose for the descriptor, without a device: "" when the descriptor is refused.
+ * (A plan whose int8 tables lie outside 2^-40 .. 2^40 runs the gather form whatever this says.) */
+const char *shl_mi355x_deconv_kernel_name(const struct shl_mi355x_conv_desc *desc);
+/* The phase decomposition of the descriptor, read-only and without a device, so that it can be checked on the CPU:
+ *   out[0] form (0 gather, 1 phase), out[1] P = stride_h * stride_w phases, then per phase (py major)
+ *   py, px, taps in y, taps in x, phase rows, phase columns       -- phase (py, px) owns the outputs with
+ *       (oy + pad_top) % stride_h == py and (ox + pad_left) % stride_w == px, its taps are ky = py + j * stride_h < Kh
+ *   then the tiles of 32 pixels x 32 channels over all phases for desc->batch images, and the workgroups of the phase
+ *   form's launch (four tiles each, every phase given the largest phase's share).  count >= 4 + 6 * P. */
+int shl_mi355x_deconv_geometry(const struct shl_mi355x_conv_desc *desc, int32_t *out, int32_t count);
 
 int shl_mi355x_conv_plan_destroy(shl_mi355x_conv_plan *plan);
 /* the algorithm the plan resolved to (enum shl_mi355x_algo) and its kernel name */

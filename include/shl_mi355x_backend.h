@@ -66,6 +66,12 @@ const char *shl_mi355x_params_kernel_name(void *params);
 /* init / exec callbacks (exported so that a reference-side setup.c can list them) */
 int shl_mi355x_conv2d_init(CSINN_CONV_ARGS);
 int shl_mi355x_conv2d_exec(CSINN_CONV_ARGS);
+/* transposed convolution (source/mi355x_opt/deconvolution.c): CSINN_OP_DECONV2D and CSINN_OP_DEPTHWISE_DECONV2D, int8 and
+ * fp16, NHWC and NCHW.  Refused at init (the layer then runs on the reference where libshl is loaded, and fails at exec
+ * otherwise): CSINN_OP_GROUP_DECONV2D, a non-zero kernel zero point, per-channel kernel records on an NCHW group-1 kernel
+ * (their axis is the INPUT channel there), per-channel activations, fp16 scales != 1, dilation != 1 */
+int shl_mi355x_deconv2d_init(CSINN_CONV_ARGS);
+int shl_mi355x_deconv2d_exec(CSINN_CONV_ARGS);
 int shl_mi355x_group_conv2d_exec(CSINN_CONV_ARGS);  /* selected by init when 1 < group < Cin */
 /* CSINN_OP_CONV2D_CHANNEL* / CSINN_OP_DEPTHWISE_CONV2D_CHANNEL* (int8 NCHW; source/reference/
  * convolution_channel.c).  The reference registers no init for these ids: exec plans on first use. */
