@@ -272,6 +272,13 @@ static const char *family_kernel_name(const char *v, bool i8)
     return i8 ? "conv_igemm_patch_i8_mfma32x32x32" : "conv_igemm_patch_f16_mfma32x32x16";
 }
 
+// an NCHW pointwise layer in the wave regime runs on the NCHW-native kernel (nchw_small.hip): the launch asks per call,
+// the plan asks at its own batch for its name.  SHL_MI355X_IGEMM counts through igemm_variant.
+static bool conv1x1_nchw_runs(const ConvArgs &a)
+{
+    return !strcmp(igemm_variant(a.M, a.Co), "wave") && conv1x1_nchw_eligible(a);
+}
+
 struct TuneResult {
     const char *variant;  // nullptr: the rules
 };
@@ -560,6 +567,10 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
         }
         else
             p->kernel_name = i8 ? "conv_igemm_tile_i8_mfma32x32x32" : "conv_igemm_tile_f16_mfma32x32x16";
+        // NCHW, a map of more than one pixel (one pixel goes to the NHWC kernels first): the NCHW-native pointwise kernel
+        // takes the layer before any of the above; as for the stem, the plan's batch decides the name
+        if (d.layout == SHL_MI355X_NCHW && !(d.in_h * d.in_w == 1 && d.out_h * d.out_w == 1) && conv1x1_nchw_runs(probe))
+            p->kernel_name = family_kernel_name("nchw1x1", i8);
         if (i8 && d.layout == SHL_MI355X_NHWC && !igemm_env_override()) {  // pointwise forms of their own (launch_conv_igemm asks them first unless a family is forced)
             probe.w_frag = &probe;  // the copy is made below for exactly these shapes
             probe.div_exact = i8_div_exact, probe.div_fma = i8_div_fma, probe.act = d.act;
@@ -1034,7 +1045,7 @@ static int conv_forward_impl(const shl_mi355x_conv_plan *plan, const void *input
             // [N,1,1,C] are the same bytes, the NHWC kernels apply as they are
             if (a.H * a.W == 1 && a.Ho * a.Wo == 1) return launch_conv_igemm(a, d.dtype, SHL_MI355X_NHWC, s);
             // latency-bound pointwise layers read and write NCHW directly (nchw_small.hip)
-            if (!strcmp(igemm_variant(a.M, a.Co), "wave") && conv1x1_nchw_eligible(a)) {
+            if (conv1x1_nchw_runs(a)) {
                 igemm_note_family("nchw1x1");
                 return launch_conv1x1_nchw(a, d.dtype, s);
             }

@@ -1,5 +1,8 @@
 """Seeded, stratified shape draws for the int8 kernels that a size rule (not a shape rule) turns on: the random sweeps of
 test_fuzz.py & co. only meet the kernels the planner picks at small and mid sizes, these six run on hand-picked lists.
+And for the NCHW-native kernels of latency-bound callers, in int8 and binary16: nchw_small.hip's pointwise kernels (staged
+with transposing LDS reads, and the gather form beyond 2048 bytes of K) and depthwise 3 x 3, conv_direct.hip's binary16
+stem -- families "nchw1x1", "dwconv3x3_nchw", "stem_f16_nchw"; no switch forces them, their shapes do.
 
   draw(family, i)        keyword arguments for cases.make_case (case i of the family)
   case_seed(family, i)   the seed of its operands
@@ -36,15 +39,20 @@ FAMILIES = {
     "conv1x1_latency": dict(n=32, offset=400, cap=1e9, env={"SHL_MI355X_PWLAT": "1"}),
     "stem_mfma": dict(n=32, offset=500, cap=1e9, env={"SHL_MI355X_STEM_MFMA": "1"}),
     "conv_gemv": dict(n=32, offset=600, cap=1e9, env={}),
+    # the NCHW-native kernels: latency-sized cases (the cap keeps the CPU oracle under about a second each)
+    "nchw1x1": dict(n=48, offset=700, cap=2e8, env={}),
+    "dwconv3x3_nchw": dict(n=32, offset=800, cap=2e8, env={}),
+    "stem_f16_nchw": dict(n=16, offset=900, cap=2e8, env={}),
 }
+NCHW_NATIVE = ("nchw1x1", "dwconv3x3_nchw", "stem_f16_nchw")   # binary16 cases of these compare bit for bit
 CHUNK = 8   # cases per GPU test (conv1x1_resident: 4, its cases are up to 1.8 GMAC of oracle each)
 # switches a case may carry; the sub-process clears them between cases.  All are read per call but SHL_MI355X_STEM_TPW
 # (once per process): the stem's chunks are therefore uniform in it.
 CASE_SWITCHES = ("SHL_MI355X_PWLAT_SPLIT", "SHL_MI355X_GEMV_OPW", "SHL_MI355X_STEM_TPW")
 
 
-def out_size(i, k, s, p0, p1):
-    return (i + p0 + p1 - (k - 1) - 1) // s + 1
+def out_size(i, k, s, p0, p1, d=1):
+    return (i + p0 + p1 - d * (k - 1) - 1) // s + 1
 
 
 def case_seed(family, i):
@@ -63,25 +71,25 @@ def _pads(rng):
     return tuple(int(v) for v in rng.integers(0, 3, 4))  # (top, left, bottom, right), each of {0, 1, 2}
 
 
-def _in_size_for(rng, out, stride, p0, p1):
-    """an input extent whose 3-tap output extent is `out` (None: the padding alone is already too much)"""
-    v = (out - 1) * stride + 3 - p0 - p1 + int(rng.integers(0, stride))
-    return v if v >= 1 and out_size(v, 3, stride, p0, p1) == out else None
+def _in_size_for(rng, out, stride, p0, p1, d=1):
+    """an input extent whose 3-tap output extent (dilation d) is `out` (None: the padding alone is already too much)"""
+    v = (out - 1) * stride + 2 * d + 1 - p0 - p1 + int(rng.integers(0, stride))
+    return v if v >= 1 and out_size(v, 3, stride, p0, p1, d) == out else None
 
 
 def geometry(kw):
-    """n, ho, wo, M and the MACs of a make_case keyword set"""
+    """n, ho, wo, M, the MACs and the layout of a make_case keyword set"""
     if kw.get("fc"):
         n, ho, wo = kw["n"], 1, 1
         kh = kw_ = 1
     else:
         kh, kw_ = kw.get("k", (3, 3))
-        pad, st = kw.get("pad", (1, 1, 1, 1)), kw.get("stride", (1, 1))
+        pad, st, dil = kw.get("pad", (1, 1, 1, 1)), kw.get("stride", (1, 1)), kw.get("dilation", (1, 1))
         n = kw.get("n", 1)
-        ho, wo = out_size(kw["h"], kh, st[0], pad[0], pad[2]), out_size(kw["w"], kw_, st[1], pad[1], pad[3])
+        ho, wo = out_size(kw["h"], kh, st[0], pad[0], pad[2], dil[0]), out_size(kw["w"], kw_, st[1], pad[1], pad[3], dil[1])
     M = n * ho * wo
     macs = M * kw["c"] * 9 if kw.get("depthwise") else M * kw["c"] * kw["co"] * kh * kw_
-    return dict(n=n, ho=ho, wo=wo, M=M, macs=macs)
+    return dict(n=n, ho=ho, wo=wo, M=M, macs=macs, layout="NHWC" if kw.get("fc") else kw.get("layout", "NHWC"))
 
 
 def epi_code(kw):
@@ -384,8 +392,151 @@ def _draw_gemv(i, rng):
     return kw
 
 
+# ------------------------------------------------------------------------------------------------ nchw1x1
+NC_KBYTES = (16, 48, 96, 192, 320, 512, 576, 1024, 1040, 2048, 2080, 4096, 4112)
+NC_CO = (1, 3, 5, 8, 31, 32, 36, 61, 64, 70, 160)
+# (K row bytes, Co or None: the Co cycle) of case j = i // 2 of either dtype: every row of the table once, then the rows again
+# that make each of staged / gather x fragment-ordered / row-ordered weights appear at least twice per dtype
+NC_PLAN = ((16, None), (48, None), (96, None), (192, None), (320, None), (512, None), (576, None), (1024, None), (1040, None),
+           (2048, 64), (2080, None), (4096, 32), (4112, None), (4096, 160), (2048, None), (1024, 160), (512, 32), (192, 64),
+           (576, None), (1040, None), (320, None), (96, None), (48, None), (2080, None))
+NC_HW = ("tiny", "lt16", "r0", "r1to15", "r16", "r17to31", "big_aligned", "big_odd", "r0_tiles")
+NC_HW_SETS = {"lt16": (3, 5, 7, 9, 11, 13, 15), "r0": (32, 64), "r1to15": (33, 35, 37, 39, 42, 45, 47), "r16": (16, 48, 80),
+              "r17to31": (17, 21, 27, 31, 49, 51, 55, 57, 63), "big_aligned": (112, 128, 144, 160, 176, 208),
+              "big_odd": (101, 105, 117, 135, 143, 165, 187, 201), "r0_tiles": (64, 96, 128)}
+
+
+def align_up(v, a):
+    return (v + a - 1) // a * a
+
+
+def nchw1x1_launch(kbytes, co=None):
+    """nchw_small.hip:launch_conv1x1_nchw for a K row of kbytes = C * esize (and conv_plan.hip's fragment-ordered weight copy
+    together with the kernels' own test for it, when co is given)"""
+    kstride = align_up(kbytes, 64)
+    nsub = kstride // 32
+    waves = 16 if nsub >= 32 else (8 if nsub >= 16 else 4)
+    per = (nsub + waves - 1) // waves
+    out = dict(kstride=kstride, nsub=nsub, waves=waves, per=per, staged=waves * per * 1024 <= 65536,
+               # the 32-byte sub-steps each wave walks (negative before the kernels' clamp: its start lies beyond the end)
+               wave_nsub=[min(per, nsub - w * per) for w in range(waves)])
+    if co is not None:
+        out["frag"] = kbytes % 64 == 0 and kbytes <= 4096 and co % 32 == 0
+    return out
+
+
+def nchw1x1_strata(i):
+    j = i // 2
+    kb, co = NC_PLAN[j]
+    f16 = i % 2 == 1
+    if co is None:
+        co = NC_CO[(j + (5 if f16 else 0)) % 11]
+    return dict(dtype="f16" if f16 else "int8", kbytes=kb, co=co, hw_class=NC_HW[i % 9], n=1 + (i + i // 9) % 3)
+
+
+def _factor(rng, hw):
+    """h, w with h * w = hw, not square where hw allows it"""
+    pairs = [(a, hw // a) for a in range(1, hw + 1) if hw % a == 0]
+    return _pick(rng, [p for p in pairs if p[0] != p[1] and min(p) > 1] or [p for p in pairs if p[0] != p[1]] or pairs)
+
+
+def _draw_nchw1x1(i, rng):
+    s = nchw1x1_strata(i)
+    es = 1 if s["dtype"] == "int8" else 2
+    c, co, n = s["kbytes"] // es, s["co"], s["n"]
+    if s["hw_class"] == "tiny":  # N * HW <= 8 on more than one pixel: the NHWC view of this shape is the GEMV's
+        hw = int(rng.integers(2, 8 // n + 1))
+    else:
+        fits = [v for v in NC_HW_SETS[s["hw_class"]] if n * v * c * co <= FAMILIES["nchw1x1"]["cap"]]
+        hw = int(_pick(rng, fits))
+    h, w = _factor(rng, hw)
+    kw = dict(layout="NCHW", dtype=s["dtype"], c=c, co=co, n=n, h=int(h), w=int(w), k=(1, 1), pad=(0, 0, 0, 0), act=i % 3)
+    if es == 1:
+        kw.update(exact=(i // 2) % 2 == 0, per_channel=bool(rng.integers(0, 2)))
+    return kw
+
+
+def exact_f16_operands(case):
+    """binary16 operands whose fp32 sums are exact in any order (the MFMA's is not the reference's): input, kernel and bias become
+    multiples of 2^-4 in [-2, 2], seeded by the case.  Every product is a multiple of 2^-8 of magnitude <= 4, so a partial sum over
+    K <= 2^14 terms is a multiple of 2^-8 below 2^16: 24 bits.  (The device of deconv_cases.py.)"""
+    rng = np.random.default_rng([int(case["seed"]), 16])
+    for key, shape in (("input", case["in_shape"]), ("kernel", case["w_shape"]), ("bias", (case["co"],))):
+        case[key] = (rng.integers(-32, 33, shape) / 16.0).astype(np.float16)
+    return case
+
+
+# ------------------------------------------------------------------------------------------------ dwconv3x3_nchw
+DN_STRIDES = ((1, 1), (2, 2), (1, 2), (3, 2))
+DN_DILATIONS = ((1, 1), (2, 2), (1, 1), (1, 2), (1, 1))
+DN_C = (2, 3, 19, 32, 100)
+DN_MAP = ("lt256", "eq256", "257to511", "gt512")   # Ho * Wo: one block row, a full one, a ragged second one, three and more
+
+
+def dwn_strata(i):
+    return dict(stride=DN_STRIDES[i % 4], dilation=DN_DILATIONS[i % 5], c=DN_C[(i // 2) % 5], n=1 + i % 3, map_class=DN_MAP[(i // 4) % 4],
+                line=i == 0, dtype="int8" if (i + i // 8) % 2 == 0 else "f16")
+
+
+def _draw_dwn(i, rng):
+    s = dwn_strata(i)
+    (sh, sw), (dh, dw) = s["stride"], s["dilation"]
+    while True:
+        if s["line"]:
+            ho, wo = _pick(rng, ((1, int(rng.integers(9, 40))), (int(rng.integers(9, 40)), 1)))
+        elif s["map_class"] == "eq256":
+            ho, wo = _pick(rng, ((8, 32), (32, 8), (4, 64), (64, 4), (2, 128), (16, 16)))
+        else:
+            lo, hi = {"lt256": (2, 255), "257to511": (257, 511), "gt512": (513, 1100)}[s["map_class"]]
+            ho, wo = int(rng.integers(2, 48)), int(rng.integers(2, 48))
+            if ho == wo or not lo <= ho * wo <= hi:
+                continue
+        pad = _pads(rng)
+        h, w = _in_size_for(rng, ho, sh, pad[0], pad[2], dh), _in_size_for(rng, wo, sw, pad[1], pad[3], dw)
+        if h and w:
+            break
+    kw = dict(layout="NCHW", dtype=s["dtype"], depthwise=True, c=s["c"], n=s["n"], h=h, w=w, stride=(sh, sw), dilation=(dh, dw),
+              pad=pad, act=(i // 2) % 3)
+    if s["dtype"] == "int8":
+        kw.update(exact=(i // 2) % 2 == 0, per_channel=bool(rng.integers(0, 2)))
+    return kw
+
+
+# ------------------------------------------------------------------------------------------------ stem_f16_nchw
+SN_CO = (1, 7, 8, 20, 33, 64)
+SN_STRIDES = ((1, 1), (2, 2), (2, 1))
+
+
+def stem_f16_threads(kw):
+    """conv_direct.hip:launch_conv_direct: one thread per (image, group of eight output channels, output pixel), 256 per workgroup"""
+    g = geometry(kw)
+    return g["n"] * ((kw["co"] + 7) // 8) * g["ho"] * g["wo"]
+
+
+def stemn_strata(i):
+    return dict(co=SN_CO[i % 6], stride=SN_STRIDES[(i + i // 6) % 3], dilation=((1, 1), (2, 2))[(i // 4) % 2], n=1 + (i // 3) % 3,
+                one_group=i % 2 == 0, act=(i // 2) % 2)
+
+
+def _draw_stemn(i, rng):
+    s = stemn_strata(i)
+    (sh, sw), (dh, dw) = s["stride"], s["dilation"]
+    while True:
+        ho, wo = (int(rng.integers(1, 8)), int(rng.integers(1, 8))) if s["one_group"] else (int(rng.integers(3, 24)), int(rng.integers(3, 24)))
+        pad = _pads(rng)
+        h, w = _in_size_for(rng, ho, sh, pad[0], pad[2], dh), _in_size_for(rng, wo, sw, pad[1], pad[3], dw)
+        if not (h and w) or ho == wo:
+            continue
+        kw = dict(layout="NCHW", dtype="f16", c=3, co=s["co"], n=s["n"], h=h, w=w, stride=(sh, sw), dilation=(dh, dw), pad=pad, act=s["act"])
+        t = stem_f16_threads(kw)
+        # one workgroup that is not full, or several with a ragged last one (the gid >= total clamp)
+        if (t < 256) if s["one_group"] else (t >= 257 and t % 256):
+            return kw
+
+
 _DRAW = {"dwconv_mfma": _draw_dw, "conv1x1_stream": _draw_stream, "conv1x1_resident": _draw_resident,
-         "conv1x1_latency": _draw_latency, "stem_mfma": _draw_stem, "conv_gemv": _draw_gemv}
+         "conv1x1_latency": _draw_latency, "stem_mfma": _draw_stem, "conv_gemv": _draw_gemv,
+         "nchw1x1": _draw_nchw1x1, "dwconv3x3_nchw": _draw_dwn, "stem_f16_nchw": _draw_stemn}
 
 
 def draw(family, i, seed=None):
@@ -405,6 +556,13 @@ def case_env(family, i):
 
 
 def kernel_name(family, kw):
+    f16 = kw.get("dtype", "int8") != "int8"
+    if family == "nchw1x1":
+        return "conv1x1_nchw_f16" if f16 else "conv1x1_nchw_i8"
+    if family == "dwconv3x3_nchw":
+        return "dwconv3x3_nchw_f16" if f16 else "dwconv3x3_nchw_i8"
+    if family == "stem_f16_nchw":   # (the plan's name for every binary16 direct kernel: admissible() restates which one the launch takes)
+        return "conv_direct_f16"
     return {"dwconv_mfma": "dwconv_mfma_i8", "conv1x1_stream": "conv1x1_stream_i8_mfma32x32x32",
             "conv1x1_resident": "conv1x1_resident_i8_mfma32x32x32", "conv1x1_latency": "conv1x1_latency_i8_mfma32x32x32",
             "stem_mfma": "conv_stem_i8_mfma32x32x32",
@@ -417,9 +575,20 @@ def _pointwise(kw):
 
 def admissible(family, kw):
     """the family's pick condition with its switch at "1" (and its rivals as FAMILIES[family]["env"] sets them), for an int8 /
-    binary16 NHWC make_case keyword set"""
+    binary16 make_case keyword set (NHWC; the three NCHW-native families: NCHW)"""
     g = geometry(kw)
     i8 = kw.get("dtype", "int8") == "int8"
+    if family == "nchw1x1":  # conv_igemm.hip:igemm_supports, igemm_variant + nchw_small.hip:conv1x1_nchw_eligible; a 1 x 1 map goes to the NHWC kernels
+        hw = kw["h"] * kw["w"]
+        return bool(g["layout"] == "NCHW" and not kw.get("depthwise") and _pointwise(kw) and (kw["c"] * (1 if i8 else 2)) % 16 == 0 and
+                    ((g["M"] + 127) // 128) * ((kw["co"] + 127) // 128) < 128 and g["n"] * ((hw + 31) // 32) <= 65535 and hw >= 2)
+    if family == "dwconv3x3_nchw":  # nchw_small.hip:dwconv_nchw_supports (make_case's zero point is -5); the dilated kernel fits the padded image
+        return bool(g["layout"] == "NCHW" and kw.get("depthwise") and kw.get("multiplier", 1) == 1 and kw["c"] > 1 and
+                    kw.get("k", (3, 3)) == (3, 3) and g["ho"] >= 1 and g["wo"] >= 1 and g["ho"] * g["wo"] <= 65535 * 256 and g["n"] * kw["c"] < 2 ** 31)
+    if family == "stem_f16_nchw":  # conv_direct.hip:launch_conv_direct (conv_plan.hip:choose_algo: 6 bytes of K are no implicit GEMM's)
+        return bool(g["layout"] == "NCHW" and not i8 and not kw.get("depthwise") and kw.get("groups", 1) == 1 and kw["c"] == 3 and
+                    kw.get("k", (3, 3)) == (3, 3) and kw["co"] <= 64 and g["ho"] >= 1 and g["wo"] >= 1 and
+                    (stem_f16_threads(kw) + 255) // 256 < 2 ** 31 - 1)
     if family == "dwconv_mfma":  # conv_plan.hip (3x3, dilation 1, dot4 packing: C % 4) + dwconv_mfma.hip:dwconv_mfma_pick, dwm_geometry
         sh, sw = kw["stride"]
         return bool(i8 and kw.get("depthwise") and kw["c"] % 32 == 0 and sh in (1, 2) and sw in (1, 2) and g["ho"] >= 1 and g["wo"] >= 1 and

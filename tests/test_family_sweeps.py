@@ -1,9 +1,14 @@
 """Seeded shape sweeps (tests/family_sweeps.py) over the kernels a size rule turns on -- dwconv_mfma.hip, conv1x1_stream.hip,
-conv1x1_resident.hip, conv1x1_latency.hip, the MFMA form of conv_stem.hip, conv_gemv.hip -- each forced by its switch.
+conv1x1_resident.hip, conv1x1_latency.hip, the MFMA form of conv_stem.hip, conv_gemv.hip -- each forced by its switch; and over
+the NCHW-native kernels that their shapes alone select, int8 and binary16: families "nchw1x1" (nchw_small.hip: the staged kernel
+with transposing LDS reads over 4 / 8 / 16 waves, the gather kernel beyond 2048 bytes of K), "dwconv3x3_nchw" (its depthwise
+3 x 3) and "stem_f16_nchw" (conv_direct.hip: the binary16 stem).
 
 CPU: the draws are reproducible, fill every stratum, stay under the MAC cap and inside the forced kernel's domain.
 GPU: per chunk of eight cases one sub-process (the switches are read once per process) runs every case through csinn_* on
-device tensors: the forced kernel's name, zero mismatches against the exact oracle (binary16 GEMV: 1e-3), then the same plan
+device tensors: the forced kernel's name, zero mismatches against the exact oracle (binary16 GEMV: 1e-3; binary16 cases of the
+NCHW-native families: zero differing words -- the depthwise and stem kernels sum in the reference's order, the pointwise
+kernels run on operands whose fp32 sums are exact in any order), then the same plan
 again through shl_mi355x_conv_forward into a buffer with 4 KiB of 0x5A on either side -- the same bytes, the bands untouched
 (the ragged-tile stores of these kernels are guarded in hand-unrolled epilogues)."""
 import collections
@@ -11,6 +16,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 import family_sweeps as fs
@@ -25,7 +31,7 @@ def count(family, key):
 
 # ------------------------------------------------------------------------------------------------ CPU: the draws
 def test_draws_are_reproducible_and_the_seed_moves_only_the_free_parameters():
-    assert [fs.FAMILIES[f]["n"] for f in fs.FAMILIES] == [40, 32, 32, 32, 32, 32]
+    assert [fs.FAMILIES[f]["n"] for f in fs.FAMILIES] == [40, 32, 32, 32, 32, 32, 48, 32, 16]
     moved = 0
     for f, i in ALL:
         a = fs.draw(f, i)
@@ -192,6 +198,131 @@ def test_conv_gemv_strata():
     assert all(fs.geometry(kw)["M"] <= 8 for kw in (fs.draw(F, i) for i in range(32)))
 
 
+def test_nchw1x1_strata():
+    F = "nchw1x1"
+    N = fs.FAMILIES[F]["n"]
+    draws = [fs.draw(F, i) for i in range(N)]
+    es = lambda kw: 1 if kw["dtype"] == "int8" else 2
+    kb = lambda kw: kw["c"] * es(kw)
+    geo = lambda kw: fs.nchw1x1_launch(kb(kw), kw["co"])
+    for i, kw in enumerate(draws):
+        s = fs.nchw1x1_strata(i)
+        assert (kw["dtype"], kb(kw), kw["co"], kw["n"], kw["act"]) == (("int8", "f16")[i % 2], s["kbytes"], s["co"], s["n"], i % 3)
+        assert kw["layout"] == "NCHW" and fs.geometry(kw)["layout"] == "NCHW" and 1 <= kw["n"] <= 3
+    for dt in ("int8", "f16"):
+        mine = [kw for kw in draws if kw["dtype"] == dt]
+        assert len(mine) == N // 2 and {kb(kw) for kw in mine} == set(fs.NC_KBYTES), dt
+        paths = collections.Counter((geo(kw)["staged"], geo(kw)["frag"]) for kw in mine)
+        assert len(paths) == 4 and min(paths.values()) >= 2, (dt, paths)   # staged / gather x fragment-ordered / row-ordered weights
+        assert len({kw["act"] for kw in mine}) == 3
+    assert {kw["co"] for kw in draws} == set(fs.NC_CO)
+    # what the K rows are in the table for, by the restatement of launch_conv1x1_nchw
+    rows = {k: fs.nchw1x1_launch(k) for k in fs.NC_KBYTES}
+    pad = lambda k: rows[k]["kstride"] - k
+    assert any(pad(k) >= 32 for k in rows) and any(pad(k) % 32 == 16 for k in rows)    # a sub-step of padding alone; one that is half padding
+    assert any(min(g["wave_nsub"][:4]) <= 0 for g in rows.values())                    # a finishing wave with no K of its own
+    assert any(0 < g["wave_nsub"][w] < g["per"] for g in rows.values() for w in range(g["waves"]))   # a short last wave
+    assert any(g["waves"] == 8 and 0 in g["wave_nsub"] for g in rows.values())         # eight waves, idle ones among them
+    assert any(g["waves"] == 16 and min(g["wave_nsub"]) > 0 for g in rows.values())
+    assert any(g["waves"] == 16 and g["staged"] and min(g["wave_nsub"]) < 0 for g in rows.values())   # a start beyond the end: the clamp
+    assert any(not g["staged"] and min(g["wave_nsub"]) < 0 for g in rows.values())
+    assert {g["waves"] for g in rows.values()} == {4, 8, 16}
+    assert any(g["staged"] and g["waves"] * g["per"] * 1024 == 65536 for g in rows.values())   # the largest staged row: 64 KiB
+    assert sorted(k for k, g in rows.items() if not g["staged"]) == [2080, 4096, 4112]
+    assert all(g["staged"] == (fs.align_up(k, 64) <= 2048) for k, g in rows.items())            # "the packed K row exceeds 2048 bytes"
+    # the map
+    hw = [kw["h"] * kw["w"] for kw in draws]
+    res = collections.Counter("0" if v % 32 == 0 else "1..15" if v % 32 < 16 else "16" if v % 32 == 16 else "17..31" for v in hw)
+    assert len(res) == 4 and min(res.values()) >= 4, res
+    assert sum(v < 16 for v in hw) >= 4 and sum(33 <= v <= 63 for v in hw) >= 4 and sum(v >= 100 for v in hw) >= 4, hw
+    assert sum(kw["h"] != kw["w"] for kw in draws) > N // 2
+    staged = [kw for kw in draws if geo(kw)["staged"]]
+    odd = sum((kw["h"] * kw["w"] * es(kw)) % 16 != 0 for kw in staged)
+    assert 3 * odd >= len(staged) and 3 * (len(staged) - odd) >= len(staged), (odd, len(staged))   # misaligned planes; aligned ones
+    for dt in ("int8", "f16"):   # ... and a misaligned plane on more than one pixel tile, where pieces of the next plane are staged
+        assert any(kw["dtype"] == dt and kw["h"] * kw["w"] > 32 and (kw["h"] * kw["w"] * es(kw)) % 16 for kw in staged), dt
+    assert any(kw["h"] * kw["w"] > 32 for kw in draws if not geo(kw)["staged"])
+    assert 2 * sum(kw["n"] > 1 for kw in draws) >= N
+    tiny = [kw for kw in draws if kw["n"] * kw["h"] * kw["w"] <= 8 and kw["h"] * kw["w"] >= 2]   # the NHWC view is the GEMV's
+    assert len(tiny) >= 2 and len({kw["dtype"] for kw in tiny}) == 2, tiny
+    i8 = [kw for kw in draws if kw["dtype"] == "int8"]
+    assert [kw["exact"] for kw in i8] == [j % 2 == 0 for j in range(len(i8))]
+    assert len({kw["per_channel"] for kw in i8}) == 2
+    assert len({(kw["exact"], kw["act"]) for kw in i8}) == 6
+
+
+def test_nchw1x1_binary16_operands_sum_exactly_in_any_order():
+    F = "nchw1x1"
+    seen = 0
+    for i in range(fs.FAMILIES[F]["n"]):
+        kw = fs.draw(F, i)
+        if kw["dtype"] == "int8":
+            continue
+        case = dict(seed=fs.case_seed(F, i), in_shape=(kw["n"], kw["c"], kw["h"], kw["w"]), w_shape=(kw["co"], kw["c"], 1, 1), co=kw["co"])
+        again = fs.exact_f16_operands(dict(case))
+        fs.exact_f16_operands(case)
+        for key in ("input", "kernel", "bias"):
+            v = case[key].astype(np.float64) * 16
+            assert case[key].dtype == np.float16 and np.array_equal(v, np.rint(v)) and np.abs(v).max() <= 32, (i, key)
+            assert np.array_equal(case[key], again[key])
+        x = np.abs(case["input"].astype(np.float64) * 16).transpose(0, 2, 3, 1).reshape(-1, kw["c"])
+        w = np.abs(case["kernel"].astype(np.float64) * 16).reshape(kw["co"], kw["c"])
+        worst = float((x @ w.T).max())   # sum |16 x| |16 w| over K: every partial sum, in units of 2^-8, is below it
+        assert worst < 2 ** 24, (i, kw, worst)
+        assert 4 * kw["c"] + 2 < 65504   # |S + bias| stays a finite binary16
+        seen += 1
+    assert seen == fs.FAMILIES[F]["n"] // 2
+
+
+def test_dwconv3x3_nchw_strata():
+    F = "dwconv3x3_nchw"
+    N = fs.FAMILIES[F]["n"]
+    draws = [fs.draw(F, i) for i in range(N)]
+    geo = [fs.geometry(kw) for kw in draws]
+    for i, kw in enumerate(draws):
+        s = fs.dwn_strata(i)
+        assert (kw["stride"], kw["dilation"], kw["c"], kw["n"], kw["dtype"]) == (s["stride"], s["dilation"], s["c"], s["n"], s["dtype"])
+        assert kw["layout"] == "NCHW" and kw["depthwise"] and all(p in (0, 1, 2) for p in kw["pad"])
+    assert {kw["stride"] for kw in draws} == {(1, 1), (2, 2), (1, 2), (3, 2)}
+    assert {kw["dilation"] for kw in draws} == {(1, 1), (2, 2), (1, 2)}
+    assert 3 * sum(kw["dilation"] != (1, 1) for kw in draws) >= N
+    assert len({(kw["stride"], kw["dilation"]) for kw in draws}) == 12
+    assert len({kw["pad"] for kw in draws}) >= 12
+    assert sum(kw["pad"][0] != kw["pad"][2] or kw["pad"][1] != kw["pad"][3] for kw in draws if kw["dilation"] != (1, 1)) >= 4   # dilation with asymmetric padding
+    assert {kw["c"] for kw in draws} == {2, 3, 19, 32, 100} and {kw["n"] for kw in draws} == {1, 2, 3}
+    assert {kw["c"] for kw in draws if kw["n"] > 1 and kw["c"] % 2} == {3, 19}   # c = plane % C on odd C behind the first image
+    cls = lambda g: "lt256" if g["ho"] * g["wo"] < 256 else "eq256" if g["ho"] * g["wo"] == 256 else "257to511" if g["ho"] * g["wo"] < 512 else "gt512"
+    maps = collections.Counter(cls(g) for g in geo)
+    assert set(maps) == set(fs.DN_MAP) and min(maps.values()) >= 6 and all(g["ho"] * g["wo"] != 512 for g in geo), maps
+    assert [cls(g) for g in geo] == [fs.dwn_strata(i)["map_class"] for i in range(N)]
+    assert len({(kw["stride"], cls(g)) for kw, g in zip(draws, geo)}) == 16
+    assert any(kw["stride"] == (3, 2) and g["ho"] * g["wo"] > 256 for kw, g in zip(draws, geo))
+    assert any(g["ho"] == 1 or g["wo"] == 1 for g in geo)
+    for dt in ("int8", "f16"):
+        mine = [(kw, g) for kw, g in zip(draws, geo) if kw["dtype"] == dt]
+        assert len(mine) == N // 2 and {cls(g) for _, g in mine} == set(fs.DN_MAP) and {kw["act"] for kw, _ in mine} == {0, 1, 2}, dt
+        assert len({kw["stride"] for kw, _ in mine}) == 4 and len({kw["dilation"] for kw, _ in mine}) == 3, dt
+    i8 = [kw for kw in draws if kw["dtype"] == "int8"]
+    assert len({kw["exact"] for kw in i8}) == 2 and len({kw["per_channel"] for kw in i8}) == 2 and len({(kw["exact"], kw["act"] > 0) for kw in i8}) == 4
+
+
+def test_stem_f16_nchw_strata():
+    F = "stem_f16_nchw"
+    N = fs.FAMILIES[F]["n"]
+    draws = [fs.draw(F, i) for i in range(N)]
+    assert all(kw["layout"] == "NCHW" and kw["dtype"] == "f16" and kw["c"] == 3 and kw.get("k", (3, 3)) == (3, 3) for kw in draws)
+    assert {kw["co"] for kw in draws} == {1, 7, 8, 20, 33, 64}
+    assert {kw["stride"] for kw in draws} == {(1, 1), (2, 2), (2, 1)} and {kw["dilation"] for kw in draws} == {(1, 1), (2, 2)}
+    assert len({(kw["stride"], kw["dilation"]) for kw in draws}) == 6
+    assert len({kw["pad"] for kw in draws}) >= 8 and {kw["n"] for kw in draws} == {1, 2, 3} and {kw["act"] for kw in draws} == {0, 1}
+    threads = [fs.stem_f16_threads(kw) for kw in draws]
+    assert sum(t < 256 for t in threads) == N // 2 and sum(t >= 257 and t % 256 != 0 for t in threads) == N // 2, threads
+    # both launch sizes meet ragged channel groups (Co % 8 != 0), full ones, and both dilations
+    for small in (True, False):
+        mine = [kw for kw, t in zip(draws, threads) if (t < 256) == small]
+        assert {kw["co"] % 8 == 0 for kw in mine} == {True, False} and {kw["dilation"] for kw in mine} == {(1, 1), (2, 2)}, small
+
+
 # ------------------------------------------------------------------------------------------------ GPU
 SCRIPT = r"""
 import os, sys, time
@@ -214,12 +345,20 @@ for i in todo:
     for v in fs.CASE_SWITCHES:
         os.environ.pop(v, None)
     os.environ.update(env)
-    case = cases.make_case(seed, **kw)
+    kw = dict(kw)
+    layout = cases.NCHW if kw.pop("layout", "NHWC") == "NCHW" else cases.NHWC
+    case = cases.make_case(seed, layout=layout, **kw)
+    if family == "nchw1x1" and case["dtype"] != "int8":
+        fs.exact_f16_operands(case)   # fp32 sums that are exact in the MFMA's order as in the reference's
     keep = []
     got = cases.csinn_run(fe, pkg.API_MI355X, case, device=dev, keep_params=keep)
     name = opt.shl_mi355x_params_kernel_name(keep[0][0]).decode()
     if case["dtype"] == "int8":
         bad, worst = cases.mismatch_report(got, cases.oracle_run(case, "exact"))
+    elif family in fs.NCHW_NATIVE:   # bit for bit
+        want = cases.oracle_run(case, "f16")
+        bad = int((np.ascontiguousarray(got).view(np.uint16) != want.view(np.uint16)).sum())
+        worst = "%%.3g" %% float(np.abs(got.astype(np.float64) - want.astype(np.float64)).max())
     else:
         bad, worst = 0, 0
         try:
@@ -281,6 +420,16 @@ def test_a_row_that_is_wrong_in_any_column_is_reported_with_its_shape():
         with pytest.raises(AssertionError) as e:
             check_row("conv1x1_stream", 7, kw, {}, row, good[2])
         assert repr(kw) in str(e.value) and str(fs.case_seed("conv1x1_stream", 7)) in str(e.value)
+    # a binary16 row of an NCHW-native family: `bad` counts differing words
+    kw = fs.draw("nchw1x1", 21)
+    good = ["CASE", "21", "conv1x1_nchw_f16", "0", "0", "0", "0", "0", "0.01"]
+    check_row("nchw1x1", 21, kw, {}, good, fs.kernel_name("nchw1x1", kw))
+    for col, value in ((2, "conv_igemm_wave_f16_mfma32x32x16"), (2, "conv_gemv_f16_fma"), (3, "1"), (5, "2"), (6, "2"), (7, "4")):
+        row = list(good)
+        row[col] = value
+        with pytest.raises(AssertionError) as e:
+            check_row("nchw1x1", 21, kw, {}, row, good[2])
+        assert repr(kw) in str(e.value) and str(fs.case_seed("nchw1x1", 21)) in str(e.value)
 
 
 @pytest.mark.gpu

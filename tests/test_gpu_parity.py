@@ -37,7 +37,7 @@ def gpu(standalone):
 def _check(case, got, expected, what, kernel_name=""):
     if case["dtype"] == "int8":
         golden_util.compare(case, got, expected, what)
-    elif "igemm" in kernel_name or "gemv" in kernel_name:
+    elif "igemm" in kernel_name or "gemv" in kernel_name or "conv1x1" in kernel_name:
         golden_util.compare_f16_tol(got, expected, what)          # different summation order
     else:
         golden_util.compare(case, got, expected, what)            # reference order: bit-exact
