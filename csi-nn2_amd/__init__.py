@@ -31,6 +31,7 @@ OP_CONV2D, OP_CONV2D_RELU, OP_CONV2D_RELU6 = 28, 29, 30
 OP_DEPTHWISE_CONV2D, OP_FULLYCONNECTED = 35, 71
 OP_AVGPOOL2D, OP_MAXPOOL2D = 14, 98
 OP_CONCAT = 26
+OP_SPLIT, OP_SHUFFLE_CHANNEL = 166, 153
 OP_SIGMOID, OP_HARD_SIGMOID, OP_SILU, OP_LEAKY_RELU, OP_MUL = 154, 78, 190, 84, 107
 OP_RESIZE = 133
 OP_DECONV2D, OP_DEPTHWISE_DECONV2D, OP_GROUP_DECONV2D = 54, 55, 56
@@ -145,6 +146,14 @@ class ConcatParams(C.Structure):
     _fields_ = [("base", ParamsBase), ("inputs_count", C.c_int32), ("axis", C.c_int32)]
 
 
+class SplitParams(C.Structure):
+    _fields_ = [("base", ParamsBase), ("split_index", C.POINTER(C.c_int32)), ("output_num", C.c_int32), ("axis", C.c_int32)]
+
+
+class ShuffleChannelParams(C.Structure):
+    _fields_ = [("base", ParamsBase), ("group", C.c_int32)]
+
+
 class ConvDesc(C.Structure):
     """struct shl_mi355x_conv_desc (include/shl_mi355x.h)"""
     _fields_ = [(n, C.c_int32) for n in (
@@ -166,6 +175,19 @@ class ConcatDesc(C.Structure):
     """struct shl_mi355x_concat_desc (include/shl_mi355x.h)"""
     _fields_ = [("dtype", C.c_int32), ("n_inputs", C.c_int32), ("outer", C.c_int64), ("out_scale", C.c_float),
                 ("out_zp", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class SplitDesc(C.Structure):
+    """struct shl_mi355x_split_desc (include/shl_mi355x.h)"""
+    _fields_ = [("dtype", C.c_int32), ("n_outputs", C.c_int32), ("outer", C.c_int64), ("in_scale", C.c_float),
+                ("in_zp", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class ShuffleDesc(C.Structure):
+    """struct shl_mi355x_shuffle_desc (include/shl_mi355x.h)"""
+    _fields_ = [("dtype", C.c_int32), ("group", C.c_int32), ("outer", C.c_int64), ("c", C.c_int64), ("inner", C.c_int64),
+                ("in_scale", C.c_float), ("in_zp", C.c_int32), ("out_scale", C.c_float), ("out_zp", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
 
 
 class ResizeDesc(C.Structure):
@@ -282,6 +304,12 @@ def load_hip():
                                         C.POINTER(ConcatDesc), vp]),
         "shl_mi355x_concat_kernel_name": (C.c_char_p, [C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(f32), C.POINTER(i32),
                                                        vp, C.POINTER(ConcatDesc)]),
+        "shl_mi355x_split": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(f32), C.POINTER(i32),
+                                       C.POINTER(SplitDesc), vp]),
+        "shl_mi355x_split_kernel_name": (C.c_char_p, [vp, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(f32), C.POINTER(i32),
+                                                      C.POINTER(SplitDesc)]),
+        "shl_mi355x_shuffle_channel": (C.c_int, [vp, vp, C.POINTER(ShuffleDesc), vp]),
+        "shl_mi355x_shuffle_channel_kernel_name": (C.c_char_p, [vp, vp, C.POINTER(ShuffleDesc)]),
         "shl_mi355x_unary_lut_i8": (C.c_int, [vp, vp, sz, vp, vp]),
         "shl_mi355x_unary_lut_i8_kernel_name": (C.c_char_p, [vp, vp]),
         "shl_mi355x_unary_f16": (C.c_int, [vp, vp, sz, i32, f32, vp]),
@@ -326,7 +354,7 @@ _FRONTEND_SIGS = {
     "shl_debug_set_level": (None, [C.c_int]),
 }
 _SISO_OPS = ("csinn_relu", "csinn_relu6", "csinn_global_avgpool2d", "csinn_softmax", "csinn_maxpool2d", "csinn_avgpool2d",
-             "csinn_sigmoid", "csinn_hard_sigmoid", "csinn_silu", "csinn_leaky_relu", "csinn_resize")
+             "csinn_sigmoid", "csinn_hard_sigmoid", "csinn_silu", "csinn_leaky_relu", "csinn_resize", "csinn_shuffle_channel")
 _CONV_OPS = ["csinn_conv2d", "csinn_conv2d_relu", "csinn_conv2d_relu6", "csinn_depthwise_conv2d",
              "csinn_depthwise_conv2d_relu", "csinn_fullyconnected", "csinn_deconv2d"] + list(_SISO_OPS)
 
@@ -363,6 +391,8 @@ def load_frontend(kind="standalone", local=False, path=None):
             fn.restype, fn.argtypes = C.c_int, [tp, tp, tp, C.c_void_p]
         fn = getattr(lib, "csinn_concat" + suffix)
         fn.restype, fn.argtypes = C.c_int, [C.POINTER(tp), tp, C.c_void_p]
+        fn = getattr(lib, "csinn_split" + suffix)
+        fn.restype, fn.argtypes = C.c_int, [tp, C.POINTER(tp), C.c_void_p]
     lib._typed = True
     lib.kind = kind
     return lib
@@ -538,8 +568,39 @@ def concat_params(fe, keep, api, layout, n, axis, sess=None, name=b"concat"):
     return p
 
 
+def split_params(fe, keep, api, layout, n, axis, split_index=None, sess=None, name=b"split"):
+    """params block of csinn_split: n outputs along `axis` (< 0: from the back); split_index: the n - 1 boundaries, or None
+    for chunks of ceil(dim / n)"""
+    p = fe.csinn_alloc_params(C.sizeof(SplitParams), sess)
+    pc = C.cast(p, C.POINTER(SplitParams)).contents
+    pc.base.api = api
+    pc.base.layout = layout
+    pc.base.name = keep.add(C.c_char_p(name)).value
+    if sess is not None:
+        pc.base.sess = sess
+    pc.output_num = n
+    pc.axis = axis
+    if split_index is not None:
+        idx = keep.add((C.c_int32 * max(len(split_index), 1))(*split_index))
+        pc.split_index = C.cast(idx, C.POINTER(C.c_int32))
+    return p
+
+
+def shuffle_channel_params(fe, keep, api, layout, group, sess=None, name=b"shuffle"):
+    """params block of csinn_shuffle_channel"""
+    p = fe.csinn_alloc_params(C.sizeof(ShuffleChannelParams), sess)
+    pc = C.cast(p, C.POINTER(ShuffleChannelParams)).contents
+    pc.base.api = api
+    pc.base.layout = layout
+    pc.base.name = keep.add(C.c_char_p(name)).value
+    if sess is not None:
+        pc.base.sess = sess
+    pc.group = group
+    return p
+
+
 def tensor_array(keep, tensors):
-    """struct csinn_tensor *[]: what csinn_concat takes as its inputs"""
+    """struct csinn_tensor *[]: what csinn_concat takes as its inputs and csinn_split as its outputs"""
     return keep.add((C.POINTER(Tensor) * len(tensors))(*tensors))
 
 

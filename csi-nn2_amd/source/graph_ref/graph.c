@@ -259,6 +259,30 @@ int shl_gref_concat(struct csinn_tensor **input, struct csinn_tensor *output, st
     return shl_gref_graph_insert(layer, shl_gref_get_graph(sess));
 }
 
+/* one input, params->output_num outputs: one layer with that many output nodes (source/graph_ref/split.c of the reference) */
+int shl_gref_split(struct csinn_tensor *input, struct csinn_tensor **output, struct csinn_split_params *params)
+{
+    const int n = params->output_num;
+    if (n < 1) {
+        shl_debug_error("%s: output_num %d\n", __func__, n);
+        return CSINN_FALSE;
+    }
+    struct shl_node *layer = shl_node_alloc(CSINN_OP_SPLIT, params->base.name, 1, n, params);
+    shl_node_add_in(layer, (struct shl_node *)input->data, 0);
+    for (int i = 0; i < n; i++) {
+        struct shl_node *produced = shl_node_var_alloc(output[i]->name, output[i]);
+        shl_node_add_out(layer, produced, i);
+        output[i]->data = produced;
+    }
+    return shl_gref_graph_insert(layer, shl_gref_get_graph(input->sess));
+}
+
+int shl_gref_shuffle_channel(struct csinn_tensor *input, struct csinn_tensor *output,
+                             struct csinn_shuffle_channel_params *params)
+{
+    return record_siso(input, output, CSINN_OP_SHUFFLE_CHANNEL, params);
+}
+
 int shl_gref_global_avgpool2d(struct csinn_tensor *input, struct csinn_tensor *output,
                               struct csinn_pool_params *params)
 {
@@ -300,6 +324,7 @@ int shl_gref_call_layer_func(void *fn, struct shl_node *node)
         case CSINN_OP_SILU:
         case CSINN_OP_LEAKY_RELU:
         case CSINN_OP_RESIZE:
+        case CSINN_OP_SHUFFLE_CHANNEL:
             return f(node->in[0]->data, node->out[0]->data, params);
         case CSINN_OP_ADD:
         case CSINN_OP_MUL:
@@ -309,6 +334,13 @@ int shl_gref_call_layer_func(void *fn, struct shl_node *node)
             for (int i = 0; i < node->in_num; i++) ins[i] = node->in[i]->data;
             int rc = f(ins, node->out[0]->data, params);
             shl_mem_free(ins);
+            return rc;
+        }
+        case CSINN_OP_SPLIT: {
+            struct csinn_tensor **outs = shl_mem_alloc((int64_t)node->out_num * sizeof(*outs));
+            for (int i = 0; i < node->out_num; i++) outs[i] = node->out[i]->data;
+            int rc = f(node->in[0]->data, outs, params);
+            shl_mem_free(outs);
             return rc;
         }
         case CSINN_OP_CONV2D:
@@ -375,6 +407,8 @@ static struct csinn_callback *gref_cb_map(int op, int dtype)
         {CSINN_OP_LEAKY_RELU, shl_gref_leaky_relu},
         {CSINN_OP_MUL, shl_gref_mul},
         {CSINN_OP_RESIZE, shl_gref_resize},
+        {CSINN_OP_SPLIT, shl_gref_split},
+        {CSINN_OP_SHUFFLE_CHANNEL, shl_gref_shuffle_channel},
     };
     _Static_assert(sizeof(table) / sizeof(table[0]) <= sizeof(g_est_only) / sizeof(g_est_only[0]), "one callback block per table row");
     for (unsigned i = 0; i < sizeof(table) / sizeof(table[0]); i++) {

@@ -36,6 +36,11 @@ int shl_mi355x_stage_out_end(struct shl_mi355x_ctx *ctx, struct csinn_tensor *t,
 #define SHL_MI355X_STAGE_ALIGN 256
 int shl_mi355x_stage_in_many(struct shl_mi355x_ctx *ctx, struct csinn_tensor **t, int n, const void **dev);
 
+/* n outputs at once (split): host tensors are packed into staging slot 1 at the same alignment, DMABUF tensors are written
+ * in place; _end downloads the host tensors and synchronises once */
+int shl_mi355x_stage_out_many_begin(struct shl_mi355x_ctx *ctx, struct csinn_tensor **t, int n, void **dev);
+int shl_mi355x_stage_out_many_end(struct shl_mi355x_ctx *ctx, struct csinn_tensor **t, int n, void *const *dev);
+
 /* perf callbacks of the windowed pools (pooling.c): single-input signature + the trailing info block */
 int shl_mi355x_maxpool2d_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params,
                               struct csinn_perf_info *info);
@@ -45,6 +50,15 @@ int shl_mi355x_avgpool2d_perf(struct csinn_tensor *input, struct csinn_tensor *o
 /* ... and of concat: the array-of-inputs signature */
 int shl_mi355x_concat_perf(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params,
                            struct csinn_perf_info *info);
+
+/* split and shuffle_channel (split.c): init (a refused layer falls through to the reference where there is one) and perf */
+int shl_mi355x_split_init(struct csinn_tensor *input, struct csinn_tensor **output, struct csinn_split_params *params);
+int shl_mi355x_split_perf(struct csinn_tensor *input, struct csinn_tensor **output, struct csinn_split_params *params,
+                          struct csinn_perf_info *info);
+int shl_mi355x_shuffle_channel_init(struct csinn_tensor *input, struct csinn_tensor *output,
+                                    struct csinn_shuffle_channel_params *params);
+int shl_mi355x_shuffle_channel_perf(struct csinn_tensor *input, struct csinn_tensor *output,
+                                    struct csinn_shuffle_channel_params *params, struct csinn_perf_info *info);
 
 /* ... and of the elementwise layers (eltwise.c): the kernel form the rules choose */
 int shl_mi355x_sigmoid_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params,

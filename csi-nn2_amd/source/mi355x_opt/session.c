@@ -46,7 +46,7 @@ enum step_kind {
 struct step {
     enum step_kind kind;
     int a, b;             /* layer indices; b = -1 for STEP_LAYER */
-    struct shl_node *out; /* the tensor node the step finally writes */
+    struct shl_node *out; /* the tensor node the step finally writes (a split: the first of them) */
 };
 
 struct dev_session {
@@ -106,9 +106,10 @@ static void drop_session(struct csinn_session *sess)
 }
 
 /* how an exec callback is called.  The value is the number of inputs such a layer has in the graph (kernel and bias
- * included); 0: as many as its params block says */
+ * included); 0: as many as its params block says; < 0: see inputs_of */
 enum call_shape {
-    CALL_ARRAY = 0, /* exec(inputs[], output, params) */
+    CALL_SPLIT = -1, /* exec(input, outputs[], params): one input, as many outputs as its params block says */
+    CALL_ARRAY = 0,  /* exec(inputs[], output, params) */
     CALL_SISO = 1,  /* exec(input, output, params) */
     CALL_DISO = 2,  /* exec(input0, input1, output, params) */
     CALL_CONV = 3,  /* exec(input, output, kernel, bias, params) */
@@ -152,6 +153,8 @@ static const struct session_op g_ops[] = {
     {CSINN_OP_LEAKY_RELU, shl_mi355x_leaky_relu_exec, CALL_SISO, 1, 1},
     {CSINN_OP_RESIZE, shl_mi355x_resize_exec, CALL_SISO, 1, 1},  /* an FPN top-down path, a U-Net decoder, a YOLO neck */
     {CSINN_OP_CONCAT, shl_mi355x_concat_exec, CALL_ARRAY, 0, 0}, /* any input may be */
+    {CSINN_OP_SPLIT, shl_mi355x_split_exec, CALL_SPLIT, 1, 1},   /* a ShuffleNetV2 unit, a CSP / C2f block */
+    {CSINN_OP_SHUFFLE_CHANNEL, shl_mi355x_shuffle_channel_exec, CALL_SISO, 1, 1},
 };
 
 /* the row of layer `n`; NULL: not a layer this file runs */
@@ -166,9 +169,18 @@ static const struct session_op *session_op(struct shl_node *n)
 /* the number of inputs layer `n` must have; 0: none will do */
 static int inputs_of(const struct session_op *op, struct shl_node *n)
 {
+    if (op->call == CALL_SPLIT) return 1;
     if (op->call != CALL_ARRAY) return op->call;
     struct csinn_concat_params *p = n->data;
     return p->inputs_count >= 1 ? p->inputs_count : 0;
+}
+
+/* the number of outputs layer `n` must have; 0: none will do */
+static int outputs_of(const struct session_op *op, struct shl_node *n)
+{
+    if (op->call != CALL_SPLIT) return 1;
+    struct csinn_split_params *p = n->data;
+    return p->output_num >= 1 ? p->output_num : 0;
 }
 
 static struct dev_tensor *lookup(struct dev_session *ds, struct shl_node *node)
@@ -336,6 +348,18 @@ static int run_layer(struct dev_session *ds, struct shl_node *n, struct dev_tens
             return in1 ? f(&in->shadow, &in1->shadow, &out->shadow, params) : CSINN_FALSE;
         case CALL_CONV:
             return f(&in->shadow, &out->shadow, n->in[1]->data, n->in[2]->data, params);
+        case CALL_SPLIT: { /* an array of the outputs' shadow tensors */
+            struct csinn_tensor **outs = calloc((size_t)n->out_num, sizeof(*outs));
+            int rc = outs ? CSINN_TRUE : CSINN_FALSE;
+            for (int j = 0; rc == CSINN_TRUE && j < n->out_num; j++) {
+                struct dev_tensor *dj = lookup(ds, n->out[j]);
+                if (dj) outs[j] = &dj->shadow;
+                else rc = CSINN_FALSE;
+            }
+            if (rc == CSINN_TRUE) rc = f(&in->shadow, outs, params);
+            free(outs);
+            return rc;
+        }
         default: { /* CALL_ARRAY: an array of shadow tensors */
             struct csinn_tensor **ins = calloc((size_t)n->in_num, sizeof(*ins));
             int rc = ins ? CSINN_TRUE : CSINN_FALSE;
@@ -463,13 +487,13 @@ int shl_mi355x_session_setup(struct csinn_session *sess)
     for (int i = 0; i < g->layer_index; i++) {
         struct shl_node *n = g->layer[i];
         const struct session_op *op = session_op(n);
-        const int inputs = op ? inputs_of(op, n) : 0;
-        if (inputs == 0 || n->in_num != inputs || n->out_num != 1) {
+        const int inputs = op ? inputs_of(op, n) : 0, outputs = op ? outputs_of(op, n) : 0;
+        if (inputs == 0 || n->in_num != inputs || outputs == 0 || n->out_num != outputs) {
             shl_debug_info("mi355x: layer %d (%s, op %d) runs on the host path: session stays host-staged\n", i,
                            n->name ? n->name : "?", n->type);
             return rc;
         }
-        tensors += 1 + (op->activations ? op->activations : inputs) - op->first_const; /* its output + constants it may bring */
+        tensors += outputs + (op->activations ? op->activations : inputs) - op->first_const; /* its outputs + constants it may bring */
     }
     struct dev_session *ds = calloc(1, sizeof(*ds));
     ds->sess = sess;
@@ -497,7 +521,7 @@ int shl_mi355x_session_setup(struct csinn_session *sess)
             }
         }
         if (!ok) break;
-        ok = adopt(ds, n->out[0]) != NULL;
+        for (int j = 0; ok && j < n->out_num; j++) ok = adopt(ds, n->out[j]) != NULL;
     }
     for (int i = 0; ok && i < g->output_num; i++) ok = lookup(ds, g->output[i]) != NULL;
     if (ok) ok = plan_fusion(ds, g);

@@ -72,7 +72,7 @@ struct shl_mi355x_ctx {
     struct {
         void *dev;
         size_t bytes;
-    } stage[3]; /* 0: first input (concat: all of them, packed), 1: output, 2: second input */
+    } stage[3]; /* 0: first input (concat: all of them, packed), 1: output (split: all of them, packed), 2: second input */
     struct shl_mi355x_ctx *next;
 };
 
@@ -539,6 +539,61 @@ void *shl_mi355x_stage_out_begin(struct shl_mi355x_ctx *c, struct csinn_tensor *
     return stage_buffer(c, slot, (size_t)csinn_tensor_byte_size(t));
 }
 
+/* the outputs of a layer with several (split): one staging buffer (slot 1, grown as for a single tensor) holds every host
+ * tensor at SHL_MI355X_STAGE_ALIGN-aligned offsets, DMABUF tensors are written in place; dev[i]: where the kernel writes
+ * tensor i.  Nothing is allocated when a tensor has no data: the caller then has written nothing */
+int shl_mi355x_stage_out_many_begin(struct shl_mi355x_ctx *c, struct csinn_tensor **t, int n, void **dev)
+{
+    size_t total = 0;
+    for (int i = 0; i < n; i++) {
+        dev[i] = NULL;
+        if (t[i]->data == NULL) {
+            shl_debug_error("mi355x: output tensor %d has no data\n", i);
+            return CSINN_FALSE;
+        }
+        if (t[i]->mtype == CSINN_MEM_TYPE_DMABUF) continue;
+        const size_t bytes = (size_t)csinn_tensor_byte_size(t[i]);
+        total += (bytes + SHL_MI355X_STAGE_ALIGN - 1) / SHL_MI355X_STAGE_ALIGN * SHL_MI355X_STAGE_ALIGN;
+    }
+    char *base = NULL;
+    if (total > 0) {
+        if (c == NULL) return CSINN_FALSE;
+        base = stage_buffer(c, 1, total);
+        if (base == NULL) return CSINN_FALSE;
+    }
+    size_t at = 0;
+    for (int i = 0; i < n; i++) {
+        if (t[i]->mtype == CSINN_MEM_TYPE_DMABUF) {
+            dev[i] = t[i]->data;
+            continue;
+        }
+        dev[i] = base + at;
+        const size_t bytes = (size_t)csinn_tensor_byte_size(t[i]);
+        at += (bytes + SHL_MI355X_STAGE_ALIGN - 1) / SHL_MI355X_STAGE_ALIGN * SHL_MI355X_STAGE_ALIGN;
+    }
+    return CSINN_TRUE;
+}
+
+/* downloads the host tensors among them, then synchronises once */
+int shl_mi355x_stage_out_many_end(struct shl_mi355x_ctx *c, struct csinn_tensor **t, int n, void *const *dev)
+{
+    void *stream = shl_mi355x_ctx_stream(c);
+    int host = 0;
+    for (int i = 0; i < n; i++) {
+        if (t[i]->mtype == CSINN_MEM_TYPE_DMABUF) continue; /* stays in HBM, stays async */
+        host++;
+        if (shl_mi355x_download(t[i]->data, dev[i], (size_t)csinn_tensor_byte_size(t[i]), stream) != SHL_MI355X_OK) {
+            shl_debug_error("mi355x: download failed: %s\n", shl_mi355x_last_error());
+            return CSINN_FALSE;
+        }
+    }
+    if (host > 0 && shl_mi355x_stream_sync(stream) != SHL_MI355X_OK) {
+        shl_debug_error("mi355x: download failed: %s\n", shl_mi355x_last_error());
+        return CSINN_FALSE;
+    }
+    return CSINN_TRUE;
+}
+
 int shl_mi355x_stage_out_end(struct shl_mi355x_ctx *c, struct csinn_tensor *t, void *dev)
 {
     if (t->mtype == CSINN_MEM_TYPE_DMABUF) return CSINN_TRUE; /* stays in HBM, stays async */
@@ -646,6 +701,10 @@ void shl_target_init_mi355x(void)
         reg(dts[i], CSINN_OP_LEAKY_RELU, NULL, shl_mi355x_leaky_relu_exec, shl_gref_leaky_relu, shl_mi355x_leaky_relu_perf);
         reg(dts[i], CSINN_OP_RESIZE, NULL, shl_mi355x_resize_exec, shl_gref_resize, shl_mi355x_resize_perf);
         reg(dts[i], CSINN_OP_CONCAT, NULL, shl_mi355x_concat_exec, shl_gref_concat, shl_mi355x_concat_perf);
+        /* (a layer they refuse falls through at init: next to libshl it runs on the reference's kernel) */
+        reg(dts[i], CSINN_OP_SPLIT, shl_mi355x_split_init, shl_mi355x_split_exec, shl_gref_split, shl_mi355x_split_perf);
+        reg(dts[i], CSINN_OP_SHUFFLE_CHANNEL, shl_mi355x_shuffle_channel_init, shl_mi355x_shuffle_channel_exec,
+            shl_gref_shuffle_channel, shl_mi355x_shuffle_channel_perf);
     }
     shl_register_op_callback(CSINN_MI355X, shl_cb_map_mi355x);
     shl_register_runtime_callback(CSINN_MI355X, shl_mi355x_runtime_callback);

@@ -10,6 +10,7 @@
  *   maxpool2d / avgpool2d  source/nn2/maxpool.c, averagepool.c
  *   concat ............ source/nn2/concat.c
  *   resize ............ source/nn2/resize.c
+ *   split / shuffle_channel  source/nn2/split.c, shuffle_channel.c
  *   deconv2d .......... source/nn2/deconvolution.c
  *   sigmoid / hard_sigmoid / silu / leaky_relu / mul  source/nn2/sigmoid.c, hard_sigmoid.c, silu.c, leaky_relu.c, mul.c
  * The only deliberate difference: a missing callback is reported (CSINN_CALLBACK_UNSET and an
@@ -314,6 +315,27 @@ int csinn_concat_init(struct csinn_tensor **input, struct csinn_tensor *output, 
     return map_and_init3(&params->base, CSINN_OP_CONCAT, output->dtype, input, output, params);
 }
 int csinn_concat(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params)
+{
+    return run3(&params->base, input, output, params);
+}
+
+/* source/nn2/split.c: one input, an array of params->output_num outputs; the callbacks are looked up by the input's dtype */
+int csinn_split_init(struct csinn_tensor *input, struct csinn_tensor **output, struct csinn_split_params *params)
+{
+    return map_and_init3(&params->base, CSINN_OP_SPLIT, input->dtype, input, output, params);
+}
+int csinn_split(struct csinn_tensor *input, struct csinn_tensor **output, struct csinn_split_params *params)
+{
+    return run3(&params->base, input, output, params);
+}
+
+/* source/nn2/shuffle_channel.c: one input, one output */
+int csinn_shuffle_channel_init(struct csinn_tensor *input, struct csinn_tensor *output,
+                               struct csinn_shuffle_channel_params *params)
+{
+    return map_and_init3(&params->base, CSINN_OP_SHUFFLE_CHANNEL, input->dtype, input, output, params);
+}
+int csinn_shuffle_channel(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_shuffle_channel_params *params)
 {
     return run3(&params->base, input, output, params);
 }

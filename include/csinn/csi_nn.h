@@ -84,6 +84,13 @@ int csinn_resize(struct csinn_tensor *input, struct csinn_tensor *output, struct
  * callbacks are looked up by the OUTPUT's dtype */
 int csinn_concat_init(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params);
 int csinn_concat(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params);
+/* split along one axis (source/nn2/split.c of the reference): `output` is an array of params->output_num tensors */
+int csinn_split_init(struct csinn_tensor *input, struct csinn_tensor **output, struct csinn_split_params *params);
+int csinn_split(struct csinn_tensor *input, struct csinn_tensor **output, struct csinn_split_params *params);
+/* shuffle_channel (source/nn2/shuffle_channel.c of the reference): one input, one output */
+int csinn_shuffle_channel_init(struct csinn_tensor *input, struct csinn_tensor *output,
+                               struct csinn_shuffle_channel_params *params);
+int csinn_shuffle_channel(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_shuffle_channel_params *params);
 /* MobileNet tail (source/nn2/global_avgpool2d.c, softmax.c of the reference) */
 int csinn_global_avgpool2d_init(struct csinn_tensor *input, struct csinn_tensor *output,
                                 struct csinn_pool_params *params);

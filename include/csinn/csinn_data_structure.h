@@ -144,8 +144,10 @@ enum csinn_op_enum {
     CSINN_OP_RELU = 127,
     CSINN_OP_RELU6 = 129,
     CSINN_OP_RESIZE = 133,
+    CSINN_OP_SHUFFLE_CHANNEL = 153,
     CSINN_OP_SIGMOID = 154,
     CSINN_OP_SOFTMAX = 159,
+    CSINN_OP_SPLIT = 166,
     CSINN_OP_SILU = 190,
     CSINN_OP_SIZE = 194,
     CSINN_OP_AND_UTILS_SIZE = 198
@@ -397,6 +399,22 @@ struct csinn_concat_params { /* 48 B */
     struct csinn_params_base base;
     int32_t inputs_count;
     int32_t axis;
+};
+
+/* split: one input, params->output_num outputs handed over as an array of tensor pointers; axis < 0 counts from the back.
+ * split_index == NULL: chunks of ceil(dim / output_num), the last output takes what is left; otherwise output i ends at
+ * split_index[i] (output_num - 1 boundaries) */
+struct csinn_split_params { /* 56 B */
+    struct csinn_params_base base;
+    int32_t *split_index;
+    int32_t output_num;
+    int32_t axis;
+};
+
+/* shuffle_channel of a 4-d tensor: out[.., j * group + k] = in[.., k * (C / group) + j] */
+struct csinn_shuffle_channel_params { /* 48 B */
+    struct csinn_params_base base;
+    int32_t group;
 };
 
 /* pooling (csinn_data_structure.h:643-662 of the reference); global_avgpool2d ignores the

@@ -81,6 +81,9 @@ int shl_gref_silu(struct csinn_tensor *input, struct csinn_tensor *output, struc
 int shl_gref_leaky_relu(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_relu_params *params);
 int shl_gref_resize(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_resize_params *params);
 int shl_gref_concat(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params);
+int shl_gref_split(struct csinn_tensor *input, struct csinn_tensor **output, struct csinn_split_params *params);
+int shl_gref_shuffle_channel(struct csinn_tensor *input, struct csinn_tensor *output,
+                             struct csinn_shuffle_channel_params *params);
 int shl_gref_global_avgpool2d(struct csinn_tensor *input, struct csinn_tensor *output,
                               struct csinn_pool_params *params);
 int shl_gref_maxpool2d(struct csinn_tensor *input, struct csinn_tensor *output,

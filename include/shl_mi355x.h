@@ -433,6 +433,61 @@ const char *shl_mi355x_concat_kernel_name(const void *const *in_dev, const int64
                                           const int32_t *in_zp, const void *out_dev,
                                           const struct shl_mi355x_concat_desc *d);
 
+/* split of an int8 / binary16 tensor along one axis into n_outputs tensors: shl_ref_split_quant
+ * (source/reference/split.c:74-92), bit for bit -- the mirror of concat.  The input is viewed as [outer][row], row = sum of
+ * len[i]; output i is [outer][len[i]] (len[i] = its axis dim times the product of the dims behind the axis, in elements,
+ * > 0) and holds columns sum of len[0..i) onwards.  Every output has its OWN record: the input is dequantised with its
+ * record and requantised with the output's (int8; an output whose record equals the input's is copied as bytes once that
+ * round trip was checked to be the identity); binary16 passes through the reference's float32 -> binary16 conversion
+ * (infinities saturate to +-65504, every NaN becomes 0x7FFF / 0xFFFF), scales and zero points are ignored.  No output may
+ * overlap the input or another output.  Up to 8 outputs travel in one launch, more in further launches.  Enqueues only: no
+ * allocation, no upload, no synchronisation (capturable in a hipGraph). */
+struct shl_mi355x_split_desc {
+    int32_t dtype;     /* SHL_MI355X_I8 / SHL_MI355X_F16 */
+    int32_t n_outputs; /* >= 1, no upper bound */
+    int64_t outer;     /* product of the dims in front of the axis */
+    float in_scale;
+    int32_t in_zp;
+    int32_t reserved[4]; /* must be zero */
+};
+
+int shl_mi355x_split(const void *in_dev, void *const *out_dev, const int64_t *len, const float *out_scale,
+                     const int32_t *out_zp, const struct shl_mi355x_split_desc *d, void *stream);
+/* the kernel form the rules choose ("split_vec": 16 bytes per thread, when every len[i] in bytes is a multiple of 16 and
+ * every pointer is 16-byte aligned; "split_generic": one element per thread; "" for invalid arguments).
+ * SHL_MI355X_SPLIT_FORM=generic forces the literal form; forcing `vec` where the arguments do not admit it gives generic.
+ * Pure host code: looks at the pointers' values only, touches no device */
+const char *shl_mi355x_split_kernel_name(const void *in_dev, void *const *out_dev, const int64_t *len, const float *out_scale,
+                                         const int32_t *out_zp, const struct shl_mi355x_split_desc *d);
+
+/* shuffle_channel: shl_ref_shuffle_channel_quant (source/reference/shuffle_channel.c), bit for bit.  The tensor is viewed
+ * as [outer][c][inner] (NHWC: outer = N H W, inner = 1; NCHW: outer = N, inner = H W); with gc = c / group,
+ * out[.., j * group + k, ..] = in[.., k * gc + j, ..] for j < gc, k < group.  Elements travel as split's do: int8 dequantised
+ * and requantised (a byte copy for equal records whose round trip is the identity), binary16 through the reference's
+ * conversion.  c % group != 0, group < 1 and an output that overlaps the input are refused.  Enqueues only: no allocation,
+ * no upload, no synchronisation (capturable in a hipGraph). */
+struct shl_mi355x_shuffle_desc {
+    int32_t dtype; /* SHL_MI355X_I8 / SHL_MI355X_F16 */
+    int32_t group;
+    int64_t outer, c, inner;
+    float in_scale;
+    int32_t in_zp;
+    float out_scale;
+    int32_t out_zp;
+    int32_t reserved[4]; /* must be zero */
+};
+
+int shl_mi355x_shuffle_channel(const void *in_dev, void *out_dev, const struct shl_mi355x_shuffle_desc *d, void *stream);
+/* the kernel form the rules choose; "" for invalid arguments.  Pure host code, touches no device.
+ *   "shuffle_plane_16" / "shuffle_plane_4"   inner in bytes a multiple of 16 / of 4, pointers aligned alike: pieces of a
+ *                                            plane are copied plane to plane
+ *   "shuffle_pixel_16" / "shuffle_pixel_4"   inner == 1, c in bytes a multiple of 16 / of 4 and at most 8192, pointers
+ *                                            aligned alike: a workgroup permutes a run of pixels through LDS
+ *   "shuffle_generic"                        one element per thread
+ * SHL_MI355X_SHUFFLE_FORM=generic | plane | pixel forces a form; one the arguments do not admit gives generic */
+const char *shl_mi355x_shuffle_channel_kernel_name(const void *in_dev, const void *out_dev,
+                                                   const struct shl_mi355x_shuffle_desc *d);
+
 /* nearest-neighbour / bilinear resize of a 4-d int8 / binary16 tensor: shl_ref_resize_quant
  * (source/reference/resize.c:464-468), bit for bit.  height_scale / width_scale are the reference's own floats, computed by
  * the CALLER as ONE float division each: (float)in / out, with align_corners (float)(in - 1) / (out - 1)

@@ -106,6 +106,13 @@ int shl_mi355x_add_exec(struct csinn_tensor *input0, struct csinn_tensor *input1
 /* concat along params->axis (-1: the last axis) of params->inputs_count tensors: every non-axis dim must equal the
  * output's and the axis dims must sum to the output's, else the call is refused; the same tensor may appear twice */
 int shl_mi355x_concat_exec(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params);
+/* split along params->axis (< 0: from the back) into params->output_num tensors, each with its own record: the outputs'
+ * dims must be the ones the reference's rule gives (split_index, or chunks of ceil(dim / output_num) with the last output
+ * taking what is left), every chunk longer than 0, else the call is refused (source/mi355x_opt/split.c) */
+int shl_mi355x_split_exec(struct csinn_tensor *input, struct csinn_tensor **output, struct csinn_split_params *params);
+/* shuffle_channel of a 4-d NHWC / NCHW tensor whose channel count is a multiple of params->group */
+int shl_mi355x_shuffle_channel_exec(struct csinn_tensor *input, struct csinn_tensor *output,
+                                    struct csinn_shuffle_channel_params *params);
 /* resize (source/mi355x_opt/resize.c): 4-d tensors, nearest-neighbour or bilinear, to the output tensor's height and
  * width; batch and channels of input and output must agree; bicubic, and align_corners with an output extent of 1 (the
  * reference divides by zero), are refused */
