@@ -32,6 +32,8 @@ OP_DEPTHWISE_CONV2D, OP_FULLYCONNECTED = 35, 71
 OP_AVGPOOL2D, OP_MAXPOOL2D = 14, 98
 OP_CONCAT = 26
 OP_SPLIT, OP_SHUFFLE_CHANNEL = 166, 153
+OP_TRANSPOSE, OP_RESHAPE, OP_FLATTEN, OP_PAD = 179, 132, 66, 115
+PAD_CONSTANT, PAD_EDGE, PAD_REFLECT = 0, 1, 2
 OP_SIGMOID, OP_HARD_SIGMOID, OP_SILU, OP_LEAKY_RELU, OP_MUL = 154, 78, 190, 84, 107
 OP_RESIZE = 133
 OP_DECONV2D, OP_DEPTHWISE_DECONV2D, OP_GROUP_DECONV2D = 54, 55, 56
@@ -154,6 +156,23 @@ class ShuffleChannelParams(C.Structure):
     _fields_ = [("base", ParamsBase), ("group", C.c_int32)]
 
 
+class TransposeParams(C.Structure):
+    _fields_ = [("base", ParamsBase), ("permute", C.POINTER(C.c_int32)), ("permute_num", C.c_int32)]
+
+
+class ReshapeParams(C.Structure):
+    _fields_ = [("base", ParamsBase), ("shape", C.POINTER(C.c_int32)), ("shape_num", C.c_int32)]
+
+
+class FlattenParams(C.Structure):
+    _fields_ = [("base", ParamsBase), ("axis", C.c_int32)]
+
+
+class PadParams(C.Structure):
+    _fields_ = [("base", ParamsBase), ("pad_before", C.POINTER(C.c_int32)), ("pad_after", C.POINTER(C.c_int32)),
+                ("pad_num", C.c_int32), ("pad_value", C.c_float), ("pad_mode", C.c_int32)]
+
+
 class ConvDesc(C.Structure):
     """struct shl_mi355x_conv_desc (include/shl_mi355x.h)"""
     _fields_ = [(n, C.c_int32) for n in (
@@ -188,6 +207,26 @@ class ShuffleDesc(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("group", C.c_int32), ("outer", C.c_int64), ("c", C.c_int64), ("inner", C.c_int64),
                 ("in_scale", C.c_float), ("in_zp", C.c_int32), ("out_scale", C.c_float), ("out_zp", C.c_int32),
                 ("reserved", C.c_int32 * 4)]
+
+
+class TransposeDesc(C.Structure):
+    """struct shl_mi355x_transpose_desc (include/shl_mi355x.h)"""
+    _fields_ = [("dtype", C.c_int32), ("rank", C.c_int32), ("dim", C.c_int32 * 8), ("perm", C.c_int32 * 8),
+                ("in_scale", C.c_float), ("in_zp", C.c_int32), ("out_scale", C.c_float), ("out_zp", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
+class MoveDesc(C.Structure):
+    """struct shl_mi355x_move_desc (include/shl_mi355x.h)"""
+    _fields_ = [("dtype", C.c_int32), ("in_scale", C.c_float), ("in_zp", C.c_int32), ("out_scale", C.c_float),
+                ("out_zp", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class PadDesc(C.Structure):
+    """struct shl_mi355x_pad_desc (include/shl_mi355x.h)"""
+    _fields_ = [("dtype", C.c_int32), ("dim", C.c_int32 * 4), ("before", C.c_int32 * 4), ("after", C.c_int32 * 4),
+                ("pad_value", C.c_float), ("in_scale", C.c_float), ("in_zp", C.c_int32), ("out_scale", C.c_float),
+                ("out_zp", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
 class ResizeDesc(C.Structure):
@@ -310,6 +349,13 @@ def load_hip():
                                                       C.POINTER(SplitDesc)]),
         "shl_mi355x_shuffle_channel": (C.c_int, [vp, vp, C.POINTER(ShuffleDesc), vp]),
         "shl_mi355x_shuffle_channel_kernel_name": (C.c_char_p, [vp, vp, C.POINTER(ShuffleDesc)]),
+        "shl_mi355x_transpose": (C.c_int, [vp, vp, C.POINTER(TransposeDesc), vp]),
+        "shl_mi355x_transpose_kernel_name": (C.c_char_p, [vp, vp, C.POINTER(TransposeDesc)]),
+        "shl_mi355x_move": (C.c_int, [vp, vp, C.c_int64, C.POINTER(MoveDesc), vp]),
+        "shl_mi355x_move_kernel_name": (C.c_char_p, [vp, vp, C.c_int64, C.POINTER(MoveDesc)]),
+        "shl_mi355x_pad": (C.c_int, [vp, vp, C.POINTER(PadDesc), vp]),
+        "shl_mi355x_pad_kernel_name": (C.c_char_p, [vp, vp, C.POINTER(PadDesc)]),
+        "shl_mi355x_pad_element": (C.c_uint32, [C.POINTER(PadDesc)]),
         "shl_mi355x_unary_lut_i8": (C.c_int, [vp, vp, sz, vp, vp]),
         "shl_mi355x_unary_lut_i8_kernel_name": (C.c_char_p, [vp, vp]),
         "shl_mi355x_unary_f16": (C.c_int, [vp, vp, sz, i32, f32, vp]),
@@ -354,7 +400,8 @@ _FRONTEND_SIGS = {
     "shl_debug_set_level": (None, [C.c_int]),
 }
 _SISO_OPS = ("csinn_relu", "csinn_relu6", "csinn_global_avgpool2d", "csinn_softmax", "csinn_maxpool2d", "csinn_avgpool2d",
-             "csinn_sigmoid", "csinn_hard_sigmoid", "csinn_silu", "csinn_leaky_relu", "csinn_resize", "csinn_shuffle_channel")
+             "csinn_sigmoid", "csinn_hard_sigmoid", "csinn_silu", "csinn_leaky_relu", "csinn_resize", "csinn_shuffle_channel",
+             "csinn_transpose", "csinn_reshape", "csinn_flatten", "csinn_pad")
 _CONV_OPS = ["csinn_conv2d", "csinn_conv2d_relu", "csinn_conv2d_relu6", "csinn_depthwise_conv2d",
              "csinn_depthwise_conv2d_relu", "csinn_fullyconnected", "csinn_deconv2d"] + list(_SISO_OPS)
 
@@ -596,6 +643,54 @@ def shuffle_channel_params(fe, keep, api, layout, group, sess=None, name=b"shuff
     if sess is not None:
         pc.base.sess = sess
     pc.group = group
+    return p
+
+
+def _move_params(fe, keep, struct, api, layout, sess, name):
+    p = fe.csinn_alloc_params(C.sizeof(struct), sess)
+    pc = C.cast(p, C.POINTER(struct)).contents
+    pc.base.api = api
+    pc.base.layout = layout
+    pc.base.name = keep.add(C.c_char_p(name)).value
+    if sess is not None:
+        pc.base.sess = sess
+    return p, pc
+
+
+def transpose_params(fe, keep, api, layout, permute, sess=None, name=b"transpose", permute_num=None):
+    """params block of csinn_transpose: output dim k is input dim permute[k]"""
+    p, pc = _move_params(fe, keep, TransposeParams, api, layout, sess, name)
+    arr = keep.add((C.c_int32 * max(len(permute), 1))(*permute))
+    pc.permute = C.cast(arr, C.POINTER(C.c_int32))
+    pc.permute_num = len(permute) if permute_num is None else permute_num
+    return p
+
+
+def reshape_params(fe, keep, api, layout, shape, sess=None, name=b"reshape"):
+    """params block of csinn_reshape: `shape` is what the output tensor's dims were derived from"""
+    p, pc = _move_params(fe, keep, ReshapeParams, api, layout, sess, name)
+    arr = keep.add((C.c_int32 * max(len(shape), 1))(*shape))
+    pc.shape = C.cast(arr, C.POINTER(C.c_int32))
+    pc.shape_num = len(shape)
+    return p
+
+
+def flatten_params(fe, keep, api, layout, axis=1, sess=None, name=b"flatten"):
+    """params block of csinn_flatten"""
+    p, pc = _move_params(fe, keep, FlattenParams, api, layout, sess, name)
+    pc.axis = axis
+    return p
+
+
+def pad_params(fe, keep, api, layout, before, after, value=0.0, mode=PAD_CONSTANT, sess=None, name=b"pad", pad_num=None):
+    """params block of csinn_pad: pads per dim in memory order"""
+    p, pc = _move_params(fe, keep, PadParams, api, layout, sess, name)
+    b = keep.add((C.c_int32 * max(len(before), 1))(*before))
+    a = keep.add((C.c_int32 * max(len(after), 1))(*after))
+    pc.pad_before, pc.pad_after = C.cast(b, C.POINTER(C.c_int32)), C.cast(a, C.POINTER(C.c_int32))
+    pc.pad_num = len(before) if pad_num is None else pad_num
+    pc.pad_value = value
+    pc.pad_mode = mode
     return p
 
 

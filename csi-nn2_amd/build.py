@@ -44,7 +44,8 @@ def _glob(d, exts):
 NO_SPILL_SOURCES = ("conv_igemm.hip", "conv_igemm_pp.hip", "conv_igemm_pc.hip",
                     "conv_igemm_halo.hip",
                     "dwpw_resident.hip",  # (its tile loop counts vector memory instructions: a scratch reload is one)
-                    "split.hip", "shuffle.hip")  # (pure data movement: scratch traffic would be most of their memory traffic)
+                    "split.hip", "shuffle.hip",  # (pure data movement: scratch traffic would be most of their memory traffic)
+                    "transpose.hip", "pad.hip")
 
 
 def spilled_kernels(usage_file):

@@ -283,6 +283,26 @@ int shl_gref_shuffle_channel(struct csinn_tensor *input, struct csinn_tensor *ou
     return record_siso(input, output, CSINN_OP_SHUFFLE_CHANNEL, params);
 }
 
+int shl_gref_transpose(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_transpose_params *params)
+{
+    return record_siso(input, output, CSINN_OP_TRANSPOSE, params);
+}
+
+int shl_gref_reshape(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reshape_params *params)
+{
+    return record_siso(input, output, CSINN_OP_RESHAPE, params);
+}
+
+int shl_gref_flatten(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_flatten_params *params)
+{
+    return record_siso(input, output, CSINN_OP_FLATTEN, params);
+}
+
+int shl_gref_pad(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pad_params *params)
+{
+    return record_siso(input, output, CSINN_OP_PAD, params);
+}
+
 int shl_gref_global_avgpool2d(struct csinn_tensor *input, struct csinn_tensor *output,
                               struct csinn_pool_params *params)
 {
@@ -325,6 +345,10 @@ int shl_gref_call_layer_func(void *fn, struct shl_node *node)
         case CSINN_OP_LEAKY_RELU:
         case CSINN_OP_RESIZE:
         case CSINN_OP_SHUFFLE_CHANNEL:
+        case CSINN_OP_TRANSPOSE:
+        case CSINN_OP_RESHAPE:
+        case CSINN_OP_FLATTEN:
+        case CSINN_OP_PAD:
             return f(node->in[0]->data, node->out[0]->data, params);
         case CSINN_OP_ADD:
         case CSINN_OP_MUL:
@@ -374,7 +398,7 @@ struct csinn_callback *shl_gref_best_callback(struct shl_node *node)
     return params->cb;
 }
 
-static struct csinn_callback g_est_only[32];
+static struct csinn_callback g_est_only[48];
 
 static struct csinn_callback *gref_cb_map(int op, int dtype)
 {
@@ -409,6 +433,10 @@ static struct csinn_callback *gref_cb_map(int op, int dtype)
         {CSINN_OP_RESIZE, shl_gref_resize},
         {CSINN_OP_SPLIT, shl_gref_split},
         {CSINN_OP_SHUFFLE_CHANNEL, shl_gref_shuffle_channel},
+        {CSINN_OP_TRANSPOSE, shl_gref_transpose},
+        {CSINN_OP_RESHAPE, shl_gref_reshape},
+        {CSINN_OP_FLATTEN, shl_gref_flatten},
+        {CSINN_OP_PAD, shl_gref_pad},
     };
     _Static_assert(sizeof(table) / sizeof(table[0]) <= sizeof(g_est_only) / sizeof(g_est_only[0]), "one callback block per table row");
     for (unsigned i = 0; i < sizeof(table) / sizeof(table[0]); i++) {

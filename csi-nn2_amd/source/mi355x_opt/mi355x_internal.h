@@ -60,6 +60,30 @@ int shl_mi355x_shuffle_channel_init(struct csinn_tensor *input, struct csinn_ten
 int shl_mi355x_shuffle_channel_perf(struct csinn_tensor *input, struct csinn_tensor *output,
                                     struct csinn_shuffle_channel_params *params, struct csinn_perf_info *info);
 
+/* shared by the callbacks of the ops that move data (split.c, move.c).  check_io: dtypes and records, what every device op
+ * asks of an (input, output) pair.  fall_through: a layer refused at init runs on the reference's kernel next to the genuine
+ * library (elsewhere exec refuses it again: the front-ends drop init's status).  perf_address: the address a tensor's bytes
+ * will have on the device as far as its alignment goes -- a DMABUF tensor's own, else a made-up one with the staging path's
+ * alignment */
+int shl_mi355x_check_io(const char *op, struct csinn_tensor *input, struct csinn_tensor *output, int *dtype);
+void shl_mi355x_fall_through(struct csinn_params_base *base, int op, int dtype);
+uintptr_t shl_mi355x_perf_address(struct csinn_tensor *t, uintptr_t *at);
+
+/* transpose, reshape, flatten and pad (move.c): init (a refused layer falls through to the reference where there is one)
+ * and perf */
+int shl_mi355x_transpose_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_transpose_params *params);
+int shl_mi355x_transpose_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_transpose_params *params,
+        struct csinn_perf_info *info);
+int shl_mi355x_reshape_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reshape_params *params);
+int shl_mi355x_reshape_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reshape_params *params,
+        struct csinn_perf_info *info);
+int shl_mi355x_flatten_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_flatten_params *params);
+int shl_mi355x_flatten_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_flatten_params *params,
+        struct csinn_perf_info *info);
+int shl_mi355x_pad_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pad_params *params);
+int shl_mi355x_pad_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pad_params *params,
+        struct csinn_perf_info *info);
+
 /* ... and of the elementwise layers (eltwise.c): the kernel form the rules choose */
 int shl_mi355x_sigmoid_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params,
                             struct csinn_perf_info *info);

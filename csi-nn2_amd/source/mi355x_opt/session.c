@@ -155,6 +155,11 @@ static const struct session_op g_ops[] = {
     {CSINN_OP_CONCAT, shl_mi355x_concat_exec, CALL_ARRAY, 0, 0}, /* any input may be */
     {CSINN_OP_SPLIT, shl_mi355x_split_exec, CALL_SPLIT, 1, 1},   /* a ShuffleNetV2 unit, a CSP / C2f block */
     {CSINN_OP_SHUFFLE_CHANNEL, shl_mi355x_shuffle_channel_exec, CALL_SISO, 1, 1},
+    /* order and shape only: a detection head, an attention block, TensorFlow's SAME padding, the classifier's flatten */
+    {CSINN_OP_TRANSPOSE, shl_mi355x_transpose_exec, CALL_SISO, 1, 1},
+    {CSINN_OP_RESHAPE, shl_mi355x_reshape_exec, CALL_SISO, 1, 1}, /* one copy node; sharing the producer's buffer is a later change */
+    {CSINN_OP_FLATTEN, shl_mi355x_flatten_exec, CALL_SISO, 1, 1},
+    {CSINN_OP_PAD, shl_mi355x_pad_exec, CALL_SISO, 1, 1},
 };
 
 /* the row of layer `n`; NULL: not a layer this file runs */

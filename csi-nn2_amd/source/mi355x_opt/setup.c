@@ -12,7 +12,7 @@
 #include "mi355x_internal.h"
 
 /* ------------------------------------------------------------------------ callback table */
-#define MI355X_CB_MAX 96
+#define MI355X_CB_MAX 128
 static struct {
     int key; /* op * CSINN_DTYPE_SIZE + dtype */
     struct csinn_callback cb;
@@ -705,6 +705,10 @@ void shl_target_init_mi355x(void)
         reg(dts[i], CSINN_OP_SPLIT, shl_mi355x_split_init, shl_mi355x_split_exec, shl_gref_split, shl_mi355x_split_perf);
         reg(dts[i], CSINN_OP_SHUFFLE_CHANNEL, shl_mi355x_shuffle_channel_init, shl_mi355x_shuffle_channel_exec,
             shl_gref_shuffle_channel, shl_mi355x_shuffle_channel_perf);
+        reg(dts[i], CSINN_OP_TRANSPOSE, shl_mi355x_transpose_init, shl_mi355x_transpose_exec, shl_gref_transpose, shl_mi355x_transpose_perf);
+        reg(dts[i], CSINN_OP_RESHAPE, shl_mi355x_reshape_init, shl_mi355x_reshape_exec, shl_gref_reshape, shl_mi355x_reshape_perf);
+        reg(dts[i], CSINN_OP_FLATTEN, shl_mi355x_flatten_init, shl_mi355x_flatten_exec, shl_gref_flatten, shl_mi355x_flatten_perf);
+        reg(dts[i], CSINN_OP_PAD, shl_mi355x_pad_init, shl_mi355x_pad_exec, shl_gref_pad, shl_mi355x_pad_perf);
     }
     shl_register_op_callback(CSINN_MI355X, shl_cb_map_mi355x);
     shl_register_runtime_callback(CSINN_MI355X, shl_mi355x_runtime_callback);

@@ -23,7 +23,7 @@ static int dtype_code(const struct csinn_tensor *t)
 }
 
 /* dtypes, records: what every device op asks of an (input, output) pair */
-static int check_io(const char *op, struct csinn_tensor *input, struct csinn_tensor *output, int *dtype)
+int shl_mi355x_check_io(const char *op, struct csinn_tensor *input, struct csinn_tensor *output, int *dtype)
 {
     *dtype = dtype_code(input);
     if (*dtype < 0 || dtype_code(output) != *dtype) {
@@ -47,7 +47,7 @@ static int check_io(const char *op, struct csinn_tensor *input, struct csinn_ten
 
 /* a layer this backend refused at init: next to the genuine library it runs on the reference's kernel, elsewhere exec
  * refuses it again (the front-ends drop init's status, source/nn2/split.c:30-35) */
-static void fall_through(struct csinn_params_base *base, int op, int dtype)
+void shl_mi355x_fall_through(struct csinn_params_base *base, int op, int dtype)
 {
     if (shl_cb_map_ref && base->cb) {
         struct csinn_callback *cb = shl_cb_map_ref(op, dtype);
@@ -106,7 +106,7 @@ static int split_prepare(struct csinn_tensor *input, struct csinn_tensor **outpu
             shl_debug_error("mi355x: split: output %d is NULL\n", i);
             return CSINN_FALSE;
         }
-        int rc = check_io("split", input, output[i], &dtype);
+        int rc = shl_mi355x_check_io("split", input, output[i], &dtype);
         if (rc != CSINN_TRUE) return rc;
         /* where output i ends: split_index[i], or i + 1 chunks; the last output ends where the axis does
          * (output_num == 1: the whole tensor, split_index is not read) */
@@ -161,7 +161,7 @@ int shl_mi355x_split_init(struct csinn_tensor *input, struct csinn_tensor **outp
 {
     struct split_call c;
     if (split_prepare(input, output, params, &c) == CSINN_TRUE) split_release(&c);
-    else fall_through(&params->base, CSINN_OP_SPLIT, input ? input->dtype : -1);
+    else shl_mi355x_fall_through(&params->base, CSINN_OP_SPLIT, input ? input->dtype : -1);
     return CSINN_TRUE;
 }
 
@@ -194,7 +194,7 @@ int shl_mi355x_split_exec(struct csinn_tensor *input, struct csinn_tensor **outp
 
 /* the address a tensor's bytes will have on the device as far as its alignment goes: a DMABUF tensor's own, else a made-up
  * one with the staging path's alignment (disjoint: nothing is staged or followed) */
-static uintptr_t perf_address(struct csinn_tensor *t, uintptr_t *at)
+uintptr_t shl_mi355x_perf_address(struct csinn_tensor *t, uintptr_t *at)
 {
     if (t->mtype == CSINN_MEM_TYPE_DMABUF && t->data) return (uintptr_t)t->data;
     const uintptr_t bytes = (uintptr_t)csinn_tensor_byte_size(t), here = *at;
@@ -210,8 +210,8 @@ int shl_mi355x_split_perf(struct csinn_tensor *input, struct csinn_tensor **outp
     int rc = split_prepare(input, output, params, &c);
     if (rc != CSINN_TRUE) return rc;
     uintptr_t at = (uintptr_t)1 << 56;
-    const void *in = (const void *)perf_address(input, &at);
-    for (int i = 0; i < c.desc.n_outputs; i++) c.dev[i] = (void *)perf_address(output[i], &at);
+    const void *in = (const void *)shl_mi355x_perf_address(input, &at);
+    for (int i = 0; i < c.desc.n_outputs; i++) c.dev[i] = (void *)shl_mi355x_perf_address(output[i], &at);
     info->kernel_name = (char *)shl_mi355x_split_kernel_name(in, c.dev, c.len, c.scale, c.zp, &c.desc);
     split_release(&c);
     return CSINN_TRUE;
@@ -223,7 +223,7 @@ static int shuffle_desc(struct csinn_tensor *input, struct csinn_tensor *output,
 {
     int dtype;
     if (input == NULL || output == NULL) return CSINN_FALSE;
-    int rc = check_io("shuffle_channel", input, output, &dtype);
+    int rc = shl_mi355x_check_io("shuffle_channel", input, output, &dtype);
     if (rc != CSINN_TRUE) return rc;
     if (input->dim_count != 4 || output->dim_count != 4) {
         shl_debug_error("mi355x: shuffle_channel expects 4-d tensors\n");
@@ -262,7 +262,7 @@ int shl_mi355x_shuffle_channel_init(struct csinn_tensor *input, struct csinn_ten
 {
     struct shl_mi355x_shuffle_desc d;
     if (shuffle_desc(input, output, params, &d) != CSINN_TRUE)
-        fall_through(&params->base, CSINN_OP_SHUFFLE_CHANNEL, input ? input->dtype : -1);
+        shl_mi355x_fall_through(&params->base, CSINN_OP_SHUFFLE_CHANNEL, input ? input->dtype : -1);
     return CSINN_TRUE;
 }
 
@@ -292,7 +292,7 @@ int shl_mi355x_shuffle_channel_perf(struct csinn_tensor *input, struct csinn_ten
     int rc = shuffle_desc(input, output, params, &d);
     if (rc != CSINN_TRUE) return rc;
     uintptr_t at = (uintptr_t)1 << 56;
-    const void *in = (const void *)perf_address(input, &at);
-    info->kernel_name = (char *)shl_mi355x_shuffle_channel_kernel_name(in, (const void *)perf_address(output, &at), &d);
+    const void *in = (const void *)shl_mi355x_perf_address(input, &at);
+    info->kernel_name = (char *)shl_mi355x_shuffle_channel_kernel_name(in, (const void *)shl_mi355x_perf_address(output, &at), &d);
     return CSINN_TRUE;
 }

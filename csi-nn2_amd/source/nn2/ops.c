@@ -11,6 +11,7 @@
  *   concat ............ source/nn2/concat.c
  *   resize ............ source/nn2/resize.c
  *   split / shuffle_channel  source/nn2/split.c, shuffle_channel.c
+ *   transpose / reshape / flatten / pad  source/nn2/transpose.c, reshape.c, flatten.c, pad.c
  *   deconv2d .......... source/nn2/deconvolution.c
  *   sigmoid / hard_sigmoid / silu / leaky_relu / mul  source/nn2/sigmoid.c, hard_sigmoid.c, silu.c, leaky_relu.c, mul.c
  * The only deliberate difference: a missing callback is reported (CSINN_CALLBACK_UNSET and an
@@ -336,6 +337,40 @@ int csinn_shuffle_channel_init(struct csinn_tensor *input, struct csinn_tensor *
     return map_and_init3(&params->base, CSINN_OP_SHUFFLE_CHANNEL, input->dtype, input, output, params);
 }
 int csinn_shuffle_channel(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_shuffle_channel_params *params)
+{
+    return run3(&params->base, input, output, params);
+}
+
+/* source/nn2/transpose.c, reshape.c, flatten.c, pad.c: one input, one output */
+int csinn_transpose_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_transpose_params *params)
+{
+    return map_and_init3(&params->base, CSINN_OP_TRANSPOSE, input->dtype, input, output, params);
+}
+int csinn_transpose(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_transpose_params *params)
+{
+    return run3(&params->base, input, output, params);
+}
+int csinn_reshape_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reshape_params *params)
+{
+    return map_and_init3(&params->base, CSINN_OP_RESHAPE, input->dtype, input, output, params);
+}
+int csinn_reshape(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reshape_params *params)
+{
+    return run3(&params->base, input, output, params);
+}
+int csinn_flatten_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_flatten_params *params)
+{
+    return map_and_init3(&params->base, CSINN_OP_FLATTEN, input->dtype, input, output, params);
+}
+int csinn_flatten(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_flatten_params *params)
+{
+    return run3(&params->base, input, output, params);
+}
+int csinn_pad_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pad_params *params)
+{
+    return map_and_init3(&params->base, CSINN_OP_PAD, input->dtype, input, output, params);
+}
+int csinn_pad(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pad_params *params)
 {
     return run3(&params->base, input, output, params);
 }

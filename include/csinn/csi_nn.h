@@ -91,6 +91,16 @@ int csinn_split(struct csinn_tensor *input, struct csinn_tensor **output, struct
 int csinn_shuffle_channel_init(struct csinn_tensor *input, struct csinn_tensor *output,
                                struct csinn_shuffle_channel_params *params);
 int csinn_shuffle_channel(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_shuffle_channel_params *params);
+/* transpose, reshape, flatten, pad (source/nn2/transpose.c, reshape.c, flatten.c, pad.c of the reference): one input, one
+ * output */
+int csinn_transpose_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_transpose_params *params);
+int csinn_transpose(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_transpose_params *params);
+int csinn_reshape_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reshape_params *params);
+int csinn_reshape(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reshape_params *params);
+int csinn_flatten_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_flatten_params *params);
+int csinn_flatten(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_flatten_params *params);
+int csinn_pad_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pad_params *params);
+int csinn_pad(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pad_params *params);
 /* MobileNet tail (source/nn2/global_avgpool2d.c, softmax.c of the reference) */
 int csinn_global_avgpool2d_init(struct csinn_tensor *input, struct csinn_tensor *output,
                                 struct csinn_pool_params *params);

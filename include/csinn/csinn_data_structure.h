@@ -135,19 +135,23 @@ enum csinn_op_enum {
     CSINN_OP_DECONV2D = 54, /* transposed convolution: group == 1 / == Cin / == Cout (csinn_deconv2d_init) */
     CSINN_OP_DEPTHWISE_DECONV2D = 55,
     CSINN_OP_GROUP_DECONV2D = 56,
+    CSINN_OP_FLATTEN = 66,
     CSINN_OP_FULLYCONNECTED = 71,
     CSINN_OP_GLOBAL_AVGPOOL2D = 74,
     CSINN_OP_HARD_SIGMOID = 78,
     CSINN_OP_LEAKY_RELU = 84,
     CSINN_OP_MAXPOOL2D = 98,
     CSINN_OP_MUL = 107,
+    CSINN_OP_PAD = 115,
     CSINN_OP_RELU = 127,
     CSINN_OP_RELU6 = 129,
+    CSINN_OP_RESHAPE = 132,
     CSINN_OP_RESIZE = 133,
     CSINN_OP_SHUFFLE_CHANNEL = 153,
     CSINN_OP_SIGMOID = 154,
     CSINN_OP_SOFTMAX = 159,
     CSINN_OP_SPLIT = 166,
+    CSINN_OP_TRANSPOSE = 179,
     CSINN_OP_SILU = 190,
     CSINN_OP_SIZE = 194,
     CSINN_OP_AND_UTILS_SIZE = 198
@@ -415,6 +419,43 @@ struct csinn_split_params { /* 56 B */
 struct csinn_shuffle_channel_params { /* 48 B */
     struct csinn_params_base base;
     int32_t group;
+};
+
+/* the operators that only change a tensor's order or shape (csinn_data_structure.h:801-808, 856-867, 887-890 of the
+ * reference).  transpose: output dim k is input dim permute[k], permute_num == dim_count.  reshape / flatten: a flat copy
+ * into the output tensor's dims -- `shape` and `axis` are what the converter derived those dims from and are not read.
+ * pad: output dim k = pad_before[k] + dim k + pad_after[k] in memory order, pad_num == 4, CSINN_PAD_CONSTANT only (the
+ * reference asserts on the other two) */
+struct csinn_transpose_params { /* 56 B */
+    struct csinn_params_base base;
+    int32_t *permute;
+    int32_t permute_num;
+};
+
+struct csinn_reshape_params { /* 56 B */
+    struct csinn_params_base base;
+    int32_t *shape;
+    int32_t shape_num;
+};
+
+struct csinn_flatten_params { /* 48 B */
+    struct csinn_params_base base;
+    int32_t axis;
+};
+
+enum csinn_pad_enum {
+    CSINN_PAD_CONSTANT = 0,
+    CSINN_PAD_EDGE = 1,
+    CSINN_PAD_REFLECT = 2,
+};
+
+struct csinn_pad_params { /* 72 B */
+    struct csinn_params_base base;
+    int32_t *pad_before;
+    int32_t *pad_after;
+    int32_t pad_num;
+    float pad_value;
+    enum csinn_pad_enum pad_mode;
 };
 
 /* pooling (csinn_data_structure.h:643-662 of the reference); global_avgpool2d ignores the

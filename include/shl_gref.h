@@ -84,6 +84,10 @@ int shl_gref_concat(struct csinn_tensor **input, struct csinn_tensor *output, st
 int shl_gref_split(struct csinn_tensor *input, struct csinn_tensor **output, struct csinn_split_params *params);
 int shl_gref_shuffle_channel(struct csinn_tensor *input, struct csinn_tensor *output,
                              struct csinn_shuffle_channel_params *params);
+int shl_gref_transpose(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_transpose_params *params);
+int shl_gref_reshape(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reshape_params *params);
+int shl_gref_flatten(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_flatten_params *params);
+int shl_gref_pad(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pad_params *params);
 int shl_gref_global_avgpool2d(struct csinn_tensor *input, struct csinn_tensor *output,
                               struct csinn_pool_params *params);
 int shl_gref_maxpool2d(struct csinn_tensor *input, struct csinn_tensor *output,

@@ -488,6 +488,95 @@ int shl_mi355x_shuffle_channel(const void *in_dev, void *out_dev, const struct s
 const char *shl_mi355x_shuffle_channel_kernel_name(const void *in_dev, const void *out_dev,
                                                    const struct shl_mi355x_shuffle_desc *d);
 
+/* The operators that only change a tensor's order or shape: transpose, pad, and the flat move behind reshape / flatten.  In
+ * the reference all of them go through shl_ref_siso_callback_base -- dequantise, move, requantise with the output's record
+ * -- so elements travel as split's do: int8 q_out = sat8(rint(((q - zp_in) * s_in) / s_out) + zp_out) (a byte copy for equal
+ * records whose round trip is the identity, div_by_scale where the records admit it, the hardware's division otherwise);
+ * binary16 through the reference's conversion (infinities saturate to +-65504, every NaN becomes 0x7FFF / 0xFFFF), scales
+ * and zero points ignored.  The output may not overlap the input.  All enqueue only: no allocation, no upload, no
+ * synchronisation (capturable in a hipGraph). */
+#define SHL_MI355X_MAX_DIM 8
+
+/* transpose: shl_ref_transpose (source/reference/transpose.c), bit for bit: output dim k is input dim perm[k].  rank
+ * 1 .. 8, perm a permutation of 0 .. rank - 1, dims >= 0; anything else is SHL_MI355X_EINVAL before anything is enqueued.
+ * The layer is canonicalised on the host -- dims of extent 1 dropped, dims adjacent in the same order in input and output
+ * merged -- and one of four forms runs:
+ *   "transpose_flat"      the canonical permutation is the identity and both pointers are 16-byte aligned: 16 bytes per
+ *                         thread, the last thread finishing a tail of fewer than 16 bytes by elements
+ *   "transpose_rows_16" / "transpose_rows_4"   the innermost canonical dim stays innermost and a run of it in bytes is a
+ *                         multiple of 16 / of 4, pointers aligned alike: one piece per thread in output order, the outer
+ *                         coordinates taken apart by division
+ *   "transpose_tile_4" / "_4_1" / "_1_4" / "_1"   the output's innermost canonical dim is not the input's: 64 x 64-element
+ *                         tiles over (input's innermost, output's innermost) through LDS, reads along the input's
+ *                         contiguous dim, writes along the output's, every other dim a batch coordinate; edge tiles are
+ *                         masked.  A side whose extent in bytes is a multiple of 4 and whose pointer is 4-byte aligned
+ *                         moves dwords, the other one element per lane (ragged extents: 7 x 7 maps, 85-value heads):
+ *                         _4 dwords on both sides, _4_1 dword loads and element stores, _1_4 the reverse, _1 elements
+ *   "transpose_generic"   one output element per thread
+ * SHL_MI355X_TRANSPOSE_FORM=generic | tile | rows forces a form; one the arguments do not admit gives generic. */
+struct shl_mi355x_transpose_desc {
+    int32_t dtype; /* SHL_MI355X_I8 / SHL_MI355X_F16 */
+    int32_t rank;
+    int32_t dim[SHL_MI355X_MAX_DIM];  /* the INPUT's dims */
+    int32_t perm[SHL_MI355X_MAX_DIM]; /* output dim k = input dim perm[k] */
+    float in_scale;
+    int32_t in_zp;
+    float out_scale;
+    int32_t out_zp;
+    int32_t reserved[4]; /* must be zero */
+};
+
+int shl_mi355x_transpose(const void *in_dev, void *out_dev, const struct shl_mi355x_transpose_desc *d, void *stream);
+/* the kernel form the rules choose; "" for invalid arguments.  Pure host code, touches no device */
+const char *shl_mi355x_transpose_kernel_name(const void *in_dev, const void *out_dev,
+                                             const struct shl_mi355x_transpose_desc *d);
+
+/* the flat requantised move of `elems` elements: what reshape and flatten are (the reference copies
+ * csinn_tensor_byte_size(input) bytes between the two conversions).  Runs "transpose_flat" when both pointers are 16-byte
+ * aligned, "transpose_rows_4" when they are 4-byte aligned and the bytes a multiple of 4, else "transpose_generic";
+ * SHL_MI355X_TRANSPOSE_FORM applies. */
+struct shl_mi355x_move_desc {
+    int32_t dtype; /* SHL_MI355X_I8 / SHL_MI355X_F16 */
+    float in_scale;
+    int32_t in_zp;
+    float out_scale;
+    int32_t out_zp;
+    int32_t reserved[3]; /* must be zero */
+};
+
+int shl_mi355x_move(const void *in_dev, void *out_dev, int64_t elems, const struct shl_mi355x_move_desc *d, void *stream);
+const char *shl_mi355x_move_kernel_name(const void *in_dev, const void *out_dev, int64_t elems,
+                                        const struct shl_mi355x_move_desc *d);
+
+/* constant pad of a 4-d tensor: shl_ref_pad_f32 (source/reference/pad.c) between the two conversions, bit for bit.  Dim k
+ * of the output is before[k] + dim[k] + after[k], in memory order -- NCHW and NHWC differ only in what the caller calls the
+ * dims.  The pad element is computed ONCE on the host as the reference's conversion of the float32 pad_value with the
+ * OUTPUT's record: int8 sat8(rint(v / s_out) + zp_out), binary16 float32_to_float16_base(v) (-inf: 0xFBFF).  Negative
+ * pads or dims are SHL_MI355X_EINVAL.  Two forms:
+ *   "pad_vec"      16 bytes per thread in output order.  With j the innermost dim that is padded (dim 0 when none is) and U
+ *                  the bytes of one step along it (the dims behind it times the element size): before[j] * U, dim[j] * U
+ *                  and after[j] * U are multiples of 16 and both pointers 16-byte aligned -- every piece then is all pad or
+ *                  all interior, and an interior piece's source is aligned.  NHWC with H / W padding only meets it whenever
+ *                  C in bytes is a multiple of 16 (W * C then is too)
+ *   "pad_generic"  one output element per thread
+ * SHL_MI355X_PAD_FORM=generic forces the literal form. */
+struct shl_mi355x_pad_desc {
+    int32_t dtype; /* SHL_MI355X_I8 / SHL_MI355X_F16 */
+    int32_t dim[4]; /* the INPUT's dims */
+    int32_t before[4], after[4];
+    float pad_value;
+    float in_scale;
+    int32_t in_zp;
+    float out_scale;
+    int32_t out_zp;
+    int32_t reserved[4]; /* must be zero */
+};
+
+int shl_mi355x_pad(const void *in_dev, void *out_dev, const struct shl_mi355x_pad_desc *d, void *stream);
+const char *shl_mi355x_pad_kernel_name(const void *in_dev, const void *out_dev, const struct shl_mi355x_pad_desc *d);
+/* the pad element as the kernels write it (low byte / low half): pure host code */
+uint32_t shl_mi355x_pad_element(const struct shl_mi355x_pad_desc *d);
+
 /* nearest-neighbour / bilinear resize of a 4-d int8 / binary16 tensor: shl_ref_resize_quant
  * (source/reference/resize.c:464-468), bit for bit.  height_scale / width_scale are the reference's own floats, computed by
  * the CALLER as ONE float division each: (float)in / out, with align_corners (float)(in - 1) / (out - 1)

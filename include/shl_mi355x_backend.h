@@ -113,6 +113,15 @@ int shl_mi355x_split_exec(struct csinn_tensor *input, struct csinn_tensor **outp
 /* shuffle_channel of a 4-d NHWC / NCHW tensor whose channel count is a multiple of params->group */
 int shl_mi355x_shuffle_channel_exec(struct csinn_tensor *input, struct csinn_tensor *output,
                                     struct csinn_shuffle_channel_params *params);
+/* transpose of a tensor of up to 8 dims under any permutation: permute_num must equal dim_count, permute be a permutation
+ * and the output's dims the permuted input dims, else the call is refused (source/mi355x_opt/move.c) */
+int shl_mi355x_transpose_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_transpose_params *params);
+/* reshape / flatten: a flat requantised copy into the output tensor's dims; unequal element counts are refused */
+int shl_mi355x_reshape_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reshape_params *params);
+int shl_mi355x_flatten_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_flatten_params *params);
+/* constant pad of a 4-d NCHW / NHWC tensor (pad_num == 4): EDGE / REFLECT, negative pads and output dims other than
+ * input + before + after are refused */
+int shl_mi355x_pad_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pad_params *params);
 /* resize (source/mi355x_opt/resize.c): 4-d tensors, nearest-neighbour or bilinear, to the output tensor's height and
  * width; batch and channels of input and output must agree; bicubic, and align_corners with an output extent of 1 (the
  * reference divides by zero), are refused */
