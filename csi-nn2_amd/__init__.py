@@ -306,6 +306,7 @@ def load_hip():
         "shl_mi355x_deconv_geometry": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(i32), i32]),
         "shl_mi355x_debug_trace": (C.c_int, [vp, i32]),
         "shl_mi355x_debug_div_check": (C.c_int, [vp, i32, vp, vp]),
+        "shl_mi355x_debug_running_sum": (C.c_int, [vp, i32, i32, vp]),
         "shl_mi355x_debug_f16_round_check": (C.c_int, [vp]),
         "shl_mi355x_debug_mfma_rate": (C.c_int, [i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "shl_mi355x_comm_available": (C.c_int, []),

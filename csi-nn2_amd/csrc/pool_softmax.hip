@@ -100,8 +100,10 @@ __global__ __launch_bounds__(64) void global_avgpool_nhwc_i8_kernel(const void *
 // the block advances by their prefix sum.  A wave evaluates 64 elements per round (t' = ((2^E + e) - 2^E) / u
 // in double arithmetic, exact), scans the increments and stops at the first element that either is a tie
 // or would carry acc out of the binade (m + prefix >= 2^24, conservatively); that element takes the literal
-// step and the next round starts from the new acc (and binade).  Bit-identical to the literal loop --
-// tests/test_tail.py compares the two forms on adversarial rows.
+// step and the next round starts from the new acc (and binade).  Bit-identical to the literal loop:
+// tests/test_tail_sweeps.py feeds both forms crafted terms (tests/softmax_sum_cases.py: ties, binade exits,
+// inf / NaN, a subnormal sum) through shl_mi355x_debug_running_sum and compares each with a numpy loop;
+// tests/test_softmax_scan.py compares the two forms' softmax outputs.
 __device__ __forceinline__ double readlane_f64(double x, int l)  // (l wave-uniform)
 {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), l), __builtin_amdgcn_readlane(__double2loint(x), l));
@@ -204,7 +206,42 @@ __device__ __forceinline__ float running_sum_exact(const double *e, int cnt, int
     return acc;
 }
 
+// The literal loop on one lane (SHL_MI355X_SOFTMAX_SEQ=1, shl_mi355x_debug_running_sum): `acc_exp += exp(...)`, a double
+// add rounded to float every step.
+__device__ __forceinline__ float running_sum_literal(const double *e, int cnt)
+{
+    float acc = 0.f;
+    int j = 0;
+    for (; j + 8 <= cnt; j += 8) {  // eight LDS reads in flight, then the dependent chain
+        double b[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) b[k] = e[j + k];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc = (float)((double)acc + b[k]);
+    }
+    for (; j < cnt; ++j) acc = (float)((double)acc + e[j]);
+    return acc;
+}
+
 constexpr int SOFTMAX_MAX_CNT = 8192;  // doubles parked in LDS: 64 KiB
+
+// Tests only (shl_mi355x_debug_running_sum): one workgroup parks the caller's terms in LDS the way softmax_kernel does
+// (256 zeros behind them) and runs one of the two forms of the running sum on them.
+__global__ __launch_bounds__(256) void running_sum_debug_kernel(const double *terms, int cnt, int literal, float *sum)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    double *e = reinterpret_cast<double *>(smem);  // [cnt + 256]
+    const int tid = threadIdx.x;
+    for (int j = tid; j < cnt; j += 256) e[j] = terms[j];
+    e[cnt + tid] = 0.0;
+    __syncthreads();
+    if (literal) {
+        if (tid == 0) *sum = running_sum_literal(e, cnt);
+    } else if (tid < 64) {
+        const float acc = running_sum_exact(e, cnt, tid);
+        if (tid == 0) *sum = acc;
+    }
+}
 
 // -DSHL_SM_TRACE=1 (tools/dev): s_memtime of thread 0 of row 0 at the phase boundaries of softmax_kernel
 #ifndef SHL_SM_TRACE
@@ -271,19 +308,7 @@ __global__ __launch_bounds__(256) void softmax_kernel(const void *in, void *out,
     __syncthreads();
     SM_STAMP(2);
     if (seq_sum) {
-        if (tid == 0) {
-            float acc = 0.f;  // `acc_exp += exp(...)`: double add, rounded to float every step
-            int j = 0;
-            for (; j + 8 <= cnt; j += 8) {  // eight LDS reads in flight, then the dependent chain
-                double b[8];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) b[k] = e[j + k];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) acc = (float)((double)acc + b[k]);
-            }
-            for (; j < cnt; ++j) acc = (float)((double)acc + e[j]);
-            red[0] = acc;
-        }
+        if (tid == 0) red[0] = running_sum_literal(e, cnt);
     } else if (tid < 64) {
         const float acc = running_sum_exact(e, cnt, tid);
         if (tid == 0) red[0] = acc;
@@ -310,6 +335,38 @@ extern "C" int shl_mi355x_debug_sm_trace(unsigned long long *host)
     return hipMemcpyFromSymbol(host, HIP_SYMBOL(shl::g_sm_trace), 64) == hipSuccess ? 0 : -1;
 }
 #endif
+
+extern "C" int shl_mi355x_debug_running_sum(const double *terms_host, int32_t count, int32_t literal, float *sum_host)
+{
+    if (!terms_host || !sum_host || count < 1 || count > shl::SOFTMAX_MAX_CNT) {
+        shl::set_error("debug_running_sum: invalid argument");
+        return SHL_MI355X_EINVAL;
+    }
+    double *d_terms = nullptr;
+    float *d_sum = nullptr;
+    SHL_HIP(hipMalloc((void **)&d_terms, (size_t)count * 8));
+    if (hipMalloc((void **)&d_sum, 4) != hipSuccess) {
+        (void)hipFree(d_terms);
+        return shl::hip_fail(hipErrorOutOfMemory, "hipMalloc");
+    }
+    int rc = SHL_MI355X_OK;
+    const size_t lds = ((size_t)count + 256) * 8;  // e[count + 256]
+    static shl::LdsOptIn opted_in;
+    if (lds > 48 * 1024) shl::lds_opt_in(opted_in, reinterpret_cast<const void *>(shl::running_sum_debug_kernel), 96 * 1024);
+    hipError_t e = hipMemcpy(d_terms, terms_host, (size_t)count * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(d_sum, 0, 4);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(shl::running_sum_debug_kernel, dim3(1), dim3(256), lds, nullptr, d_terms, (int)count,
+                           literal ? 1 : 0, d_sum);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(sum_host, d_sum, 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = shl::hip_fail(e, "debug_running_sum");
+    (void)hipFree(d_terms);
+    (void)hipFree(d_sum);
+    return rc;
+}
 
 extern "C" int shl_mi355x_global_avgpool2d(const void *input_dev, void *output_dev, int32_t dtype, int32_t layout,
                                            int32_t batch, int32_t channels, int32_t pixels, float in_scale,

@@ -211,6 +211,10 @@ int shl_mi355x_debug_trace(uint64_t *host, int32_t count);
  * `x / scale`): for each of the `n` divisors every significand of the dividend is compared with the hardware's
  * correctly rounded division.  *mismatches = number of differing quotients, first_pair[0..1] = one (f, s). */
 int shl_mi355x_debug_div_check(const float *divisors_host, int32_t n, uint64_t *mismatches, float *first_pair);
+/* Tests only.  The float running sum of softmax, acc = (float)((double)acc + term[j]) for j = 0 .. count - 1 from
+ * acc = 0, on crafted terms (csrc/pool_softmax.hip): the wave-parallel scan, or with literal != 0 the one-lane loop.
+ * 1 <= count <= 8192; the terms are what softmax produces: non-negative, +inf or NaN.  *sum_host = acc. */
+int shl_mi355x_debug_running_sum(const double *terms_host, int32_t count, int32_t literal, float *sum_host);
 /* Tests only.  The binary16 epilogues round with one hardware conversion + a fix-up instead of the ~25 integer
  * operations of float32_to_float16_base (source/nn2/utils.c:576-620): every one of the 2^32 float32 bit patterns is
  * pushed through both the one-value and the packed two-value shortcut (csrc/common.h) and compared with the literal
