@@ -34,6 +34,12 @@ OP_CONCAT = 26
 OP_SPLIT, OP_SHUFFLE_CHANNEL = 166, 153
 OP_TRANSPOSE, OP_RESHAPE, OP_FLATTEN, OP_PAD = 179, 132, 66, 115
 PAD_CONSTANT, PAD_EDGE, PAD_REFLECT = 0, 1, 2
+OP_MEAN, OP_SUM, OP_MAX, OP_MIN = 101, 173, 96, 103
+OP_REDUCE_MEAN, OP_REDUCE_SUM, OP_REDUCE_MAX, OP_REDUCE_MIN = 123, 126, 122, 124
+OP_GLOBAL_MAXPOOL2D = 75
+REDUCE_SUM, REDUCE_MEAN, REDUCE_MAX, REDUCE_MIN = 0, 1, 2, 3   # shl_mi355x_reduce_desc.kind
+REDUCE_INIT_FLT_MAX, REDUCE_INIT_FIRST = 0, 1                   # .init
+REDUCE_GROUPS, REDUCE_CHUNK_BYTES = 4, 256
 OP_SIGMOID, OP_HARD_SIGMOID, OP_SILU, OP_LEAKY_RELU, OP_MUL = 154, 78, 190, 84, 107
 OP_RESIZE = 133
 OP_DECONV2D, OP_DEPTHWISE_DECONV2D, OP_GROUP_DECONV2D = 54, 55, 56
@@ -173,6 +179,13 @@ class PadParams(C.Structure):
                 ("pad_num", C.c_int32), ("pad_value", C.c_float), ("pad_mode", C.c_int32)]
 
 
+class ReduceParams(C.Structure):
+    """struct csinn_reduce_params (include/csinn/csinn_data_structure.h)"""
+    _fields_ = [("base", ParamsBase), ("out_strides", C.POINTER(C.c_int32)), ("out_extents", C.POINTER(C.c_int32)),
+                ("n", C.c_int32), ("inner_strides", C.POINTER(C.c_int32)), ("inner_extents", C.POINTER(C.c_int32)),
+                ("m", C.c_int32), ("axis", C.POINTER(C.c_int32)), ("axis_count", C.c_int32), ("keepdims", C.c_bool)]
+
+
 class ConvDesc(C.Structure):
     """struct shl_mi355x_conv_desc (include/shl_mi355x.h)"""
     _fields_ = [(n, C.c_int32) for n in (
@@ -227,6 +240,15 @@ class PadDesc(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("dim", C.c_int32 * 4), ("before", C.c_int32 * 4), ("after", C.c_int32 * 4),
                 ("pad_value", C.c_float), ("in_scale", C.c_float), ("in_zp", C.c_int32), ("out_scale", C.c_float),
                 ("out_zp", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class ReduceDesc(C.Structure):
+    """struct shl_mi355x_reduce_desc (include/shl_mi355x.h)"""
+    _fields_ = [("dtype", C.c_int32), ("kind", C.c_int32), ("init", C.c_int32), ("n_out", C.c_int32), ("n_inner", C.c_int32),
+                ("out_extent", C.c_int32 * 8), ("out_stride", C.c_int32 * 8), ("inner_extent", C.c_int32 * 8),
+                ("inner_stride", C.c_int32 * 8), ("reserved0", C.c_int32), ("in_elems", C.c_int64),
+                ("in_scale", C.c_float), ("in_zp", C.c_int32), ("out_scale", C.c_float), ("out_zp", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
 
 
 class ResizeDesc(C.Structure):
@@ -357,6 +379,8 @@ def load_hip():
         "shl_mi355x_pad": (C.c_int, [vp, vp, C.POINTER(PadDesc), vp]),
         "shl_mi355x_pad_kernel_name": (C.c_char_p, [vp, vp, C.POINTER(PadDesc)]),
         "shl_mi355x_pad_element": (C.c_uint32, [C.POINTER(PadDesc)]),
+        "shl_mi355x_reduce": (C.c_int, [vp, vp, C.POINTER(ReduceDesc), vp]),
+        "shl_mi355x_reduce_kernel_name": (C.c_char_p, [vp, vp, C.POINTER(ReduceDesc)]),
         "shl_mi355x_unary_lut_i8": (C.c_int, [vp, vp, sz, vp, vp]),
         "shl_mi355x_unary_lut_i8_kernel_name": (C.c_char_p, [vp, vp]),
         "shl_mi355x_unary_f16": (C.c_int, [vp, vp, sz, i32, f32, vp]),
@@ -402,7 +426,9 @@ _FRONTEND_SIGS = {
 }
 _SISO_OPS = ("csinn_relu", "csinn_relu6", "csinn_global_avgpool2d", "csinn_softmax", "csinn_maxpool2d", "csinn_avgpool2d",
              "csinn_sigmoid", "csinn_hard_sigmoid", "csinn_silu", "csinn_leaky_relu", "csinn_resize", "csinn_shuffle_channel",
-             "csinn_transpose", "csinn_reshape", "csinn_flatten", "csinn_pad")
+             "csinn_transpose", "csinn_reshape", "csinn_flatten", "csinn_pad",
+             "csinn_mean", "csinn_sum", "csinn_max", "csinn_min", "csinn_reduce_mean", "csinn_reduce_sum", "csinn_reduce_max",
+             "csinn_reduce_min", "csinn_global_maxpool2d")
 _CONV_OPS = ["csinn_conv2d", "csinn_conv2d_relu", "csinn_conv2d_relu6", "csinn_depthwise_conv2d",
              "csinn_depthwise_conv2d_relu", "csinn_fullyconnected", "csinn_deconv2d"] + list(_SISO_OPS)
 
@@ -692,6 +718,37 @@ def pad_params(fe, keep, api, layout, before, after, value=0.0, mode=PAD_CONSTAN
     pc.pad_num = len(before) if pad_num is None else pad_num
     pc.pad_value = value
     pc.pad_mode = mode
+    return p
+
+
+def reduce_groups(shape, axes):
+    """(out_extents, out_strides, inner_extents, inner_strides) of a reduction of a dense tensor of `shape` over `axes`, in
+    the tensor's dim order: what struct csinn_reduce_params and shl_mi355x_reduce_desc take (strides in elements)"""
+    rank = len(shape)
+    axes = sorted(a % rank for a in axes)
+    assert len(set(axes)) == len(axes)
+    stride = [1] * rank
+    for k in range(rank - 2, -1, -1):
+        stride[k] = stride[k + 1] * shape[k + 1]
+    keep_dims = [k for k in range(rank) if k not in axes]
+    return ([shape[k] for k in keep_dims], [stride[k] for k in keep_dims], [shape[k] for k in axes], [stride[k] for k in axes])
+
+
+def reduce_params(fe, keep, api, layout, groups=None, axis=None, sess=None, name=b"reduce", axis_count=None):
+    """params block of csinn_mean / _sum / _max / _min (groups: what reduce_groups returns, or four lists) and of
+    csinn_reduce_mean / _sum / _max / _min (axis: a list, [-1] for the whole tensor)"""
+    p, pc = _move_params(fe, keep, ReduceParams, api, layout, sess, name)
+    ip = C.POINTER(C.c_int32)
+    if groups is not None:
+        oe, os_, ie, is_ = [keep.add((C.c_int32 * max(len(g), 1))(*g)) for g in groups]
+        pc.out_extents, pc.out_strides = C.cast(oe, ip), C.cast(os_, ip)
+        pc.inner_extents, pc.inner_strides = C.cast(ie, ip), C.cast(is_, ip)
+        pc.n, pc.m = len(groups[0]), len(groups[2])
+    axis = list(axis) if axis is not None else []
+    arr = keep.add((C.c_int32 * max(len(axis), 1))(*axis))
+    pc.axis = C.cast(arr, ip)
+    pc.axis_count = len(axis) if axis_count is None else axis_count
+    pc.keepdims = True
     return p
 
 

@@ -45,7 +45,8 @@ NO_SPILL_SOURCES = ("conv_igemm.hip", "conv_igemm_pp.hip", "conv_igemm_pc.hip",
                     "conv_igemm_halo.hip",
                     "dwpw_resident.hip",  # (its tile loop counts vector memory instructions: a scratch reload is one)
                     "split.hip", "shuffle.hip",  # (pure data movement: scratch traffic would be most of their memory traffic)
-                    "transpose.hip", "pad.hip")
+                    "transpose.hip", "pad.hip",
+                    "reduce.hip")  # (its chains wait on one addition per element: a scratch reload in the loop would double that)
 
 
 def spilled_kernels(usage_file):

@@ -303,6 +303,51 @@ int shl_gref_pad(struct csinn_tensor *input, struct csinn_tensor *output, struct
     return record_siso(input, output, CSINN_OP_PAD, params);
 }
 
+int shl_gref_mean(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params)
+{
+    return record_siso(input, output, CSINN_OP_MEAN, params);
+}
+
+int shl_gref_sum(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params)
+{
+    return record_siso(input, output, CSINN_OP_SUM, params);
+}
+
+int shl_gref_max(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params)
+{
+    return record_siso(input, output, CSINN_OP_MAX, params);
+}
+
+int shl_gref_min(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params)
+{
+    return record_siso(input, output, CSINN_OP_MIN, params);
+}
+
+int shl_gref_reduce_mean(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params)
+{
+    return record_siso(input, output, CSINN_OP_REDUCE_MEAN, params);
+}
+
+int shl_gref_reduce_sum(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params)
+{
+    return record_siso(input, output, CSINN_OP_REDUCE_SUM, params);
+}
+
+int shl_gref_reduce_max(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params)
+{
+    return record_siso(input, output, CSINN_OP_REDUCE_MAX, params);
+}
+
+int shl_gref_reduce_min(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params)
+{
+    return record_siso(input, output, CSINN_OP_REDUCE_MIN, params);
+}
+
+int shl_gref_global_maxpool2d(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params)
+{
+    return record_siso(input, output, CSINN_OP_GLOBAL_MAXPOOL2D, params);
+}
+
 int shl_gref_global_avgpool2d(struct csinn_tensor *input, struct csinn_tensor *output,
                               struct csinn_pool_params *params)
 {
@@ -349,6 +394,15 @@ int shl_gref_call_layer_func(void *fn, struct shl_node *node)
         case CSINN_OP_RESHAPE:
         case CSINN_OP_FLATTEN:
         case CSINN_OP_PAD:
+        case CSINN_OP_MEAN:
+        case CSINN_OP_SUM:
+        case CSINN_OP_MAX:
+        case CSINN_OP_MIN:
+        case CSINN_OP_REDUCE_MEAN:
+        case CSINN_OP_REDUCE_SUM:
+        case CSINN_OP_REDUCE_MAX:
+        case CSINN_OP_REDUCE_MIN:
+        case CSINN_OP_GLOBAL_MAXPOOL2D:
             return f(node->in[0]->data, node->out[0]->data, params);
         case CSINN_OP_ADD:
         case CSINN_OP_MUL:
@@ -398,7 +452,7 @@ struct csinn_callback *shl_gref_best_callback(struct shl_node *node)
     return params->cb;
 }
 
-static struct csinn_callback g_est_only[48];
+static struct csinn_callback g_est_only[64];
 
 static struct csinn_callback *gref_cb_map(int op, int dtype)
 {
@@ -437,6 +491,15 @@ static struct csinn_callback *gref_cb_map(int op, int dtype)
         {CSINN_OP_RESHAPE, shl_gref_reshape},
         {CSINN_OP_FLATTEN, shl_gref_flatten},
         {CSINN_OP_PAD, shl_gref_pad},
+        {CSINN_OP_MEAN, shl_gref_mean},
+        {CSINN_OP_SUM, shl_gref_sum},
+        {CSINN_OP_MAX, shl_gref_max},
+        {CSINN_OP_MIN, shl_gref_min},
+        {CSINN_OP_REDUCE_MEAN, shl_gref_reduce_mean},
+        {CSINN_OP_REDUCE_SUM, shl_gref_reduce_sum},
+        {CSINN_OP_REDUCE_MAX, shl_gref_reduce_max},
+        {CSINN_OP_REDUCE_MIN, shl_gref_reduce_min},
+        {CSINN_OP_GLOBAL_MAXPOOL2D, shl_gref_global_maxpool2d},
     };
     _Static_assert(sizeof(table) / sizeof(table[0]) <= sizeof(g_est_only) / sizeof(g_est_only[0]), "one callback block per table row");
     for (unsigned i = 0; i < sizeof(table) / sizeof(table[0]); i++) {

@@ -84,6 +84,35 @@ int shl_mi355x_pad_init(struct csinn_tensor *input, struct csinn_tensor *output,
 int shl_mi355x_pad_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pad_params *params,
         struct csinn_perf_info *info);
 
+/* the reductions (reduce.c): init (a refused layer falls through to the reference where there is one) and perf */
+int shl_mi355x_mean_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int shl_mi355x_mean_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params,
+        struct csinn_perf_info *info);
+int shl_mi355x_sum_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int shl_mi355x_sum_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params,
+        struct csinn_perf_info *info);
+int shl_mi355x_max_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int shl_mi355x_max_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params,
+        struct csinn_perf_info *info);
+int shl_mi355x_min_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int shl_mi355x_min_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params,
+        struct csinn_perf_info *info);
+int shl_mi355x_reduce_mean_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int shl_mi355x_reduce_mean_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params,
+        struct csinn_perf_info *info);
+int shl_mi355x_reduce_sum_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int shl_mi355x_reduce_sum_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params,
+        struct csinn_perf_info *info);
+int shl_mi355x_reduce_max_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int shl_mi355x_reduce_max_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params,
+        struct csinn_perf_info *info);
+int shl_mi355x_reduce_min_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int shl_mi355x_reduce_min_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params,
+        struct csinn_perf_info *info);
+int shl_mi355x_global_maxpool2d_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params);
+int shl_mi355x_global_maxpool2d_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params,
+        struct csinn_perf_info *info);
+
 /* ... and of the elementwise layers (eltwise.c): the kernel form the rules choose */
 int shl_mi355x_sigmoid_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params,
                             struct csinn_perf_info *info);

@@ -160,6 +160,17 @@ static const struct session_op g_ops[] = {
     {CSINN_OP_RESHAPE, shl_mi355x_reshape_exec, CALL_SISO, 1, 1}, /* one copy node; sharing the producer's buffer is a later change */
     {CSINN_OP_FLATTEN, shl_mi355x_flatten_exec, CALL_SISO, 1, 1},
     {CSINN_OP_PAD, shl_mi355x_pad_exec, CALL_SISO, 1, 1},
+    /* reductions: TensorFlow's global pooling (mean over H and W), CBAM's channel max / mean and global max pool, a head's
+     * reduce_max / reduce_sum */
+    {CSINN_OP_MEAN, shl_mi355x_mean_exec, CALL_SISO, 1, 1},
+    {CSINN_OP_SUM, shl_mi355x_sum_exec, CALL_SISO, 1, 1},
+    {CSINN_OP_MAX, shl_mi355x_max_exec, CALL_SISO, 1, 1},
+    {CSINN_OP_MIN, shl_mi355x_min_exec, CALL_SISO, 1, 1},
+    {CSINN_OP_REDUCE_MEAN, shl_mi355x_reduce_mean_exec, CALL_SISO, 1, 1},
+    {CSINN_OP_REDUCE_SUM, shl_mi355x_reduce_sum_exec, CALL_SISO, 1, 1},
+    {CSINN_OP_REDUCE_MAX, shl_mi355x_reduce_max_exec, CALL_SISO, 1, 1},
+    {CSINN_OP_REDUCE_MIN, shl_mi355x_reduce_min_exec, CALL_SISO, 1, 1},
+    {CSINN_OP_GLOBAL_MAXPOOL2D, shl_mi355x_global_maxpool2d_exec, CALL_SISO, 1, 1},
 };
 
 /* the row of layer `n`; NULL: not a layer this file runs */

@@ -12,7 +12,7 @@
 #include "mi355x_internal.h"
 
 /* ------------------------------------------------------------------------ callback table */
-#define MI355X_CB_MAX 128
+#define MI355X_CB_MAX 160
 static struct {
     int key; /* op * CSINN_DTYPE_SIZE + dtype */
     struct csinn_callback cb;
@@ -709,6 +709,16 @@ void shl_target_init_mi355x(void)
         reg(dts[i], CSINN_OP_RESHAPE, shl_mi355x_reshape_init, shl_mi355x_reshape_exec, shl_gref_reshape, shl_mi355x_reshape_perf);
         reg(dts[i], CSINN_OP_FLATTEN, shl_mi355x_flatten_init, shl_mi355x_flatten_exec, shl_gref_flatten, shl_mi355x_flatten_perf);
         reg(dts[i], CSINN_OP_PAD, shl_mi355x_pad_init, shl_mi355x_pad_exec, shl_gref_pad, shl_mi355x_pad_perf);
+        reg(dts[i], CSINN_OP_MEAN, shl_mi355x_mean_init, shl_mi355x_mean_exec, shl_gref_mean, shl_mi355x_mean_perf);
+        reg(dts[i], CSINN_OP_SUM, shl_mi355x_sum_init, shl_mi355x_sum_exec, shl_gref_sum, shl_mi355x_sum_perf);
+        reg(dts[i], CSINN_OP_MAX, shl_mi355x_max_init, shl_mi355x_max_exec, shl_gref_max, shl_mi355x_max_perf);
+        reg(dts[i], CSINN_OP_MIN, shl_mi355x_min_init, shl_mi355x_min_exec, shl_gref_min, shl_mi355x_min_perf);
+        reg(dts[i], CSINN_OP_REDUCE_MEAN, shl_mi355x_reduce_mean_init, shl_mi355x_reduce_mean_exec, shl_gref_reduce_mean, shl_mi355x_reduce_mean_perf);
+        reg(dts[i], CSINN_OP_REDUCE_SUM, shl_mi355x_reduce_sum_init, shl_mi355x_reduce_sum_exec, shl_gref_reduce_sum, shl_mi355x_reduce_sum_perf);
+        reg(dts[i], CSINN_OP_REDUCE_MAX, shl_mi355x_reduce_max_init, shl_mi355x_reduce_max_exec, shl_gref_reduce_max, shl_mi355x_reduce_max_perf);
+        reg(dts[i], CSINN_OP_REDUCE_MIN, shl_mi355x_reduce_min_init, shl_mi355x_reduce_min_exec, shl_gref_reduce_min, shl_mi355x_reduce_min_perf);
+        reg(dts[i], CSINN_OP_GLOBAL_MAXPOOL2D, shl_mi355x_global_maxpool2d_init, shl_mi355x_global_maxpool2d_exec,
+            shl_gref_global_maxpool2d, shl_mi355x_global_maxpool2d_perf);
     }
     shl_register_op_callback(CSINN_MI355X, shl_cb_map_mi355x);
     shl_register_runtime_callback(CSINN_MI355X, shl_mi355x_runtime_callback);

@@ -12,6 +12,7 @@
  *   resize ............ source/nn2/resize.c
  *   split / shuffle_channel  source/nn2/split.c, shuffle_channel.c
  *   transpose / reshape / flatten / pad  source/nn2/transpose.c, reshape.c, flatten.c, pad.c
+ *   mean / sum / max / min / reduce_* / global_maxpool2d  source/nn2/mean.c, sum.c, max.c, min.c, reduce_*.c, global_maxpool2d.c
  *   deconv2d .......... source/nn2/deconvolution.c
  *   sigmoid / hard_sigmoid / silu / leaky_relu / mul  source/nn2/sigmoid.c, hard_sigmoid.c, silu.c, leaky_relu.c, mul.c
  * The only deliberate difference: a missing callback is reported (CSINN_CALLBACK_UNSET and an
@@ -371,6 +372,81 @@ int csinn_pad_init(struct csinn_tensor *input, struct csinn_tensor *output, stru
     return map_and_init3(&params->base, CSINN_OP_PAD, input->dtype, input, output, params);
 }
 int csinn_pad(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pad_params *params)
+{
+    return run3(&params->base, input, output, params);
+}
+
+/* source/nn2/mean.c, sum.c, max.c, min.c, reduce_mean.c, reduce_sum.c, reduce_max.c, reduce_min.c, global_maxpool2d.c: one
+ * input, one output */
+int csinn_mean_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params)
+{
+    return map_and_init3(&params->base, CSINN_OP_MEAN, input->dtype, input, output, params);
+}
+int csinn_mean(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params)
+{
+    return run3(&params->base, input, output, params);
+}
+int csinn_sum_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params)
+{
+    return map_and_init3(&params->base, CSINN_OP_SUM, input->dtype, input, output, params);
+}
+int csinn_sum(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params)
+{
+    return run3(&params->base, input, output, params);
+}
+int csinn_max_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params)
+{
+    return map_and_init3(&params->base, CSINN_OP_MAX, input->dtype, input, output, params);
+}
+int csinn_max(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params)
+{
+    return run3(&params->base, input, output, params);
+}
+int csinn_min_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params)
+{
+    return map_and_init3(&params->base, CSINN_OP_MIN, input->dtype, input, output, params);
+}
+int csinn_min(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params)
+{
+    return run3(&params->base, input, output, params);
+}
+int csinn_reduce_mean_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params)
+{
+    return map_and_init3(&params->base, CSINN_OP_REDUCE_MEAN, input->dtype, input, output, params);
+}
+int csinn_reduce_mean(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params)
+{
+    return run3(&params->base, input, output, params);
+}
+int csinn_reduce_sum_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params)
+{
+    return map_and_init3(&params->base, CSINN_OP_REDUCE_SUM, input->dtype, input, output, params);
+}
+int csinn_reduce_sum(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params)
+{
+    return run3(&params->base, input, output, params);
+}
+int csinn_reduce_max_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params)
+{
+    return map_and_init3(&params->base, CSINN_OP_REDUCE_MAX, input->dtype, input, output, params);
+}
+int csinn_reduce_max(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params)
+{
+    return run3(&params->base, input, output, params);
+}
+int csinn_reduce_min_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params)
+{
+    return map_and_init3(&params->base, CSINN_OP_REDUCE_MIN, input->dtype, input, output, params);
+}
+int csinn_reduce_min(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params)
+{
+    return run3(&params->base, input, output, params);
+}
+int csinn_global_maxpool2d_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params)
+{
+    return map_and_init3(&params->base, CSINN_OP_GLOBAL_MAXPOOL2D, input->dtype, input, output, params);
+}
+int csinn_global_maxpool2d(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params)
 {
     return run3(&params->base, input, output, params);
 }

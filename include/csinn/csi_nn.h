@@ -101,6 +101,25 @@ int csinn_flatten_init(struct csinn_tensor *input, struct csinn_tensor *output, 
 int csinn_flatten(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_flatten_params *params);
 int csinn_pad_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pad_params *params);
 int csinn_pad(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pad_params *params);
+/* reductions (source/nn2/mean.c, sum.c, max.c, min.c, reduce_*.c, global_maxpool2d.c of the reference): one input, one output */
+int csinn_mean_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int csinn_mean(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int csinn_sum_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int csinn_sum(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int csinn_max_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int csinn_max(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int csinn_min_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int csinn_min(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int csinn_reduce_mean_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int csinn_reduce_mean(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int csinn_reduce_sum_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int csinn_reduce_sum(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int csinn_reduce_max_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int csinn_reduce_max(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int csinn_reduce_min_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int csinn_reduce_min(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int csinn_global_maxpool2d_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params);
+int csinn_global_maxpool2d(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params);
 /* MobileNet tail (source/nn2/global_avgpool2d.c, softmax.c of the reference) */
 int csinn_global_avgpool2d_init(struct csinn_tensor *input, struct csinn_tensor *output,
                                 struct csinn_pool_params *params);

@@ -138,11 +138,19 @@ enum csinn_op_enum {
     CSINN_OP_FLATTEN = 66,
     CSINN_OP_FULLYCONNECTED = 71,
     CSINN_OP_GLOBAL_AVGPOOL2D = 74,
+    CSINN_OP_GLOBAL_MAXPOOL2D = 75,
     CSINN_OP_HARD_SIGMOID = 78,
     CSINN_OP_LEAKY_RELU = 84,
+    CSINN_OP_MAX = 96, /* the stride family of reductions: MAX, MEAN, MIN, SUM (struct csinn_reduce_params) */
     CSINN_OP_MAXPOOL2D = 98,
+    CSINN_OP_MEAN = 101,
+    CSINN_OP_MIN = 103,
     CSINN_OP_MUL = 107,
     CSINN_OP_PAD = 115,
+    CSINN_OP_REDUCE_MAX = 122, /* the axis family: one axis, or axis[0] == -1 for the whole tensor */
+    CSINN_OP_REDUCE_MEAN = 123,
+    CSINN_OP_REDUCE_MIN = 124,
+    CSINN_OP_REDUCE_SUM = 126,
     CSINN_OP_RELU = 127,
     CSINN_OP_RELU6 = 129,
     CSINN_OP_RESHAPE = 132,
@@ -151,6 +159,7 @@ enum csinn_op_enum {
     CSINN_OP_SIGMOID = 154,
     CSINN_OP_SOFTMAX = 159,
     CSINN_OP_SPLIT = 166,
+    CSINN_OP_SUM = 173,
     CSINN_OP_TRANSPOSE = 179,
     CSINN_OP_SILU = 190,
     CSINN_OP_SIZE = 194,
@@ -456,6 +465,25 @@ struct csinn_pad_params { /* 72 B */
     int32_t pad_num;
     float pad_value;
     enum csinn_pad_enum pad_mode;
+};
+
+/* reductions (csinn_data_structure.h:1072-1083 of the reference).  The stride family (CSINN_OP_MEAN, _SUM, _MAX, _MIN) reads
+ * the two group lists: output o (0 .. product of out_extents - 1) starts at the mixed-radix index of o over (out_extents,
+ * out_strides) -- the first group the outermost digit -- and reduces the product of inner_extents elements at the
+ * mixed-radix indices over (inner_extents, inner_strides), in that order; strides in input elements.  The axis family
+ * (CSINN_OP_REDUCE_MEAN, _SUM, _MAX, _MIN) reads axis[0] only (axis_count must be 1; -1: the whole tensor to one value) and
+ * the input tensor's dims.  keepdims is not read: the output tensor's dims are the caller's */
+struct csinn_reduce_params { /* 104 B */
+    struct csinn_params_base base;
+    int32_t *out_strides;
+    int32_t *out_extents;
+    int32_t n;
+    int32_t *inner_strides;
+    int32_t *inner_extents;
+    int32_t m;
+    int32_t *axis;
+    int32_t axis_count;
+    bool keepdims;
 };
 
 /* pooling (csinn_data_structure.h:643-662 of the reference); global_avgpool2d ignores the

@@ -88,6 +88,15 @@ int shl_gref_transpose(struct csinn_tensor *input, struct csinn_tensor *output, 
 int shl_gref_reshape(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reshape_params *params);
 int shl_gref_flatten(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_flatten_params *params);
 int shl_gref_pad(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pad_params *params);
+int shl_gref_mean(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int shl_gref_sum(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int shl_gref_max(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int shl_gref_min(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int shl_gref_reduce_mean(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int shl_gref_reduce_sum(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int shl_gref_reduce_max(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int shl_gref_reduce_min(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int shl_gref_global_maxpool2d(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params);
 int shl_gref_global_avgpool2d(struct csinn_tensor *input, struct csinn_tensor *output,
                               struct csinn_pool_params *params);
 int shl_gref_maxpool2d(struct csinn_tensor *input, struct csinn_tensor *output,

@@ -581,6 +581,59 @@ const char *shl_mi355x_pad_kernel_name(const void *in_dev, const void *out_dev, 
 /* the pad element as the kernels write it (low byte / low half): pure host code */
 uint32_t shl_mi355x_pad_element(const struct shl_mi355x_pad_desc *d);
 
+/* Reductions: sum, mean, max and min of an int8 / binary16 tensor over any set of dims -- what CSINN_OP_MEAN / _SUM / _MAX /
+ * _MIN (shl_ref_*_stride_f32), CSINN_OP_REDUCE_MEAN / _SUM / _MAX / _MIN (shl_ref_reduce_*_f32) and
+ * CSINN_OP_GLOBAL_MAXPOOL2D are behind shl_ref_siso_callback_base, bit for bit.  Output o (0 .. product of out_extent - 1)
+ * reads in[index(o, out) + index(i, inner)] for i = 0 .. product of inner_extent - 1 IN THAT ORDER, index() being the
+ * reference's mixed-radix index (shl_ref_get_reduction_index: the first group is the outermost digit), strides in input
+ * elements.  sum / mean: a float32 chain from 0 in that order, mean ends with one division by the count.  max / min: the C
+ * library's fmax / fmin in that order (a NaN loses, of two NaNs the first stays, of +0 and -0 the later one), from -FLT_MAX /
+ * +FLT_MAX (SHL_MI355X_REDUCE_INIT_FLT_MAX: the stride family, global_maxpool2d -- a row of NaNs gives -FLT_MAX, which
+ * binary16 rounds to -65504) or from the row's first element (SHL_MI355X_REDUCE_INIT_FIRST: the axis family); `init` is
+ * ignored by sum and mean.  Elements: int8 (q - zp_in) * s_in, binary16 exact; outputs: int8 sat8(rint(x / s_out) + zp_out),
+ * binary16 the reference's conversion.
+ * SHL_MI355X_EINVAL before anything is enqueued: more than 8 groups in a list; a negative extent or stride, an inner extent
+ * below 1; in_elems below 1 or 2^31 and above; 2^31 or more outputs or elements per output; an index that reaches in_elems;
+ * a pointer not aligned to its elements; an output that overlaps the input; more than SHL_MI355X_REDUCE_GROUPS groups left in
+ * a list after canonicalisation (extent-1 groups dropped, a group merged into the one before it when that one's stride is
+ * this one's extent times its stride).  No outputs (an outer extent of 0): SHL_MI355X_OK, nothing enqueued.  Enqueues only:
+ * no allocation, no synchronisation (capturable in a hipGraph).  Forms:
+ *   SHL_MI355X_REDUCE_ROWS     the innermost canonical inner group has stride 1: a workgroup stages windows of its rows
+ *                              into LDS with 16-byte loads (element loads where a row's head or tail is off the 16-byte
+ *                              grid), one lane per row then adds in order.  The staging chunk is
+ *                              SHL_MI355X_REDUCE_CHUNK_BYTES per row and pass
+ *   SHL_MI355X_REDUCE_COLS     else, the innermost canonical outer group has stride 1: one output per thread, coalesced
+ *                              loads issued in batches ahead of the additions
+ *   SHL_MI355X_REDUCE_GENERIC  one output per thread, every index by division
+ * SHL_MI355X_REDUCE_FORM=generic forces the last. */
+#define SHL_MI355X_REDUCE_GROUPS 4
+#define SHL_MI355X_REDUCE_CHUNK_BYTES 256
+#define SHL_MI355X_REDUCE_ROWS "reduce_rows"
+#define SHL_MI355X_REDUCE_COLS "reduce_cols"
+#define SHL_MI355X_REDUCE_GENERIC "reduce_generic"
+enum { SHL_MI355X_REDUCE_SUM = 0, SHL_MI355X_REDUCE_MEAN = 1, SHL_MI355X_REDUCE_MAX = 2, SHL_MI355X_REDUCE_MIN = 3 };
+enum { SHL_MI355X_REDUCE_INIT_FLT_MAX = 0, SHL_MI355X_REDUCE_INIT_FIRST = 1 };
+
+struct shl_mi355x_reduce_desc {
+    int32_t dtype; /* SHL_MI355X_I8 / SHL_MI355X_F16 */
+    int32_t kind;  /* SHL_MI355X_REDUCE_SUM .. _MIN */
+    int32_t init;  /* SHL_MI355X_REDUCE_INIT_* */
+    int32_t n_out, n_inner;
+    int32_t out_extent[SHL_MI355X_MAX_DIM], out_stride[SHL_MI355X_MAX_DIM];
+    int32_t inner_extent[SHL_MI355X_MAX_DIM], inner_stride[SHL_MI355X_MAX_DIM];
+    int32_t reserved0; /* must be zero */
+    int64_t in_elems;  /* elements of the input tensor: no index may reach it */
+    float in_scale;
+    int32_t in_zp;
+    float out_scale;
+    int32_t out_zp;
+    int32_t reserved[4]; /* must be zero */
+};
+
+int shl_mi355x_reduce(const void *in_dev, void *out_dev, const struct shl_mi355x_reduce_desc *d, void *stream);
+/* the kernel form the rules choose; "" for invalid arguments.  Pure host code, touches no device */
+const char *shl_mi355x_reduce_kernel_name(const void *in_dev, const void *out_dev, const struct shl_mi355x_reduce_desc *d);
+
 /* nearest-neighbour / bilinear resize of a 4-d int8 / binary16 tensor: shl_ref_resize_quant
  * (source/reference/resize.c:464-468), bit for bit.  height_scale / width_scale are the reference's own floats, computed by
  * the CALLER as ONE float division each: (float)in / out, with align_corners (float)(in - 1) / (out - 1)

@@ -122,6 +122,19 @@ int shl_mi355x_flatten_exec(struct csinn_tensor *input, struct csinn_tensor *out
 /* constant pad of a 4-d NCHW / NHWC tensor (pad_num == 4): EDGE / REFLECT, negative pads and output dims other than
  * input + before + after are refused */
 int shl_mi355x_pad_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pad_params *params);
+/* reductions (source/mi355x_opt/reduce.c): mean / sum / max / min over the params' two group lists (up to 8 groups a list,
+ * 4 after canonicalisation), reduce_mean / _sum / _max / _min over ONE axis or the whole tensor (axis[0] == -1), and
+ * global_maxpool2d of a 4-d NCHW / NHWC tensor.  A layer the kernels' descriptor cannot express (axis_count != 1, an index
+ * past the input, an output tensor of another size) is refused */
+int shl_mi355x_mean_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int shl_mi355x_sum_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int shl_mi355x_max_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int shl_mi355x_min_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int shl_mi355x_reduce_mean_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int shl_mi355x_reduce_sum_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int shl_mi355x_reduce_max_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int shl_mi355x_reduce_min_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
+int shl_mi355x_global_maxpool2d_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params);
 /* resize (source/mi355x_opt/resize.c): 4-d tensors, nearest-neighbour or bilinear, to the output tensor's height and
  * width; batch and channels of input and output must agree; bicubic, and align_corners with an output extent of 1 (the
  * reference divides by zero), are refused */
