@@ -40,6 +40,8 @@ OP_GLOBAL_MAXPOOL2D = 75
 REDUCE_SUM, REDUCE_MEAN, REDUCE_MAX, REDUCE_MIN = 0, 1, 2, 3   # shl_mi355x_reduce_desc.kind
 REDUCE_INIT_FLT_MAX, REDUCE_INIT_FIRST = 0, 1                   # .init
 REDUCE_GROUPS, REDUCE_CHUNK_BYTES = 4, 256
+OP_MATMUL = 95
+MATMUL_CHAIN, MATMUL_MFMA, MATMUL_MFMA_MAX_K = "matmul_chain", "matmul_mfma", 32768  # shl_mi355x_matmul's forms
 OP_SIGMOID, OP_HARD_SIGMOID, OP_SILU, OP_LEAKY_RELU, OP_MUL = 154, 78, 190, 84, 107
 OP_RESIZE = 133
 OP_DECONV2D, OP_DEPTHWISE_DECONV2D, OP_GROUP_DECONV2D = 54, 55, 56
@@ -184,6 +186,22 @@ class ReduceParams(C.Structure):
     _fields_ = [("base", ParamsBase), ("out_strides", C.POINTER(C.c_int32)), ("out_extents", C.POINTER(C.c_int32)),
                 ("n", C.c_int32), ("inner_strides", C.POINTER(C.c_int32)), ("inner_extents", C.POINTER(C.c_int32)),
                 ("m", C.c_int32), ("axis", C.POINTER(C.c_int32)), ("axis_count", C.c_int32), ("keepdims", C.c_bool)]
+
+
+class MatmulParams(C.Structure):
+    """struct csinn_matmul_params (include/csinn/csinn_data_structure.h)"""
+    _fields_ = [("base", ParamsBase), ("trans_a", C.c_bool), ("trans_b", C.c_bool)]
+
+
+class MatmulDesc(C.Structure):
+    """struct shl_mi355x_matmul_desc (include/shl_mi355x.h)"""
+    _fields_ = [("dtype", C.c_int32), ("batches", C.c_int32), ("m", C.c_int32), ("n", C.c_int32), ("k", C.c_int32),
+                ("reserved0", C.c_int32),
+                ("a_batch_stride", C.c_int64), ("a_row_stride", C.c_int64), ("a_k_stride", C.c_int64),
+                ("b_batch_stride", C.c_int64), ("b_col_stride", C.c_int64), ("b_k_stride", C.c_int64),
+                ("a_elems", C.c_int64), ("b_elems", C.c_int64), ("out_elems", C.c_int64),
+                ("a_scale", C.c_float), ("a_zp", C.c_int32), ("b_scale", C.c_float), ("b_zp", C.c_int32),
+                ("out_scale", C.c_float), ("out_zp", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
 class ConvDesc(C.Structure):
@@ -381,6 +399,9 @@ def load_hip():
         "shl_mi355x_pad_element": (C.c_uint32, [C.POINTER(PadDesc)]),
         "shl_mi355x_reduce": (C.c_int, [vp, vp, C.POINTER(ReduceDesc), vp]),
         "shl_mi355x_reduce_kernel_name": (C.c_char_p, [vp, vp, C.POINTER(ReduceDesc)]),
+        "shl_mi355x_matmul": (C.c_int, [vp, vp, vp, C.POINTER(MatmulDesc), vp]),
+        "shl_mi355x_matmul_kernel_name": (C.c_char_p, [vp, vp, vp, C.POINTER(MatmulDesc)]),
+        "shl_mi355x_matmul_is_exact": (C.c_int, [C.POINTER(MatmulDesc)]),
         "shl_mi355x_unary_lut_i8": (C.c_int, [vp, vp, sz, vp, vp]),
         "shl_mi355x_unary_lut_i8_kernel_name": (C.c_char_p, [vp, vp]),
         "shl_mi355x_unary_f16": (C.c_int, [vp, vp, sz, i32, f32, vp]),
@@ -460,7 +481,7 @@ def load_frontend(kind="standalone", local=False, path=None):
             fn.restype = C.c_int
             fn.argtypes = [tp, tp] + ([C.c_void_p] if nargs == 3 else [tp, tp, C.c_void_p])
     for suffix in ("_init", ""):
-        for op in ("csinn_add", "csinn_mul"):
+        for op in ("csinn_add", "csinn_mul", "csinn_matmul"):
             fn = getattr(lib, op + suffix)
             fn.restype, fn.argtypes = C.c_int, [tp, tp, tp, C.c_void_p]
         fn = getattr(lib, "csinn_concat" + suffix)
@@ -750,6 +771,44 @@ def reduce_params(fe, keep, api, layout, groups=None, axis=None, sess=None, name
     pc.axis_count = len(axis) if axis_count is None else axis_count
     pc.keepdims = True
     return p
+
+
+def matmul_params(fe, keep, api, layout, trans_a=False, trans_b=False, sess=None, name=b"matmul"):
+    """params block of csinn_matmul"""
+    p, pc = _move_params(fe, keep, MatmulParams, api, layout, sess, name)
+    pc.trans_a, pc.trans_b = bool(trans_a), bool(trans_b)
+    return p
+
+
+def matmul_desc(dtype, a_shape, b_shape, trans_a=False, trans_b=False, a_q=(1.0, 0), b_q=(1.0, 0), out_q=(1.0, 0)):
+    """shl_mi355x_matmul_desc of csinn_matmul on two dense tensors: the leading dims of each operand are one batch count,
+    the transposes become strides, the reference's "dense" broadcast (one mat1 for every batch of mat0, no transposes) a batch
+    stride of 0.  ValueError for the shapes the reference refuses.  dtype: SHL_I8 / SHL_F16; the records are (scale, zp)"""
+    a_shape, b_shape = [int(v) for v in a_shape], [int(v) for v in b_shape]
+    if len(a_shape) < 2 or len(b_shape) < 2:
+        raise ValueError("matmul needs tensors of two or more dims")
+    prod = lambda dims: int(np.prod(dims, dtype=np.int64))
+    ba, bb = prod(a_shape[:-2]), prod(b_shape[:-2])
+    m, k = (a_shape[-1], a_shape[-2]) if trans_a else (a_shape[-2], a_shape[-1])
+    n, k1 = (b_shape[-2], b_shape[-1]) if trans_b else (b_shape[-1], b_shape[-2])
+    if k1 != k:
+        raise ValueError("the operands disagree on K: %d and %d" % (k, k1))
+    if not (ba == bb or (ba > 1 and bb == 1 and not trans_a and not trans_b)):
+        raise ValueError("batches %d and %d: a broadcast the reference refuses" % (ba, bb))
+    d = MatmulDesc()
+    d.dtype, d.batches, d.m, d.n, d.k = dtype, ba, m, n, k
+    d.a_batch_stride, d.a_row_stride, d.a_k_stride = m * k, (1 if trans_a else k), (m if trans_a else 1)
+    d.b_batch_stride, d.b_col_stride, d.b_k_stride = (0 if bb == 1 and ba > 1 else k * n), (k if trans_b else 1), (1 if trans_b else n)
+    d.a_elems, d.b_elems, d.out_elems = prod(a_shape), prod(b_shape), ba * m * n
+    (d.a_scale, d.a_zp), (d.b_scale, d.b_zp), (d.out_scale, d.out_zp) = a_q, b_q, out_q
+    return d
+
+
+def matmul(hip, a_dev, b_dev, out_dev, desc, stream=None):
+    """enqueue out = a x b (device pointers) on `stream`; raises MI355XError on a refusal.  Returns the form that ran"""
+    name = hip.shl_mi355x_matmul_kernel_name(a_dev, b_dev, out_dev, C.byref(desc)).decode()
+    check(hip.shl_mi355x_matmul(a_dev, b_dev, out_dev, C.byref(desc), stream), hip, "shl_mi355x_matmul")
+    return name
 
 
 def tensor_array(keep, tensors):

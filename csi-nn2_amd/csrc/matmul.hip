@@ -1,0 +1,292 @@
+// matmul.hip -- batched matrix product of two int8 / binary16 tensors, both transposes and the reference's "dense"
+// broadcast: CSINN_OP_MATMUL.
+//
+// Restates shl_ref_matmul_f32 behind shl_ref_diso_callback_base (source/reference/matmul.c:21-132, utils.c:623-637): both
+// operands converted to float32 with their records, per output `total = 0; for k: total += a * b` in float32 with k
+// ascending, the result converted with the output's record.  The layer's nine loop nests differ in their offsets only; here
+// they are strides of one descriptor (element (b, i, k) of A at b abs + i ars + k aks, element (b, k, j) of B at
+// b bbs + j brs + k bks; the broadcast is bbs == 0).
+//
+// Two forms, chosen by mm_form (matmul_canon.h) for the launch and for shl_mi355x_matmul_kernel_name:
+//   matmul_chain  one output per thread, the literal chain: one __fmaf_rn per step (the reference's build contracts
+//                 `total += a * b`), k ascending, the loads of eight steps issued ahead of their additions.  Bit-identical to the reference for any records.
+//                 A binary16 chain can meet NaNs, and float32_to_float16_base keeps a NaN's sign: the steps restate which
+//                 NaN an x86 multiplication and addition hand on instead of trusting this machine's
+//   matmul_mfma   a workgroup of four waves owns a 64 x 64 output tile of one batch, a wave a 32 x 32 quarter
+//                 (v_mfma_i32_32x32x32_i8 / v_mfma_f32_32x32x16_f16: 16 bytes of k per lane and operand).  The K loop walks
+//                 slabs of 64 bytes of k: every thread loads ONE 16-byte piece of A and one of B along the operand's
+//                 contiguous dimension (one uint4 where the plan proved every piece aligned, else element loads), the
+//                 next slab's pieces are in flight while this slab's MFMAs run, and the pieces are written to LDS as
+//                 [row][k] for both operands -- a transposed operand is transposed by that write.  Rows past M / N and k
+//                 past K are written as zeros.  LDS: 2 x 64 rows x 80 bytes (64 + 16: the 32 rows a fragment read walks
+//                 fall on different banks) + 512 bytes of row sums = 10.5 KiB.
+//                 int8 multiplies the RAW bytes and corrects afterwards: S = sum qa qb - zb sum_k qa - za sum_k qb +
+//                 K za zb.  The row sums of A and the column sums of B come from the fragments the wave holds anyway
+//                 (v_dot4 against ones), only when the other operand's zero point is not 0; the zero-filled K tail adds
+//                 nothing to any of the three sums, the constant term uses the true K.  Then f = (float)S * mult,
+//                 sat8(rint(f / s_out) + zp_out) with div_by_scale where mm_fma_ok admits the records.
+//                 binary16: exact products, float32 accumulation on the matrix cores, the reference's conversion.
+#include <stdlib.h>
+#include <string.h>
+
+#include <type_traits>
+
+#include "igemm_common.h"
+#include "matmul_canon.h"  // the host side: validation, the exactness proof, the form rule (a stand-alone program compiles it too)
+
+namespace shl {
+
+constexpr int MM_T = 64;      // tile rows and columns
+constexpr int MM_KB = 64;     // bytes of k per slab and row
+constexpr int MM_PITCH = 80;  // bytes per LDS row
+
+struct MmArgs {
+    const void *a, *b;
+    void *out;
+    int32_t batches, M, N, K;
+    int64_t abs, ars, aks, bbs, brs, bks;  // strides in elements
+    int32_t a_kc, b_kc, a_vec, b_vec;
+    int32_t iza, izb, div_fma, tiles_m, tiles_n;
+    float sa, za, sb, zb, so, zo, inv_so, mult;
+};
+
+template <bool F16>
+__device__ __forceinline__ uint32_t mm_load(const void *p, int64_t at)
+{
+    if constexpr (F16) return static_cast<const uint16_t *>(p)[at];
+    else return static_cast<const uint8_t *>(p)[at];
+}
+
+template <bool F16>
+__device__ __forceinline__ float mm_cvt(uint32_t raw, float z, float s)
+{
+    if constexpr (F16) return f16_bits_to_float((uint16_t)raw);
+    else return __fmul_rn(__fsub_rn((float)(int8_t)raw, z), s);  // int8_to_float_base
+}
+
+// total += x * y as the reference's build computes it: -O3 -mfma contracts the product and the sum into ONE fused
+// multiply-add (the genuine library's outputs show it: with converter scales a rounded product followed by a rounded sum
+// differs in about one output of two thousand).  binary16 only: a NaN result hands on the accumulator's NaN, else an
+// operand's, else (inf * 0, inf - inf) the default NaN, whose sign bit is set on x86
+template <bool F16>
+__device__ __forceinline__ float mm_step(float acc, float x, float y)
+{
+    const float r = __fmaf_rn(x, y, acc);
+    if constexpr (F16) return r == r ? r : (acc != acc ? acc : (x != x ? x : (y != y ? y : __uint_as_float(0xFFC00000u))));
+    else return r;
+}
+
+template <bool F16>
+__device__ __forceinline__ void mm_store(const MmArgs &a, int64_t o, float f)
+{
+    if constexpr (F16) {
+        if (f != f) static_cast<uint16_t *>(a.out)[o] = (__float_as_uint(f) >> 31) ? 0xFFFFu : 0x7FFFu;
+        else static_cast<uint16_t *>(a.out)[o] = float_to_f16_bits_ref(f);
+    } else {
+        const float d = a.div_fma ? div_by_scale(f, a.so, a.inv_so) : __fdiv_rn(f, a.so);
+        static_cast<int8_t *>(a.out)[o] = (int8_t)sat8_from_float(__fadd_rn(rintf(d), a.zo));  // float_to_int8_base
+    }
+}
+
+template <bool F16>
+__global__ __launch_bounds__(256) void matmul_chain_kernel(MmArgs a)
+{
+    constexpr int B = 8;  // loads in flight ahead of the additions
+    const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (o >= (int64_t)a.batches * a.M * a.N) return;  // (the product is the output's element count: below 2^31)
+    const uint32_t mn = (uint32_t)a.M * (uint32_t)a.N;
+    const uint32_t bi = (uint32_t)o / mn, r = (uint32_t)o - bi * mn;
+    const uint32_t m = r / (uint32_t)a.N, n = r - m * (uint32_t)a.N;
+    const int64_t pa = (int64_t)bi * a.abs + (int64_t)m * a.ars, pb = (int64_t)bi * a.bbs + (int64_t)n * a.brs;
+    float acc = 0.0f;
+    int32_t k = 0;
+    for (; k + B <= a.K; k += B) {
+        uint32_t ra[B], rb[B];
+#pragma unroll
+        for (int j = 0; j < B; ++j) {
+            ra[j] = mm_load<F16>(a.a, pa + (int64_t)(k + j) * a.aks);
+            rb[j] = mm_load<F16>(a.b, pb + (int64_t)(k + j) * a.bks);
+        }
+#pragma unroll
+        for (int j = 0; j < B; ++j) acc = mm_step<F16>(acc, mm_cvt<F16>(ra[j], a.za, a.sa), mm_cvt<F16>(rb[j], a.zb, a.sb));
+    }
+    for (; k < a.K; ++k)
+        acc = mm_step<F16>(acc, mm_cvt<F16>(mm_load<F16>(a.a, pa + (int64_t)k * a.aks), a.za, a.sa),
+                           mm_cvt<F16>(mm_load<F16>(a.b, pb + (int64_t)k * a.bks), a.zb, a.sb));
+    mm_store<F16>(a, o, acc);
+}
+
+// ---- the mfma form ---------------------------------------------------------------------------------------------------------
+// One thread's 16-byte piece of a slab.  base: the operand's first element of this batch; `os` the stride of the dimension the
+// piece does not walk.  kc: the piece walks k (thread t: row t / 4, piece t % 4 of the row's 64 bytes); else it walks the
+// tile's rows (k = t / PPK of the slab, rows 16 / ES (t % PPK) on).  Elements outside the operand come back as zeros
+template <bool F16>
+__device__ __forceinline__ uint4 mm_piece(const void *base, int64_t os, int row0, int rows, int k0, int K, int kc, int vec, int tid)
+{
+    using E = typename std::conditional<F16, uint16_t, uint8_t>::type;
+    constexpr int ES = (int)sizeof(E), EPP = 16 / ES, PPK = MM_T / EPP;
+    const E *p = static_cast<const E *>(base);
+    const int outer = kc ? row0 + (tid >> 2) : k0 + tid / PPK;   // the coordinate the piece does not walk
+    const int outer_end = kc ? rows : K;
+    const int first = kc ? k0 + (tid & 3) * EPP : row0 + (tid % PPK) * EPP;  // the piece's first coordinate along its walk
+    const int end = kc ? K : rows;
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (outer >= outer_end || first >= end) return v;
+    const E *src = p + (int64_t)outer * os + first;
+    if (vec && first + EPP <= end) return *reinterpret_cast<const uint4 *>(src);
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int e = 0; e < EPP; ++e)
+        if (first + e < end) w[e * ES / 4] |= (uint32_t)src[e] << (8 * (e * ES % 4));
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// ... and its place in the LDS image [row][k]
+template <bool F16>
+__device__ __forceinline__ void mm_put(char *lds, const uint4 &v, int kc, int tid)
+{
+    using E = typename std::conditional<F16, uint16_t, uint8_t>::type;
+    constexpr int ES = (int)sizeof(E), EPP = 16 / ES, PPK = MM_T / EPP;
+    if (kc) {
+        *reinterpret_cast<uint4 *>(lds + (tid >> 2) * MM_PITCH + (tid & 3) * 16) = v;
+        return;
+    }
+    const int kk = tid / PPK, r0 = (tid % PPK) * EPP;
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int e = 0; e < EPP; ++e)
+        *reinterpret_cast<E *>(lds + (r0 + e) * MM_PITCH + kk * ES) = (E)(w[e * ES / 4] >> (8 * (e * ES % 4)));
+}
+
+template <bool F16>
+__global__ __launch_bounds__(256) void matmul_mfma_kernel(MmArgs a)
+{
+    using Acc = typename AccT<!F16>::type;
+    constexpr int ES = F16 ? 2 : 1, KS = MM_KB / ES;  // elements of k per slab
+    __shared__ __attribute__((aligned(16))) char lds_a[MM_T * MM_PITCH];
+    __shared__ __attribute__((aligned(16))) char lds_b[MM_T * MM_PITCH];
+    __shared__ int32_t row_sum[4][32];
+    const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int wm = wave >> 1, wn = wave & 1, fr = lane & 31, fh = lane >> 5;
+    const uint32_t tiles = (uint32_t)a.tiles_m * (uint32_t)a.tiles_n;
+    const uint32_t bi = blockIdx.x / tiles, t = blockIdx.x - bi * tiles;
+    const int m0 = (int)(t / (uint32_t)a.tiles_n) * MM_T, n0 = (int)(t % (uint32_t)a.tiles_n) * MM_T;
+    const void *pa = static_cast<const char *>(a.a) + (int64_t)bi * a.abs * ES;
+    const void *pb = static_cast<const char *>(a.b) + (int64_t)bi * a.bbs * ES;
+    const int64_t a_os = a.a_kc ? a.ars : a.aks, b_os = a.b_kc ? a.brs : a.bks;
+
+    Acc acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0;
+    int32_t rs = 0, cs = 0;
+    uint4 va = mm_piece<F16>(pa, a_os, m0, a.M, 0, a.K, a.a_kc, a.a_vec, tid);
+    uint4 vb = mm_piece<F16>(pb, b_os, n0, a.N, 0, a.K, a.b_kc, a.b_vec, tid);
+    for (int k0 = 0; k0 < a.K; k0 += KS) {
+        __syncthreads();  // the previous slab's fragments were read
+        mm_put<F16>(lds_a, va, a.a_kc, tid);
+        mm_put<F16>(lds_b, vb, a.b_kc, tid);
+        __syncthreads();
+        if (k0 + KS < a.K) {  // the next slab's pieces travel while this slab's MFMAs run
+            va = mm_piece<F16>(pa, a_os, m0, a.M, k0 + KS, a.K, a.a_kc, a.a_vec, tid);
+            vb = mm_piece<F16>(pb, b_os, n0, a.N, k0 + KS, a.K, a.b_kc, a.b_vec, tid);
+        }
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const v4i fa = *reinterpret_cast<const v4i *>(lds_a + (wm * 32 + fr) * MM_PITCH + s * 32 + fh * 16);
+            const v4i fb = *reinterpret_cast<const v4i *>(lds_b + (wn * 32 + fr) * MM_PITCH + s * 32 + fh * 16);
+            acc = mfma<!F16>(fa, fb, acc);
+            if constexpr (!F16) {
+                if (a.izb != 0) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) rs = __builtin_amdgcn_sdot4(fa[j], 0x01010101, rs, false);
+                }
+                if (a.iza != 0) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) cs = __builtin_amdgcn_sdot4(fb[j], 0x01010101, cs, false);
+                }
+            }
+        }
+    }
+    if constexpr (!F16) {
+        // a lane holds half of its row's / column's k: the other half is 32 lanes away
+        rs += __shfl_xor(rs, 32);
+        cs += __shfl_xor(cs, 32);
+        if (fh == 0) row_sum[wave][fr] = rs;
+        __syncthreads();
+    }
+    // C/D layout: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+    const int n = n0 + wn * 32 + fr;
+    const int32_t kzz = a.K * a.iza * a.izb;  // (K <= 32768, |zp| <= 128: below 2^30)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * fh;
+        const int m = m0 + wm * 32 + row;
+        if (m >= a.M || n >= a.N) continue;
+        const int64_t o = ((int64_t)bi * a.M + m) * a.N + n;
+        if constexpr (F16) {
+            mm_store<true>(a, o, acc[r]);
+        } else {
+            // (every term and the true sum fit 32 bits; unsigned arithmetic, so that no intermediate wrap is undefined)
+            const uint32_t S = (uint32_t)acc[r] - (uint32_t)(a.izb * row_sum[wave][row]) - (uint32_t)(a.iza * cs) + (uint32_t)kzz;
+            mm_store<false>(a, o, __fmul_rn((float)(int32_t)S, a.mult));
+        }
+    }
+}
+
+// ---- host side (validation, the proof and the form rule are in matmul_canon.h) -----------------------------------------
+static int matmul_launch(const void *a_dev, const void *b_dev, void *out_dev, const shl_mi355x_matmul_desc *d, hipStream_t s)
+{
+    const bool f16 = d->dtype == SHL_MI355X_F16;
+    MmPlan p;
+    mm_plan(a_dev, b_dev, d, &p);
+    const int form = mm_form(d, &p);
+    MmArgs a;
+    memset(&a, 0, sizeof(a));
+    a.a = a_dev, a.b = b_dev, a.out = out_dev;
+    a.batches = d->batches, a.M = d->m, a.N = d->n, a.K = d->k;
+    a.abs = d->a_batch_stride, a.ars = d->a_row_stride, a.aks = d->a_k_stride;
+    a.bbs = d->b_batch_stride, a.brs = d->b_col_stride, a.bks = d->b_k_stride;
+    a.a_kc = p.a_kcontig, a.b_kc = p.b_kcontig, a.a_vec = p.a_vec, a.b_vec = p.b_vec;
+    a.sa = d->a_scale, a.za = (float)d->a_zp, a.sb = d->b_scale, a.zb = (float)d->b_zp;
+    a.so = d->out_scale, a.zo = (float)d->out_zp, a.inv_so = 1.0f / d->out_scale;
+    a.iza = d->a_zp, a.izb = d->b_zp;
+    a.mult = d->a_scale * d->b_scale;  // rounded once, here
+    a.div_fma = !f16 && mm_fma_ok(d);
+    a.tiles_m = (d->m + MM_T - 1) / MM_T, a.tiles_n = (d->n + MM_T - 1) / MM_T;
+    if (form == MM_MFMA) {
+        const int64_t groups = (int64_t)d->batches * a.tiles_m * a.tiles_n;  // (at most the output's element count)
+        const dim3 grid((unsigned)groups), block(256);
+        hipLaunchKernelGGL(f16 ? matmul_mfma_kernel<true> : matmul_mfma_kernel<false>, grid, block, 0, s, a);
+    } else {
+        const dim3 grid((unsigned)((d->out_elems + 255) / 256)), block(256);
+        hipLaunchKernelGGL(f16 ? matmul_chain_kernel<true> : matmul_chain_kernel<false>, grid, block, 0, s, a);
+    }
+    SHL_HIP(hipGetLastError());
+    return SHL_MI355X_OK;
+}
+
+}  // namespace shl
+
+extern "C" const char *shl_mi355x_matmul_kernel_name(const void *a_dev, const void *b_dev, const void *out_dev,
+                                                     const struct shl_mi355x_matmul_desc *d)
+{
+    using namespace shl;
+    if (mm_validate(a_dev, b_dev, out_dev, d)) return "";
+    MmPlan p;
+    mm_plan(a_dev, b_dev, d, &p);
+    return mm_form_name(mm_form(d, &p));
+}
+
+extern "C" int shl_mi355x_matmul_is_exact(const struct shl_mi355x_matmul_desc *d) { return shl::mm_is_exact(d) ? 1 : 0; }
+
+extern "C" int shl_mi355x_matmul(const void *a_dev, const void *b_dev, void *out_dev, const struct shl_mi355x_matmul_desc *d,
+                                 void *stream)
+{
+    using namespace shl;
+    const char *why = mm_validate(a_dev, b_dev, out_dev, d);
+    if (why) {
+        set_error("matmul: %s", why);
+        return SHL_MI355X_EINVAL;
+    }
+    return matmul_launch(a_dev, b_dev, out_dev, d, (hipStream_t)stream);
+}

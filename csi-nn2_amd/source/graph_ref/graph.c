@@ -239,6 +239,14 @@ int shl_gref_mul(struct csinn_tensor *input0, struct csinn_tensor *input1, struc
     return record_diso(input0, input1, output, CSINN_OP_MUL, params);
 }
 
+/* matmul (source/graph_ref/matmul.c of the reference): recorded like the other two-input layers; only the params' base is
+ * read here */
+int shl_gref_matmul(struct csinn_tensor *mat0, struct csinn_tensor *mat1, struct csinn_tensor *output,
+                    struct csinn_matmul_params *params)
+{
+    return record_diso(mat0, mat1, output, CSINN_OP_MATMUL, (struct csinn_diso_params *)params);
+}
+
 /* params->inputs_count inputs, any of which may be a constant tensor (it becomes a const node), one output */
 int shl_gref_concat(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params)
 {
@@ -406,6 +414,7 @@ int shl_gref_call_layer_func(void *fn, struct shl_node *node)
             return f(node->in[0]->data, node->out[0]->data, params);
         case CSINN_OP_ADD:
         case CSINN_OP_MUL:
+        case CSINN_OP_MATMUL:
             return f(node->in[0]->data, node->in[1]->data, node->out[0]->data, params);
         case CSINN_OP_CONCAT: {
             struct csinn_tensor **ins = shl_mem_alloc((int64_t)node->in_num * sizeof(*ins));
@@ -484,6 +493,7 @@ static struct csinn_callback *gref_cb_map(int op, int dtype)
         {CSINN_OP_SILU, shl_gref_silu},
         {CSINN_OP_LEAKY_RELU, shl_gref_leaky_relu},
         {CSINN_OP_MUL, shl_gref_mul},
+        {CSINN_OP_MATMUL, shl_gref_matmul},
         {CSINN_OP_RESIZE, shl_gref_resize},
         {CSINN_OP_SPLIT, shl_gref_split},
         {CSINN_OP_SHUFFLE_CHANNEL, shl_gref_shuffle_channel},

@@ -113,6 +113,12 @@ int shl_mi355x_global_maxpool2d_init(struct csinn_tensor *input, struct csinn_te
 int shl_mi355x_global_maxpool2d_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params,
         struct csinn_perf_info *info);
 
+/* matmul (matmul.c): init (a refused layer falls through to the reference where there is one) and perf */
+int shl_mi355x_matmul_init(struct csinn_tensor *mat0, struct csinn_tensor *mat1, struct csinn_tensor *output,
+        struct csinn_matmul_params *params);
+int shl_mi355x_matmul_perf(struct csinn_tensor *mat0, struct csinn_tensor *mat1, struct csinn_tensor *output,
+        struct csinn_matmul_params *params, struct csinn_perf_info *info);
+
 /* ... and of the elementwise layers (eltwise.c): the kernel form the rules choose */
 int shl_mi355x_sigmoid_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params,
                             struct csinn_perf_info *info);

@@ -171,6 +171,8 @@ static const struct session_op g_ops[] = {
     {CSINN_OP_REDUCE_MAX, shl_mi355x_reduce_max_exec, CALL_SISO, 1, 1},
     {CSINN_OP_REDUCE_MIN, shl_mi355x_reduce_min_exec, CALL_SISO, 1, 1},
     {CSINN_OP_GLOBAL_MAXPOOL2D, shl_mi355x_global_maxpool2d_exec, CALL_SISO, 1, 1},
+    /* QK^T and PV of an attention block (two activations), a linear layer exported as MatMul (the second operand a constant) */
+    {CSINN_OP_MATMUL, shl_mi355x_matmul_exec, CALL_DISO, 2, 1},
 };
 
 /* the row of layer `n`; NULL: not a layer this file runs */

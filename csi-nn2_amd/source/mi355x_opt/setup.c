@@ -709,6 +709,7 @@ void shl_target_init_mi355x(void)
         reg(dts[i], CSINN_OP_RESHAPE, shl_mi355x_reshape_init, shl_mi355x_reshape_exec, shl_gref_reshape, shl_mi355x_reshape_perf);
         reg(dts[i], CSINN_OP_FLATTEN, shl_mi355x_flatten_init, shl_mi355x_flatten_exec, shl_gref_flatten, shl_mi355x_flatten_perf);
         reg(dts[i], CSINN_OP_PAD, shl_mi355x_pad_init, shl_mi355x_pad_exec, shl_gref_pad, shl_mi355x_pad_perf);
+        reg(dts[i], CSINN_OP_MATMUL, shl_mi355x_matmul_init, shl_mi355x_matmul_exec, shl_gref_matmul, shl_mi355x_matmul_perf);
         reg(dts[i], CSINN_OP_MEAN, shl_mi355x_mean_init, shl_mi355x_mean_exec, shl_gref_mean, shl_mi355x_mean_perf);
         reg(dts[i], CSINN_OP_SUM, shl_mi355x_sum_init, shl_mi355x_sum_exec, shl_gref_sum, shl_mi355x_sum_perf);
         reg(dts[i], CSINN_OP_MAX, shl_mi355x_max_init, shl_mi355x_max_exec, shl_gref_max, shl_mi355x_max_perf);

@@ -13,6 +13,7 @@
  *   split / shuffle_channel  source/nn2/split.c, shuffle_channel.c
  *   transpose / reshape / flatten / pad  source/nn2/transpose.c, reshape.c, flatten.c, pad.c
  *   mean / sum / max / min / reduce_* / global_maxpool2d  source/nn2/mean.c, sum.c, max.c, min.c, reduce_*.c, global_maxpool2d.c
+ *   matmul ............ source/nn2/matmul.c
  *   deconv2d .......... source/nn2/deconvolution.c
  *   sigmoid / hard_sigmoid / silu / leaky_relu / mul  source/nn2/sigmoid.c, hard_sigmoid.c, silu.c, leaky_relu.c, mul.c
  * The only deliberate difference: a missing callback is reported (CSINN_CALLBACK_UNSET and an
@@ -282,6 +283,18 @@ int csinn_mul(struct csinn_tensor *input0, struct csinn_tensor *input1, struct c
               struct csinn_diso_params *params)
 {
     return run4(&params->base, input0, input1, output, params);
+}
+
+/* source/nn2/matmul.c of the reference: two inputs, one output, the dtype of the first input picks the callback */
+int csinn_matmul_init(struct csinn_tensor *mat0, struct csinn_tensor *mat1, struct csinn_tensor *output,
+                      struct csinn_matmul_params *params)
+{
+    return map_and_init4(&params->base, CSINN_OP_MATMUL, mat0, mat1, output, params);
+}
+int csinn_matmul(struct csinn_tensor *mat0, struct csinn_tensor *mat1, struct csinn_tensor *output,
+                 struct csinn_matmul_params *params)
+{
+    return run4(&params->base, mat0, mat1, output, params);
 }
 
 /* source/nn2/deconvolution.c:26-46 of the reference: the op id by the group count alone, and the init callback's status

@@ -101,6 +101,11 @@ int csinn_flatten_init(struct csinn_tensor *input, struct csinn_tensor *output, 
 int csinn_flatten(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_flatten_params *params);
 int csinn_pad_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pad_params *params);
 int csinn_pad(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pad_params *params);
+/* batched matrix product (source/nn2/matmul.c of the reference): two inputs, either of which may be a constant */
+int csinn_matmul_init(struct csinn_tensor *mat0, struct csinn_tensor *mat1, struct csinn_tensor *output,
+                      struct csinn_matmul_params *params);
+int csinn_matmul(struct csinn_tensor *mat0, struct csinn_tensor *mat1, struct csinn_tensor *output,
+                 struct csinn_matmul_params *params);
 /* reductions (source/nn2/mean.c, sum.c, max.c, min.c, reduce_*.c, global_maxpool2d.c of the reference): one input, one output */
 int csinn_mean_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
 int csinn_mean(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);

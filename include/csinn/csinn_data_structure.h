@@ -141,6 +141,7 @@ enum csinn_op_enum {
     CSINN_OP_GLOBAL_MAXPOOL2D = 75,
     CSINN_OP_HARD_SIGMOID = 78,
     CSINN_OP_LEAKY_RELU = 84,
+    CSINN_OP_MATMUL = 95,
     CSINN_OP_MAX = 96, /* the stride family of reductions: MAX, MEAN, MIN, SUM (struct csinn_reduce_params) */
     CSINN_OP_MAXPOOL2D = 98,
     CSINN_OP_MEAN = 101,
@@ -465,6 +466,15 @@ struct csinn_pad_params { /* 72 B */
     int32_t pad_num;
     float pad_value;
     enum csinn_pad_enum pad_mode;
+};
+
+/* matmul (csinn_data_structure.h:784-788 of the reference): output[.., i, j] = sum over k of mat0[.., i, k] * mat1[.., k, j];
+ * trans_a / trans_b say that the operand's last two dims are stored the other way round.  The leading dims of each operand
+ * are multiplied into a batch count; the counts must be equal, or mat1's 1 with no transposes */
+struct csinn_matmul_params { /* 64 B */
+    struct csinn_params_base base;
+    bool trans_a;
+    bool trans_b;
 };
 
 /* reductions (csinn_data_structure.h:1072-1083 of the reference).  The stride family (CSINN_OP_MEAN, _SUM, _MAX, _MIN) reads

@@ -88,6 +88,8 @@ int shl_gref_transpose(struct csinn_tensor *input, struct csinn_tensor *output, 
 int shl_gref_reshape(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reshape_params *params);
 int shl_gref_flatten(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_flatten_params *params);
 int shl_gref_pad(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pad_params *params);
+int shl_gref_matmul(struct csinn_tensor *mat0, struct csinn_tensor *mat1, struct csinn_tensor *output,
+                    struct csinn_matmul_params *params);
 int shl_gref_mean(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
 int shl_gref_sum(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
 int shl_gref_max(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);

@@ -634,6 +634,58 @@ int shl_mi355x_reduce(const void *in_dev, void *out_dev, const struct shl_mi355x
 /* the kernel form the rules choose; "" for invalid arguments.  Pure host code, touches no device */
 const char *shl_mi355x_reduce_kernel_name(const void *in_dev, const void *out_dev, const struct shl_mi355x_reduce_desc *d);
 
+/* Batched matrix product of two int8 / binary16 tensors: out[b][i][j] = sum over k of A[b][i][k] * B[b][k][j] -- what
+ * CSINN_OP_MATMUL (shl_ref_matmul_f32 behind shl_ref_diso_callback_base, source/reference/matmul.c) computes.  The
+ * caller turns the layer into strides, in elements: element (b, i, k) of A is at b a_batch_stride + i a_row_stride +
+ * k a_k_stride, element (b, k, j) of B at b b_batch_stride + j b_col_stride + k b_k_stride; trans_a / trans_b swap an
+ * operand's two strides, the reference's "dense" broadcast (one B for every batch of A) is b_batch_stride == 0.  The output
+ * is dense: [batches][m][n].  Two forms (shl_mi355x_matmul_kernel_name says which the rule picks):
+ *   SHL_MI355X_MATMUL_CHAIN  one output per thread, the reference's own float32 chain: int8 operands dequantised as
+ *                            ((float)q - zp) * scale, one fused multiply-add per step (the reference's build contracts
+ *                            `total += a * b`), k ascending, then
+ *                            sat8(rint(x / s_out) + zp_out); binary16 exact widening and the reference's conversion.
+ *                            Bit-identical to the reference for any records and any strides
+ *   SHL_MI355X_MATMUL_MFMA   64 x 64 output tiles on the matrix cores.  int8: S = sum (qa - za)(qb - zb) exactly in int32,
+ *                            f = (float)S * mult with mult = a_scale * b_scale rounded once, sat8(rint(f / s_out) + zp_out);
+ *                            equal to the reference bit for bit when shl_mi355x_matmul_is_exact(), within 1 LSB otherwise.
+ *                            binary16: exact products, float32 accumulation in another order than the chain's.  Needs
+ *                            every operand to have a unit stride (k or row / column) and, int8, k <= 32768
+ * SHL_MI355X_MATMUL_FORM=chain|mfma forces a form (mfma: where its geometry fits, else chain); read per call.
+ * binary16 operands carry no records: the scales and zero points are ignored.
+ * SHL_MI355X_EINVAL before anything is enqueued: batches, m, n or k below 1; a negative stride; a_elems / b_elems /
+ * out_elems below 1 or 2^31 and above; out_elems other than batches * m * n; an index that reaches a_elems / b_elems;
+ * pointers not aligned to their elements; the output overlapping an operand.  Enqueues only: no allocation, no
+ * synchronisation (capturable in a hipGraph). */
+#define SHL_MI355X_MATMUL_CHAIN "matmul_chain"
+#define SHL_MI355X_MATMUL_MFMA "matmul_mfma"
+#define SHL_MI355X_MATMUL_MFMA_MAX_K 32768
+
+struct shl_mi355x_matmul_desc {
+    int32_t dtype; /* SHL_MI355X_I8 / SHL_MI355X_F16 */
+    int32_t batches;
+    int32_t m, n, k;
+    int32_t reserved0; /* must be zero */
+    int64_t a_batch_stride, a_row_stride, a_k_stride; /* elements */
+    int64_t b_batch_stride, b_col_stride, b_k_stride;
+    int64_t a_elems, b_elems, out_elems; /* elements of the three tensors */
+    float a_scale;
+    int32_t a_zp;
+    float b_scale;
+    int32_t b_zp;
+    float out_scale;
+    int32_t out_zp;
+    int32_t reserved[4]; /* must be zero */
+};
+
+int shl_mi355x_matmul(const void *a_dev, const void *b_dev, void *out_dev, const struct shl_mi355x_matmul_desc *d, void *stream);
+/* the kernel form the rules choose; "" for invalid arguments.  Pure host code, touches no device */
+const char *shl_mi355x_matmul_kernel_name(const void *a_dev, const void *b_dev, const void *out_dev,
+                                          const struct shl_mi355x_matmul_desc *d);
+/* 1 when the int8 mfma form is PROVEN equal to the reference's chain for every input: with each scale written m 2^e, m
+ * odd, k * max(127 - za, za + 128) * max(127 - zb, zb + 128) * ma * mb < 2^24 -- every dequantised value, product and partial
+ * sum of the chain then is exact.  Depends on k and the records only.  0 otherwise, for binary16 and for a NULL descriptor */
+int shl_mi355x_matmul_is_exact(const struct shl_mi355x_matmul_desc *d);
+
 /* nearest-neighbour / bilinear resize of a 4-d int8 / binary16 tensor: shl_ref_resize_quant
  * (source/reference/resize.c:464-468), bit for bit.  height_scale / width_scale are the reference's own floats, computed by
  * the CALLER as ONE float division each: (float)in / out, with align_corners (float)(in - 1) / (out - 1)

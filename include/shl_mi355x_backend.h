@@ -135,6 +135,11 @@ int shl_mi355x_reduce_sum_exec(struct csinn_tensor *input, struct csinn_tensor *
 int shl_mi355x_reduce_max_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
 int shl_mi355x_reduce_min_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
 int shl_mi355x_global_maxpool2d_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params);
+/* matmul (source/mi355x_opt/matmul.c): tensors of 2 .. 8 dims, the leading dims of each multiplied into a batch count; equal
+ * counts with any transposes, or mat1's count of 1 with none (the reference's "dense" broadcast).  mat1 may be a constant.
+ * Any other broadcast, operands that disagree on K and an output tensor of another size are refused */
+int shl_mi355x_matmul_exec(struct csinn_tensor *mat0, struct csinn_tensor *mat1, struct csinn_tensor *output,
+                           struct csinn_matmul_params *params);
 /* resize (source/mi355x_opt/resize.c): 4-d tensors, nearest-neighbour or bilinear, to the output tensor's height and
  * width; batch and channels of input and output must agree; bicubic, and align_corners with an output extent of 1 (the
  * reference divides by zero), are refused */
