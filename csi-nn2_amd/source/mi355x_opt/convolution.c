@@ -36,13 +36,6 @@ static int layout_of(struct csinn_conv2d_params *params)
     return -1;
 }
 
-static int dtype_of(struct csinn_tensor *t)
-{
-    if (t->dtype == CSINN_DTYPE_INT8) return SHL_MI355X_I8;
-    if (t->dtype == CSINN_DTYPE_FLOAT16) return SHL_MI355X_F16;
-    return -1;
-}
-
 static int scale_is_one(float s) { return fabsf(s - 1.0f) <= 1.1920929e-07f; }
 
 /* fp32 image of the bias as the reference computes it, and the per-channel multipliers.
@@ -215,12 +208,12 @@ static int conv_init_common(struct csinn_tensor *input, struct csinn_tensor *out
     struct shl_mi355x_conv_desc d;
     memset(&d, 0, sizeof(d));
     d.layout = layout_of(params);
-    d.dtype = dtype_of(input);
+    d.dtype = shl_mi355x_dtype_code(input);
     if (d.layout < 0) {
         shl_debug_error("mi355x: conv2d layout %d unsupported\n", params->base.layout);
         return CSINN_UNSUPPORT_LAYOUT;
     }
-    if (d.dtype < 0 || dtype_of(kernel) != d.dtype || dtype_of(output) != d.dtype) {
+    if (d.dtype < 0 || shl_mi355x_dtype_code(kernel) != d.dtype || shl_mi355x_dtype_code(output) != d.dtype) {
         shl_debug_error("mi355x: conv2d dtypes in=%d kernel=%d out=%d unsupported\n", input->dtype,
                         kernel->dtype, output->dtype);
         return CSINN_UNSUPPORT_DTYPE;
@@ -576,8 +569,8 @@ int shl_mi355x_fullyconnected_init(struct csinn_tensor *input, struct csinn_tens
     struct shl_mi355x_conv_desc d;
     memset(&d, 0, sizeof(d));
     d.layout = SHL_MI355X_NHWC;
-    d.dtype = dtype_of(input);
-    if (d.dtype < 0 || dtype_of(weights) != d.dtype || dtype_of(output) != d.dtype) {
+    d.dtype = shl_mi355x_dtype_code(input);
+    if (d.dtype < 0 || shl_mi355x_dtype_code(weights) != d.dtype || shl_mi355x_dtype_code(output) != d.dtype) {
         shl_debug_error("mi355x: fullyconnected dtypes in=%d w=%d out=%d unsupported\n",
                         input->dtype, weights->dtype, output->dtype);
         return CSINN_UNSUPPORT_DTYPE;
@@ -629,22 +622,15 @@ static int relu_common(struct csinn_tensor *input, struct csinn_tensor *output, 
         shl_debug_error("mi355x: relu needs one quantisation record per tensor\n");
         return CSINN_UNSUPPORT_DTYPE;
     }
-    struct shl_mi355x_ctx *ctx = shl_mi355x_ctx_of(params->base.sess);
-    const void *in_dev = shl_mi355x_stage_in(ctx, input, 0);
-    void *out_dev = shl_mi355x_stage_out_begin(ctx, output, 1);
-    if (in_dev == NULL || out_dev == NULL) return CSINN_FALSE;
+    struct shl_mi355x_staged s;
+    if (shl_mi355x_staged_begin(&params->base, input, NULL, output, &s) != CSINN_TRUE) return CSINN_FALSE;
     int st;
     if (i8)
-        st = shl_mi355x_relu_i8(in_dev, out_dev, (size_t)csinn_tensor_size(input), input->qinfo->scale,
-                                input->qinfo->zero_point, output->qinfo->scale, output->qinfo->zero_point, relu6,
-                                shl_mi355x_ctx_stream(ctx));
+        st = shl_mi355x_relu_i8(s.in[0], s.out, (size_t)csinn_tensor_size(input), input->qinfo->scale,
+                                input->qinfo->zero_point, output->qinfo->scale, output->qinfo->zero_point, relu6, s.stream);
     else
-        st = shl_mi355x_relu_f16(in_dev, out_dev, (size_t)csinn_tensor_size(input), relu6, shl_mi355x_ctx_stream(ctx));
-    if (st != SHL_MI355X_OK) {
-        shl_debug_error("mi355x: relu launch failed (%d): %s\n", st, shl_mi355x_last_error());
-        return CSINN_FALSE;
-    }
-    return shl_mi355x_stage_out_end(ctx, output, out_dev);
+        st = shl_mi355x_relu_f16(s.in[0], s.out, (size_t)csinn_tensor_size(input), relu6, s.stream);
+    return shl_mi355x_staged_end(relu6 ? "relu6" : "relu", &s, output, st);
 }
 
 int shl_mi355x_relu_exec(struct csinn_tensor *input, struct csinn_tensor *output,

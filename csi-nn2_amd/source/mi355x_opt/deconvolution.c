@@ -18,17 +18,12 @@
 
 #include "mi355x_internal.h"
 
-struct csinn_callback *shl_cb_map_ref(int op, int dtype) __attribute__((weak));
-
 static int refuse(struct csinn_conv2d_params *params, int op, int dtype, int rc)
 {
     /* csinn_deconv2d_init drops this status (source/nn2/deconvolution.c:41-45), so the callback itself must not stay: next
      * to the genuine library the layer runs on the reference's kernel, elsewhere exec finds no plan and fails */
     shl_mi355x_release_params(params);
-    if (shl_cb_map_ref) {
-        struct csinn_callback *cb = shl_cb_map_ref(op, dtype);
-        if (cb && cb->exec) params->base.cb->exec = cb->exec;
-    }
+    shl_mi355x_fall_through(&params->base, op, dtype);
     return rc;
 }
 

@@ -15,41 +15,6 @@
 
 #include "mi355x_internal.h"
 
-static int dtype_code(const struct csinn_tensor *t)
-{
-    if (t->dtype == CSINN_DTYPE_INT8) return SHL_MI355X_I8;
-    if (t->dtype == CSINN_DTYPE_FLOAT16) return SHL_MI355X_F16;
-    return -1;
-}
-
-/* one tensor of an elementwise layer: int8 or binary16 (*dtype: the first tensor's, every later one must match), one
- * quantisation record, binary16 with scale 1 */
-static int check_tensor(const char *op, const char *what, struct csinn_tensor *t, int *dtype)
-{
-    const int dt = dtype_code(t);
-    if (dt < 0 || (*dtype >= 0 && dt != *dtype)) {
-        shl_debug_error("mi355x: %s: dtype %d of the %s is unsupported or differs from the other tensors'\n", op, t->dtype, what);
-        return CSINN_UNSUPPORT_DTYPE;
-    }
-    *dtype = dt;
-    if (t->qinfo == NULL) {
-        shl_debug_error("mi355x: %s needs quantisation records\n", op);
-        return CSINN_FALSE;
-    }
-    if (t->quant_channel > 1) {
-        /* the reference's converters honour per-channel activation records (source/nn2/utils.c:1504-1642); the device
-         * path carries one record per activation tensor */
-        shl_debug_error("mi355x: %s: per-channel quantised activations are not supported\n", op);
-        return CSINN_UNSUPPORT_DTYPE;
-    }
-    if (dt == SHL_MI355X_F16 && t->qinfo->scale != 1.0f) {
-        /* f16_to_float / float_to_f16 scale by qinfo->scale when it differs from 1 (source/nn2/utils.c:1175-1205) */
-        shl_debug_error("mi355x: %s fp16 with qinfo scale != 1 is not supported\n", op);
-        return CSINN_FALSE;
-    }
-    return CSINN_TRUE;
-}
-
 /* ---- the reference's per-element functions, each in the precision its source uses ------------------------------ */
 static float f_sigmoid(float val, float n)
 {
@@ -118,9 +83,7 @@ static const char *const g_unary_name[] = {"sigmoid", "hard_sigmoid", "silu", "l
 static int unary_check(int kind, struct csinn_tensor *input, struct csinn_tensor *output, int *dtype)
 {
     const char *op = g_unary_name[kind];
-    *dtype = -1;
-    int rc = check_tensor(op, "input", input, dtype);
-    if (rc == CSINN_TRUE) rc = check_tensor(op, "output", output, dtype);
+    int rc = shl_mi355x_check_io(op, input, output, dtype);
     if (rc != CSINN_TRUE) return rc;
     if (csinn_tensor_size(input) != csinn_tensor_size(output)) {
         shl_debug_error("mi355x: %s: input and output hold different numbers of elements\n", op);
@@ -136,32 +99,18 @@ static int unary_exec(int kind, float n, struct csinn_tensor *input, struct csin
     if (rc != CSINN_TRUE) return rc;
     const size_t count = (size_t)csinn_tensor_size(output);
     if (count == 0) return CSINN_TRUE;
-    struct shl_mi355x_ctx *ctx = shl_mi355x_ctx_of(base->sess);
-    const void *in_dev = shl_mi355x_stage_in(ctx, input, 0);
-    void *out_dev = shl_mi355x_stage_out_begin(ctx, output, 1);
-    if (in_dev == NULL || out_dev == NULL) return CSINN_FALSE;
+    struct shl_mi355x_staged s;
+    if (shl_mi355x_staged_begin(base, input, NULL, output, &s) != CSINN_TRUE) return CSINN_FALSE;
     int st;
     if (dtype == SHL_MI355X_I8) {
         uint8_t table[256];
         build_table(g_unary_f[kind], n, input->qinfo->scale, input->qinfo->zero_point, output->qinfo->scale,
                     output->qinfo->zero_point, table);
-        st = shl_mi355x_unary_lut_i8(in_dev, out_dev, count, table, shl_mi355x_ctx_stream(ctx));
+        st = shl_mi355x_unary_lut_i8(s.in[0], s.out, count, table, s.stream);
     } else {
-        st = shl_mi355x_unary_f16(in_dev, out_dev, count, kind, n, shl_mi355x_ctx_stream(ctx));
+        st = shl_mi355x_unary_f16(s.in[0], s.out, count, kind, n, s.stream);
     }
-    if (st != SHL_MI355X_OK) {
-        shl_debug_error("mi355x: %s failed (%d): %s\n", g_unary_name[kind], st, shl_mi355x_last_error());
-        return CSINN_FALSE;
-    }
-    return shl_mi355x_stage_out_end(ctx, output, out_dev);
-}
-
-/* the address a tensor's bytes will have on the device as far as its alignment goes: a DMABUF tensor's own, the staging
- * buffers' alignment for a host tensor (made-up, disjoint: nothing is staged or followed) */
-static const void *perf_address(struct csinn_tensor *t, int slot)
-{
-    if (t->mtype == CSINN_MEM_TYPE_DMABUF && t->data) return t->data;
-    return (const void *)(((uintptr_t)1 << 56) + ((uintptr_t)slot << 48));
+    return shl_mi355x_staged_end(g_unary_name[kind], &s, output, st);
 }
 
 static int unary_perf(int kind, struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_perf_info *info)
@@ -169,8 +118,9 @@ static int unary_perf(int kind, struct csinn_tensor *input, struct csinn_tensor 
     int dtype;
     int rc = unary_check(kind, input, output, &dtype);
     if (rc != CSINN_TRUE) return rc;
-    info->kernel_name = dtype == SHL_MI355X_F16 ? "unary_f16"
-                                                : (char *)shl_mi355x_unary_lut_i8_kernel_name(perf_address(input, 0), perf_address(output, 1));
+    uintptr_t at = SHL_MI355X_PERF_BASE;
+    const void *in = (const void *)shl_mi355x_perf_address(input, &at), *out = (const void *)shl_mi355x_perf_address(output, &at);
+    info->kernel_name = dtype == SHL_MI355X_F16 ? "unary_f16" : (char *)shl_mi355x_unary_lut_i8_kernel_name(in, out);
     return CSINN_TRUE;
 }
 
@@ -230,9 +180,9 @@ static int mul_prepare(struct csinn_tensor *input0, struct csinn_tensor *input1,
                        struct csinn_tensor **full, struct csinn_tensor **small, struct shl_mi355x_mul_desc *desc)
 {
     int dtype = -1;
-    int rc = check_tensor("mul", "first input", input0, &dtype);
-    if (rc == CSINN_TRUE) rc = check_tensor("mul", "second input", input1, &dtype);
-    if (rc == CSINN_TRUE) rc = check_tensor("mul", "output", output, &dtype);
+    int rc = shl_mi355x_check_tensor("mul", "first input", input0, &dtype);
+    if (rc == CSINN_TRUE) rc = shl_mi355x_check_tensor("mul", "second input", input1, &dtype);
+    if (rc == CSINN_TRUE) rc = shl_mi355x_check_tensor("mul", "output", output, &dtype);
     if (rc != CSINN_TRUE) return rc;
     const int rank = output->dim_count;
     if (rank < 1 || rank > MAX_DIM) {
@@ -312,19 +262,12 @@ int shl_mi355x_mul_exec(struct csinn_tensor *input0, struct csinn_tensor *input1
     int rc = mul_prepare(input0, input1, output, &full, &small, &d);
     if (rc != CSINN_TRUE) return rc;
     if (csinn_tensor_size(output) == 0) return CSINN_TRUE;
-    struct shl_mi355x_ctx *ctx = shl_mi355x_ctx_of(params->base.sess);
-    /* slot 0 holds the first input and slot 2 the second, whichever of them is the broadcast one */
-    const void *dev0 = shl_mi355x_stage_in(ctx, input0, 0);
-    const void *dev1 = shl_mi355x_stage_in(ctx, input1, 2);
-    void *out_dev = shl_mi355x_stage_out_begin(ctx, output, 1);
-    if (dev0 == NULL || dev1 == NULL || out_dev == NULL) return CSINN_FALSE;
-    const void *a_dev = full == input0 ? dev0 : dev1, *b_dev = full == input0 ? dev1 : dev0;
-    int st = shl_mi355x_mul(a_dev, b_dev, out_dev, &d, shl_mi355x_ctx_stream(ctx));
-    if (st != SHL_MI355X_OK) {
-        shl_debug_error("mi355x: mul failed (%d): %s\n", st, shl_mi355x_last_error());
-        return CSINN_FALSE;
-    }
-    return shl_mi355x_stage_out_end(ctx, output, out_dev);
+    /* the inputs are staged in their own order, whichever of them is the broadcast one */
+    struct shl_mi355x_staged s;
+    if (shl_mi355x_staged_begin(&params->base, input0, input1, output, &s) != CSINN_TRUE) return CSINN_FALSE;
+    const int a = full == input0 ? 0 : 1;
+    int st = shl_mi355x_mul(s.in[a], s.in[1 - a], s.out, &d, s.stream);
+    return shl_mi355x_staged_end("mul", &s, output, st);
 }
 
 int shl_mi355x_mul_perf(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
@@ -335,7 +278,10 @@ int shl_mi355x_mul_perf(struct csinn_tensor *input0, struct csinn_tensor *input1
     struct shl_mi355x_mul_desc d;
     int rc = mul_prepare(input0, input1, output, &full, &small, &d);
     if (rc != CSINN_TRUE) return rc;
-    info->kernel_name = (char *)shl_mi355x_mul_kernel_name(&d, perf_address(full, full == input0 ? 0 : 2),
-                                                           perf_address(small, small == input0 ? 0 : 2), perf_address(output, 1));
+    uintptr_t at = SHL_MI355X_PERF_BASE;
+    const void *in[2];
+    in[0] = (const void *)shl_mi355x_perf_address(input0, &at), in[1] = (const void *)shl_mi355x_perf_address(input1, &at);
+    const int a = full == input0 ? 0 : 1;
+    info->kernel_name = (char *)shl_mi355x_mul_kernel_name(&d, in[a], in[1 - a], (const void *)shl_mi355x_perf_address(output, &at));
     return CSINN_TRUE;
 }

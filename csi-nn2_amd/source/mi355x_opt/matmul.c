@@ -15,51 +15,11 @@
 
 #include "mi355x_internal.h"
 
+/* one tensor: what the device carries, 2 .. MAX_DIM dims of at least 1, fewer than 2^31 elements */
 static int check_one(const char *what, struct csinn_tensor *t, int *dtype)
 {
-    if (t == NULL || t->qinfo == NULL) {
-        shl_debug_error("mi355x: matmul: the %s is missing or has no quantisation record\n", what);
-        return CSINN_FALSE;
-    }
-    const int dt = t->dtype == CSINN_DTYPE_INT8 ? SHL_MI355X_I8 : t->dtype == CSINN_DTYPE_FLOAT16 ? SHL_MI355X_F16 : -1;
-    if (dt < 0 || (*dtype >= 0 && dt != *dtype)) {
-        shl_debug_error("mi355x: matmul: dtype %d of the %s is unsupported or differs from the other tensors'\n", t->dtype, what);
-        return CSINN_UNSUPPORT_DTYPE;
-    }
-    *dtype = dt;
-    if (t->quant_channel > 1) {
-        shl_debug_error("mi355x: matmul: per-channel quantised tensors are not supported\n");
-        return CSINN_UNSUPPORT_DTYPE;
-    }
-    if (dt == SHL_MI355X_F16 && t->qinfo->scale != 1.0f) {
-        /* f16_to_float / float_to_f16 scale by qinfo->scale when it differs from 1 (source/nn2/utils.c:1175-1205) */
-        shl_debug_error("mi355x: matmul fp16 with qinfo scale != 1 is not supported\n");
-        return CSINN_FALSE;
-    }
-    if (t->dim_count < 2 || t->dim_count > MAX_DIM) {
-        shl_debug_error("mi355x: matmul: the %s has %d dims (2 .. %d)\n", what, t->dim_count, MAX_DIM);
-        return CSINN_FALSE;
-    }
-    int64_t n = 1;
-    for (int k = 0; k < t->dim_count; k++) {
-        if (t->dim[k] < 1) {
-            shl_debug_error("mi355x: matmul: dim %d of the %s is %d\n", k, what, t->dim[k]);
-            return CSINN_FALSE;
-        }
-        n *= t->dim[k];
-        if (n > 0x7FFFFFFFll) {
-            shl_debug_error("mi355x: matmul: the %s has 2^31 or more elements\n", what);
-            return CSINN_FALSE;
-        }
-    }
-    return CSINN_TRUE;
-}
-
-static int64_t elems_of(const struct csinn_tensor *t)
-{
-    int64_t n = 1;
-    for (int k = 0; k < t->dim_count; k++) n *= t->dim[k];
-    return n;
+    int rc = shl_mi355x_check_tensor("matmul", what, t, dtype);
+    return rc == CSINN_TRUE ? shl_mi355x_check_dims("matmul", what, t, 2, 1, SHL_MI355X_INT32_ELEMS) : rc;
 }
 
 /* the layer as a descriptor; CSINN_TRUE, or why not */
@@ -92,7 +52,8 @@ static int matmul_prepare(struct csinn_tensor *mat0, struct csinn_tensor *mat1, 
     d->dtype = dtype, d->batches = (int32_t)batches_a, d->m = m, d->n = n, d->k = k;
     d->a_batch_stride = (int64_t)m * k, d->a_row_stride = ta ? 1 : k, d->a_k_stride = ta ? m : 1;
     d->b_batch_stride = batches_b == 1 && batches_a > 1 ? 0 : (int64_t)k * n, d->b_col_stride = tb ? k : 1, d->b_k_stride = tb ? 1 : n;
-    d->a_elems = elems_of(mat0), d->b_elems = elems_of(mat1), d->out_elems = elems_of(output);
+    d->a_elems = shl_mi355x_tensor_elems(mat0), d->b_elems = shl_mi355x_tensor_elems(mat1);
+    d->out_elems = shl_mi355x_tensor_elems(output);
     d->a_scale = mat0->qinfo->scale, d->a_zp = mat0->qinfo->zero_point;
     d->b_scale = mat1->qinfo->scale, d->b_zp = mat1->qinfo->zero_point;
     d->out_scale = output->qinfo->scale, d->out_zp = output->qinfo->zero_point;
@@ -122,17 +83,10 @@ int shl_mi355x_matmul_exec(struct csinn_tensor *mat0, struct csinn_tensor *mat1,
     struct shl_mi355x_matmul_desc d;
     int rc = matmul_prepare(mat0, mat1, output, params, &d);
     if (rc != CSINN_TRUE) return rc;
-    struct shl_mi355x_ctx *ctx = shl_mi355x_ctx_of(params->base.sess);
-    const void *a_dev = shl_mi355x_stage_in(ctx, mat0, 0);
-    const void *b_dev = shl_mi355x_stage_in(ctx, mat1, 2);
-    void *out_dev = shl_mi355x_stage_out_begin(ctx, output, 1);
-    if (a_dev == NULL || b_dev == NULL || out_dev == NULL) return CSINN_FALSE;
-    int st = shl_mi355x_matmul(a_dev, b_dev, out_dev, &d, shl_mi355x_ctx_stream(ctx));
-    if (st != SHL_MI355X_OK) {
-        shl_debug_error("mi355x: matmul failed (%d): %s\n", st, shl_mi355x_last_error());
-        return CSINN_FALSE;
-    }
-    return shl_mi355x_stage_out_end(ctx, output, out_dev);
+    struct shl_mi355x_staged s;
+    if (shl_mi355x_staged_begin(&params->base, mat0, mat1, output, &s) != CSINN_TRUE) return CSINN_FALSE;
+    int st = shl_mi355x_matmul(s.in[0], s.in[1], s.out, &d, s.stream);
+    return shl_mi355x_staged_end("matmul", &s, output, st);
 }
 
 int shl_mi355x_matmul_perf(struct csinn_tensor *mat0, struct csinn_tensor *mat1, struct csinn_tensor *output,
@@ -141,7 +95,7 @@ int shl_mi355x_matmul_perf(struct csinn_tensor *mat0, struct csinn_tensor *mat1,
     struct shl_mi355x_matmul_desc d;
     int rc = matmul_prepare(mat0, mat1, output, params, &d);
     if (rc != CSINN_TRUE) return rc;
-    uintptr_t at = (uintptr_t)1 << 56;
+    uintptr_t at = SHL_MI355X_PERF_BASE;
     const void *a = (const void *)shl_mi355x_perf_address(mat0, &at);
     const void *b = (const void *)shl_mi355x_perf_address(mat1, &at);
     const void *o = (const void *)shl_mi355x_perf_address(output, &at);

@@ -41,99 +41,126 @@ int shl_mi355x_stage_in_many(struct shl_mi355x_ctx *ctx, struct csinn_tensor **t
 int shl_mi355x_stage_out_many_begin(struct shl_mi355x_ctx *ctx, struct csinn_tensor **t, int n, void **dev);
 int shl_mi355x_stage_out_many_end(struct shl_mi355x_ctx *ctx, struct csinn_tensor **t, int n, void *const *dev);
 
-/* perf callbacks of the windowed pools (pooling.c): single-input signature + the trailing info block */
-int shl_mi355x_maxpool2d_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params,
-                              struct csinn_perf_info *info);
-int shl_mi355x_avgpool2d_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params,
-                              struct csinn_perf_info *info);
+/* ------------------------------------------------------------------------ layer.c: what every layer callback shares
+ * (the order to call them in is at the top of that file) */
+int shl_mi355x_dtype_code(const struct csinn_tensor *t); /* SHL_MI355X_I8 / _F16, or -1 */
+/* one tensor: int8 or binary16, one quantisation record, binary16 with scale 1.  *dtype < 0: the layer's first tensor, which
+ * sets it; every later tensor must match.  check_io: an (input, output) pair */
+int shl_mi355x_check_tensor(const char *op, const char *what, struct csinn_tensor *t, int *dtype);
+int shl_mi355x_check_io(const char *op, struct csinn_tensor *input, struct csinn_tensor *output, int *dtype);
+/* rank min_rank .. MAX_DIM, extents of at least min_extent (0 or 1), at most max_elems elements (0: any number: the ops
+ * that only move data count in 64 bits).  SHL_MI355X_INT32_ELEMS: for descriptors that index with 32 bits */
+#define SHL_MI355X_INT32_ELEMS 0x7FFFFFFFll
+int shl_mi355x_check_dims(const char *op, const char *what, const struct csinn_tensor *t, int min_rank, int min_extent,
+                          int64_t max_elems);
+int64_t shl_mi355x_tensor_elems(const struct csinn_tensor *t); /* 0-d: 0 */
+/* fall_through: a layer refused at init runs on the reference's kernel next to the genuine library (elsewhere exec refuses
+ * it again: the front-ends drop init's status).  perf_address: the address a tensor's bytes will have on the device as far
+ * as its alignment goes -- a DMABUF tensor's own, else a made-up one with the staging path's alignment; `at` is a cursor
+ * that starts at SHL_MI355X_PERF_BASE and runs through the layer's tensors */
+void shl_mi355x_fall_through(struct csinn_params_base *base, int op, int dtype);
+#define SHL_MI355X_PERF_BASE ((uintptr_t)1 << 56)
+uintptr_t shl_mi355x_perf_address(struct csinn_tensor *t, uintptr_t *at);
+/* the staging sequence around a launch: begin stages in0 (slot 0), in1 (slot 2; may be NULL) and finds the output's address
+ * (slot 1); the launch is the caller's own call on s.in[], s.out, s.stream; end reports a failed launch ("<op> failed (status):
+ * message") or fetches the output.  Both return CSINN_TRUE or CSINN_FALSE */
+struct shl_mi355x_staged {
+    struct shl_mi355x_ctx *ctx;
+    void *stream;
+    const void *in[2];
+    void *out;
+};
+int shl_mi355x_staged_begin(struct csinn_params_base *base, struct csinn_tensor *in0, struct csinn_tensor *in1,
+                            struct csinn_tensor *out, struct shl_mi355x_staged *s);
+int shl_mi355x_staged_end(const char *op, struct shl_mi355x_staged *s, struct csinn_tensor *out, int status);
 
-/* ... and of concat: the array-of-inputs signature */
+/* ------------------------------------------------------------------------ the operator table (setup.c)
+ * how an exec callback is called.  The value is the number of inputs such a layer has in the graph (kernel and bias
+ * included); 0: as many as its params block says; < 0: see inputs_of (session.c) */
+enum call_shape {
+    CALL_NONE = -2,  /* no session row: a session with such a layer stays host-staged */
+    CALL_SPLIT = -1, /* exec(input, outputs[], params): one input, as many outputs as its params block says */
+    CALL_ARRAY = 0,  /* exec(inputs[], output, params) */
+    CALL_SISO = 1,   /* exec(input, output, params) */
+    CALL_DISO = 2,   /* exec(input0, input1, output, params) */
+    CALL_CONV = 3,   /* exec(input, output, kernel, bias, params) */
+};
+
+/* All the backend knows about an operator, one row per op id: what shl_target_init_mi355x registers for it, and what a
+ * session needs to run it on the device */
+struct shl_mi355x_op {
+    int type;
+    unsigned dtypes; /* SHL_MI355X_OP_I8 | SHL_MI355X_OP_F16 */
+    void *init, *exec, *est, *perf;
+    enum call_shape call;
+    int activations; /* the leading inputs that are activations; 0: all of them */
+    int first_const; /* of those, the ones from this index on may be constants instead: uploaded once, kept resident */
+};
+#define SHL_MI355X_OP_I8 1u
+#define SHL_MI355X_OP_F16 2u
+const struct shl_mi355x_op *shl_mi355x_op_row(int type); /* NULL: not an op of this backend */
+
+/* ------------------------------------------------------------------------ init and perf callbacks, for the table
+ * (the exec callbacks are public: shl_mi355x_backend.h).  An init of these files refuses nothing: a layer it would refuse
+ * falls through to the reference where there is one.  perf reports the kernel form the rules choose */
+#define SISO_INIT(name, PARAMS) \
+    int shl_mi355x_##name##_init(struct csinn_tensor *input, struct csinn_tensor *output, struct PARAMS *params);
+#define SISO_PERF(name, PARAMS)                                                                                  \
+    int shl_mi355x_##name##_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct PARAMS *params, \
+                                 struct csinn_perf_info *info);
+/* pooling.c, eltwise.c, resize.c */
+SISO_PERF(maxpool2d, csinn_pool_params)
+SISO_PERF(avgpool2d, csinn_pool_params)
+SISO_PERF(sigmoid, csinn_sigmoid_params)
+SISO_PERF(hard_sigmoid, csinn_sigmoid_params)
+SISO_PERF(silu, csinn_sigmoid_params)
+SISO_PERF(leaky_relu, csinn_relu_params)
+SISO_PERF(resize, csinn_resize_params)
+/* split.c */
+SISO_INIT(shuffle_channel, csinn_shuffle_channel_params)
+SISO_PERF(shuffle_channel, csinn_shuffle_channel_params)
+/* move.c */
+SISO_INIT(transpose, csinn_transpose_params)
+SISO_PERF(transpose, csinn_transpose_params)
+SISO_INIT(reshape, csinn_reshape_params)
+SISO_PERF(reshape, csinn_reshape_params)
+SISO_INIT(flatten, csinn_flatten_params)
+SISO_PERF(flatten, csinn_flatten_params)
+SISO_INIT(pad, csinn_pad_params)
+SISO_PERF(pad, csinn_pad_params)
+/* reduce.c */
+SISO_INIT(mean, csinn_reduce_params)
+SISO_PERF(mean, csinn_reduce_params)
+SISO_INIT(sum, csinn_reduce_params)
+SISO_PERF(sum, csinn_reduce_params)
+SISO_INIT(max, csinn_reduce_params)
+SISO_PERF(max, csinn_reduce_params)
+SISO_INIT(min, csinn_reduce_params)
+SISO_PERF(min, csinn_reduce_params)
+SISO_INIT(reduce_mean, csinn_reduce_params)
+SISO_PERF(reduce_mean, csinn_reduce_params)
+SISO_INIT(reduce_sum, csinn_reduce_params)
+SISO_PERF(reduce_sum, csinn_reduce_params)
+SISO_INIT(reduce_max, csinn_reduce_params)
+SISO_PERF(reduce_max, csinn_reduce_params)
+SISO_INIT(reduce_min, csinn_reduce_params)
+SISO_PERF(reduce_min, csinn_reduce_params)
+SISO_INIT(global_maxpool2d, csinn_pool_params)
+SISO_PERF(global_maxpool2d, csinn_pool_params)
+#undef SISO_INIT
+#undef SISO_PERF
+/* the other call shapes: mul (eltwise.c), matmul (matmul.c), concat (pooling.c), split (split.c) */
+int shl_mi355x_mul_perf(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
+                        struct csinn_diso_params *params, struct csinn_perf_info *info);
+int shl_mi355x_matmul_init(struct csinn_tensor *mat0, struct csinn_tensor *mat1, struct csinn_tensor *output,
+                           struct csinn_matmul_params *params);
+int shl_mi355x_matmul_perf(struct csinn_tensor *mat0, struct csinn_tensor *mat1, struct csinn_tensor *output,
+                           struct csinn_matmul_params *params, struct csinn_perf_info *info);
 int shl_mi355x_concat_perf(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params,
                            struct csinn_perf_info *info);
-
-/* split and shuffle_channel (split.c): init (a refused layer falls through to the reference where there is one) and perf */
 int shl_mi355x_split_init(struct csinn_tensor *input, struct csinn_tensor **output, struct csinn_split_params *params);
 int shl_mi355x_split_perf(struct csinn_tensor *input, struct csinn_tensor **output, struct csinn_split_params *params,
                           struct csinn_perf_info *info);
-int shl_mi355x_shuffle_channel_init(struct csinn_tensor *input, struct csinn_tensor *output,
-                                    struct csinn_shuffle_channel_params *params);
-int shl_mi355x_shuffle_channel_perf(struct csinn_tensor *input, struct csinn_tensor *output,
-                                    struct csinn_shuffle_channel_params *params, struct csinn_perf_info *info);
-
-/* shared by the callbacks of the ops that move data (split.c, move.c).  check_io: dtypes and records, what every device op
- * asks of an (input, output) pair.  fall_through: a layer refused at init runs on the reference's kernel next to the genuine
- * library (elsewhere exec refuses it again: the front-ends drop init's status).  perf_address: the address a tensor's bytes
- * will have on the device as far as its alignment goes -- a DMABUF tensor's own, else a made-up one with the staging path's
- * alignment */
-int shl_mi355x_check_io(const char *op, struct csinn_tensor *input, struct csinn_tensor *output, int *dtype);
-void shl_mi355x_fall_through(struct csinn_params_base *base, int op, int dtype);
-uintptr_t shl_mi355x_perf_address(struct csinn_tensor *t, uintptr_t *at);
-
-/* transpose, reshape, flatten and pad (move.c): init (a refused layer falls through to the reference where there is one)
- * and perf */
-int shl_mi355x_transpose_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_transpose_params *params);
-int shl_mi355x_transpose_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_transpose_params *params,
-        struct csinn_perf_info *info);
-int shl_mi355x_reshape_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reshape_params *params);
-int shl_mi355x_reshape_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reshape_params *params,
-        struct csinn_perf_info *info);
-int shl_mi355x_flatten_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_flatten_params *params);
-int shl_mi355x_flatten_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_flatten_params *params,
-        struct csinn_perf_info *info);
-int shl_mi355x_pad_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pad_params *params);
-int shl_mi355x_pad_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pad_params *params,
-        struct csinn_perf_info *info);
-
-/* the reductions (reduce.c): init (a refused layer falls through to the reference where there is one) and perf */
-int shl_mi355x_mean_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
-int shl_mi355x_mean_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params,
-        struct csinn_perf_info *info);
-int shl_mi355x_sum_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
-int shl_mi355x_sum_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params,
-        struct csinn_perf_info *info);
-int shl_mi355x_max_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
-int shl_mi355x_max_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params,
-        struct csinn_perf_info *info);
-int shl_mi355x_min_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
-int shl_mi355x_min_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params,
-        struct csinn_perf_info *info);
-int shl_mi355x_reduce_mean_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
-int shl_mi355x_reduce_mean_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params,
-        struct csinn_perf_info *info);
-int shl_mi355x_reduce_sum_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
-int shl_mi355x_reduce_sum_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params,
-        struct csinn_perf_info *info);
-int shl_mi355x_reduce_max_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
-int shl_mi355x_reduce_max_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params,
-        struct csinn_perf_info *info);
-int shl_mi355x_reduce_min_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params);
-int shl_mi355x_reduce_min_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reduce_params *params,
-        struct csinn_perf_info *info);
-int shl_mi355x_global_maxpool2d_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params);
-int shl_mi355x_global_maxpool2d_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params,
-        struct csinn_perf_info *info);
-
-/* matmul (matmul.c): init (a refused layer falls through to the reference where there is one) and perf */
-int shl_mi355x_matmul_init(struct csinn_tensor *mat0, struct csinn_tensor *mat1, struct csinn_tensor *output,
-        struct csinn_matmul_params *params);
-int shl_mi355x_matmul_perf(struct csinn_tensor *mat0, struct csinn_tensor *mat1, struct csinn_tensor *output,
-        struct csinn_matmul_params *params, struct csinn_perf_info *info);
-
-/* ... and of the elementwise layers (eltwise.c): the kernel form the rules choose */
-int shl_mi355x_sigmoid_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params,
-                            struct csinn_perf_info *info);
-int shl_mi355x_hard_sigmoid_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params,
-                                 struct csinn_perf_info *info);
-int shl_mi355x_silu_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_sigmoid_params *params,
-                         struct csinn_perf_info *info);
-int shl_mi355x_leaky_relu_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_relu_params *params,
-                               struct csinn_perf_info *info);
-int shl_mi355x_mul_perf(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
-                        struct csinn_diso_params *params, struct csinn_perf_info *info);
-
-/* ... and of resize (resize.c) */
-int shl_mi355x_resize_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_resize_params *params,
-                           struct csinn_perf_info *info);
 
 float shl_mi355x_half_to_float(uint16_t h);
 

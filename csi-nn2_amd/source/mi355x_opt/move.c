@@ -13,28 +13,14 @@
 
 #include "mi355x_internal.h"
 
-/* check_io of split.c, and what tensors of any rank add to it */
+/* dtypes and records of the pair, and what tensors of any rank add: dims that fit (a tensor may hold 2^31 elements or more:
+ * the kernels count in 64 bits) */
 static int check_io(const char *op, struct csinn_tensor *input, struct csinn_tensor *output, int *dtype)
 {
-    if (input == NULL || output == NULL) return CSINN_FALSE;
     int rc = shl_mi355x_check_io(op, input, output, dtype);
-    if (rc != CSINN_TRUE) return rc;
-    if (input->dim_count < 0 || input->dim_count > MAX_DIM || output->dim_count < 0 || output->dim_count > MAX_DIM) {
-        shl_debug_error("mi355x: %s: a tensor of more than %d dims\n", op, MAX_DIM);
-        return CSINN_FALSE;
-    }
-    for (int k = 0; k < input->dim_count; k++)
-        if (input->dim[k] < 0) return CSINN_FALSE;
-    for (int k = 0; k < output->dim_count; k++)
-        if (output->dim[k] < 0) return CSINN_FALSE;
-    return CSINN_TRUE;
-}
-
-static int64_t elems_of(const struct csinn_tensor *t)
-{
-    int64_t n = 1;
-    for (int k = 0; k < t->dim_count; k++) n *= t->dim[k];
-    return t->dim_count == 0 ? 0 : n;
+    if (rc == CSINN_TRUE) rc = shl_mi355x_check_dims(op, "input", input, 0, 0, 0);
+    if (rc == CSINN_TRUE) rc = shl_mi355x_check_dims(op, "output", output, 0, 0, 0);
+    return rc;
 }
 
 /* what the three ops have in common once their descriptor exists: stage, run, fetch */
@@ -53,26 +39,19 @@ static int move_run(const char *op, struct csinn_tensor *input, struct csinn_ten
                     const struct move_call *c)
 {
     if (csinn_tensor_size(output) == 0) return CSINN_TRUE;
-    struct shl_mi355x_ctx *ctx = shl_mi355x_ctx_of(base->sess);
-    const void *in_dev = shl_mi355x_stage_in(ctx, input, 0);
-    void *out_dev = shl_mi355x_stage_out_begin(ctx, output, 1);
-    if (in_dev == NULL || out_dev == NULL) return CSINN_FALSE;
-    void *stream = shl_mi355x_ctx_stream(ctx);
+    struct shl_mi355x_staged s;
+    if (shl_mi355x_staged_begin(base, input, NULL, output, &s) != CSINN_TRUE) return CSINN_FALSE;
     int st;
-    if (c->kind == MOVE_TRANSPOSE) st = shl_mi355x_transpose(in_dev, out_dev, &c->d.transpose, stream);
-    else if (c->kind == MOVE_PAD) st = shl_mi355x_pad(in_dev, out_dev, &c->d.pad, stream);
-    else st = shl_mi355x_move(in_dev, out_dev, c->elems, &c->d.flat, stream);
-    if (st != SHL_MI355X_OK) {
-        shl_debug_error("mi355x: %s failed (%d): %s\n", op, st, shl_mi355x_last_error());
-        return CSINN_FALSE;
-    }
-    return shl_mi355x_stage_out_end(ctx, output, out_dev);
+    if (c->kind == MOVE_TRANSPOSE) st = shl_mi355x_transpose(s.in[0], s.out, &c->d.transpose, s.stream);
+    else if (c->kind == MOVE_PAD) st = shl_mi355x_pad(s.in[0], s.out, &c->d.pad, s.stream);
+    else st = shl_mi355x_move(s.in[0], s.out, c->elems, &c->d.flat, s.stream);
+    return shl_mi355x_staged_end(op, &s, output, st);
 }
 
 static int move_perf(struct csinn_tensor *input, struct csinn_tensor *output, const struct move_call *c,
                      struct csinn_perf_info *info)
 {
-    uintptr_t at = (uintptr_t)1 << 56;
+    uintptr_t at = SHL_MI355X_PERF_BASE;
     const void *in = (const void *)shl_mi355x_perf_address(input, &at);
     const void *out = (const void *)shl_mi355x_perf_address(output, &at);
     if (c->kind == MOVE_TRANSPOSE) info->kernel_name = (char *)shl_mi355x_transpose_kernel_name(in, out, &c->d.transpose);
@@ -84,11 +63,11 @@ static int move_perf(struct csinn_tensor *input, struct csinn_tensor *output, co
 /* ------------------------------------------------------------------------ transpose */
 /* the descriptor of the layer, or why there is none; looks at dims, dtypes and records only (never at `data`: in graph
  * mode that is a node while the graph is built) */
-static int transpose_prepare(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_transpose_params *params,
-                             struct move_call *c)
+static int transpose_prepare(const char *op, struct csinn_tensor *input, struct csinn_tensor *output,
+                             struct csinn_transpose_params *params, struct move_call *c)
 {
     int dtype;
-    int rc = check_io("transpose", input, output, &dtype);
+    int rc = check_io(op, input, output, &dtype);
     if (rc != CSINN_TRUE) return rc;
     const int rank = input->dim_count;
     if (rank < 1 || params->permute_num != rank || output->dim_count != rank || params->permute == NULL) {
@@ -120,109 +99,37 @@ static int transpose_prepare(struct csinn_tensor *input, struct csinn_tensor *ou
     return CSINN_TRUE;
 }
 
-int shl_mi355x_transpose_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_transpose_params *params)
-{
-    struct move_call c;
-    if (transpose_prepare(input, output, params, &c) != CSINN_TRUE)
-        shl_mi355x_fall_through(&params->base, CSINN_OP_TRANSPOSE, input ? input->dtype : -1);
-    return CSINN_TRUE;
-}
-
-int shl_mi355x_transpose_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_transpose_params *params)
-{
-    struct move_call c;
-    int rc = transpose_prepare(input, output, params, &c);
-    if (rc != CSINN_TRUE) return rc;
-    return move_run("transpose", input, output, &params->base, &c);
-}
-
-int shl_mi355x_transpose_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_transpose_params *params,
-                              struct csinn_perf_info *info)
-{
-    struct move_call c;
-    int rc = transpose_prepare(input, output, params, &c);
-    if (rc != CSINN_TRUE) return rc;
-    return move_perf(input, output, &c, info);
-}
-
 /* ------------------------------------------------------------------------ reshape, flatten */
 /* a flat requantised copy of the input's elements: the output must hold as many (the reference copies
  * csinn_tensor_byte_size(input) bytes whatever the output's size) */
-static int flat_prepare(const char *op, struct csinn_tensor *input, struct csinn_tensor *output, struct move_call *c)
+static int flat_prepare(const char *op, struct csinn_tensor *input, struct csinn_tensor *output, const void *params,
+                        struct move_call *c)
 {
+    (void)params; /* reshape's and flatten's: the output tensor's dims say it all */
     int dtype;
     int rc = check_io(op, input, output, &dtype);
     if (rc != CSINN_TRUE) return rc;
-    if (input->dim_count < 1 || output->dim_count < 1 || elems_of(input) != elems_of(output)) {
-        shl_debug_error("mi355x: %s: the input holds %lld elements, the output %lld\n", op, (long long)elems_of(input),
-                        (long long)elems_of(output));
+    const int64_t elems = shl_mi355x_tensor_elems(input);
+    if (input->dim_count < 1 || output->dim_count < 1 || elems != shl_mi355x_tensor_elems(output)) {
+        shl_debug_error("mi355x: %s: the input holds %lld elements, the output %lld\n", op, (long long)elems,
+                        (long long)shl_mi355x_tensor_elems(output));
         return CSINN_FALSE;
     }
     memset(c, 0, sizeof(*c));
     c->kind = MOVE_FLAT;
-    c->elems = elems_of(input);
+    c->elems = elems;
     c->d.flat.dtype = dtype;
     c->d.flat.in_scale = input->qinfo->scale, c->d.flat.in_zp = input->qinfo->zero_point;
     c->d.flat.out_scale = output->qinfo->scale, c->d.flat.out_zp = output->qinfo->zero_point;
     return CSINN_TRUE;
 }
 
-int shl_mi355x_reshape_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reshape_params *params)
-{
-    struct move_call c;
-    if (flat_prepare("reshape", input, output, &c) != CSINN_TRUE)
-        shl_mi355x_fall_through(&params->base, CSINN_OP_RESHAPE, input ? input->dtype : -1);
-    return CSINN_TRUE;
-}
-
-int shl_mi355x_reshape_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reshape_params *params)
-{
-    struct move_call c;
-    int rc = flat_prepare("reshape", input, output, &c);
-    if (rc != CSINN_TRUE) return rc;
-    return move_run("reshape", input, output, &params->base, &c);
-}
-
-int shl_mi355x_reshape_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_reshape_params *params,
-                            struct csinn_perf_info *info)
-{
-    struct move_call c;
-    int rc = flat_prepare("reshape", input, output, &c);
-    if (rc != CSINN_TRUE) return rc;
-    return move_perf(input, output, &c, info);
-}
-
-int shl_mi355x_flatten_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_flatten_params *params)
-{
-    struct move_call c;
-    if (flat_prepare("flatten", input, output, &c) != CSINN_TRUE)
-        shl_mi355x_fall_through(&params->base, CSINN_OP_FLATTEN, input ? input->dtype : -1);
-    return CSINN_TRUE;
-}
-
-int shl_mi355x_flatten_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_flatten_params *params)
-{
-    struct move_call c;
-    int rc = flat_prepare("flatten", input, output, &c);
-    if (rc != CSINN_TRUE) return rc;
-    return move_run("flatten", input, output, &params->base, &c);
-}
-
-int shl_mi355x_flatten_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_flatten_params *params,
-                            struct csinn_perf_info *info)
-{
-    struct move_call c;
-    int rc = flat_prepare("flatten", input, output, &c);
-    if (rc != CSINN_TRUE) return rc;
-    return move_perf(input, output, &c, info);
-}
-
 /* ------------------------------------------------------------------------ pad */
-static int pad_prepare(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pad_params *params,
+static int pad_prepare(const char *op, struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pad_params *params,
                        struct move_call *c)
 {
     int dtype;
-    int rc = check_io("pad", input, output, &dtype);
+    int rc = check_io(op, input, output, &dtype);
     if (rc != CSINN_TRUE) return rc;
     if (params->base.layout != CSINN_LAYOUT_NCHW && params->base.layout != CSINN_LAYOUT_NHWC) return CSINN_UNSUPPORT_LAYOUT;
     if (params->pad_mode != CSINN_PAD_CONSTANT) {
@@ -258,26 +165,33 @@ static int pad_prepare(struct csinn_tensor *input, struct csinn_tensor *output, 
     return CSINN_TRUE;
 }
 
-int shl_mi355x_pad_init(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pad_params *params)
-{
-    struct move_call c;
-    if (pad_prepare(input, output, params, &c) != CSINN_TRUE) shl_mi355x_fall_through(&params->base, CSINN_OP_PAD, input ? input->dtype : -1);
-    return CSINN_TRUE;
-}
+/* init (a refused layer falls through to the reference where there is one), exec and perf around a prepare function */
+#define MOVE_OP(name, OP, PARAMS, prepare)                                                                                     \
+    int shl_mi355x_##name##_init(struct csinn_tensor *input, struct csinn_tensor *output, struct PARAMS *params)               \
+    {                                                                                                                          \
+        struct move_call c;                                                                                                    \
+        if (prepare(#name, input, output, params, &c) != CSINN_TRUE)                                                           \
+            shl_mi355x_fall_through(&params->base, OP, input ? input->dtype : -1);                                             \
+        return CSINN_TRUE;                                                                                                     \
+    }                                                                                                                          \
+    int shl_mi355x_##name##_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct PARAMS *params)               \
+    {                                                                                                                          \
+        struct move_call c;                                                                                                    \
+        int rc = prepare(#name, input, output, params, &c);                                                                    \
+        if (rc != CSINN_TRUE) return rc;                                                                                       \
+        return move_run(#name, input, output, &params->base, &c);                                                              \
+    }                                                                                                                          \
+    int shl_mi355x_##name##_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct PARAMS *params,               \
+                                 struct csinn_perf_info *info)                                                                 \
+    {                                                                                                                          \
+        struct move_call c;                                                                                                    \
+        int rc = prepare(#name, input, output, params, &c);                                                                    \
+        if (rc != CSINN_TRUE) return rc;                                                                                       \
+        return move_perf(input, output, &c, info);                                                                             \
+    }
 
-int shl_mi355x_pad_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pad_params *params)
-{
-    struct move_call c;
-    int rc = pad_prepare(input, output, params, &c);
-    if (rc != CSINN_TRUE) return rc;
-    return move_run("pad", input, output, &params->base, &c);
-}
+MOVE_OP(transpose, CSINN_OP_TRANSPOSE, csinn_transpose_params, transpose_prepare)
+MOVE_OP(reshape, CSINN_OP_RESHAPE, csinn_reshape_params, flat_prepare)
+MOVE_OP(flatten, CSINN_OP_FLATTEN, csinn_flatten_params, flat_prepare)
+MOVE_OP(pad, CSINN_OP_PAD, csinn_pad_params, pad_prepare)
 
-int shl_mi355x_pad_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pad_params *params,
-                        struct csinn_perf_info *info)
-{
-    struct move_call c;
-    int rc = pad_prepare(input, output, params, &c);
-    if (rc != CSINN_TRUE) return rc;
-    return move_perf(input, output, &c, info);
-}

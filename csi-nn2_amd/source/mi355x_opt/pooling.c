@@ -13,44 +13,11 @@
 
 #include "mi355x_internal.h"
 
-static int dtype_code(const struct csinn_tensor *t)
-{
-    if (t->dtype == CSINN_DTYPE_INT8) return SHL_MI355X_I8;
-    if (t->dtype == CSINN_DTYPE_FLOAT16) return SHL_MI355X_F16;
-    return -1;
-}
-
-static int check_io(const char *op, struct csinn_tensor *input, struct csinn_tensor *output, int *dtype)
-{
-    *dtype = dtype_code(input);
-    if (*dtype < 0 || dtype_code(output) != *dtype) {
-        shl_debug_error("mi355x: %s dtypes in=%d out=%d unsupported\n", op, input->dtype, output->dtype);
-        return CSINN_UNSUPPORT_DTYPE;
-    }
-    if (input->qinfo == NULL || output->qinfo == NULL) {
-        shl_debug_error("mi355x: %s needs quantisation records\n", op);
-        return CSINN_FALSE;
-    }
-    if (input->quant_channel > 1 || output->quant_channel > 1) {
-        /* the reference's converters honour per-channel activation records
-         * (source/nn2/utils.c:1504-1642); the device path carries one record per activation tensor */
-        shl_debug_error("mi355x: %s: per-channel quantised activations are not supported\n", op);
-        return CSINN_UNSUPPORT_DTYPE;
-    }
-    if (*dtype == SHL_MI355X_F16 && (input->qinfo->scale != 1.0f || output->qinfo->scale != 1.0f)) {
-        /* f16_to_float / float_to_f16 scale by qinfo->scale when it differs from 1
-         * (source/nn2/utils.c:1175-1205); not carried to the device */
-        shl_debug_error("mi355x: %s fp16 with qinfo scale != 1 is not supported\n", op);
-        return CSINN_FALSE;
-    }
-    return CSINN_TRUE;
-}
-
 int shl_mi355x_global_avgpool2d_exec(struct csinn_tensor *input, struct csinn_tensor *output,
                                      struct csinn_pool_params *params)
 {
     int dtype;
-    int rc = check_io("global_avgpool2d", input, output, &dtype);
+    int rc = shl_mi355x_check_io("global_avgpool2d", input, output, &dtype);
     if (rc != CSINN_TRUE) return rc;
     if (input->dim_count != 4) {
         shl_debug_error("mi355x: global_avgpool2d expects a 4-d tensor\n");
@@ -68,19 +35,11 @@ int shl_mi355x_global_avgpool2d_exec(struct csinn_tensor *input, struct csinn_te
     } else {
         return CSINN_UNSUPPORT_LAYOUT;
     }
-    struct shl_mi355x_ctx *ctx = shl_mi355x_ctx_of(params->base.sess);
-    const void *in_dev = shl_mi355x_stage_in(ctx, input, 0);
-    void *out_dev = shl_mi355x_stage_out_begin(ctx, output, 1);
-    if (in_dev == NULL || out_dev == NULL) return CSINN_FALSE;
-    int st = shl_mi355x_global_avgpool2d(in_dev, out_dev, dtype, layout, input->dim[0], c, hw,
-                                         input->qinfo->scale, input->qinfo->zero_point,
-                                         output->qinfo->scale, output->qinfo->zero_point,
-                                         shl_mi355x_ctx_stream(ctx));
-    if (st != SHL_MI355X_OK) {
-        shl_debug_error("mi355x: global_avgpool2d failed (%d): %s\n", st, shl_mi355x_last_error());
-        return CSINN_FALSE;
-    }
-    return shl_mi355x_stage_out_end(ctx, output, out_dev);
+    struct shl_mi355x_staged s;
+    if (shl_mi355x_staged_begin(&params->base, input, NULL, output, &s) != CSINN_TRUE) return CSINN_FALSE;
+    int st = shl_mi355x_global_avgpool2d(s.in[0], s.out, dtype, layout, input->dim[0], c, hw, input->qinfo->scale,
+                                         input->qinfo->zero_point, output->qinfo->scale, output->qinfo->zero_point, s.stream);
+    return shl_mi355x_staged_end("global_avgpool2d", &s, output, st);
 }
 
 /* maxpool2d / avgpool2d (source/reference/maxpool.c:113-124, averagepool.c:127-138): the window geometry comes
@@ -89,7 +48,7 @@ static int pool2d_desc(const char *op, int kind, struct csinn_tensor *input, str
                        struct csinn_pool_params *params, struct shl_mi355x_pool_desc *desc)
 {
     int dtype;
-    int rc = check_io(op, input, output, &dtype);
+    int rc = shl_mi355x_check_io(op, input, output, &dtype);
     if (rc != CSINN_TRUE) return rc;
     if (input->dim_count != 4 || output->dim_count != 4) {
         shl_debug_error("mi355x: %s expects a 4-d tensor\n", op);
@@ -132,16 +91,10 @@ static int pool2d_exec(const char *op, int kind, struct csinn_tensor *input, str
     struct shl_mi355x_pool_desc d;
     int rc = pool2d_desc(op, kind, input, output, params, &d);
     if (rc != CSINN_TRUE) return rc;
-    struct shl_mi355x_ctx *ctx = shl_mi355x_ctx_of(params->base.sess);
-    const void *in_dev = shl_mi355x_stage_in(ctx, input, 0);
-    void *out_dev = shl_mi355x_stage_out_begin(ctx, output, 1);
-    if (in_dev == NULL || out_dev == NULL) return CSINN_FALSE;
-    int st = shl_mi355x_pool2d(in_dev, out_dev, &d, shl_mi355x_ctx_stream(ctx));
-    if (st != SHL_MI355X_OK) {
-        shl_debug_error("mi355x: %s failed (%d): %s\n", op, st, shl_mi355x_last_error());
-        return CSINN_FALSE;
-    }
-    return shl_mi355x_stage_out_end(ctx, output, out_dev);
+    struct shl_mi355x_staged s;
+    if (shl_mi355x_staged_begin(&params->base, input, NULL, output, &s) != CSINN_TRUE) return CSINN_FALSE;
+    int st = shl_mi355x_pool2d(s.in[0], s.out, &d, s.stream);
+    return shl_mi355x_staged_end(op, &s, output, st);
 }
 
 int shl_mi355x_maxpool2d_exec(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_pool_params *params)
@@ -181,7 +134,7 @@ int shl_mi355x_softmax_exec(struct csinn_tensor *input, struct csinn_tensor *out
                             struct csinn_softmax_params *params)
 {
     int dtype;
-    int rc = check_io("softmax", input, output, &dtype);
+    int rc = shl_mi355x_check_io("softmax", input, output, &dtype);
     if (rc != CSINN_TRUE) return rc;
     const int axis = params->axis;
     if (axis < 0 || axis >= input->dim_count) {
@@ -191,18 +144,11 @@ int shl_mi355x_softmax_exec(struct csinn_tensor *input, struct csinn_tensor *out
     int64_t outer = 1, inner = 1;
     for (int i = 0; i < axis; i++) outer *= input->dim[i];
     for (int i = axis + 1; i < input->dim_count; i++) inner *= input->dim[i];
-    struct shl_mi355x_ctx *ctx = shl_mi355x_ctx_of(params->base.sess);
-    const void *in_dev = shl_mi355x_stage_in(ctx, input, 0);
-    void *out_dev = shl_mi355x_stage_out_begin(ctx, output, 1);
-    if (in_dev == NULL || out_dev == NULL) return CSINN_FALSE;
-    int st = shl_mi355x_softmax(in_dev, out_dev, dtype, outer, input->dim[axis], inner, input->qinfo->scale,
-                                input->qinfo->zero_point, output->qinfo->scale, output->qinfo->zero_point,
-                                shl_mi355x_ctx_stream(ctx));
-    if (st != SHL_MI355X_OK) {
-        shl_debug_error("mi355x: softmax failed (%d): %s\n", st, shl_mi355x_last_error());
-        return CSINN_FALSE;
-    }
-    return shl_mi355x_stage_out_end(ctx, output, out_dev);
+    struct shl_mi355x_staged s;
+    if (shl_mi355x_staged_begin(&params->base, input, NULL, output, &s) != CSINN_TRUE) return CSINN_FALSE;
+    int st = shl_mi355x_softmax(s.in[0], s.out, dtype, outer, input->dim[axis], inner, input->qinfo->scale,
+                                input->qinfo->zero_point, output->qinfo->scale, output->qinfo->zero_point, s.stream);
+    return shl_mi355x_staged_end("softmax", &s, output, st);
 }
 
 /* residual add, two same-shape inputs (source/reference/add.c:21-41); shapes that would need the
@@ -211,9 +157,10 @@ int shl_mi355x_add_exec(struct csinn_tensor *input0, struct csinn_tensor *input1
                         struct csinn_diso_params *params)
 {
     int dtype;
-    int rc = check_io("add", input0, output, &dtype);
+    int rc = shl_mi355x_check_io("add", input0, output, &dtype);
     if (rc != CSINN_TRUE) return rc;
-    if (dtype_code(input1) != dtype || input1->qinfo == NULL || input1->quant_channel > 1 ||
+    /* (every defect of the second input is CSINN_UNSUPPORT_DTYPE, unlike shl_mi355x_check_tensor's statuses) */
+    if (shl_mi355x_dtype_code(input1) != dtype || input1->qinfo == NULL || input1->quant_channel > 1 ||
         (dtype == SHL_MI355X_F16 && input1->qinfo->scale != 1.0f)) {
         shl_debug_error("mi355x: add: second input dtype / quantisation unsupported\n");
         return CSINN_UNSUPPORT_DTYPE;
@@ -227,19 +174,12 @@ int shl_mi355x_add_exec(struct csinn_tensor *input0, struct csinn_tensor *input1
             shl_debug_error("mi355x: add: broadcasting is not supported\n");
             return CSINN_FALSE;
         }
-    struct shl_mi355x_ctx *ctx = shl_mi355x_ctx_of(params->base.sess);
-    const void *a_dev = shl_mi355x_stage_in(ctx, input0, 0);
-    const void *b_dev = shl_mi355x_stage_in(ctx, input1, 2);
-    void *out_dev = shl_mi355x_stage_out_begin(ctx, output, 1);
-    if (a_dev == NULL || b_dev == NULL || out_dev == NULL) return CSINN_FALSE;
-    int st = shl_mi355x_add(a_dev, b_dev, out_dev, (size_t)csinn_tensor_size(output), dtype, input0->qinfo->scale,
+    struct shl_mi355x_staged s;
+    if (shl_mi355x_staged_begin(&params->base, input0, input1, output, &s) != CSINN_TRUE) return CSINN_FALSE;
+    int st = shl_mi355x_add(s.in[0], s.in[1], s.out, (size_t)csinn_tensor_size(output), dtype, input0->qinfo->scale,
                             input0->qinfo->zero_point, input1->qinfo->scale, input1->qinfo->zero_point,
-                            output->qinfo->scale, output->qinfo->zero_point, shl_mi355x_ctx_stream(ctx));
-    if (st != SHL_MI355X_OK) {
-        shl_debug_error("mi355x: add failed (%d): %s\n", st, shl_mi355x_last_error());
-        return CSINN_FALSE;
-    }
-    return shl_mi355x_stage_out_end(ctx, output, out_dev);
+                            output->qinfo->scale, output->qinfo->zero_point, s.stream);
+    return shl_mi355x_staged_end("add", &s, output, st);
 }
 
 /* concat (source/reference/concat.c:21-76): a variable number of inputs.  The reference trusts the shapes; here a
@@ -286,7 +226,7 @@ static int concat_prepare(struct csinn_tensor **input, struct csinn_tensor *outp
             shl_debug_error("mi355x: concat: input %d is NULL\n", i);
             return CSINN_FALSE;
         }
-        int rc = check_io("concat", input[i], output, &dtype);
+        int rc = shl_mi355x_check_io("concat", input[i], output, &dtype);
         if (rc != CSINN_TRUE) return rc;
         if (input[i]->dim_count != dims) {
             shl_debug_error("mi355x: concat: input %d is %d-d, the output %d-d\n", i, input[i]->dim_count, dims);
@@ -360,18 +300,9 @@ int shl_mi355x_concat_perf(struct csinn_tensor **input, struct csinn_tensor *out
     struct concat_call c;
     int rc = concat_prepare(input, output, params, &c);
     if (rc != CSINN_TRUE) return rc;
-    const int es = c.desc.dtype == SHL_MI355X_F16 ? 2 : 1;
-    uintptr_t at = (uintptr_t)1 << 56;
-    for (int i = 0; i < c.desc.n_inputs; i++) {
-        if (input[i]->mtype == CSINN_MEM_TYPE_DMABUF && input[i]->data) {
-            c.dev[i] = input[i]->data;
-            continue;
-        }
-        const uintptr_t bytes = (uintptr_t)(c.len[i] * c.desc.outer * es);
-        c.dev[i] = (const void *)at;
-        at += (bytes + SHL_MI355X_STAGE_ALIGN - 1) / SHL_MI355X_STAGE_ALIGN * SHL_MI355X_STAGE_ALIGN + SHL_MI355X_STAGE_ALIGN;
-    }
-    const void *out = output->mtype == CSINN_MEM_TYPE_DMABUF && output->data ? output->data : (const void *)((uintptr_t)1 << 57);
+    uintptr_t at = SHL_MI355X_PERF_BASE;
+    for (int i = 0; i < c.desc.n_inputs; i++) c.dev[i] = (const void *)shl_mi355x_perf_address(input[i], &at);
+    const void *out = (const void *)shl_mi355x_perf_address(output, &at);
     info->kernel_name = (char *)shl_mi355x_concat_kernel_name(c.dev, c.len, c.scale, c.zp, out, &c.desc);
     concat_release(&c);
     return CSINN_TRUE;

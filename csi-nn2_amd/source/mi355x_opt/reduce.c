@@ -15,37 +15,16 @@
 
 #include "mi355x_internal.h"
 
-static int64_t elems_of(const struct csinn_tensor *t)
-{
-    int64_t n = 1;
-    for (int k = 0; k < t->dim_count; k++) n *= t->dim[k];
-    return t->dim_count == 0 ? 0 : n;
-}
-
 /* what every family asks of the pair: dtypes, records, dims that fit; *d gets the dtype, the records and in_elems */
 static int reduce_io(const char *op, struct csinn_tensor *input, struct csinn_tensor *output, struct shl_mi355x_reduce_desc *d)
 {
-    if (input == NULL || output == NULL) return CSINN_FALSE;
     int dtype;
     int rc = shl_mi355x_check_io(op, input, output, &dtype);
+    if (rc == CSINN_TRUE) rc = shl_mi355x_check_dims(op, "input", input, 1, 1, SHL_MI355X_INT32_ELEMS);
+    if (rc == CSINN_TRUE) rc = shl_mi355x_check_dims(op, "output", output, 0, 0, 0);
     if (rc != CSINN_TRUE) return rc;
-    if (input->dim_count < 1 || input->dim_count > MAX_DIM || output->dim_count < 0 || output->dim_count > MAX_DIM) {
-        shl_debug_error("mi355x: %s: a tensor of %d / %d dims\n", op, input->dim_count, output->dim_count);
-        return CSINN_FALSE;
-    }
-    int64_t n = 1;
-    for (int k = 0; k < input->dim_count; k++) {
-        if (input->dim[k] < 1) return CSINN_FALSE;
-        n *= input->dim[k];
-        if (n > 0x7FFFFFFFll) {
-            shl_debug_error("mi355x: %s: the input has 2^31 or more elements\n", op);
-            return CSINN_FALSE;
-        }
-    }
-    for (int k = 0; k < output->dim_count; k++)
-        if (output->dim[k] < 0) return CSINN_FALSE;
     memset(d, 0, sizeof(*d));
-    d->dtype = dtype, d->in_elems = n;
+    d->dtype = dtype, d->in_elems = shl_mi355x_tensor_elems(input);
     d->in_scale = input->qinfo->scale, d->in_zp = input->qinfo->zero_point;
     d->out_scale = output->qinfo->scale, d->out_zp = output->qinfo->zero_point;
     return CSINN_TRUE;
@@ -57,9 +36,9 @@ static int reduce_settle(const char *op, struct csinn_tensor *output, const stru
 {
     int64_t outs = 1;
     for (int k = 0; k < d->n_out; k++) outs *= d->out_extent[k];
-    if (outs != elems_of(output)) {
+    if (outs != shl_mi355x_tensor_elems(output)) {
         shl_debug_error("mi355x: %s: the layer gives %lld outputs, the output tensor holds %lld\n", op, (long long)outs,
-                        (long long)elems_of(output));
+                        (long long)shl_mi355x_tensor_elems(output));
         return CSINN_FALSE;
     }
     const void *in = (const void *)((uintptr_t)1 << 56), *out = (const void *)((uintptr_t)1 << 57);
@@ -156,22 +135,16 @@ static int reduce_run(const char *op, struct csinn_tensor *input, struct csinn_t
                       const struct shl_mi355x_reduce_desc *d)
 {
     if (csinn_tensor_size(output) == 0) return CSINN_TRUE;
-    struct shl_mi355x_ctx *ctx = shl_mi355x_ctx_of(base->sess);
-    const void *in_dev = shl_mi355x_stage_in(ctx, input, 0);
-    void *out_dev = shl_mi355x_stage_out_begin(ctx, output, 1);
-    if (in_dev == NULL || out_dev == NULL) return CSINN_FALSE;
-    int st = shl_mi355x_reduce(in_dev, out_dev, d, shl_mi355x_ctx_stream(ctx));
-    if (st != SHL_MI355X_OK) {
-        shl_debug_error("mi355x: %s failed (%d): %s\n", op, st, shl_mi355x_last_error());
-        return CSINN_FALSE;
-    }
-    return shl_mi355x_stage_out_end(ctx, output, out_dev);
+    struct shl_mi355x_staged s;
+    if (shl_mi355x_staged_begin(base, input, NULL, output, &s) != CSINN_TRUE) return CSINN_FALSE;
+    int st = shl_mi355x_reduce(s.in[0], s.out, d, s.stream);
+    return shl_mi355x_staged_end(op, &s, output, st);
 }
 
 static int reduce_perf(struct csinn_tensor *input, struct csinn_tensor *output, const struct shl_mi355x_reduce_desc *d,
                        struct csinn_perf_info *info)
 {
-    uintptr_t at = (uintptr_t)1 << 56;
+    uintptr_t at = SHL_MI355X_PERF_BASE;
     const void *in = (const void *)shl_mi355x_perf_address(input, &at);
     const void *out = (const void *)shl_mi355x_perf_address(output, &at);
     info->kernel_name = (char *)shl_mi355x_reduce_kernel_name(in, out, d);

@@ -38,25 +38,8 @@ static int resize_desc(struct csinn_tensor *input, struct csinn_tensor *output, 
                        struct shl_mi355x_resize_desc *desc)
 {
     int dtype;
-    if (input->dtype == CSINN_DTYPE_INT8) dtype = SHL_MI355X_I8;
-    else if (input->dtype == CSINN_DTYPE_FLOAT16) dtype = SHL_MI355X_F16;
-    else dtype = -1;
-    if (dtype < 0 || output->dtype != input->dtype) {
-        shl_debug_error("mi355x: resize dtypes in=%d out=%d unsupported\n", input->dtype, output->dtype);
-        return CSINN_UNSUPPORT_DTYPE;
-    }
-    if (input->qinfo == NULL || output->qinfo == NULL) {
-        shl_debug_error("mi355x: resize needs quantisation records\n");
-        return CSINN_FALSE;
-    }
-    if (input->quant_channel > 1 || output->quant_channel > 1) {
-        shl_debug_error("mi355x: resize: per-channel quantised activations are not supported\n");
-        return CSINN_UNSUPPORT_DTYPE;
-    }
-    if (dtype == SHL_MI355X_F16 && (input->qinfo->scale != 1.0f || output->qinfo->scale != 1.0f)) {
-        shl_debug_error("mi355x: resize fp16 with qinfo scale != 1 is not supported\n");
-        return CSINN_FALSE;
-    }
+    int rc = shl_mi355x_check_io("resize", input, output, &dtype);
+    if (rc != CSINN_TRUE) return rc;
     if (input->dim_count != 4 || output->dim_count != 4) {
         shl_debug_error("mi355x: resize expects 4-d tensors\n");
         return CSINN_FALSE;
@@ -114,24 +97,10 @@ int shl_mi355x_resize_exec(struct csinn_tensor *input, struct csinn_tensor *outp
     int rc = resize_desc(input, output, params, &d);
     if (rc != CSINN_TRUE) return rc;
     if (csinn_tensor_size(output) == 0) return CSINN_TRUE;
-    struct shl_mi355x_ctx *ctx = shl_mi355x_ctx_of(params->base.sess);
-    const void *in_dev = shl_mi355x_stage_in(ctx, input, 0);
-    void *out_dev = shl_mi355x_stage_out_begin(ctx, output, 1);
-    if (in_dev == NULL || out_dev == NULL) return CSINN_FALSE;
-    int st = shl_mi355x_resize(in_dev, out_dev, &d, shl_mi355x_ctx_stream(ctx));
-    if (st != SHL_MI355X_OK) {
-        shl_debug_error("mi355x: resize failed (%d): %s\n", st, shl_mi355x_last_error());
-        return CSINN_FALSE;
-    }
-    return shl_mi355x_stage_out_end(ctx, output, out_dev);
-}
-
-/* the address a tensor's bytes will have on the device as far as its alignment goes: a DMABUF tensor's own, the staging
- * buffers' alignment for a host tensor (made-up, disjoint: nothing is staged or followed) */
-static const void *perf_address(struct csinn_tensor *t, int slot)
-{
-    if (t->mtype == CSINN_MEM_TYPE_DMABUF && t->data) return t->data;
-    return (const void *)(((uintptr_t)1 << 56) + ((uintptr_t)slot << 48));
+    struct shl_mi355x_staged s;
+    if (shl_mi355x_staged_begin(&params->base, input, NULL, output, &s) != CSINN_TRUE) return CSINN_FALSE;
+    int st = shl_mi355x_resize(s.in[0], s.out, &d, s.stream);
+    return shl_mi355x_staged_end("resize", &s, output, st);
 }
 
 int shl_mi355x_resize_perf(struct csinn_tensor *input, struct csinn_tensor *output, struct csinn_resize_params *params,
@@ -140,6 +109,8 @@ int shl_mi355x_resize_perf(struct csinn_tensor *input, struct csinn_tensor *outp
     struct shl_mi355x_resize_desc d;
     int rc = resize_desc(input, output, params, &d);
     if (rc != CSINN_TRUE) return rc;
-    info->kernel_name = (char *)shl_mi355x_resize_kernel_name(&d, perf_address(input, 0), perf_address(output, 1));
+    uintptr_t at = SHL_MI355X_PERF_BASE;
+    const void *in = (const void *)shl_mi355x_perf_address(input, &at);
+    info->kernel_name = (char *)shl_mi355x_resize_kernel_name(&d, in, (const void *)shl_mi355x_perf_address(output, &at));
     return CSINN_TRUE;
 }

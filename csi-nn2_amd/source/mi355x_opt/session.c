@@ -105,87 +105,18 @@ static void drop_session(struct csinn_session *sess)
     }
 }
 
-/* how an exec callback is called.  The value is the number of inputs such a layer has in the graph (kernel and bias
- * included); 0: as many as its params block says; < 0: see inputs_of */
-enum call_shape {
-    CALL_SPLIT = -1, /* exec(input, outputs[], params): one input, as many outputs as its params block says */
-    CALL_ARRAY = 0,  /* exec(inputs[], output, params) */
-    CALL_SISO = 1,  /* exec(input, output, params) */
-    CALL_DISO = 2,  /* exec(input0, input1, output, params) */
-    CALL_CONV = 3,  /* exec(input, output, kernel, bias, params) */
-};
-
-/* All a session knows about an operator it runs on the device, one row per op id.  A layer qualifies when its op has a
- * row and its callback is the row's: the one setup.c registers, which runs on the GPU and honours DMABUF tensors.  (The
- * per-channel op ids have no row: their sessions stay host-staged.) */
-struct session_op {
-    int type;
-    void *exec;
-    enum call_shape call;
-    int activations; /* the leading inputs that are activations; 0: all of them */
-    int first_const; /* of those, the ones from this index on may be constants instead: uploaded once, kept resident */
-};
-
-static const struct session_op g_ops[] = {
-    {CSINN_OP_CONV2D, shl_mi355x_conv2d_exec, CALL_CONV, 1, 1},
-    {CSINN_OP_CONV2D_RELU, shl_mi355x_conv2d_exec, CALL_CONV, 1, 1},
-    {CSINN_OP_CONV2D_RELU6, shl_mi355x_conv2d_exec, CALL_CONV, 1, 1},
-    {CSINN_OP_DEPTHWISE_CONV2D, shl_mi355x_conv2d_exec, CALL_CONV, 1, 1},
-    {CSINN_OP_DEPTHWISE_CONV2D_RELU, shl_mi355x_conv2d_exec, CALL_CONV, 1, 1},
-    {CSINN_OP_DEPTHWISE_CONV2D_RELU6, shl_mi355x_conv2d_exec, CALL_CONV, 1, 1},
-    {CSINN_OP_GROUP_CONV2D, shl_mi355x_group_conv2d_exec, CALL_CONV, 1, 1},
-    {CSINN_OP_GROUP_CONV2D_RELU, shl_mi355x_group_conv2d_exec, CALL_CONV, 1, 1},
-    {CSINN_OP_GROUP_CONV2D_RELU6, shl_mi355x_group_conv2d_exec, CALL_CONV, 1, 1},
-    {CSINN_OP_DECONV2D, shl_mi355x_deconv2d_exec, CALL_CONV, 1, 1}, /* the learned upsampling of a decoder */
-    {CSINN_OP_DEPTHWISE_DECONV2D, shl_mi355x_deconv2d_exec, CALL_CONV, 1, 1},
-    {CSINN_OP_FULLYCONNECTED, shl_mi355x_fullyconnected_exec, CALL_CONV, 1, 1},
-    {CSINN_OP_RELU, shl_mi355x_relu_exec, CALL_SISO, 1, 1},
-    {CSINN_OP_RELU6, shl_mi355x_relu6_exec, CALL_SISO, 1, 1},
-    {CSINN_OP_GLOBAL_AVGPOOL2D, shl_mi355x_global_avgpool2d_exec, CALL_SISO, 1, 1},
-    {CSINN_OP_MAXPOOL2D, shl_mi355x_maxpool2d_exec, CALL_SISO, 1, 1},
-    {CSINN_OP_AVGPOOL2D, shl_mi355x_avgpool2d_exec, CALL_SISO, 1, 1},
-    {CSINN_OP_SOFTMAX, shl_mi355x_softmax_exec, CALL_SISO, 1, 1},
-    {CSINN_OP_ADD, shl_mi355x_add_exec, CALL_DISO, 2, 1},        /* the second operand may be a constant */
-    {CSINN_OP_MUL, shl_mi355x_mul_exec, CALL_DISO, 2, 1},        /* ... and may be broadcast (an SE gate, a per-channel scale) */
-    {CSINN_OP_SIGMOID, shl_mi355x_sigmoid_exec, CALL_SISO, 1, 1},
-    {CSINN_OP_HARD_SIGMOID, shl_mi355x_hard_sigmoid_exec, CALL_SISO, 1, 1},
-    {CSINN_OP_SILU, shl_mi355x_silu_exec, CALL_SISO, 1, 1},
-    {CSINN_OP_LEAKY_RELU, shl_mi355x_leaky_relu_exec, CALL_SISO, 1, 1},
-    {CSINN_OP_RESIZE, shl_mi355x_resize_exec, CALL_SISO, 1, 1},  /* an FPN top-down path, a U-Net decoder, a YOLO neck */
-    {CSINN_OP_CONCAT, shl_mi355x_concat_exec, CALL_ARRAY, 0, 0}, /* any input may be */
-    {CSINN_OP_SPLIT, shl_mi355x_split_exec, CALL_SPLIT, 1, 1},   /* a ShuffleNetV2 unit, a CSP / C2f block */
-    {CSINN_OP_SHUFFLE_CHANNEL, shl_mi355x_shuffle_channel_exec, CALL_SISO, 1, 1},
-    /* order and shape only: a detection head, an attention block, TensorFlow's SAME padding, the classifier's flatten */
-    {CSINN_OP_TRANSPOSE, shl_mi355x_transpose_exec, CALL_SISO, 1, 1},
-    {CSINN_OP_RESHAPE, shl_mi355x_reshape_exec, CALL_SISO, 1, 1}, /* one copy node; sharing the producer's buffer is a later change */
-    {CSINN_OP_FLATTEN, shl_mi355x_flatten_exec, CALL_SISO, 1, 1},
-    {CSINN_OP_PAD, shl_mi355x_pad_exec, CALL_SISO, 1, 1},
-    /* reductions: TensorFlow's global pooling (mean over H and W), CBAM's channel max / mean and global max pool, a head's
-     * reduce_max / reduce_sum */
-    {CSINN_OP_MEAN, shl_mi355x_mean_exec, CALL_SISO, 1, 1},
-    {CSINN_OP_SUM, shl_mi355x_sum_exec, CALL_SISO, 1, 1},
-    {CSINN_OP_MAX, shl_mi355x_max_exec, CALL_SISO, 1, 1},
-    {CSINN_OP_MIN, shl_mi355x_min_exec, CALL_SISO, 1, 1},
-    {CSINN_OP_REDUCE_MEAN, shl_mi355x_reduce_mean_exec, CALL_SISO, 1, 1},
-    {CSINN_OP_REDUCE_SUM, shl_mi355x_reduce_sum_exec, CALL_SISO, 1, 1},
-    {CSINN_OP_REDUCE_MAX, shl_mi355x_reduce_max_exec, CALL_SISO, 1, 1},
-    {CSINN_OP_REDUCE_MIN, shl_mi355x_reduce_min_exec, CALL_SISO, 1, 1},
-    {CSINN_OP_GLOBAL_MAXPOOL2D, shl_mi355x_global_maxpool2d_exec, CALL_SISO, 1, 1},
-    /* QK^T and PV of an attention block (two activations), a linear layer exported as MatMul (the second operand a constant) */
-    {CSINN_OP_MATMUL, shl_mi355x_matmul_exec, CALL_DISO, 2, 1},
-};
-
-/* the row of layer `n`; NULL: not a layer this file runs */
-static const struct session_op *session_op(struct shl_node *n)
+/* the row of layer `n` in the operator table (setup.c); NULL: not a layer this file runs.  A layer qualifies when its op's row
+ * has a call shape and its callback is the row's: the one the backend registers, which runs on the GPU and honours DMABUF
+ * tensors (a layer that fell through to the reference at init has another) */
+static const struct shl_mi355x_op *session_op(struct shl_node *n)
 {
     struct csinn_params_base *params = n->data;
-    for (size_t i = 0; i < sizeof(g_ops) / sizeof(g_ops[0]); i++)
-        if (g_ops[i].type == n->type) return params->cb && (void *)params->cb->exec == g_ops[i].exec ? &g_ops[i] : NULL;
-    return NULL;
+    const struct shl_mi355x_op *op = shl_mi355x_op_row(n->type);
+    return op && op->call != CALL_NONE && params->cb && (void *)params->cb->exec == op->exec ? op : NULL;
 }
 
 /* the number of inputs layer `n` must have; 0: none will do */
-static int inputs_of(const struct session_op *op, struct shl_node *n)
+static int inputs_of(const struct shl_mi355x_op *op, struct shl_node *n)
 {
     if (op->call == CALL_SPLIT) return 1;
     if (op->call != CALL_ARRAY) return op->call;
@@ -194,7 +125,7 @@ static int inputs_of(const struct session_op *op, struct shl_node *n)
 }
 
 /* the number of outputs layer `n` must have; 0: none will do */
-static int outputs_of(const struct session_op *op, struct shl_node *n)
+static int outputs_of(const struct shl_mi355x_op *op, struct shl_node *n)
 {
     if (op->call != CALL_SPLIT) return 1;
     struct csinn_split_params *p = n->data;
@@ -504,7 +435,7 @@ int shl_mi355x_session_setup(struct csinn_session *sess)
     int tensors = g->input_num;
     for (int i = 0; i < g->layer_index; i++) {
         struct shl_node *n = g->layer[i];
-        const struct session_op *op = session_op(n);
+        const struct shl_mi355x_op *op = session_op(n);
         const int inputs = op ? inputs_of(op, n) : 0, outputs = op ? outputs_of(op, n) : 0;
         if (inputs == 0 || n->in_num != inputs || outputs == 0 || n->out_num != outputs) {
             shl_debug_info("mi355x: layer %d (%s, op %d) runs on the host path: session stays host-staged\n", i,
@@ -525,7 +456,7 @@ int shl_mi355x_session_setup(struct csinn_session *sess)
     for (int i = 0; ok && i < g->input_num; i++) ok = adopt(ds, g->input[i]) != NULL;
     for (int i = 0; ok && i < g->layer_index; i++) {
         struct shl_node *n = g->layer[i];
-        const struct session_op *op = session_op(n);
+        const struct shl_mi355x_op *op = session_op(n);
         const int activations = op->activations ? op->activations : n->in_num;
         for (int j = 0; ok && j < activations; j++) {
             if (lookup(ds, n->in[j]) != NULL) continue;

@@ -11,14 +11,7 @@
 
 #include "mi355x_internal.h"
 
-/* ------------------------------------------------------------------------ callback table */
-#define MI355X_CB_MAX 160
-static struct {
-    int key; /* op * CSINN_DTYPE_SIZE + dtype */
-    struct csinn_callback cb;
-} g_table[MI355X_CB_MAX];
-static int g_table_len;
-
+/* ------------------------------------------------------------------------ the operator table */
 static int conv_caps() { return CSINN_OPT_INTRINSIC; }
 
 static int conv_perf(struct csinn_tensor *input, struct csinn_tensor *output,
@@ -30,20 +23,116 @@ static int conv_perf(struct csinn_tensor *input, struct csinn_tensor *output,
     return CSINN_TRUE;
 }
 
-static void reg(int dtype, int op, void *init, void *exec, void *est, void *perf)
+/* the reference's gref has no est for CSINN_OP_GROUP_CONV2D_RELU6 (no such symbol): next to it that row is not registered */
+#pragma weak shl_gref_group_conv2d_relu6
+
+/* One row per op id: {op, dtypes, init, exec, est, perf, call shape, activations, first_const}.  shl_target_init_mi355x
+ * registers the first six columns; a session (session.c) runs a layer on the device when its op's row has a call shape and
+ * the layer's exec callback is still the row's (one that fell through to the reference at init is not) */
+#define BOTH (SHL_MI355X_OP_I8 | SHL_MI355X_OP_F16)
+#define I8 SHL_MI355X_OP_I8
+static const struct shl_mi355x_op g_ops[] = {
+    {CSINN_OP_CONV2D, BOTH, shl_mi355x_conv2d_init, shl_mi355x_conv2d_exec, shl_gref_conv2d, conv_perf, CALL_CONV, 1, 1},
+    {CSINN_OP_CONV2D_RELU, BOTH, shl_mi355x_conv2d_relu_init, shl_mi355x_conv2d_exec, shl_gref_conv2d_relu, conv_perf, CALL_CONV, 1, 1},
+    {CSINN_OP_CONV2D_RELU6, BOTH, shl_mi355x_conv2d_relu6_init, shl_mi355x_conv2d_exec, shl_gref_conv2d_relu6, conv_perf, CALL_CONV, 1, 1},
+    {CSINN_OP_DEPTHWISE_CONV2D, BOTH, shl_mi355x_conv2d_init, shl_mi355x_conv2d_exec, shl_gref_depthwise_conv2d, conv_perf, CALL_CONV, 1, 1},
+    {CSINN_OP_DEPTHWISE_CONV2D_RELU, BOTH, shl_mi355x_conv2d_relu_init, shl_mi355x_conv2d_exec, shl_gref_depthwise_conv2d_relu, conv_perf,
+     CALL_CONV, 1, 1},
+    {CSINN_OP_DEPTHWISE_CONV2D_RELU6, BOTH, shl_mi355x_conv2d_relu6_init, shl_mi355x_conv2d_exec, shl_gref_depthwise_conv2d_relu6, conv_perf,
+     CALL_CONV, 1, 1},
+    {CSINN_OP_GROUP_CONV2D, BOTH, shl_mi355x_conv2d_init, shl_mi355x_group_conv2d_exec, shl_gref_group_conv2d, conv_perf, CALL_CONV, 1, 1},
+    {CSINN_OP_GROUP_CONV2D_RELU, BOTH, shl_mi355x_conv2d_relu_init, shl_mi355x_group_conv2d_exec, shl_gref_group_conv2d_relu, conv_perf,
+     CALL_CONV, 1, 1},
+    {CSINN_OP_GROUP_CONV2D_RELU6, BOTH, shl_mi355x_conv2d_relu6_init, shl_mi355x_group_conv2d_exec, shl_gref_group_conv2d_relu6, conv_perf,
+     CALL_CONV, 1, 1},
+    /* the learned upsampling of a decoder */
+    {CSINN_OP_DECONV2D, BOTH, shl_mi355x_deconv2d_init, shl_mi355x_deconv2d_exec, shl_gref_deconv2d, shl_mi355x_deconv2d_perf, CALL_CONV, 1, 1},
+    {CSINN_OP_DEPTHWISE_DECONV2D, BOTH, shl_mi355x_deconv2d_init, shl_mi355x_deconv2d_exec, shl_gref_depthwise_deconv2d,
+     shl_mi355x_deconv2d_perf, CALL_CONV, 1, 1},
+    /* (refused at init with a message: next to libshl the layer then runs on the reference's kernel) */
+    {CSINN_OP_GROUP_DECONV2D, BOTH, shl_mi355x_deconv2d_init, shl_mi355x_deconv2d_exec, shl_gref_group_deconv2d, shl_mi355x_deconv2d_perf,
+     CALL_NONE, 0, 0},
+    {CSINN_OP_FULLYCONNECTED, BOTH, shl_mi355x_fullyconnected_init, shl_mi355x_fullyconnected_exec, shl_gref_fullyconnected, conv_perf,
+     CALL_CONV, 1, 1},
+    /* the per-channel op ids exist for int8 only (reference/setup.c:786-808 registers them for every dtype,
+     * convolution_channel.c implements u8 / i8); their sessions stay host-staged */
+    {CSINN_OP_CONV2D_CHANNEL, I8, shl_mi355x_conv2d_channel_init, shl_mi355x_conv2d_channel_exec, shl_gref_conv2d, conv_perf, CALL_NONE, 0, 0},
+    {CSINN_OP_CONV2D_CHANNEL_RELU, I8, shl_mi355x_conv2d_channel_relu_init, shl_mi355x_conv2d_channel_relu_exec, shl_gref_conv2d_relu,
+     conv_perf, CALL_NONE, 0, 0},
+    {CSINN_OP_CONV2D_CHANNEL_RELU6, I8, shl_mi355x_conv2d_channel_relu6_init, shl_mi355x_conv2d_channel_relu6_exec, shl_gref_conv2d_relu6,
+     conv_perf, CALL_NONE, 0, 0},
+    {CSINN_OP_GROUP_CONV2D_CHANNEL, I8, shl_mi355x_group_conv2d_channel_init, shl_mi355x_group_conv2d_channel_exec, shl_gref_group_conv2d,
+     conv_perf, CALL_NONE, 0, 0},
+    {CSINN_OP_GROUP_CONV2D_CHANNEL_RELU, I8, shl_mi355x_group_conv2d_channel_relu_init, shl_mi355x_group_conv2d_channel_relu_exec,
+     shl_gref_group_conv2d_relu, conv_perf, CALL_NONE, 0, 0},
+    {CSINN_OP_DEPTHWISE_CONV2D_CHANNEL, I8, shl_mi355x_depthwise_conv2d_channel_init, shl_mi355x_depthwise_conv2d_channel_exec,
+     shl_gref_depthwise_conv2d, conv_perf, CALL_NONE, 0, 0},
+    {CSINN_OP_DEPTHWISE_CONV2D_CHANNEL_RELU, I8, shl_mi355x_depthwise_conv2d_channel_relu_init, shl_mi355x_depthwise_conv2d_channel_relu_exec,
+     shl_gref_depthwise_conv2d_relu, conv_perf, CALL_NONE, 0, 0},
+    {CSINN_OP_DEPTHWISE_CONV2D_CHANNEL_RELU6, I8, shl_mi355x_depthwise_conv2d_channel_relu6_init, shl_mi355x_depthwise_conv2d_channel_relu6_exec,
+     shl_gref_depthwise_conv2d_relu6, conv_perf, CALL_NONE, 0, 0},
+    {CSINN_OP_RELU, BOTH, NULL, shl_mi355x_relu_exec, shl_gref_relu, conv_perf, CALL_SISO, 1, 1},
+    {CSINN_OP_RELU6, BOTH, NULL, shl_mi355x_relu6_exec, shl_gref_relu6, conv_perf, CALL_SISO, 1, 1},
+    {CSINN_OP_GLOBAL_AVGPOOL2D, BOTH, NULL, shl_mi355x_global_avgpool2d_exec, shl_gref_global_avgpool2d, conv_perf, CALL_SISO, 1, 1},
+    {CSINN_OP_MAXPOOL2D, BOTH, NULL, shl_mi355x_maxpool2d_exec, shl_gref_maxpool2d, shl_mi355x_maxpool2d_perf, CALL_SISO, 1, 1},
+    {CSINN_OP_AVGPOOL2D, BOTH, NULL, shl_mi355x_avgpool2d_exec, shl_gref_avgpool2d, shl_mi355x_avgpool2d_perf, CALL_SISO, 1, 1},
+    {CSINN_OP_SOFTMAX, BOTH, NULL, shl_mi355x_softmax_exec, shl_gref_softmax, conv_perf, CALL_SISO, 1, 1},
+    /* the second operand may be a constant */
+    {CSINN_OP_ADD, BOTH, NULL, shl_mi355x_add_exec, shl_gref_add, conv_perf, CALL_DISO, 2, 1},
+    /* ... and may be broadcast (an SE gate, a per-channel scale) */
+    {CSINN_OP_MUL, BOTH, NULL, shl_mi355x_mul_exec, shl_gref_mul, shl_mi355x_mul_perf, CALL_DISO, 2, 1},
+    {CSINN_OP_SIGMOID, BOTH, NULL, shl_mi355x_sigmoid_exec, shl_gref_sigmoid, shl_mi355x_sigmoid_perf, CALL_SISO, 1, 1},
+    {CSINN_OP_HARD_SIGMOID, BOTH, NULL, shl_mi355x_hard_sigmoid_exec, shl_gref_hard_sigmoid, shl_mi355x_hard_sigmoid_perf, CALL_SISO, 1, 1},
+    {CSINN_OP_SILU, BOTH, NULL, shl_mi355x_silu_exec, shl_gref_silu, shl_mi355x_silu_perf, CALL_SISO, 1, 1},
+    {CSINN_OP_LEAKY_RELU, BOTH, NULL, shl_mi355x_leaky_relu_exec, shl_gref_leaky_relu, shl_mi355x_leaky_relu_perf, CALL_SISO, 1, 1},
+    /* an FPN top-down path, a U-Net decoder, a YOLO neck */
+    {CSINN_OP_RESIZE, BOTH, NULL, shl_mi355x_resize_exec, shl_gref_resize, shl_mi355x_resize_perf, CALL_SISO, 1, 1},
+    /* any input may be a constant */
+    {CSINN_OP_CONCAT, BOTH, NULL, shl_mi355x_concat_exec, shl_gref_concat, shl_mi355x_concat_perf, CALL_ARRAY, 0, 0},
+    /* from here on: a layer the op refuses falls through at init (next to libshl it runs on the reference's kernel) */
+    /* a ShuffleNetV2 unit, a CSP / C2f block */
+    {CSINN_OP_SPLIT, BOTH, shl_mi355x_split_init, shl_mi355x_split_exec, shl_gref_split, shl_mi355x_split_perf, CALL_SPLIT, 1, 1},
+    {CSINN_OP_SHUFFLE_CHANNEL, BOTH, shl_mi355x_shuffle_channel_init, shl_mi355x_shuffle_channel_exec, shl_gref_shuffle_channel,
+     shl_mi355x_shuffle_channel_perf, CALL_SISO, 1, 1},
+    /* order and shape only: a detection head, an attention block, TensorFlow's SAME padding, the classifier's flatten */
+    {CSINN_OP_TRANSPOSE, BOTH, shl_mi355x_transpose_init, shl_mi355x_transpose_exec, shl_gref_transpose, shl_mi355x_transpose_perf,
+     CALL_SISO, 1, 1},
+    /* (one copy node; sharing the producer's buffer is a later change) */
+    {CSINN_OP_RESHAPE, BOTH, shl_mi355x_reshape_init, shl_mi355x_reshape_exec, shl_gref_reshape, shl_mi355x_reshape_perf, CALL_SISO, 1, 1},
+    {CSINN_OP_FLATTEN, BOTH, shl_mi355x_flatten_init, shl_mi355x_flatten_exec, shl_gref_flatten, shl_mi355x_flatten_perf, CALL_SISO, 1, 1},
+    {CSINN_OP_PAD, BOTH, shl_mi355x_pad_init, shl_mi355x_pad_exec, shl_gref_pad, shl_mi355x_pad_perf, CALL_SISO, 1, 1},
+    /* QK^T and PV of an attention block (two activations), a linear layer exported as MatMul (the second operand a constant) */
+    {CSINN_OP_MATMUL, BOTH, shl_mi355x_matmul_init, shl_mi355x_matmul_exec, shl_gref_matmul, shl_mi355x_matmul_perf, CALL_DISO, 2, 1},
+    /* reductions: TensorFlow's global pooling (mean over H and W), CBAM's channel max / mean and global max pool, a head's
+     * reduce_max / reduce_sum */
+    {CSINN_OP_MEAN, BOTH, shl_mi355x_mean_init, shl_mi355x_mean_exec, shl_gref_mean, shl_mi355x_mean_perf, CALL_SISO, 1, 1},
+    {CSINN_OP_SUM, BOTH, shl_mi355x_sum_init, shl_mi355x_sum_exec, shl_gref_sum, shl_mi355x_sum_perf, CALL_SISO, 1, 1},
+    {CSINN_OP_MAX, BOTH, shl_mi355x_max_init, shl_mi355x_max_exec, shl_gref_max, shl_mi355x_max_perf, CALL_SISO, 1, 1},
+    {CSINN_OP_MIN, BOTH, shl_mi355x_min_init, shl_mi355x_min_exec, shl_gref_min, shl_mi355x_min_perf, CALL_SISO, 1, 1},
+    {CSINN_OP_REDUCE_MEAN, BOTH, shl_mi355x_reduce_mean_init, shl_mi355x_reduce_mean_exec, shl_gref_reduce_mean, shl_mi355x_reduce_mean_perf,
+     CALL_SISO, 1, 1},
+    {CSINN_OP_REDUCE_SUM, BOTH, shl_mi355x_reduce_sum_init, shl_mi355x_reduce_sum_exec, shl_gref_reduce_sum, shl_mi355x_reduce_sum_perf,
+     CALL_SISO, 1, 1},
+    {CSINN_OP_REDUCE_MAX, BOTH, shl_mi355x_reduce_max_init, shl_mi355x_reduce_max_exec, shl_gref_reduce_max, shl_mi355x_reduce_max_perf,
+     CALL_SISO, 1, 1},
+    {CSINN_OP_REDUCE_MIN, BOTH, shl_mi355x_reduce_min_init, shl_mi355x_reduce_min_exec, shl_gref_reduce_min, shl_mi355x_reduce_min_perf,
+     CALL_SISO, 1, 1},
+    {CSINN_OP_GLOBAL_MAXPOOL2D, BOTH, shl_mi355x_global_maxpool2d_init, shl_mi355x_global_maxpool2d_exec, shl_gref_global_maxpool2d,
+     shl_mi355x_global_maxpool2d_perf, CALL_SISO, 1, 1},
+};
+#undef BOTH
+#undef I8
+#define N_OPS (sizeof(g_ops) / sizeof(g_ops[0]))
+
+const struct shl_mi355x_op *shl_mi355x_op_row(int type)
 {
-    if (g_table_len >= MI355X_CB_MAX) {
-        shl_debug_error("mi355x: callback table full\n");
-        return;
-    }
-    g_table[g_table_len].key = op * CSINN_DTYPE_SIZE + dtype;
-    g_table[g_table_len].cb.init = init;
-    g_table[g_table_len].cb.exec = exec;
-    g_table[g_table_len].cb.est = est;
-    g_table[g_table_len].cb.caps = conv_caps;
-    g_table[g_table_len].cb.perf = perf;
-    g_table_len++;
+    for (size_t i = 0; i < N_OPS; i++)
+        if (g_ops[i].type == type) return &g_ops[i];
+    return NULL;
 }
+
+/* what shl_target_init_mi355x made of the rows: [row][0] int8, [row][1] binary16; exec == NULL: not registered */
+static struct csinn_callback g_cb[N_OPS][2];
 
 /* present when the backend is loaded next to the genuine library: unsupported (op, dtype)
  * pairs fall through to the C reference, as c920v2 falls through to rvv */
@@ -51,9 +140,11 @@ struct csinn_callback *shl_cb_map_ref(int op, int dtype) __attribute__((weak));
 
 struct csinn_callback *shl_cb_map_mi355x(int op, int dtype)
 {
-    const int key = op * CSINN_DTYPE_SIZE + dtype;
-    for (int i = 0; i < g_table_len; i++)
-        if (g_table[i].key == key) return &g_table[i].cb;
+    const struct shl_mi355x_op *row = shl_mi355x_op_row(op);
+    if (row && (dtype == CSINN_DTYPE_INT8 || dtype == CSINN_DTYPE_FLOAT16)) {
+        struct csinn_callback *cb = &g_cb[row - g_ops][dtype == CSINN_DTYPE_FLOAT16];
+        if (cb->exec) return cb;
+    }
     if (shl_cb_map_ref) return shl_cb_map_ref(op, dtype);
     return NULL;
 }
@@ -632,94 +723,18 @@ void *shl_mi355x_runtime_callback(int op)
     }
 }
 
-#pragma weak shl_gref_group_conv2d_relu6
-
 void shl_target_init_mi355x(void)
 {
     static int done;
     if (done) return;
     done = 1;
-    const int dts[2] = {CSINN_DTYPE_INT8, CSINN_DTYPE_FLOAT16};
-    for (int i = 0; i < 2; i++) {
-        const int dt = dts[i];
-        reg(dt, CSINN_OP_CONV2D, shl_mi355x_conv2d_init, shl_mi355x_conv2d_exec, shl_gref_conv2d, conv_perf);
-        reg(dt, CSINN_OP_CONV2D_RELU, shl_mi355x_conv2d_relu_init, shl_mi355x_conv2d_exec,
-            shl_gref_conv2d_relu, conv_perf);
-        reg(dt, CSINN_OP_CONV2D_RELU6, shl_mi355x_conv2d_relu6_init, shl_mi355x_conv2d_exec,
-            shl_gref_conv2d_relu6, conv_perf);
-        reg(dt, CSINN_OP_DEPTHWISE_CONV2D, shl_mi355x_conv2d_init, shl_mi355x_conv2d_exec,
-            shl_gref_depthwise_conv2d, conv_perf);
-        reg(dt, CSINN_OP_DEPTHWISE_CONV2D_RELU, shl_mi355x_conv2d_relu_init, shl_mi355x_conv2d_exec,
-            shl_gref_depthwise_conv2d_relu, conv_perf);
-        reg(dt, CSINN_OP_DEPTHWISE_CONV2D_RELU6, shl_mi355x_conv2d_relu6_init,
-            shl_mi355x_conv2d_exec, shl_gref_depthwise_conv2d_relu6, conv_perf);
-        reg(dt, CSINN_OP_GROUP_CONV2D, shl_mi355x_conv2d_init, shl_mi355x_group_conv2d_exec, shl_gref_group_conv2d, conv_perf);
-        reg(dt, CSINN_OP_GROUP_CONV2D_RELU, shl_mi355x_conv2d_relu_init, shl_mi355x_group_conv2d_exec,
-            shl_gref_group_conv2d_relu, conv_perf);
-        /* the reference's gref has no est for this op id (no shl_gref_group_conv2d_relu6 symbol) */
-        if (shl_gref_group_conv2d_relu6)
-            reg(dt, CSINN_OP_GROUP_CONV2D_RELU6, shl_mi355x_conv2d_relu6_init, shl_mi355x_group_conv2d_exec,
-                shl_gref_group_conv2d_relu6, conv_perf);
-        reg(dt, CSINN_OP_DECONV2D, shl_mi355x_deconv2d_init, shl_mi355x_deconv2d_exec, shl_gref_deconv2d, shl_mi355x_deconv2d_perf);
-        reg(dt, CSINN_OP_DEPTHWISE_DECONV2D, shl_mi355x_deconv2d_init, shl_mi355x_deconv2d_exec, shl_gref_depthwise_deconv2d,
-            shl_mi355x_deconv2d_perf);
-        /* (refused at init with a message: next to libshl the layer then runs on the reference's kernel) */
-        reg(dt, CSINN_OP_GROUP_DECONV2D, shl_mi355x_deconv2d_init, shl_mi355x_deconv2d_exec, shl_gref_group_deconv2d, shl_mi355x_deconv2d_perf);
-        reg(dt, CSINN_OP_FULLYCONNECTED, shl_mi355x_fullyconnected_init,
-            shl_mi355x_fullyconnected_exec, shl_gref_fullyconnected, conv_perf);
-    }
-    /* the per-channel op ids exist for int8 only (reference/setup.c:786-808 registers them for every dtype,
-     * convolution_channel.c implements u8 / i8) */
-    reg(CSINN_DTYPE_INT8, CSINN_OP_CONV2D_CHANNEL, shl_mi355x_conv2d_channel_init, shl_mi355x_conv2d_channel_exec,
-        shl_gref_conv2d, conv_perf);
-    reg(CSINN_DTYPE_INT8, CSINN_OP_CONV2D_CHANNEL_RELU, shl_mi355x_conv2d_channel_relu_init,
-        shl_mi355x_conv2d_channel_relu_exec, shl_gref_conv2d_relu, conv_perf);
-    reg(CSINN_DTYPE_INT8, CSINN_OP_CONV2D_CHANNEL_RELU6, shl_mi355x_conv2d_channel_relu6_init,
-        shl_mi355x_conv2d_channel_relu6_exec, shl_gref_conv2d_relu6, conv_perf);
-    reg(CSINN_DTYPE_INT8, CSINN_OP_GROUP_CONV2D_CHANNEL, shl_mi355x_group_conv2d_channel_init,
-        shl_mi355x_group_conv2d_channel_exec, shl_gref_group_conv2d, conv_perf);
-    reg(CSINN_DTYPE_INT8, CSINN_OP_GROUP_CONV2D_CHANNEL_RELU, shl_mi355x_group_conv2d_channel_relu_init,
-        shl_mi355x_group_conv2d_channel_relu_exec, shl_gref_group_conv2d_relu, conv_perf);
-    reg(CSINN_DTYPE_INT8, CSINN_OP_DEPTHWISE_CONV2D_CHANNEL, shl_mi355x_depthwise_conv2d_channel_init,
-        shl_mi355x_depthwise_conv2d_channel_exec, shl_gref_depthwise_conv2d, conv_perf);
-    reg(CSINN_DTYPE_INT8, CSINN_OP_DEPTHWISE_CONV2D_CHANNEL_RELU, shl_mi355x_depthwise_conv2d_channel_relu_init,
-        shl_mi355x_depthwise_conv2d_channel_relu_exec, shl_gref_depthwise_conv2d_relu, conv_perf);
-    reg(CSINN_DTYPE_INT8, CSINN_OP_DEPTHWISE_CONV2D_CHANNEL_RELU6, shl_mi355x_depthwise_conv2d_channel_relu6_init,
-        shl_mi355x_depthwise_conv2d_channel_relu6_exec, shl_gref_depthwise_conv2d_relu6, conv_perf);
-    for (int i = 0; i < 2; i++) {
-        reg(dts[i], CSINN_OP_RELU, NULL, shl_mi355x_relu_exec, shl_gref_relu, conv_perf);
-        reg(dts[i], CSINN_OP_RELU6, NULL, shl_mi355x_relu6_exec, shl_gref_relu6, conv_perf);
-        reg(dts[i], CSINN_OP_GLOBAL_AVGPOOL2D, NULL, shl_mi355x_global_avgpool2d_exec, shl_gref_global_avgpool2d, conv_perf);
-        reg(dts[i], CSINN_OP_MAXPOOL2D, NULL, shl_mi355x_maxpool2d_exec, shl_gref_maxpool2d, shl_mi355x_maxpool2d_perf);
-        reg(dts[i], CSINN_OP_AVGPOOL2D, NULL, shl_mi355x_avgpool2d_exec, shl_gref_avgpool2d, shl_mi355x_avgpool2d_perf);
-        reg(dts[i], CSINN_OP_SOFTMAX, NULL, shl_mi355x_softmax_exec, shl_gref_softmax, conv_perf);
-        reg(dts[i], CSINN_OP_ADD, NULL, shl_mi355x_add_exec, shl_gref_add, conv_perf);
-        reg(dts[i], CSINN_OP_MUL, NULL, shl_mi355x_mul_exec, shl_gref_mul, shl_mi355x_mul_perf);
-        reg(dts[i], CSINN_OP_SIGMOID, NULL, shl_mi355x_sigmoid_exec, shl_gref_sigmoid, shl_mi355x_sigmoid_perf);
-        reg(dts[i], CSINN_OP_HARD_SIGMOID, NULL, shl_mi355x_hard_sigmoid_exec, shl_gref_hard_sigmoid, shl_mi355x_hard_sigmoid_perf);
-        reg(dts[i], CSINN_OP_SILU, NULL, shl_mi355x_silu_exec, shl_gref_silu, shl_mi355x_silu_perf);
-        reg(dts[i], CSINN_OP_LEAKY_RELU, NULL, shl_mi355x_leaky_relu_exec, shl_gref_leaky_relu, shl_mi355x_leaky_relu_perf);
-        reg(dts[i], CSINN_OP_RESIZE, NULL, shl_mi355x_resize_exec, shl_gref_resize, shl_mi355x_resize_perf);
-        reg(dts[i], CSINN_OP_CONCAT, NULL, shl_mi355x_concat_exec, shl_gref_concat, shl_mi355x_concat_perf);
-        /* (a layer they refuse falls through at init: next to libshl it runs on the reference's kernel) */
-        reg(dts[i], CSINN_OP_SPLIT, shl_mi355x_split_init, shl_mi355x_split_exec, shl_gref_split, shl_mi355x_split_perf);
-        reg(dts[i], CSINN_OP_SHUFFLE_CHANNEL, shl_mi355x_shuffle_channel_init, shl_mi355x_shuffle_channel_exec,
-            shl_gref_shuffle_channel, shl_mi355x_shuffle_channel_perf);
-        reg(dts[i], CSINN_OP_TRANSPOSE, shl_mi355x_transpose_init, shl_mi355x_transpose_exec, shl_gref_transpose, shl_mi355x_transpose_perf);
-        reg(dts[i], CSINN_OP_RESHAPE, shl_mi355x_reshape_init, shl_mi355x_reshape_exec, shl_gref_reshape, shl_mi355x_reshape_perf);
-        reg(dts[i], CSINN_OP_FLATTEN, shl_mi355x_flatten_init, shl_mi355x_flatten_exec, shl_gref_flatten, shl_mi355x_flatten_perf);
-        reg(dts[i], CSINN_OP_PAD, shl_mi355x_pad_init, shl_mi355x_pad_exec, shl_gref_pad, shl_mi355x_pad_perf);
-        reg(dts[i], CSINN_OP_MATMUL, shl_mi355x_matmul_init, shl_mi355x_matmul_exec, shl_gref_matmul, shl_mi355x_matmul_perf);
-        reg(dts[i], CSINN_OP_MEAN, shl_mi355x_mean_init, shl_mi355x_mean_exec, shl_gref_mean, shl_mi355x_mean_perf);
-        reg(dts[i], CSINN_OP_SUM, shl_mi355x_sum_init, shl_mi355x_sum_exec, shl_gref_sum, shl_mi355x_sum_perf);
-        reg(dts[i], CSINN_OP_MAX, shl_mi355x_max_init, shl_mi355x_max_exec, shl_gref_max, shl_mi355x_max_perf);
-        reg(dts[i], CSINN_OP_MIN, shl_mi355x_min_init, shl_mi355x_min_exec, shl_gref_min, shl_mi355x_min_perf);
-        reg(dts[i], CSINN_OP_REDUCE_MEAN, shl_mi355x_reduce_mean_init, shl_mi355x_reduce_mean_exec, shl_gref_reduce_mean, shl_mi355x_reduce_mean_perf);
-        reg(dts[i], CSINN_OP_REDUCE_SUM, shl_mi355x_reduce_sum_init, shl_mi355x_reduce_sum_exec, shl_gref_reduce_sum, shl_mi355x_reduce_sum_perf);
-        reg(dts[i], CSINN_OP_REDUCE_MAX, shl_mi355x_reduce_max_init, shl_mi355x_reduce_max_exec, shl_gref_reduce_max, shl_mi355x_reduce_max_perf);
-        reg(dts[i], CSINN_OP_REDUCE_MIN, shl_mi355x_reduce_min_init, shl_mi355x_reduce_min_exec, shl_gref_reduce_min, shl_mi355x_reduce_min_perf);
-        reg(dts[i], CSINN_OP_GLOBAL_MAXPOOL2D, shl_mi355x_global_maxpool2d_init, shl_mi355x_global_maxpool2d_exec,
-            shl_gref_global_maxpool2d, shl_mi355x_global_maxpool2d_perf);
+    for (size_t i = 0; i < N_OPS; i++) {
+        const struct shl_mi355x_op *row = &g_ops[i];
+        if (row->est == NULL) continue; /* (the weak shl_gref_group_conv2d_relu6) */
+        for (int f16 = 0; f16 < 2; f16++)
+            if (row->dtypes & (f16 ? SHL_MI355X_OP_F16 : SHL_MI355X_OP_I8))
+                g_cb[i][f16] = (struct csinn_callback){
+                    .init = row->init, .exec = row->exec, .est = row->est, .caps = conv_caps, .perf = row->perf};
     }
     shl_register_op_callback(CSINN_MI355X, shl_cb_map_mi355x);
     shl_register_runtime_callback(CSINN_MI355X, shl_mi355x_runtime_callback);

@@ -13,48 +13,6 @@
 
 #include "mi355x_internal.h"
 
-struct csinn_callback *shl_cb_map_ref(int op, int dtype) __attribute__((weak));
-
-static int dtype_code(const struct csinn_tensor *t)
-{
-    if (t->dtype == CSINN_DTYPE_INT8) return SHL_MI355X_I8;
-    if (t->dtype == CSINN_DTYPE_FLOAT16) return SHL_MI355X_F16;
-    return -1;
-}
-
-/* dtypes, records: what every device op asks of an (input, output) pair */
-int shl_mi355x_check_io(const char *op, struct csinn_tensor *input, struct csinn_tensor *output, int *dtype)
-{
-    *dtype = dtype_code(input);
-    if (*dtype < 0 || dtype_code(output) != *dtype) {
-        shl_debug_error("mi355x: %s dtypes in=%d out=%d unsupported\n", op, input->dtype, output->dtype);
-        return CSINN_UNSUPPORT_DTYPE;
-    }
-    if (input->qinfo == NULL || output->qinfo == NULL) {
-        shl_debug_error("mi355x: %s needs quantisation records\n", op);
-        return CSINN_FALSE;
-    }
-    if (input->quant_channel > 1 || output->quant_channel > 1) {
-        shl_debug_error("mi355x: %s: per-channel quantised activations are not supported\n", op);
-        return CSINN_UNSUPPORT_DTYPE;
-    }
-    if (*dtype == SHL_MI355X_F16 && (input->qinfo->scale != 1.0f || output->qinfo->scale != 1.0f)) {
-        shl_debug_error("mi355x: %s fp16 with qinfo scale != 1 is not supported\n", op);
-        return CSINN_FALSE;
-    }
-    return CSINN_TRUE;
-}
-
-/* a layer this backend refused at init: next to the genuine library it runs on the reference's kernel, elsewhere exec
- * refuses it again (the front-ends drop init's status, source/nn2/split.c:30-35) */
-void shl_mi355x_fall_through(struct csinn_params_base *base, int op, int dtype)
-{
-    if (shl_cb_map_ref && base->cb) {
-        struct csinn_callback *cb = shl_cb_map_ref(op, dtype);
-        if (cb && cb->exec) base->cb->exec = cb->exec;
-    }
-}
-
 /* ------------------------------------------------------------------------ split */
 struct split_call {
     struct shl_mi355x_split_desc desc;
@@ -192,16 +150,6 @@ int shl_mi355x_split_exec(struct csinn_tensor *input, struct csinn_tensor **outp
     return rc;
 }
 
-/* the address a tensor's bytes will have on the device as far as its alignment goes: a DMABUF tensor's own, else a made-up
- * one with the staging path's alignment (disjoint: nothing is staged or followed) */
-uintptr_t shl_mi355x_perf_address(struct csinn_tensor *t, uintptr_t *at)
-{
-    if (t->mtype == CSINN_MEM_TYPE_DMABUF && t->data) return (uintptr_t)t->data;
-    const uintptr_t bytes = (uintptr_t)csinn_tensor_byte_size(t), here = *at;
-    *at += (bytes + SHL_MI355X_STAGE_ALIGN - 1) / SHL_MI355X_STAGE_ALIGN * SHL_MI355X_STAGE_ALIGN + SHL_MI355X_STAGE_ALIGN;
-    return here;
-}
-
 /* the form the rules choose for this layer */
 int shl_mi355x_split_perf(struct csinn_tensor *input, struct csinn_tensor **output, struct csinn_split_params *params,
                           struct csinn_perf_info *info)
@@ -209,7 +157,7 @@ int shl_mi355x_split_perf(struct csinn_tensor *input, struct csinn_tensor **outp
     struct split_call c;
     int rc = split_prepare(input, output, params, &c);
     if (rc != CSINN_TRUE) return rc;
-    uintptr_t at = (uintptr_t)1 << 56;
+    uintptr_t at = SHL_MI355X_PERF_BASE;
     const void *in = (const void *)shl_mi355x_perf_address(input, &at);
     for (int i = 0; i < c.desc.n_outputs; i++) c.dev[i] = (void *)shl_mi355x_perf_address(output[i], &at);
     info->kernel_name = (char *)shl_mi355x_split_kernel_name(in, c.dev, c.len, c.scale, c.zp, &c.desc);
@@ -222,7 +170,6 @@ static int shuffle_desc(struct csinn_tensor *input, struct csinn_tensor *output,
                         struct shl_mi355x_shuffle_desc *desc)
 {
     int dtype;
-    if (input == NULL || output == NULL) return CSINN_FALSE;
     int rc = shl_mi355x_check_io("shuffle_channel", input, output, &dtype);
     if (rc != CSINN_TRUE) return rc;
     if (input->dim_count != 4 || output->dim_count != 4) {
@@ -273,16 +220,10 @@ int shl_mi355x_shuffle_channel_exec(struct csinn_tensor *input, struct csinn_ten
     int rc = shuffle_desc(input, output, params, &d);
     if (rc != CSINN_TRUE) return rc;
     if (csinn_tensor_size(output) == 0) return CSINN_TRUE;
-    struct shl_mi355x_ctx *ctx = shl_mi355x_ctx_of(params->base.sess);
-    const void *in_dev = shl_mi355x_stage_in(ctx, input, 0);
-    void *out_dev = shl_mi355x_stage_out_begin(ctx, output, 1);
-    if (in_dev == NULL || out_dev == NULL) return CSINN_FALSE;
-    int st = shl_mi355x_shuffle_channel(in_dev, out_dev, &d, shl_mi355x_ctx_stream(ctx));
-    if (st != SHL_MI355X_OK) {
-        shl_debug_error("mi355x: shuffle_channel failed (%d): %s\n", st, shl_mi355x_last_error());
-        return CSINN_FALSE;
-    }
-    return shl_mi355x_stage_out_end(ctx, output, out_dev);
+    struct shl_mi355x_staged s;
+    if (shl_mi355x_staged_begin(&params->base, input, NULL, output, &s) != CSINN_TRUE) return CSINN_FALSE;
+    int st = shl_mi355x_shuffle_channel(s.in[0], s.out, &d, s.stream);
+    return shl_mi355x_staged_end("shuffle_channel", &s, output, st);
 }
 
 int shl_mi355x_shuffle_channel_perf(struct csinn_tensor *input, struct csinn_tensor *output,
@@ -291,7 +232,7 @@ int shl_mi355x_shuffle_channel_perf(struct csinn_tensor *input, struct csinn_ten
     struct shl_mi355x_shuffle_desc d;
     int rc = shuffle_desc(input, output, params, &d);
     if (rc != CSINN_TRUE) return rc;
-    uintptr_t at = (uintptr_t)1 << 56;
+    uintptr_t at = SHL_MI355X_PERF_BASE;
     const void *in = (const void *)shl_mi355x_perf_address(input, &at);
     info->kernel_name = (char *)shl_mi355x_shuffle_channel_kernel_name(in, (const void *)shl_mi355x_perf_address(output, &at), &d);
     return CSINN_TRUE;

@@ -568,15 +568,6 @@ void *shl_mi355x_ctx_stream(struct shl_mi355x_ctx *) { abort(); }
 const void *shl_mi355x_stage_in(struct shl_mi355x_ctx *, struct csinn_tensor *, int) { abort(); }
 void *shl_mi355x_stage_out_begin(struct shl_mi355x_ctx *, struct csinn_tensor *, int) { abort(); }
 int shl_mi355x_stage_out_end(struct shl_mi355x_ctx *, struct csinn_tensor *, void *) { abort(); }
-// split.c travels along for the helpers move.c shares with it; what only its own callbacks reach
-int shl_mi355x_stage_out_many_begin(struct shl_mi355x_ctx *, struct csinn_tensor **, int, void **) { abort(); }
-int shl_mi355x_stage_out_many_end(struct shl_mi355x_ctx *, struct csinn_tensor **, int, void *const *) { abort(); }
-int shl_mi355x_split(const void *, void *const *, const int64_t *, const float *, const int32_t *, const struct shl_mi355x_split_desc *,
-                     void *) { abort(); }
-const char *shl_mi355x_split_kernel_name(const void *, void *const *, const int64_t *, const float *, const int32_t *,
-                                         const struct shl_mi355x_split_desc *) { abort(); }
-int shl_mi355x_shuffle_channel(const void *, void *, const struct shl_mi355x_shuffle_desc *, void *) { abort(); }
-const char *shl_mi355x_shuffle_channel_kernel_name(const void *, const void *, const struct shl_mi355x_shuffle_desc *) { abort(); }
 }
 
 static void tensor(struct csinn_tensor *t, struct csinn_quant_info *q, int dtype, int layout, int rank, const int *dims, float s, int zp)
@@ -699,7 +690,7 @@ def _line(case, **kw):
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc to compile with")
 @pytest.mark.skipif(os.path.exists("/dev/kfd"), reason="sanitizer builds run on machines without a GPU")
 def test_descriptor_code_runs_clean_under_address_and_undefined_sanitizers(built, tmp_path):
-    """csrc/transpose.hip, csrc/pad.hip (host side: -Xarch_host) and source/mi355x_opt/move.c compiled with
+    """csrc/transpose.hip, csrc/pad.hip (host side: -Xarch_host) and source/mi355x_opt/move.c and layer.c compiled with
     -fsanitize=address,undefined into a program of their own, which takes every case's and every refused layer's descriptor
     apart -- init, perf, canonicalisation, form choice, pad element -- and must name the same forms the library does."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -710,7 +701,7 @@ def test_descriptor_code_runs_clean_under_address_and_undefined_sanitizers(built
     san = "-fsanitize=address,undefined"
     (tmp_path / "driver.cpp").write_text(DRIVER)
     incs = ["-I" + inc, "-I" + os.path.join(inc, "csinn"), "-I" + csrc, "-I" + opt_dir]
-    for name in ("move", "split"):  # (split.c holds the helpers move.c shares with it)
+    for name in ("move", "layer"):
         subprocess.run(["gcc", "-std=gnu99", "-O1", "-g", san, "-fno-sanitize-recover=undefined", "-ffp-contract=off", "-c",
                         os.path.join(opt_dir, name + ".c"), "-o", str(tmp_path / (name + ".o"))] + incs, check=True)
     hip_flags = ["--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-fno-gpu-rdc", "-ffp-contract=off", "-Xarch_host", san,
@@ -721,7 +712,7 @@ def test_descriptor_code_runs_clean_under_address_and_undefined_sanitizers(built
     subprocess.run([hipcc] + hip_flags + incs + ["-x", "hip", "-c", str(tmp_path / "driver.cpp"), "-o", str(tmp_path / "driver.o")],
                    check=True)
     exe = str(tmp_path / "move_host")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-fno-gpu-rdc", san] + [str(tmp_path / (n + ".o")) for n in ("driver", "transpose", "pad", "move", "split")]
+    subprocess.run([hipcc, "--offload-arch=gfx950", "-fno-gpu-rdc", san] + [str(tmp_path / (n + ".o")) for n in ("driver", "transpose", "pad", "move", "layer")]
                    + ["-o", exe], check=True)
     lines = [_line(c) for c in CASES]
     refused = [_line(BY_KEY[key], **kw) for _, key, kw in REFUSED_LAYERS if "in_scales" not in kw and "out_dt" not in kw]
