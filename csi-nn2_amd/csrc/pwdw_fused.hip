@@ -55,7 +55,31 @@ struct alignas(32) PwDwLateArgs {
     int32_t reserved;
 };
 
+// what stands in front of the fragment loads: everything the workgroup's slice, rectangle and fragment addresses are made of, in one
+// aligned block at the very front of the kernel arguments -- two 16-dword scalar loads into registers of their own, ONE scalar
+// round trip.  (Read field by field from the two layers and the members below, the batch came out as thirteen loads, and the
+// register allocator gave a late one a destination inside an earlier, still outstanding one: a second s_waitcnt, a second round
+// trip, in every compile-time form -- profiles/operand_first_notes.md.)  The host copies the few ConvArgs fields (fill_early).
+struct alignas(64) PwDwEarlyArgs {
+    const void *w_frag;        // pw.w_frag
+    int32_t xg, xg_log2, spg;  // (as below)
+    uint32_t spg_magic, tx_magic;
+    int32_t tiles_x;
+    int32_t nrect, nsub, nsw;
+    uint32_t ty_magic;         // ceil(2^32 / tiles_y): ty / tiles_y == mulhi(ty, ty_magic) for ty < 65536 (the grid's limit)
+    int32_t tiles_y, mt;
+    const void *in;            // pw.in
+    int64_t img_stride;
+    int32_t bh, bw, ex_lo, ey_lo, iwm;
+    uint32_t iwm_magic;
+    int32_t H, W, C;           // pw.H, pw.W, pw.C
+    int32_t sh, sw, pt, pl;    // dw.sh, dw.sw, dw.pt, dw.pl
+    int32_t reserved;
+};
+static_assert(sizeof(PwDwEarlyArgs) == 128, "pwdw_fused: the early block is two 16-dword scalar loads");
+
 struct PwDwArgs {
+    PwDwEarlyArgs early;  // (first: offset 0 of the kernel-argument segment)
     ConvArgs pw;  // in = the pair's input tensor; out unused
     ConvArgs dw;  // in unused; out = the pair's output tensor
     int32_t bh, bw;            // depthwise output rectangle of a workgroup (the first / last of an axis: + ey_lo / ey_hi, ex_lo / ex_hi)
@@ -117,39 +141,45 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // scalar control around MFMA
     const int frow = lane & 31, fhalf = lane >> 5;
-    // every kernel argument the prologue needs, fetched in ONE batch in front of the first branch (an empty asm "uses" them here):
-    // the compiler otherwise fetches an argument inside the branch that first reads it -- four dependent s_load / s_waitcnt round
-    // trips of ~200 cycles in front of the first fragment load
-    asm volatile("" ::"s"(f.xg), "s"(f.xg_log2), "s"(f.spg), "s"(f.spg_magic), "s"(f.tx_magic), "s"(f.nrect), "s"(f.tiles_x), "s"(f.tiles_y));
-    asm volatile("" ::"s"(f.bh), "s"(f.bw), "s"(f.mt), "s"(f.ks), "s"(f.nsw), "s"(f.nsub),
-                 "s"(f.ks_log2), "s"(f.mwn), "s"(f.img_stride));
-    asm volatile("" ::"s"(q.in), "s"(q.w_frag), "s"(q.H), "s"(q.W), "s"(q.C), "s"(d.sh), "s"(d.sw), "s"(d.pt), "s"(d.pl), "s"(d.N));
-    asm volatile("" ::"s"(f.ex_lo), "s"(f.ey_lo), "s"(f.iwm), "s"(f.iwm_magic));
+    // every kernel argument the prologue needs: the early block, two 16-dword scalar loads with destinations of their own in front
+    // of the first branch -- ONE scalar round trip.  (The compiler otherwise fetches an argument inside the branch that first
+    // reads it: four dependent s_load / s_waitcnt round trips of ~200 cycles in front of the first fragment load.)
+    PwDwEarlyArgs e;
+    {
+        typedef const __attribute__((address_space(4))) v16i *KernargV16;
+        const KernargV16 kp = (KernargV16)__builtin_amdgcn_kernarg_segment_ptr();
+        static_assert(offsetof(PwDwArgs, early) == 0, "pwdw_fused: the early block leads the kernel arguments");
+        const v16i e0 = kp[0], e1 = kp[1];
+        __builtin_memcpy(&e, &e0, 64);
+        __builtin_memcpy(reinterpret_cast<char *>(&e) + 64, &e1, 64);
+        // (both halves HERE: the compiler otherwise sinks the second load behind the weight loads, where its first field is used)
+        asm volatile("" ::"s"(e.w_frag), "s"(e.nrect), "s"(e.in), "s"(e.img_stride), "s"(e.iwm_magic), "s"(e.H), "s"(e.pl));
+    }
+    // (the two pointers came through integer registers: say that they are global memory, or the loads are flat ones)
+    typedef const __attribute__((address_space(1))) char *GlobalBytes;
+    typedef const __attribute__((address_space(1))) v4i *GlobalV4;
+    if constexpr (!FIXED) asm volatile("" ::"s"(f.ks), "s"(f.ks_log2), "s"(f.mwn), "s"(f.nwaves));  // (the run-time form's own)
     // (only what stands in front of the fragment loads: with the epilogue's and the depthwise phase's arguments in THIS batch the pass
     // got 0.5 us slower in round 6 -- that trial had put them IN FRONT of the fragment loads.  Nor do those arguments "hide under the fragments'
     // latency where the compiler puts them", as this comment used to say: the compiler fetches each in the block of its first use,
     // behind the MFMAs and the barriers -- four exposed scalar round trips.  They get a batch of their own BEHIND the fragment loads:
     // "the shadow" below.)
-    int slice = blockIdx.x, tx = blockIdx.y, ty = blockIdx.z, n = 0;
+    int slice = blockIdx.x, tx = blockIdx.y, ty = blockIdx.z;
     {
-        // (computed whether or not the grid is XCD-mapped and then selected: inside `if (f.xg)` the fields below were fetched
+        // (computed whether or not the grid is XCD-mapped and then selected: inside `if (xg)` the fields below were fetched
         // from the kernel arguments in two further dependent s_load / s_waitcnt round trips, ~200 cycles each)
         const int L = blockIdx.x;
         const int x = L & 7, j = L >> 3;                        // XCD, index among that XCD's workgroups
-        const int b = (int)(((uint32_t)j * f.spg_magic) >> 20);
-        const int xslice = (x & (f.xg - 1)) * f.spg + (j - b * f.spg);  // a group = spg ADJACENT slices
-        const int rect = b * (8 >> f.xg_log2) + (x >> f.xg_log2);
-        const int xty = (int)(((uint32_t)rect * f.tx_magic) >> 20);
-        const int xtx = rect - xty * f.tiles_x;
-        const bool mapped = f.xg != 0;
-        if (mapped && rect >= f.nrect) return;
+        const int b = (int)(((uint32_t)j * e.spg_magic) >> 20);
+        const int xslice = (x & (e.xg - 1)) * e.spg + (j - b * e.spg);  // a group = spg ADJACENT slices
+        const int rect = b * (8 >> e.xg_log2) + (x >> e.xg_log2);
+        const int xty = (int)(((uint32_t)rect * e.tx_magic) >> 20);
+        const int xtx = rect - xty * e.tiles_x;
+        const bool mapped = e.xg != 0;
+        if (mapped && rect >= e.nrect) return;
         slice = mapped ? xslice : slice;
         ty = mapped ? xty : ty;
         tx = mapped ? xtx : tx;
-    }
-    if (d.N > 1) {
-        n = ty / f.tiles_y;
-        ty -= n * f.tiles_y;
     }
 
     const int nwaves = FIXED ? 4 : f.nwaves;  // 4 or 8
@@ -160,35 +190,41 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
     const int kpart = wave & (ks - 1);
     const int mw = wave >> (FIXED ? (KSV == 4 ? 2 : (KSV == 2 ? 1 : 0)) : f.ks_log2);  // wave group over tiles
     const int mwn = FIXED ? 4 / (KSV ? KSV : 1) : f.mwn;                                // number of wave groups = nwaves / ks
-    const int mtp = FIXED ? TPW * (4 / (KSV ? KSV : 1)) : f.mt;                         // tiles the waves run (padded)
-    const int mt = (FIXED && EMT) ? mtp : f.mt;                                         // tiles of the patch
-    const int sub0 = kpart * f.nsw;
+    const int mtp = FIXED ? TPW * (4 / (KSV ? KSV : 1)) : e.mt;                         // tiles the waves run (padded)
+    const int mt = (FIXED && EMT) ? mtp : e.mt;                                         // tiles of the patch
+    const int sub0 = kpart * (EXACT ? NSW : e.nsw);         // (EXACT: every wave has NSW sub-steps, nsub = ks NSW)
+    const int nsub = FIXED ? KSV * NSW : e.nsub;
     int nsw = NSW;
     if constexpr (!EXACT) {
-        nsw = f.nsub - sub0;
-        nsw = nsw < f.nsw ? nsw : f.nsw;  // may be <= 0 for a ragged last part
+        nsw = e.nsub - sub0;
+        nsw = nsw < e.nsw ? nsw : e.nsw;  // may be <= 0 for a ragged last part
     }
 
-    const char *img = static_cast<const char *>(q.in) + (n ? (int64_t)n * f.img_stride : (int64_t)0);
     // weights: the plan's fragment-ordered copy (one coalesced 1 KiB load per fragment; every pointwise plan the pair test
-    // admits has one: conv_plan.hip `frag_copy`)
-    const char *wp = static_cast<const char *>(q.w_frag) + ((int64_t)slice * f.nsub + sub0) * 1024 + lane * 16;
+    // admits has one: conv_plan.hip `frag_copy`).  They need the slice and nothing else: the image stands behind them.
+    const GlobalBytes wp = (GlobalBytes)e.w_frag + ((int64_t)slice * nsub + sub0) * 1024 + lane * 16;
     constexpr int wstep = 1024;
     v4i fa[NSW];
 #pragma unroll
     for (int s = 0; s < NSW; ++s)
-        if (s < nsw) fa[s] = *reinterpret_cast<const v4i *>(wp + s * wstep);
+        if (s < nsw) fa[s] = *(GlobalV4)(wp + s * wstep);
     if constexpr (FIXED) __builtin_amdgcn_sched_barrier(0);  // (the weight fragments are requested before anything of the pixel addresses is computed)
+    // the image: ty counts the rectangle rows of all images.  Without a branch (a division by a magic, and at batch 1 a product
+    // with zero): the conditional forms stood in front of the weight loads as three blocks and eleven instructions.
+    int n = (int)__umulhi((uint32_t)ty, e.ty_magic);
+    n = e.ty_magic ? n : ty;  // (tiles_y == 1: the magic 2^32 does not fit, the host stores 0)
+    ty -= n * e.tiles_y;
+    const GlobalBytes img = (GlobalBytes)e.in + (uint64_t)(uint32_t)n * (uint32_t)e.img_stride;  // (wave-uniform: the scalar unit; shapes_pair: an image is below 2 GiB)
     // The workgroup's rectangle starts at output pixel (oy0, ox0); its patch at (ry0, rx0) of the image (may be -pad); its window
     // = patch intersected with the image, from (wy0, wx0) to, not including, (wye, wxe).  MFMA row j is window pixel (r, c) =
     // (j / iwm, j % iwm) with the launch's widest window iwm: one magic from the host.  In front of the pixel loads stands only
     // what their addresses need -- the origins; where the window ends waits for the shadow.
-    const int oy0 = ty * f.bh + min(ty, f.ey_lo), ox0 = tx * f.bw + min(tx, f.ex_lo);  // (e_lo is 0 or 1: + e_lo behind the first rectangle)
-    const int ry0 = oy0 * d.sh - d.pt, rx0 = ox0 * d.sw - d.pl;
+    const int oy0 = ty * e.bh + min(ty, e.ey_lo), ox0 = tx * e.bw + min(tx, e.ex_lo);  // (e_lo is 0 or 1: + e_lo behind the first rectangle)
+    const int ry0 = oy0 * e.sh - e.pt, rx0 = ox0 * e.sw - e.pl;
     const int wy0 = max(ry0, 0), wx0 = max(rx0, 0);
     auto win_rc = [&](int j, int &r, int &c) {
-        r = (int)(((uint32_t)j * f.iwm_magic) >> 20);
-        c = j - r * f.iwm;
+        r = (int)(((uint32_t)j * e.iwm_magic) >> 20);
+        c = j - r * e.iwm;
     };
     v4i fb[MTW][NSW];
     int lr[MTW], lc[MTW];  // (this wave's rows: with four K parts they are the workgroup's, and the shadow takes them from here)
@@ -198,11 +234,13 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
         if (FIXED || tile < mt) {
             win_rc(tile * 32 + frow, lr[i], lc[i]);
             // rows that hold no pixel of this window (past its width or its height): any valid address, the sums are never used
-            const int y = min(wy0 + lr[i], q.H - 1), x = min(wx0 + lc[i], q.W - 1);
-            const char *px = img + (y * q.W + x) * q.C + fhalf * 16 + sub0 * 32;
+            const int y = min(wy0 + lr[i], e.H - 1), x = min(wx0 + lc[i], e.W - 1);
+            // scalar image base + a 32-bit lane offset, as the weights (shapes_pair: an image is below 2 GiB)
+            const uint32_t off = (uint32_t)((y * e.W + x) * e.C + fhalf * 16 + sub0 * 32);
+            const GlobalBytes px = img + off;
 #pragma unroll
             for (int s = 0; s < NSW; ++s)
-                if (s < nsw) fb[i][s] = *reinterpret_cast<const v4i *>(px + s * 32);
+                if (s < nsw) fb[i][s] = *(GlobalV4)(px + s * 32);
         }
     }
     // ---- the shadow: from here (every fragment load issued) to the first MFMA's wait the wave idles for a whole global-memory
@@ -235,7 +273,7 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
     // the rest of the workgroup's geometry.  One past the rectangle's last output row / column: where the next rectangle begins, the
     // map's edge for the last one (which may be e_hi longer, or stick out of the map in a uniform grid); the rectangle's own
     // size for the depthwise phase's `live`.
-    const int oye = ty == fl.ylast ? dl.Ho : ty * f.bh + fl.bhe, oxe = tx == fl.xlast ? dl.Wo : tx * f.bw + fl.bwe;
+    const int oye = ty == fl.ylast ? dl.Ho : ty * e.bh + fl.bhe, oxe = tx == fl.xlast ? dl.Wo : tx * e.bw + fl.bwe;
     // the depthwise phase's index arithmetic (dw_patch.h)
     DwPatchGeom g;
     g.bh = fl.dbh, g.bw = fl.dbw, g.lbh = oye - oy0, g.lbw = oxe - ox0, g.rw = fl.rw, g.bw_magic = bw_magic, g.pitch = dw_patch_pitch(fl.npx);
@@ -255,7 +293,7 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
 
     // ---- behind the shadow, in the MFMAs' block: a wave's MFMAs are a dependent chain of 16-pass instructions, and the scalar
     // and vector instructions below issue between them.  Where the window ends:
-    const int wye = min(oye * dl.sh + fl.cy, q.H), wxe = min(oxe * dl.sw + fl.cx, q.W);
+    const int wye = min(oye * dl.sh + fl.cy, e.H), wxe = min(oxe * dl.sw + fl.cx, e.W);
     // window pixel (r, c) -> whether this workgroup's window has it, and its slot in the patch (the patch keeps the largest
     // rectangle's layout: rw pixels per row).  Rows without a pixel go to the plane's last dword, which no reader looks at
     // (dw_patch_pitch: 8 spare dwords per plane).
@@ -584,6 +622,22 @@ bool pwdw_fused_geometry(const ConvArgs &q, const ConvArgs &d, int32_t out[SHL_P
     return true;
 }
 
+// the early block: copies of what the kernel's prologue reads (PwDwEarlyArgs), from the two layers and the chosen geometry
+static void fill_early(const ConvArgs &q, const ConvArgs &d, PwDwArgs &f)
+{
+    PwDwEarlyArgs &e = f.early;
+    e.w_frag = q.w_frag, e.in = q.in;
+    e.xg = f.xg, e.xg_log2 = f.xg_log2, e.spg = f.spg, e.spg_magic = f.spg_magic, e.tx_magic = f.tx_magic;
+    e.tiles_x = f.tiles_x, e.tiles_y = f.tiles_y, e.nrect = f.nrect, e.nsub = f.nsub, e.nsw = f.nsw, e.mt = f.mt;
+    // ceil(2^32 / tiles_y): exact for every ty < 65536 (pwdw_fusable admits tiles_y N <= 65535, and a grid's z extent is no larger); 0 stands for 2^32
+    e.ty_magic = f.tiles_y > 1 ? (uint32_t)((((uint64_t)1 << 32) + f.tiles_y - 1) / f.tiles_y) : 0u;
+    e.img_stride = f.img_stride;
+    e.bh = f.bh, e.bw = f.bw, e.ex_lo = f.ex_lo, e.ey_lo = f.ey_lo, e.iwm = f.iwm, e.iwm_magic = f.iwm_magic;
+    e.H = q.H, e.W = q.W, e.C = q.C;
+    e.sh = d.sh, e.sw = d.sw, e.pt = d.pt, e.pl = d.pl;
+    e.reserved = 0;
+}
+
 int launch_pwdw_fused(const ConvArgs &q, const ConvArgs &d, hipStream_t s)
 {
     PwDwArgs f;
@@ -593,6 +647,7 @@ int launch_pwdw_fused(const ConvArgs &q, const ConvArgs &d, hipStream_t s)
         set_error("pwdw_fused: the pair does not qualify");
         return SHL_MI355X_ENOTSUP;
     }
+    fill_early(q, d, f);
     dim3 grid((unsigned)(q.Co >> 5), (unsigned)f.tiles_x, (unsigned)(f.tiles_y * d.N));
     if (f.xg) {
         const int rpg = 8 / f.xg;
