@@ -402,11 +402,15 @@ def load_hip():
         "shl_mi355x_matmul": (C.c_int, [vp, vp, vp, C.POINTER(MatmulDesc), vp]),
         "shl_mi355x_matmul_kernel_name": (C.c_char_p, [vp, vp, vp, C.POINTER(MatmulDesc)]),
         "shl_mi355x_matmul_is_exact": (C.c_int, [C.POINTER(MatmulDesc)]),
+        "shl_mi355x_matmul_bias": (C.c_int, [vp, vp, vp, vp, C.POINTER(MatmulDesc), f32, i32, f32, i32, i32, vp]),
+        "shl_mi355x_matmul_bias_kernel_name": (C.c_char_p, [vp, vp, vp, vp, C.POINTER(MatmulDesc)]),
         "shl_mi355x_unary_lut_i8": (C.c_int, [vp, vp, sz, vp, vp]),
         "shl_mi355x_unary_lut_i8_kernel_name": (C.c_char_p, [vp, vp]),
         "shl_mi355x_unary_f16": (C.c_int, [vp, vp, sz, i32, f32, vp]),
         "shl_mi355x_mul": (C.c_int, [vp, vp, vp, C.POINTER(MulDesc), vp]),
         "shl_mi355x_mul_kernel_name": (C.c_char_p, [C.POINTER(MulDesc), vp, vp, vp]),
+        "shl_mi355x_add_bcast": (C.c_int, [vp, vp, vp, C.POINTER(MulDesc), vp]),
+        "shl_mi355x_add_bcast_kernel_name": (C.c_char_p, [C.POINTER(MulDesc), vp, vp, vp]),
         "shl_mi355x_resize": (C.c_int, [vp, vp, C.POINTER(ResizeDesc), vp]),
         "shl_mi355x_resize_kernel_name": (C.c_char_p, [C.POINTER(ResizeDesc), vp, vp]),
     }
@@ -516,6 +520,7 @@ def load_backend(frontend):
         opt.shl_mi355x_registry_get.restype = C.c_void_p
         opt.shl_mi355x_registry_get.argtypes = [C.c_void_p]
         opt.shl_mi355x_session_folded_activations.argtypes = [C.POINTER(Session)]
+        opt.shl_mi355x_session_fused_linears.argtypes = [C.POINTER(Session)]
         opt.shl_mi355x_session_stream.argtypes = [C.POINTER(Session)]
         opt.shl_mi355x_session_stream.restype = C.c_void_p
         opt.shl_mi355x_session_set_stream.argtypes = [C.POINTER(Session), C.c_void_p]

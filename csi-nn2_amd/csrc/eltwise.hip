@@ -28,12 +28,18 @@
 //   generic   one output per thread, any groups and alignment (SHL_MI355X_MUL_FORM=generic forces it)
 // vec and row need a and out (vec: b too, unless it is a scalar) on the 16-byte grid; elements behind the last whole
 // piece take the one-output path inside the same launch.
+//
+// The broadcasting add (CSINN_OP_ADD with operands of different shapes: source/reference/add.c:21-41, the same
+// shl_ref_diso_callback_base and the same broadcast) is these three kernels instantiated with the sum as the element
+// function: add_vec / add_row / add_generic, the same form rule (SHL_MI355X_ADD_FORM=generic forces the last), the same
+// descriptor.  [.., N] + [N] with N in whole pieces -- a linear layer's bias -- is the vec form.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <type_traits>
 
+#include "add_step.h"
 #include "common.h"
 
 namespace shl {
@@ -119,7 +125,8 @@ __global__ __launch_bounds__(256) void unary_f16_kernel(const uint16_t *in, uint
         out[i] = unary_f16_one<KIND>(in[i], alpha);
 }
 
-// ------------------------------------------------------------------------------------------ mul
+// ------------------------------------------------------------------------------------------ mul, broadcasting add
+enum { OP_MUL = 0, OP_ADD = 1 };  // what the three kernels below compute: they are shared, the element function is not
 enum { MUL_VEC = 0, MUL_ROW = 1, MUL_GENERIC = 2 };
 enum { B_SAME = 0, B_SCALAR = 1, B_INNER = 2 };  // how the vec form finds b
 
@@ -130,7 +137,7 @@ struct MulArgs {
     uint64_t dim[4];    // the output's groups, outermost first, padded in front with 1
     uint64_t bs[4];     // b's stride per group, in elements
     float sa, za, sb, zb, so, zo, inv_so;
-    int32_t fma_div;    // div_by_scale is exact for every product these records can give
+    int32_t fma_div;    // div_by_scale is exact for every product (sum) these records can give
     int32_t b_mode;     // vec form: B_*
     int32_t a_second;   // a is the reference's SECOND input (the callback swapped the operands): whose NaN goes through
 };
@@ -175,28 +182,48 @@ __device__ __forceinline__ uint16_t mul_f16_one(uint16_t ha, uint16_t hb, const 
     return float_to_f16_bits_ref(p);
 }
 
-template <bool F16>
+// add: the element function of add_step.h, which the fused matmul + bias store (matmul.hip) applies as well
+__device__ __forceinline__ int add_i8_one(int qa, int qb, const MulArgs &m)
+{
+    const AddRec r = {m.sa, m.za, m.sb, m.zb, m.so, m.zo, m.inv_so, m.fma_div};
+    return add_i8_step(qa, qb, r);
+}
+
+__device__ __forceinline__ uint16_t add_f16_one(uint16_t ha, uint16_t hb, const MulArgs &m)
+{
+    return m.a_second ? add_f16_step(hb, ha) : add_f16_step(ha, hb);  // (the reference's input0, input1)
+}
+
+template <bool F16, int OP>
+__device__ __forceinline__ auto elem_one(typename std::conditional<F16, uint16_t, int>::type va,
+                                         typename std::conditional<F16, uint16_t, int>::type vb, const MulArgs &m)
+{
+    if constexpr (F16) return OP == OP_ADD ? add_f16_one(va, vb, m) : mul_f16_one(va, vb, m);
+    else return OP == OP_ADD ? add_i8_one(va, vb, m) : mul_i8_one(va, vb, m);
+}
+
+template <bool F16, int OP>
 __device__ __forceinline__ void mul_one(const MulArgs &m, uint64_t e, uint64_t bi)
 {
     if constexpr (F16) {
-        static_cast<uint16_t *>(m.out)[e] = mul_f16_one(static_cast<const uint16_t *>(m.a)[e], static_cast<const uint16_t *>(m.b)[bi], m);
+        static_cast<uint16_t *>(m.out)[e] = elem_one<true, OP>(static_cast<const uint16_t *>(m.a)[e], static_cast<const uint16_t *>(m.b)[bi], m);
     } else {
-        static_cast<int8_t *>(m.out)[e] = (int8_t)mul_i8_one(static_cast<const int8_t *>(m.a)[e], static_cast<const int8_t *>(m.b)[bi], m);
+        static_cast<int8_t *>(m.out)[e] = (int8_t)elem_one<false, OP>(static_cast<const int8_t *>(m.a)[e], static_cast<const int8_t *>(m.b)[bi], m);
     }
 }
 
-template <bool F16>
+template <bool F16, int OP>
 __device__ __forceinline__ uint32_t mul_word(uint32_t wa, uint32_t wb, const MulArgs &m)
 {
     if constexpr (F16) {
-        return (uint32_t)mul_f16_one((uint16_t)wa, (uint16_t)wb, m) | ((uint32_t)mul_f16_one((uint16_t)(wa >> 16), (uint16_t)(wb >> 16), m) << 16);
+        return (uint32_t)elem_one<true, OP>((uint16_t)wa, (uint16_t)wb, m) | ((uint32_t)elem_one<true, OP>((uint16_t)(wa >> 16), (uint16_t)(wb >> 16), m) << 16);
     } else {
-        return pack4_i8(mul_i8_one((int8_t)wa, (int8_t)wb, m), mul_i8_one((int8_t)(wa >> 8), (int8_t)(wb >> 8), m),
-                        mul_i8_one((int8_t)(wa >> 16), (int8_t)(wb >> 16), m), mul_i8_one((int8_t)(wa >> 24), (int8_t)(wb >> 24), m));
+        return pack4_i8(elem_one<false, OP>((int8_t)wa, (int8_t)wb, m), elem_one<false, OP>((int8_t)(wa >> 8), (int8_t)(wb >> 8), m),
+                        elem_one<false, OP>((int8_t)(wa >> 16), (int8_t)(wb >> 16), m), elem_one<false, OP>((int8_t)(wa >> 24), (int8_t)(wb >> 24), m));
     }
 }
 
-template <bool F16>
+template <bool F16, int OP = OP_MUL>
 __global__ __launch_bounds__(256) void mul_vec_kernel(MulArgs m)
 {
     constexpr uint64_t E = F16 ? 8 : 16;  // elements per piece
@@ -213,15 +240,15 @@ __global__ __launch_bounds__(256) void mul_vec_kernel(MulArgs m)
         if (m.b_mode == B_SAME) vb = static_cast<const uint4 *>(m.b)[i];
         else if (m.b_mode == B_INNER) vb = *reinterpret_cast<const uint4 *>(static_cast<const char *>(m.b) + mul_b_index(m, i * E) * (F16 ? 2 : 1));
         uint4 r;
-        r.x = mul_word<F16>(va.x, vb.x, m), r.y = mul_word<F16>(va.y, vb.y, m);
-        r.z = mul_word<F16>(va.z, vb.z, m), r.w = mul_word<F16>(va.w, vb.w, m);
+        r.x = mul_word<F16, OP>(va.x, vb.x, m), r.y = mul_word<F16, OP>(va.y, vb.y, m);
+        r.z = mul_word<F16, OP>(va.z, vb.z, m), r.w = mul_word<F16, OP>(va.w, vb.w, m);
         static_cast<uint4 *>(m.out)[i] = r;
     }
-    for (uint64_t e = nvec * E + t; e < m.count; e += stride) mul_one<F16>(m, e, mul_b_index(m, e));
+    for (uint64_t e = nvec * E + t; e < m.count; e += stride) mul_one<F16, OP>(m, e, mul_b_index(m, e));
 }
 
 // the innermost group (run = dim[3]) is broadcast: element e takes b's element of its row e / run
-template <bool F16>
+template <bool F16, int OP = OP_MUL>
 __global__ __launch_bounds__(256) void mul_row_kernel(MulArgs m)
 {
     constexpr int E = F16 ? 8 : 16;
@@ -246,18 +273,18 @@ __global__ __launch_bounds__(256) void mul_row_kernel(MulArgs m)
             wb[k * (F16 ? 2 : 1) / 4] |= bv << (F16 ? 16 * (k & 1) : 8 * (k & 3));
         }
         uint4 r;
-        r.x = mul_word<F16>(wa[0], wb[0], m), r.y = mul_word<F16>(wa[1], wb[1], m);
-        r.z = mul_word<F16>(wa[2], wb[2], m), r.w = mul_word<F16>(wa[3], wb[3], m);
+        r.x = mul_word<F16, OP>(wa[0], wb[0], m), r.y = mul_word<F16, OP>(wa[1], wb[1], m);
+        r.z = mul_word<F16, OP>(wa[2], wb[2], m), r.w = mul_word<F16, OP>(wa[3], wb[3], m);
         static_cast<uint4 *>(m.out)[i] = r;
     }
-    for (uint64_t e = nvec * E + t; e < m.count; e += stride) mul_one<F16>(m, e, mul_b_index(m, e));
+    for (uint64_t e = nvec * E + t; e < m.count; e += stride) mul_one<F16, OP>(m, e, mul_b_index(m, e));
 }
 
-template <bool F16>
+template <bool F16, int OP = OP_MUL>
 __global__ __launch_bounds__(256) void mul_generic_kernel(MulArgs m)
 {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < m.count; e += stride) mul_one<F16>(m, e, mul_b_index(m, e));
+    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < m.count; e += stride) mul_one<F16, OP>(m, e, mul_b_index(m, e));
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------
@@ -295,11 +322,11 @@ static const char *mul_invalid(const void *a, const void *b, const void *out, co
     return NULL;
 }
 
-// The one place that chooses the form (launch and name); *b_mode: how the vec form finds b.
-// SHL_MI355X_MUL_FORM=generic forces the literal form (A/B runs, tests); read per call.
-static int mul_form(const void *a, const void *b, const void *out, const shl_mi355x_mul_desc *d, int *b_mode)
+// The one place that chooses the form (launch and name), for mul and for the broadcasting add; *b_mode: how the vec form
+// finds b.  SHL_MI355X_MUL_FORM=generic / SHL_MI355X_ADD_FORM=generic forces the literal form (A/B runs, tests); read per call.
+static int mul_form(int op, const void *a, const void *b, const void *out, const shl_mi355x_mul_desc *d, int *b_mode)
 {
-    const char *force = getenv("SHL_MI355X_MUL_FORM");
+    const char *force = getenv(op == OP_ADD ? "SHL_MI355X_ADD_FORM" : "SHL_MI355X_MUL_FORM");
     if (force && strcmp(force, "generic") == 0) return MUL_GENERIC;
     if ((((uintptr_t)a | (uintptr_t)out) & 15) != 0) return MUL_GENERIC;
     const int64_t E = d->dtype == SHL_MI355X_F16 ? 8 : 16;
@@ -326,7 +353,58 @@ static int mul_form(const void *a, const void *b, const void *out, const shl_mi3
     return MUL_GENERIC;
 }
 
-static const char *const kMulNames[] = {"mul_vec", "mul_row", "mul_generic"};
+static const char *const kMulNames[2][3] = {{"mul_vec", "mul_row", "mul_generic"}, {"add_vec", "add_row", "add_generic"}};
+
+static const char *bcast_kernel_name(int op, const shl_mi355x_mul_desc *d, const void *a, const void *b, const void *out)
+{
+    uint64_t count, b_count;
+    int b_mode = 0;
+    if (mul_invalid(a, b, out, d, &count, &b_count)) return "";
+    return kMulNames[op][mul_form(op, a, b, out, d, &b_mode)];
+}
+
+// validate, choose the form, enqueue: shl_mi355x_mul and shl_mi355x_add_bcast
+template <int OP>
+static int bcast_launch(const char *what, const void *a_dev, const void *b_dev, void *out_dev, const shl_mi355x_mul_desc *d,
+                        void *stream)
+{
+    uint64_t count, b_count;
+    const char *why = mul_invalid(a_dev, b_dev, out_dev, d, &count, &b_count);
+    if (why) {
+        set_error("%s: %s", what, why);
+        return SHL_MI355X_EINVAL;
+    }
+    if (count == 0) return SHL_MI355X_OK;
+    const bool f16 = d->dtype == SHL_MI355X_F16;
+    MulArgs m;
+    memset(&m, 0, sizeof(m));
+    m.a = a_dev, m.b = b_dev, m.out = out_dev, m.count = count;
+    for (int g = 0; g < 4; ++g) {
+        const int src = g - (4 - d->ngroups);
+        m.dim[g] = src >= 0 ? (uint64_t)d->dim[src] : 1;
+        m.bs[g] = src >= 0 && d->dim[src] > 1 ? (uint64_t)d->b_stride[src] : 0;
+    }
+    m.sa = d->a_scale, m.za = (float)d->a_zp, m.sb = d->b_scale, m.zb = (float)d->b_zp;
+    m.so = d->out_scale, m.zo = (float)d->out_zp, m.inv_so = 1.0f / d->out_scale;
+    // div_by_scale(p, so, RN(1 / so)) == p / so for every product (sum) these records can give (common.h; the range
+    // conv_plan.hip:fma_division_ok admits: 2^-40 <= so <= 2^40, |p| <= 2^60, p finite)
+    const double bound = (128.0 + fabs((double)d->a_zp)) * fabs((double)d->a_scale) * (128.0 + fabs((double)d->b_zp)) * fabs((double)d->b_scale);
+    m.fma_div = d->out_scale >= 0x1p-40f && d->out_scale <= 0x1p40f && bound <= 0x1p60;  // (false for NaN)
+    if (OP == OP_ADD) m.fma_div = add_rec(d->a_scale, d->a_zp, d->b_scale, d->b_zp, d->out_scale, d->out_zp).fma_div;  // (the sum's bound)
+    m.a_second = d->a_is_second ? 1 : 0;
+    const int form = mul_form(OP, a_dev, b_dev, out_dev, d, &m.b_mode);
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 block(256);
+    const uint64_t pieces = count / (f16 ? 8 : 16);
+    if (form == MUL_VEC)
+        hipLaunchKernelGGL((f16 ? mul_vec_kernel<true, OP> : mul_vec_kernel<false, OP>), dim3(grid_for(pieces)), block, 0, s, m);
+    else if (form == MUL_ROW)
+        hipLaunchKernelGGL((f16 ? mul_row_kernel<true, OP> : mul_row_kernel<false, OP>), dim3(grid_for(pieces)), block, 0, s, m);
+    else
+        hipLaunchKernelGGL((f16 ? mul_generic_kernel<true, OP> : mul_generic_kernel<false, OP>), dim3(grid_for(count)), block, 0, s, m);
+    SHL_HIP(hipGetLastError());
+    return SHL_MI355X_OK;
+}
 
 }  // namespace shl
 
@@ -407,49 +485,23 @@ extern "C" int shl_mi355x_unary_f16(const uint16_t *input_dev, uint16_t *output_
 extern "C" const char *shl_mi355x_mul_kernel_name(const struct shl_mi355x_mul_desc *d, const void *a_dev, const void *b_dev,
                                                   const void *out_dev)
 {
-    uint64_t count, b_count;
-    int b_mode = 0;
-    if (shl::mul_invalid(a_dev, b_dev, out_dev, d, &count, &b_count)) return "";
-    return shl::kMulNames[shl::mul_form(a_dev, b_dev, out_dev, d, &b_mode)];
+    return shl::bcast_kernel_name(shl::OP_MUL, d, a_dev, b_dev, out_dev);
 }
 
 extern "C" int shl_mi355x_mul(const void *a_dev, const void *b_dev, void *out_dev, const struct shl_mi355x_mul_desc *d,
                               void *stream)
 {
-    using namespace shl;
-    uint64_t count, b_count;
-    const char *why = mul_invalid(a_dev, b_dev, out_dev, d, &count, &b_count);
-    if (why) {
-        set_error("mul: %s", why);
-        return SHL_MI355X_EINVAL;
-    }
-    if (count == 0) return SHL_MI355X_OK;
-    const bool f16 = d->dtype == SHL_MI355X_F16;
-    MulArgs m;
-    memset(&m, 0, sizeof(m));
-    m.a = a_dev, m.b = b_dev, m.out = out_dev, m.count = count;
-    for (int g = 0; g < 4; ++g) {
-        const int src = g - (4 - d->ngroups);
-        m.dim[g] = src >= 0 ? (uint64_t)d->dim[src] : 1;
-        m.bs[g] = src >= 0 && d->dim[src] > 1 ? (uint64_t)d->b_stride[src] : 0;
-    }
-    m.sa = d->a_scale, m.za = (float)d->a_zp, m.sb = d->b_scale, m.zb = (float)d->b_zp;
-    m.so = d->out_scale, m.zo = (float)d->out_zp, m.inv_so = 1.0f / d->out_scale;
-    // div_by_scale(p, so, RN(1 / so)) == p / so for every product these records can give (common.h; the range
-    // conv_plan.hip:fma_division_ok admits: 2^-40 <= so <= 2^40, |p| <= 2^60, p finite)
-    const double bound = (128.0 + fabs((double)d->a_zp)) * fabs((double)d->a_scale) * (128.0 + fabs((double)d->b_zp)) * fabs((double)d->b_scale);
-    m.fma_div = d->out_scale >= 0x1p-40f && d->out_scale <= 0x1p40f && bound <= 0x1p60;  // (false for NaN)
-    m.a_second = d->a_is_second ? 1 : 0;
-    const int form = mul_form(a_dev, b_dev, out_dev, d, &m.b_mode);
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 block(256);
-    const uint64_t pieces = count / (f16 ? 8 : 16);
-    if (form == MUL_VEC)
-        hipLaunchKernelGGL(f16 ? mul_vec_kernel<true> : mul_vec_kernel<false>, dim3(grid_for(pieces)), block, 0, s, m);
-    else if (form == MUL_ROW)
-        hipLaunchKernelGGL(f16 ? mul_row_kernel<true> : mul_row_kernel<false>, dim3(grid_for(pieces)), block, 0, s, m);
-    else
-        hipLaunchKernelGGL(f16 ? mul_generic_kernel<true> : mul_generic_kernel<false>, dim3(grid_for(count)), block, 0, s, m);
-    SHL_HIP(hipGetLastError());
-    return SHL_MI355X_OK;
+    return shl::bcast_launch<shl::OP_MUL>("mul", a_dev, b_dev, out_dev, d, stream);
+}
+
+extern "C" const char *shl_mi355x_add_bcast_kernel_name(const struct shl_mi355x_mul_desc *d, const void *a_dev, const void *b_dev,
+                                                        const void *out_dev)
+{
+    return shl::bcast_kernel_name(shl::OP_ADD, d, a_dev, b_dev, out_dev);
+}
+
+extern "C" int shl_mi355x_add_bcast(const void *a_dev, const void *b_dev, void *out_dev, const struct shl_mi355x_mul_desc *d,
+                                    void *stream)
+{
+    return shl::bcast_launch<shl::OP_ADD>("add_bcast", a_dev, b_dev, out_dev, d, stream);
 }

@@ -26,11 +26,18 @@
 //                 nothing to any of the three sums, the constant term uses the true K.  Then f = (float)S * mult,
 //                 sat8(rint(f / s_out) + zp_out) with div_by_scale where mm_fma_ok admits the records.
 //                 binary16: exact products, float32 accumulation on the matrix cores, the reference's conversion.
+//
+// matmul + add(constant bias[N]) as one launch (shl_mi355x_matmul_bias; a session's STEP_MATMUL_BIAS): both kernels have a
+// second instantiation, BIAS, that differs in mm_store alone.  There the value the plain kernel would STORE -- the int8 byte
+// under the intermediate record, the rounded half -- stays in a register and goes through the add's own element function
+// (add_step.h) with bias[n], n the output's column: matmul followed by add, bit for bit, without the intermediate tensor's
+// trip through HBM.  The plain instantiations do not contain the epilogue.
 #include <stdlib.h>
 #include <string.h>
 
 #include <type_traits>
 
+#include "add_step.h"
 #include "igemm_common.h"
 #include "matmul_canon.h"  // the host side: validation, the exactness proof, the form rule (a stand-alone program compiles it too)
 
@@ -47,7 +54,12 @@ struct MmArgs {
     int64_t abs, ars, aks, bbs, brs, bks;  // strides in elements
     int32_t a_kc, b_kc, a_vec, b_vec;
     int32_t iza, izb, div_fma, tiles_m, tiles_n;
-    float sa, za, sb, zb, so, zo, inv_so, mult;
+    float sa, za, sb, zb, so, zo, inv_so, mult;  // so, zo: the record the product is stored under (BIAS: the intermediate's)
+    // BIAS only: the bias (N elements), the add's records (a: the intermediate, b: the bias) and whether the bias is the add
+    // layer's first input
+    const void *bias;
+    AddRec add;
+    int32_t bias_first;
 };
 
 template <bool F16>
@@ -76,19 +88,28 @@ __device__ __forceinline__ float mm_step(float acc, float x, float y)
     else return r;
 }
 
-template <bool F16>
-__device__ __forceinline__ void mm_store(const MmArgs &a, int64_t o, float f)
+// braw: the raw bias element of the output's column (BIAS only).  The kernels fetch it BEFORE their K loop: a lane's outputs
+// share one column, and a load issued between the stores would have to wait for each of them (the pointers may alias)
+template <bool F16, bool BIAS = false>
+__device__ __forceinline__ void mm_store(const MmArgs &a, int64_t o, float f, uint32_t braw = 0)
 {
     if constexpr (F16) {
-        if (f != f) static_cast<uint16_t *>(a.out)[o] = (__float_as_uint(f) >> 31) ? 0xFFFFu : 0x7FFFu;
-        else static_cast<uint16_t *>(a.out)[o] = float_to_f16_bits_ref(f);
+        const uint16_t h = f != f ? ((__float_as_uint(f) >> 31) ? 0xFFFFu : 0x7FFFu) : float_to_f16_bits_ref(f);
+        if constexpr (BIAS) {
+            const uint16_t hb = (uint16_t)braw;
+            static_cast<uint16_t *>(a.out)[o] = a.bias_first ? add_f16_step(hb, h) : add_f16_step(h, hb);
+        } else {
+            static_cast<uint16_t *>(a.out)[o] = h;
+        }
     } else {
         const float d = a.div_fma ? div_by_scale(f, a.so, a.inv_so) : __fdiv_rn(f, a.so);
-        static_cast<int8_t *>(a.out)[o] = (int8_t)sat8_from_float(__fadd_rn(rintf(d), a.zo));  // float_to_int8_base
+        const int q = sat8_from_float(__fadd_rn(rintf(d), a.zo));  // float_to_int8_base
+        if constexpr (BIAS) static_cast<int8_t *>(a.out)[o] = (int8_t)add_i8_step(q, (int8_t)braw, a.add);
+        else static_cast<int8_t *>(a.out)[o] = (int8_t)q;
     }
 }
 
-template <bool F16>
+template <bool F16, bool BIAS = false>
 __global__ __launch_bounds__(256) void matmul_chain_kernel(MmArgs a)
 {
     constexpr int B = 8;  // loads in flight ahead of the additions
@@ -98,6 +119,8 @@ __global__ __launch_bounds__(256) void matmul_chain_kernel(MmArgs a)
     const uint32_t bi = (uint32_t)o / mn, r = (uint32_t)o - bi * mn;
     const uint32_t m = r / (uint32_t)a.N, n = r - m * (uint32_t)a.N;
     const int64_t pa = (int64_t)bi * a.abs + (int64_t)m * a.ars, pb = (int64_t)bi * a.bbs + (int64_t)n * a.brs;
+    uint32_t braw = 0;
+    if constexpr (BIAS) braw = mm_load<F16>(a.bias, n);
     float acc = 0.0f;
     int32_t k = 0;
     for (; k + B <= a.K; k += B) {
@@ -113,7 +136,7 @@ __global__ __launch_bounds__(256) void matmul_chain_kernel(MmArgs a)
     for (; k < a.K; ++k)
         acc = mm_step<F16>(acc, mm_cvt<F16>(mm_load<F16>(a.a, pa + (int64_t)k * a.aks), a.za, a.sa),
                            mm_cvt<F16>(mm_load<F16>(a.b, pb + (int64_t)k * a.bks), a.zb, a.sb));
-    mm_store<F16>(a, o, acc);
+    mm_store<F16, BIAS>(a, o, acc, braw);
 }
 
 // ---- the mfma form ---------------------------------------------------------------------------------------------------------
@@ -158,7 +181,7 @@ __device__ __forceinline__ void mm_put(char *lds, const uint4 &v, int kc, int ti
         *reinterpret_cast<E *>(lds + (r0 + e) * MM_PITCH + kk * ES) = (E)(w[e * ES / 4] >> (8 * (e * ES % 4)));
 }
 
-template <bool F16>
+template <bool F16, bool BIAS = false>
 __global__ __launch_bounds__(256) void matmul_mfma_kernel(MmArgs a)
 {
     using Acc = typename AccT<!F16>::type;
@@ -175,6 +198,11 @@ __global__ __launch_bounds__(256) void matmul_mfma_kernel(MmArgs a)
     const void *pb = static_cast<const char *>(a.b) + (int64_t)bi * a.bbs * ES;
     const int64_t a_os = a.a_kc ? a.ars : a.aks, b_os = a.b_kc ? a.brs : a.bks;
 
+    uint32_t braw = 0;  // the lane's column of the output is one for all its sixteen outputs
+    if constexpr (BIAS) {
+        const int col = n0 + wn * 32 + fr;
+        if (col < a.N) braw = mm_load<F16>(a.bias, col);
+    }
     Acc acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0;
@@ -224,17 +252,25 @@ __global__ __launch_bounds__(256) void matmul_mfma_kernel(MmArgs a)
         if (m >= a.M || n >= a.N) continue;
         const int64_t o = ((int64_t)bi * a.M + m) * a.N + n;
         if constexpr (F16) {
-            mm_store<true>(a, o, acc[r]);
+            mm_store<true, BIAS>(a, o, acc[r], braw);
         } else {
             // (every term and the true sum fit 32 bits; unsigned arithmetic, so that no intermediate wrap is undefined)
             const uint32_t S = (uint32_t)acc[r] - (uint32_t)(a.izb * row_sum[wave][row]) - (uint32_t)(a.iza * cs) + (uint32_t)kzz;
-            mm_store<false>(a, o, __fmul_rn((float)(int32_t)S, a.mult));
+            mm_store<false, BIAS>(a, o, __fmul_rn((float)(int32_t)S, a.mult), braw);
         }
     }
 }
 
 // ---- host side (validation, the proof and the form rule are in matmul_canon.h) -----------------------------------------
-static int matmul_launch(const void *a_dev, const void *b_dev, void *out_dev, const shl_mi355x_matmul_desc *d, hipStream_t s)
+// the fused bias of shl_mi355x_matmul_bias: NULL for the plain product
+struct MmBias {
+    const void *dev;
+    float scale, mid_scale;
+    int32_t zp, mid_zp, first;
+};
+
+static int matmul_launch(const void *a_dev, const void *b_dev, void *out_dev, const shl_mi355x_matmul_desc *d, const MmBias *bias,
+                         hipStream_t s)
 {
     const bool f16 = d->dtype == SHL_MI355X_F16;
     MmPlan p;
@@ -252,14 +288,25 @@ static int matmul_launch(const void *a_dev, const void *b_dev, void *out_dev, co
     a.iza = d->a_zp, a.izb = d->b_zp;
     a.mult = d->a_scale * d->b_scale;  // rounded once, here
     a.div_fma = !f16 && mm_fma_ok(d);
+    if (bias) {
+        // the product is stored under the intermediate's record, the descriptor's output record is the add's
+        shl_mi355x_matmul_desc mid = *d;
+        mid.out_scale = bias->mid_scale, mid.out_zp = bias->mid_zp;
+        a.so = mid.out_scale, a.zo = (float)mid.out_zp, a.inv_so = 1.0f / mid.out_scale;
+        a.div_fma = !f16 && mm_fma_ok(&mid);
+        a.bias = bias->dev, a.bias_first = bias->first ? 1 : 0;
+        a.add = add_rec(bias->mid_scale, bias->mid_zp, bias->scale, bias->zp, d->out_scale, d->out_zp);
+    }
     a.tiles_m = (d->m + MM_T - 1) / MM_T, a.tiles_n = (d->n + MM_T - 1) / MM_T;
     if (form == MM_MFMA) {
         const int64_t groups = (int64_t)d->batches * a.tiles_m * a.tiles_n;  // (at most the output's element count)
         const dim3 grid((unsigned)groups), block(256);
-        hipLaunchKernelGGL(f16 ? matmul_mfma_kernel<true> : matmul_mfma_kernel<false>, grid, block, 0, s, a);
+        if (bias) hipLaunchKernelGGL((f16 ? matmul_mfma_kernel<true, true> : matmul_mfma_kernel<false, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL(f16 ? matmul_mfma_kernel<true> : matmul_mfma_kernel<false>, grid, block, 0, s, a);
     } else {
         const dim3 grid((unsigned)((d->out_elems + 255) / 256)), block(256);
-        hipLaunchKernelGGL(f16 ? matmul_chain_kernel<true> : matmul_chain_kernel<false>, grid, block, 0, s, a);
+        if (bias) hipLaunchKernelGGL((f16 ? matmul_chain_kernel<true, true> : matmul_chain_kernel<false, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL(f16 ? matmul_chain_kernel<true> : matmul_chain_kernel<false>, grid, block, 0, s, a);
     }
     SHL_HIP(hipGetLastError());
     return SHL_MI355X_OK;
@@ -288,5 +335,30 @@ extern "C" int shl_mi355x_matmul(const void *a_dev, const void *b_dev, void *out
         set_error("matmul: %s", why);
         return SHL_MI355X_EINVAL;
     }
-    return matmul_launch(a_dev, b_dev, out_dev, d, (hipStream_t)stream);
+    return matmul_launch(a_dev, b_dev, out_dev, d, NULL, (hipStream_t)stream);
+}
+
+extern "C" const char *shl_mi355x_matmul_bias_kernel_name(const void *a_dev, const void *b_dev, const void *bias_dev,
+                                                          const void *out_dev, const struct shl_mi355x_matmul_desc *d)
+{
+    using namespace shl;
+    if (mm_validate(a_dev, b_dev, out_dev, d) || mm_validate_bias(bias_dev, out_dev, d)) return "";
+    MmPlan p;
+    mm_plan(a_dev, b_dev, d, &p);
+    return mm_form(d, &p) == MM_MFMA ? SHL_MI355X_MATMUL_MFMA_BIAS : SHL_MI355X_MATMUL_CHAIN_BIAS;
+}
+
+extern "C" int shl_mi355x_matmul_bias(const void *a_dev, const void *b_dev, const void *bias_dev, void *out_dev,
+                                      const struct shl_mi355x_matmul_desc *d, float bias_scale, int32_t bias_zp, float mid_scale,
+                                      int32_t mid_zp, int32_t bias_is_first, void *stream)
+{
+    using namespace shl;
+    const char *why = mm_validate(a_dev, b_dev, out_dev, d);
+    if (!why) why = mm_validate_bias(bias_dev, out_dev, d);
+    if (why) {
+        set_error("matmul_bias: %s", why);
+        return SHL_MI355X_EINVAL;
+    }
+    const MmBias bias = {bias_dev, bias_scale, mid_scale, bias_zp, mid_zp, bias_is_first};
+    return matmul_launch(a_dev, b_dev, out_dev, d, &bias, (hipStream_t)stream);
 }

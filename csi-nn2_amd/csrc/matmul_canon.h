@@ -64,6 +64,18 @@ static inline const char *mm_validate(const void *a_dev, const void *b_dev, cons
     return NULL;
 }
 
+// the bias of shl_mi355x_matmul_bias, for a descriptor mm_validate has passed: n elements of the descriptor's dtype
+static inline const char *mm_validate_bias(const void *bias_dev, const void *out_dev, const shl_mi355x_matmul_desc *d)
+{
+    if (!bias_dev) return "NULL argument";
+    const int64_t es = d->dtype == SHL_MI355X_F16 ? 2 : 1;
+    const uintptr_t c0 = (uintptr_t)bias_dev, c1 = c0 + (uintptr_t)(d->n * es), o0 = (uintptr_t)out_dev, o1 = o0 + (uintptr_t)(d->out_elems * es);
+    if (c0 & (uintptr_t)(es - 1)) return "a pointer that is not aligned to its elements";
+    if (c1 < c0) return "a buffer that wraps around the address space";
+    if (c0 < o1 && o0 < c1) return "the output overlaps the bias";
+    return NULL;
+}
+
 // a float32 scale as m 2^e with m odd: false for zero, NaN and infinities
 static inline bool mm_odd_mantissa(float s, int64_t *m, int *e)
 {

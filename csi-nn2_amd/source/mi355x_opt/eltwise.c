@@ -172,28 +172,29 @@ int shl_mi355x_leaky_relu_perf(struct csinn_tensor *input, struct csinn_tensor *
     return unary_perf(SHL_MI355X_UNARY_LEAKY_RELU, input, output, info);
 }
 
-/* ---- mul ------------------------------------------------------------------------------------------------------ */
+/* ---- mul, and the broadcasting add (pooling.c) ------------------------------------------------------------------ */
 /* Which operand has the output's shape (*full) and which is broadcast to it (*small), and the descriptor of the pair.
  * The rule is shl_ref_broadcast_to_shape_f32's (source/reference/utils.c:692-785): ranks right-aligned, every dim of an
- * operand equals the output's or is 1.  The fp32 product is commutative, so the operands may swap. */
-static int mul_prepare(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
-                       struct csinn_tensor **full, struct csinn_tensor **small, struct shl_mi355x_mul_desc *desc)
+ * operand equals the output's or is 1.  The fp32 product and sum are commutative, so the operands may swap.  `op`: "mul" or
+ * "add", for the messages */
+int shl_mi355x_bcast_prepare(const char *op, struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
+                             struct csinn_tensor **full, struct csinn_tensor **small, struct shl_mi355x_mul_desc *desc)
 {
     int dtype = -1;
-    int rc = shl_mi355x_check_tensor("mul", "first input", input0, &dtype);
-    if (rc == CSINN_TRUE) rc = shl_mi355x_check_tensor("mul", "second input", input1, &dtype);
-    if (rc == CSINN_TRUE) rc = shl_mi355x_check_tensor("mul", "output", output, &dtype);
+    int rc = shl_mi355x_check_tensor(op, "first input", input0, &dtype);
+    if (rc == CSINN_TRUE) rc = shl_mi355x_check_tensor(op, "second input", input1, &dtype);
+    if (rc == CSINN_TRUE) rc = shl_mi355x_check_tensor(op, "output", output, &dtype);
     if (rc != CSINN_TRUE) return rc;
     const int rank = output->dim_count;
     if (rank < 1 || rank > MAX_DIM) {
-        shl_debug_error("mul: a %d-d output\n", rank);
+        shl_debug_error("%s: a %d-d output\n", op, rank);
         return CSINN_FALSE;
     }
     struct csinn_tensor *in[2] = {input0, input1};
     int same[2];
     for (int k = 0; k < 2; k++) {
         if (in[k]->dim_count < 1 || in[k]->dim_count > rank) {
-            shl_debug_error("mi355x: mul: a %d-d operand cannot be broadcast to the %d-d output\n", in[k]->dim_count, rank);
+            shl_debug_error("mi355x: %s: a %d-d operand cannot be broadcast to the %d-d output\n", op, in[k]->dim_count, rank);
             return CSINN_FALSE;
         }
         same[k] = 1;
@@ -201,14 +202,14 @@ static int mul_prepare(struct csinn_tensor *input0, struct csinn_tensor *input1,
             const int j = i - (rank - in[k]->dim_count);
             const int32_t d = j >= 0 ? in[k]->dim[j] : 1;
             if (d != output->dim[i] && d != 1) {
-                shl_debug_error("mi355x: mul: dim %d of operand %d is %d, the output's %d: not a broadcast\n", j, k, d, output->dim[i]);
+                shl_debug_error("mi355x: %s: dim %d of operand %d is %d, the output's %d: not a broadcast\n", op, j, k, d, output->dim[i]);
                 return CSINN_FALSE;
             }
             if (d != output->dim[i]) same[k] = 0;
         }
     }
     if (!same[0] && !same[1]) {
-        shl_debug_error("mi355x: mul: both operands need broadcasting, which is not supported\n");
+        shl_debug_error("mi355x: %s: both operands need broadcasting, which is not supported\n", op);
         return CSINN_FALSE;
     }
     const int s = same[0] ? 1 : 0; /* the broadcast operand (or the second of two full ones) */
@@ -229,7 +230,7 @@ static int mul_prepare(struct csinn_tensor *input0, struct csinn_tensor *input1,
             continue;
         }
         if (ng == 4) {
-            shl_debug_error("mi355x: mul: the broadcast pattern has more than 4 groups of dims\n");
+            shl_debug_error("mi355x: %s: the broadcast pattern has more than 4 groups of dims\n", op);
             return CSINN_FALSE;
         }
         cls[ng] = varies;
@@ -259,7 +260,7 @@ int shl_mi355x_mul_exec(struct csinn_tensor *input0, struct csinn_tensor *input1
 {
     struct csinn_tensor *full, *small;
     struct shl_mi355x_mul_desc d;
-    int rc = mul_prepare(input0, input1, output, &full, &small, &d);
+    int rc = shl_mi355x_bcast_prepare("mul", input0, input1, output, &full, &small, &d);
     if (rc != CSINN_TRUE) return rc;
     if (csinn_tensor_size(output) == 0) return CSINN_TRUE;
     /* the inputs are staged in their own order, whichever of them is the broadcast one */
@@ -276,7 +277,7 @@ int shl_mi355x_mul_perf(struct csinn_tensor *input0, struct csinn_tensor *input1
     (void)params;
     struct csinn_tensor *full, *small;
     struct shl_mi355x_mul_desc d;
-    int rc = mul_prepare(input0, input1, output, &full, &small, &d);
+    int rc = shl_mi355x_bcast_prepare("mul", input0, input1, output, &full, &small, &d);
     if (rc != CSINN_TRUE) return rc;
     uintptr_t at = SHL_MI355X_PERF_BASE;
     const void *in[2];

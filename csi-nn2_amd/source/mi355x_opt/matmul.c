@@ -89,6 +89,26 @@ int shl_mi355x_matmul_exec(struct csinn_tensor *mat0, struct csinn_tensor *mat1,
     return shl_mi355x_staged_end("matmul", &s, output, st);
 }
 
+/* session.c: the matmul layer (mat0, mat1, params; `mid` its output tensor) and the add of the constant `bias` behind it
+ * (`output` the add's output) as ONE launch on device buffers; bias_is_first: the bias is the add's first input */
+int shl_mi355x_matmul_bias_forward(struct csinn_tensor *mat0, struct csinn_tensor *mat1, struct csinn_tensor *mid,
+                                   struct csinn_tensor *bias, struct csinn_tensor *output, struct csinn_matmul_params *params,
+                                   int bias_is_first, const void *a_dev, const void *b_dev, const void *bias_dev, void *out_dev,
+                                   void *stream)
+{
+    struct shl_mi355x_matmul_desc d;
+    int rc = matmul_prepare(mat0, mat1, mid, params, &d);
+    if (rc != CSINN_TRUE) return rc;
+    d.out_scale = output->qinfo->scale, d.out_zp = output->qinfo->zero_point;
+    int st = shl_mi355x_matmul_bias(a_dev, b_dev, bias_dev, out_dev, &d, bias->qinfo->scale, bias->qinfo->zero_point,
+                                    mid->qinfo->scale, mid->qinfo->zero_point, bias_is_first, stream);
+    if (st != SHL_MI355X_OK) {
+        shl_debug_error("mi355x: matmul + bias failed (%d): %s\n", st, shl_mi355x_last_error());
+        return CSINN_FALSE;
+    }
+    return CSINN_TRUE;
+}
+
 int shl_mi355x_matmul_perf(struct csinn_tensor *mat0, struct csinn_tensor *mat1, struct csinn_tensor *output,
                            struct csinn_matmul_params *params, struct csinn_perf_info *info)
 {

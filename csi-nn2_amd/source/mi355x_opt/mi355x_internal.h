@@ -149,13 +149,24 @@ SISO_INIT(global_maxpool2d, csinn_pool_params)
 SISO_PERF(global_maxpool2d, csinn_pool_params)
 #undef SISO_INIT
 #undef SISO_PERF
-/* the other call shapes: mul (eltwise.c), matmul (matmul.c), concat (pooling.c), split (split.c) */
+/* the other call shapes: mul (eltwise.c), add (pooling.c), matmul (matmul.c), concat (pooling.c), split (split.c) */
 int shl_mi355x_mul_perf(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
                         struct csinn_diso_params *params, struct csinn_perf_info *info);
+int shl_mi355x_add_perf(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
+                        struct csinn_diso_params *params, struct csinn_perf_info *info);
+/* eltwise.c: the broadcast geometry of a two-operand layer (`op`: "mul" / "add", for the messages): which operand has the
+ * output's shape, which is broadcast to it, and the descriptor of the pair; refuses with a message what the kernels do not take */
+int shl_mi355x_bcast_prepare(const char *op, struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
+                             struct csinn_tensor **full, struct csinn_tensor **small, struct shl_mi355x_mul_desc *desc);
 int shl_mi355x_matmul_init(struct csinn_tensor *mat0, struct csinn_tensor *mat1, struct csinn_tensor *output,
                            struct csinn_matmul_params *params);
 int shl_mi355x_matmul_perf(struct csinn_tensor *mat0, struct csinn_tensor *mat1, struct csinn_tensor *output,
                            struct csinn_matmul_params *params, struct csinn_perf_info *info);
+/* matmul.c, for session.c: a matmul layer and the add of a constant bias behind it as one launch on device buffers */
+int shl_mi355x_matmul_bias_forward(struct csinn_tensor *mat0, struct csinn_tensor *mat1, struct csinn_tensor *mid,
+                                   struct csinn_tensor *bias, struct csinn_tensor *output, struct csinn_matmul_params *params,
+                                   int bias_is_first, const void *a_dev, const void *b_dev, const void *bias_dev, void *out_dev,
+                                   void *stream);
 int shl_mi355x_concat_perf(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params,
                            struct csinn_perf_info *info);
 int shl_mi355x_split_init(struct csinn_tensor *input, struct csinn_tensor **output, struct csinn_split_params *params);

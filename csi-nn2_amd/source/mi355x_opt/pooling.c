@@ -2,7 +2,7 @@
  * pooling.c -- global_avgpool2d and softmax callbacks of the MI355X backend: the two operators
  * between MobileNetV1's last pointwise convolution and its output (SURVEY 8f1;
  * example/c906_mobilenetv1_f16.c:1805-1886 of the reference); the windowed maxpool2d / avgpool2d (ResNet's stem
- * pool, Inception-style average pools); the residual add; concat (the end of every Fire module and Inception block).
+ * pool, Inception-style average pools); add (residual, and with one operand broadcast); concat (the end of every Fire module and Inception block).
  *
  * exec(input, output, params) with the reference's signatures
  * (source/reference/global_averagepool.c:46-50, maxpool.c:113-124, averagepool.c:127-138, softmax.c:68-72,
@@ -151,35 +151,74 @@ int shl_mi355x_softmax_exec(struct csinn_tensor *input, struct csinn_tensor *out
     return shl_mi355x_staged_end("softmax", &s, output, st);
 }
 
-/* residual add, two same-shape inputs (source/reference/add.c:21-41); shapes that would need the
- * reference's broadcasting are refused so that they fall to an error rather than a wrong answer */
-int shl_mi355x_add_exec(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
-                        struct csinn_diso_params *params)
+/* add (source/reference/add.c:21-41).  Two same-shape inputs (the residual add) go to shl_mi355x_add; a layer with one
+ * operand broadcast to the other (a bias, a mask, a positional embedding) to shl_mi355x_add_bcast, by mul's geometry rule
+ * (eltwise.c).  add_check: CSINN_TRUE with *same_shape set, or the status to return */
+static int add_check(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output, int *dtype,
+                     int *same_shape)
 {
-    int dtype;
-    int rc = shl_mi355x_check_io("add", input0, output, &dtype);
+    int rc = shl_mi355x_check_io("add", input0, output, dtype);
     if (rc != CSINN_TRUE) return rc;
     /* (every defect of the second input is CSINN_UNSUPPORT_DTYPE, unlike shl_mi355x_check_tensor's statuses) */
-    if (shl_mi355x_dtype_code(input1) != dtype || input1->qinfo == NULL || input1->quant_channel > 1 ||
-        (dtype == SHL_MI355X_F16 && input1->qinfo->scale != 1.0f)) {
+    if (shl_mi355x_dtype_code(input1) != *dtype || input1->qinfo == NULL || input1->quant_channel > 1 ||
+        (*dtype == SHL_MI355X_F16 && input1->qinfo->scale != 1.0f)) {
         shl_debug_error("mi355x: add: second input dtype / quantisation unsupported\n");
         return CSINN_UNSUPPORT_DTYPE;
     }
-    if (input0->dim_count != input1->dim_count || input0->dim_count != output->dim_count) {
-        shl_debug_error("mi355x: add: broadcasting is not supported\n");
-        return CSINN_FALSE;
-    }
-    for (int i = 0; i < input0->dim_count; i++)
-        if (input0->dim[i] != input1->dim[i] || input0->dim[i] != output->dim[i]) {
-            shl_debug_error("mi355x: add: broadcasting is not supported\n");
-            return CSINN_FALSE;
-        }
+    *same_shape = input0->dim_count == input1->dim_count && input0->dim_count == output->dim_count;
+    for (int i = 0; *same_shape && i < input0->dim_count; i++)
+        *same_shape = input0->dim[i] == input1->dim[i] && input0->dim[i] == output->dim[i];
+    return CSINN_TRUE;
+}
+
+int shl_mi355x_add_exec(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
+                        struct csinn_diso_params *params)
+{
+    int dtype, same_shape;
+    int rc = add_check(input0, input1, output, &dtype, &same_shape);
+    if (rc != CSINN_TRUE) return rc;
     struct shl_mi355x_staged s;
+    if (same_shape) {
+        if (shl_mi355x_staged_begin(&params->base, input0, input1, output, &s) != CSINN_TRUE) return CSINN_FALSE;
+        int st = shl_mi355x_add(s.in[0], s.in[1], s.out, (size_t)csinn_tensor_size(output), dtype, input0->qinfo->scale,
+                                input0->qinfo->zero_point, input1->qinfo->scale, input1->qinfo->zero_point,
+                                output->qinfo->scale, output->qinfo->zero_point, s.stream);
+        return shl_mi355x_staged_end("add", &s, output, st);
+    }
+    struct csinn_tensor *full, *small;
+    struct shl_mi355x_mul_desc d;
+    rc = shl_mi355x_bcast_prepare("add", input0, input1, output, &full, &small, &d);
+    if (rc != CSINN_TRUE) return rc;
+    if (csinn_tensor_size(output) == 0) return CSINN_TRUE;
+    /* the inputs are staged in their own order, whichever of them is the broadcast one */
     if (shl_mi355x_staged_begin(&params->base, input0, input1, output, &s) != CSINN_TRUE) return CSINN_FALSE;
-    int st = shl_mi355x_add(s.in[0], s.in[1], s.out, (size_t)csinn_tensor_size(output), dtype, input0->qinfo->scale,
-                            input0->qinfo->zero_point, input1->qinfo->scale, input1->qinfo->zero_point,
-                            output->qinfo->scale, output->qinfo->zero_point, s.stream);
+    const int a = full == input0 ? 0 : 1;
+    int st = shl_mi355x_add_bcast(s.in[a], s.in[1 - a], s.out, &d, s.stream);
     return shl_mi355x_staged_end("add", &s, output, st);
+}
+
+/* a broadcasting layer: the form the rule chooses; a same-shape one: the name under its params block (there is none: "") */
+int shl_mi355x_add_perf(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
+                        struct csinn_diso_params *params, struct csinn_perf_info *info)
+{
+    int dtype, same_shape;
+    int rc = add_check(input0, input1, output, &dtype, &same_shape);
+    if (rc != CSINN_TRUE) return rc;
+    if (same_shape) {
+        info->kernel_name = (char *)shl_mi355x_params_kernel_name(params);
+        return CSINN_TRUE;
+    }
+    struct csinn_tensor *full, *small;
+    struct shl_mi355x_mul_desc d;
+    rc = shl_mi355x_bcast_prepare("add", input0, input1, output, &full, &small, &d);
+    if (rc != CSINN_TRUE) return rc;
+    uintptr_t at = SHL_MI355X_PERF_BASE;
+    const void *in[2];
+    in[0] = (const void *)shl_mi355x_perf_address(input0, &at), in[1] = (const void *)shl_mi355x_perf_address(input1, &at);
+    const int a = full == input0 ? 0 : 1;
+    info->kernel_name =
+        (char *)shl_mi355x_add_bcast_kernel_name(&d, in[a], in[1 - a], (const void *)shl_mi355x_perf_address(output, &at));
+    return CSINN_TRUE;
 }
 
 /* concat (source/reference/concat.c:21-76): a variable number of inputs.  The reference trusts the shapes; here a

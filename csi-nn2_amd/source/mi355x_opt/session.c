@@ -41,6 +41,7 @@ enum step_kind {
     STEP_PWDW,      /* a pointwise and a depthwise layer, in either order (shl_mi355x_pwdw_forward) */
     STEP_POOL_CONV, /* global_avgpool2d a + the convolution / fullyconnected layer b on the pooled map */
     STEP_CONV_POOL, /* 1x1 convolution a + global_avgpool2d b */
+    STEP_MATMUL_BIAS, /* matmul a + the add b of a constant bias [N] to its output (shl_mi355x_matmul_bias) */
 };
 
 struct step {
@@ -61,6 +62,7 @@ struct dev_session {
     int nsteps;
     int nfused, nfolded;
     int npool; /* global_avgpool2d layers that run inside their consumer's launch */
+    int nlinear; /* matmul layers that add the constant bias behind them in their own launch */
     struct dev_session *next;
 };
 
@@ -180,10 +182,37 @@ static int consumers_of(struct shl_ref_graph *g, struct shl_node *tensor)
     return consumers;
 }
 
+/* matmul a -> add b, the add's other operand a constant whose only dim that is not 1 is the last and equals N ([N], [1,N],
+ * [1,1,N], ...): the index (0 or 1) of that constant among the add's inputs, -1 when the pair does not fuse.  The add must be
+ * a broadcasting one that the backend takes (one record per tensor, equal dtypes) and reads `mid` once */
+static int linear_bias_input(struct shl_node *a, struct shl_node *b, struct shl_node *mid)
+{
+    if (a->type != CSINN_OP_MATMUL || b->type != CSINN_OP_ADD || session_op(a) == NULL || session_op(b) == NULL) return -1;
+    if (a->in_num != 2 || b->in_num != 2 || (b->in[0] == mid) == (b->in[1] == mid)) return -1;
+    const int k = b->in[0] == mid ? 1 : 0;
+    struct csinn_tensor *c = b->in[k]->data, *tm = mid->data, *out = b->out[0]->data;
+    if (!c->is_const || c->data == NULL || c->dim_count < 1 || tm->dim_count < 2 || out->dim_count != tm->dim_count) return -1;
+    const int32_t n = tm->dim[tm->dim_count - 1];
+    if (c->dim[c->dim_count - 1] != n || n < 2) return -1;
+    for (int i = 0; i < c->dim_count - 1; i++)
+        if (c->dim[i] != 1) return -1;
+    int64_t rows = 1;
+    for (int i = 0; i < tm->dim_count; i++) {
+        if (out->dim[i] != tm->dim[i]) return -1;
+        if (i < tm->dim_count - 1) rows *= tm->dim[i];
+    }
+    if (rows < 2) return -1; /* (one row: a same-shape add, which has its own kernel) */
+    struct csinn_tensor *full, *small;
+    struct shl_mi355x_mul_desc d;
+    return shl_mi355x_bcast_prepare("add", b->in[0]->data, b->in[1]->data, out, &full, &small, &d) == CSINN_TRUE && small == c ? k : -1;
+}
+
 /* can steps `s` and `next` (adjacent, each still one layer) run as one launch, and as which?  STEP_LAYER: no */
 static enum step_kind merged_kind(struct shl_ref_graph *g, const struct step *s, const struct step *next)
 {
     struct shl_node *a = g->layer[s->a], *b = g->layer[next->a], *mid = s->out;
+    /* a linear layer as converters export it: MatMul(x, W) -> Add(., bias[N]), the bias on either side of the add */
+    if (consumers_of(g, mid) == 1 && linear_bias_input(a, b, mid) >= 0) return STEP_MATMUL_BIAS;
     if (b->in[0] != mid || consumers_of(g, mid) != 1) return STEP_LAYER;
     /* global_avgpool2d -> the convolution / fullyconnected layer on the pooled map: one launch (csrc/conv_gemv.hip) */
     if (a->type == CSINN_OP_GLOBAL_AVGPOOL2D && (is_conv_op(b->type) || b->type == CSINN_OP_FULLYCONNECTED)) {
@@ -226,6 +255,9 @@ static enum step_kind merged_kind(struct shl_ref_graph *g, const struct step *s,
  *   depthwise 3x3 -> 1x1 convolution   one launch of csrc/dwpw_stream.hip at throughput batches (32 / 64 / 128 / 256 channels:
  *        the requantised depthwise tile is the pointwise MFMA operand); the latency form of this pairing recomputed the
  *        depthwise tile in every channel slice and is parked (attic/README.md)
+ *   matmul -> add of a constant bias [N], the matmul's only consumer   one launch of csrc/matmul.hip's BIAS instantiation
+ *        (STEP_MATMUL_BIAS): the linear layer a converter exports as MatMul + Add; the add's arithmetic runs on the value the
+ *        matmul would have stored, so the step equals the two layers bit for bit
  * Fills ds->steps. */
 static int plan_fusion(struct dev_session *ds, struct shl_ref_graph *g)
 {
@@ -268,14 +300,17 @@ static int plan_fusion(struct dev_session *ds, struct shl_ref_graph *g)
         }
         shl_mi355x_conv_plan_set_no_stream_consumer(pa, !streams);
     }
-    /* merge adjacent steps greedily from the front; a merged step is not the first half of another merge */
+    /* merge adjacent steps greedily from the front; a merged step is not the first half of another merge
+     * (SHL_MI355X_NO_FUSION=1 also keeps a matmul and its bias add apart: the switch of the linear fusion's A/B runs) */
     for (int k = 0; k < ns; k++) {
         struct step s = steps[k];
-        const enum step_kind kind = k + 1 < ns ? merged_kind(g, &s, &steps[k + 1]) : STEP_LAYER;
+        enum step_kind kind = k + 1 < ns ? merged_kind(g, &s, &steps[k + 1]) : STEP_LAYER;
+        if (kind == STEP_MATMUL_BIAS && !fold) kind = STEP_LAYER;
         if (kind != STEP_LAYER) {
             k++; /* the second step is taken */
             s = (struct step){kind, s.a, steps[k].a, steps[k].out};
             if (kind == STEP_PWDW) ds->nfused++;
+            else if (kind == STEP_MATMUL_BIAS) ds->nlinear++;
             else ds->npool++;
         }
         steps[ds->nsteps++] = s;
@@ -348,6 +383,15 @@ static int enqueue_layers(struct dev_session *ds, struct shl_ref_graph *g)
                 rc = status_of(shl_mi355x_conv_pool_forward(shl_mi355x_registry_get(n->data), in->dev, NULL, out->dev, batch,
                                                             pmid->qinfo->scale, pmid->qinfo->zero_point, pout->qinfo->scale,
                                                             pout->qinfo->zero_point, ds->stream));
+                break;
+            }
+            case STEP_MATMUL_BIAS: {
+                const int kb = linear_bias_input(n, nx, n->out[0]);
+                struct dev_tensor *b = lookup(ds, n->in[1]), *bias = kb >= 0 ? lookup(ds, nx->in[kb]) : NULL;
+                rc = b && bias ? shl_mi355x_matmul_bias_forward(n->in[0]->data, n->in[1]->data, n->out[0]->data, nx->in[kb]->data,
+                                                                nx->out[0]->data, n->data, kb == 0, in->dev, b->dev, bias->dev,
+                                                                out->dev, ds->stream)
+                               : CSINN_FALSE;
                 break;
             }
             case STEP_PWDW:
@@ -587,6 +631,13 @@ int shl_mi355x_session_folded_activations(struct csinn_session *sess)
 {
     struct dev_session *ds = find_session(sess);
     return ds ? ds->nfolded : 0;
+}
+
+/* number of matmul layers of `sess` that add the constant bias behind them inside their own launch */
+int shl_mi355x_session_fused_linears(struct csinn_session *sess)
+{
+    struct dev_session *ds = find_session(sess);
+    return ds ? ds->nlinear : 0;
 }
 
 /* 2 when `sess` executes as one device-resident hipGraph, 1 when device-resident with every run enqueueing its layers

@@ -77,8 +77,8 @@ static const struct shl_mi355x_op g_ops[] = {
     {CSINN_OP_MAXPOOL2D, BOTH, NULL, shl_mi355x_maxpool2d_exec, shl_gref_maxpool2d, shl_mi355x_maxpool2d_perf, CALL_SISO, 1, 1},
     {CSINN_OP_AVGPOOL2D, BOTH, NULL, shl_mi355x_avgpool2d_exec, shl_gref_avgpool2d, shl_mi355x_avgpool2d_perf, CALL_SISO, 1, 1},
     {CSINN_OP_SOFTMAX, BOTH, NULL, shl_mi355x_softmax_exec, shl_gref_softmax, conv_perf, CALL_SISO, 1, 1},
-    /* the second operand may be a constant */
-    {CSINN_OP_ADD, BOTH, NULL, shl_mi355x_add_exec, shl_gref_add, conv_perf, CALL_DISO, 2, 1},
+    /* either operand may be a constant (a bias, a mask, a positional embedding) and may be broadcast to the other */
+    {CSINN_OP_ADD, BOTH, NULL, shl_mi355x_add_exec, shl_gref_add, shl_mi355x_add_perf, CALL_DISO, 2, 0},
     /* ... and may be broadcast (an SE gate, a per-channel scale) */
     {CSINN_OP_MUL, BOTH, NULL, shl_mi355x_mul_exec, shl_gref_mul, shl_mi355x_mul_perf, CALL_DISO, 2, 1},
     {CSINN_OP_SIGMOID, BOTH, NULL, shl_mi355x_sigmoid_exec, shl_gref_sigmoid, shl_mi355x_sigmoid_perf, CALL_SISO, 1, 1},

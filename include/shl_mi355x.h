@@ -686,6 +686,24 @@ const char *shl_mi355x_matmul_kernel_name(const void *a_dev, const void *b_dev, 
  * sum of the chain then is exact.  Depends on k and the records only.  0 otherwise, for binary16 and for a NULL descriptor */
 int shl_mi355x_matmul_is_exact(const struct shl_mi355x_matmul_desc *d);
 
+/* A linear layer as converters export it -- MatMul(x, W) followed by Add(., bias[n]) -- as ONE launch: shl_mi355x_matmul with
+ * the add in its store.  Per output the kernel computes the intermediate exactly as shl_mi355x_matmul would store it under
+ * the record (mid_scale, mid_zp) -- int8: sat8(rint(f / mid_scale) + mid_zp), binary16: the rounded half, NaN rule included
+ * -- keeps it in a register and applies shl_mi355x_add_bcast's arithmetic with bias[j], j the output's column, the same
+ * for every batch and row: by construction the result equals shl_mi355x_matmul followed by shl_mi355x_add_bcast bit for bit,
+ * in both forms and dtypes, whatever the records.  d->out_scale / out_zp are the record of the FINAL output (the add's),
+ * bias_scale / bias_zp the bias's; bias_is_first: the bias is the add layer's first input (of two binary16 NaNs the second
+ * input's goes through).  binary16 ignores every record.  bias_dev holds n elements of d's dtype; it must be aligned to its
+ * elements and must not overlap the output.  Validation and form rule are shl_mi355x_matmul's; the kernels report as
+ * "matmul_chain_bias" / "matmul_mfma_bias".  Enqueues only (capturable in a hipGraph). */
+#define SHL_MI355X_MATMUL_CHAIN_BIAS "matmul_chain_bias"
+#define SHL_MI355X_MATMUL_MFMA_BIAS "matmul_mfma_bias"
+int shl_mi355x_matmul_bias(const void *a_dev, const void *b_dev, const void *bias_dev, void *out_dev,
+                           const struct shl_mi355x_matmul_desc *d, float bias_scale, int32_t bias_zp, float mid_scale,
+                           int32_t mid_zp, int32_t bias_is_first, void *stream);
+const char *shl_mi355x_matmul_bias_kernel_name(const void *a_dev, const void *b_dev, const void *bias_dev, const void *out_dev,
+                                               const struct shl_mi355x_matmul_desc *d);
+
 /* nearest-neighbour / bilinear resize of a 4-d int8 / binary16 tensor: shl_ref_resize_quant
  * (source/reference/resize.c:464-468), bit for bit.  height_scale / width_scale are the reference's own floats, computed by
  * the CALLER as ONE float division each: (float)in / out, with align_corners (float)(in - 1) / (out - 1)
@@ -779,6 +797,18 @@ int shl_mi355x_mul(const void *a_dev, const void *b_dev, void *out_dev, const st
  * SHL_MI355X_MUL_FORM=generic forces it); "" for invalid arguments.  Pure host code: looks at the pointers' values only */
 const char *shl_mi355x_mul_kernel_name(const struct shl_mi355x_mul_desc *d, const void *a_dev, const void *b_dev,
                                        const void *out_dev);
+
+/* elementwise sum with one broadcast operand: shl_ref_add_quant (source/reference/add.c:21-41) on a layer whose operands
+ * differ in shape (a bias [.., N] + [N], an attention mask [B,H,T,T] + [1,H,T,T], a positional embedding): both operands
+ * dequantised, one fp32 sum, requantised; bit for bit.  Geometry, descriptor, validation and kernel forms are
+ * shl_mi355x_mul's ("add_vec", "add_row", "add_generic"; SHL_MI355X_ADD_FORM=generic forces the last).  a_is_second: a is
+ * the layer's second input (the sum commutes; of two binary16 NaNs the reference hands on its second input's, and
+ * inf + -inf comes out as 0xFFFF).  f16: scales and zero points are ignored.  Enqueues only: no allocation, no upload, no
+ * synchronisation (capturable in a hipGraph).  Two same-shape tensors may equally go through shl_mi355x_add. */
+int shl_mi355x_add_bcast(const void *a_dev, const void *b_dev, void *out_dev, const struct shl_mi355x_mul_desc *d, void *stream);
+/* the kernel form the rules choose, "" for invalid arguments.  Pure host code: looks at the pointers' values only */
+const char *shl_mi355x_add_bcast_kernel_name(const struct shl_mi355x_mul_desc *d, const void *a_dev, const void *b_dev,
+                                             const void *out_dev);
 
 /* softmax along one axis of a tensor viewed as [outer, count, inner]:
  * shl_ref_softmax_quant (source/reference/softmax.c:21-72): float max, double exp, float running

@@ -192,6 +192,8 @@ int shl_mi355x_session_fused_pairs(struct csinn_session *sess);
 int shl_mi355x_session_fused_pools(struct csinn_session *sess);
 /* relu / relu6 layers of `sess` that were folded into the epilogue of the convolution they follow */
 int shl_mi355x_session_folded_activations(struct csinn_session *sess);
+/* matmul layers of `sess` that run the add of a constant bias behind them inside their own launch (shl_mi355x_matmul_bias) */
+int shl_mi355x_session_fused_linears(struct csinn_session *sess);
 
 #ifdef __cplusplus
 }
