@@ -44,7 +44,7 @@ def _glob(d, exts):
 NO_SPILL_SOURCES = ("conv_igemm.hip", "conv_igemm_pp.hip", "conv_igemm_pc.hip",
                     "conv_igemm_halo.hip",
                     "dwpw_resident.hip",  # (its tile loop counts vector memory instructions: a scratch reload is one)
-                    "split.hip", "shuffle.hip",  # (pure data movement: scratch traffic would be most of their memory traffic)
+                    "slab.hip", "shuffle.hip",  # (pure data movement: scratch traffic would be most of their memory traffic)
                     "transpose.hip", "pad.hip",
                     "reduce.hip",  # (its chains wait on one addition per element: a scratch reload in the loop would double that)
                     "matmul.hip")  # (the chain likewise; the mfma form's K loop holds one slab's pieces in flight in registers)

@@ -22,7 +22,7 @@ static inline AddRec add_rec(float a_scale, int32_t a_zp, float b_scale, int32_t
     r.sa = a_scale, r.za = (float)a_zp, r.sb = b_scale, r.zb = (float)b_zp;
     r.so = out_scale, r.zo = (float)out_zp, r.inv_so = 1.0f / out_scale;
     const double bound = (128.0 + fabs((double)a_zp)) * fabs((double)a_scale) + (128.0 + fabs((double)b_zp)) * fabs((double)b_scale);
-    r.fma_div = out_scale >= 0x1p-40f && out_scale <= 0x1p40f && bound <= 0x1p60;  // (false for NaN)
+    r.fma_div = fma_div_ok(bound, out_scale);
     return r;
 }
 

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fma_div_ok.h"
 #include "shl_mi355x.h"
 
 namespace shl {

@@ -389,7 +389,7 @@ static int bcast_launch(const char *what, const void *a_dev, const void *b_dev, 
     // div_by_scale(p, so, RN(1 / so)) == p / so for every product (sum) these records can give (common.h; the range
     // conv_plan.hip:fma_division_ok admits: 2^-40 <= so <= 2^40, |p| <= 2^60, p finite)
     const double bound = (128.0 + fabs((double)d->a_zp)) * fabs((double)d->a_scale) * (128.0 + fabs((double)d->b_zp)) * fabs((double)d->b_scale);
-    m.fma_div = d->out_scale >= 0x1p-40f && d->out_scale <= 0x1p40f && bound <= 0x1p60;  // (false for NaN)
+    m.fma_div = fma_div_ok(bound, d->out_scale);
     if (OP == OP_ADD) m.fma_div = add_rec(d->a_scale, d->a_zp, d->b_scale, d->b_zp, d->out_scale, d->out_zp).fma_div;  // (the sum's bound)
     m.a_second = d->a_is_second ? 1 : 0;
     const int form = mul_form(OP, a_dev, b_dev, out_dev, d, &m.b_mode);

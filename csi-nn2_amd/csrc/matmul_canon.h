@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "fma_div_ok.h"
 #include "shl_mi355x.h"
 
 namespace shl {
@@ -114,9 +115,7 @@ static inline bool mm_is_exact(const shl_mi355x_matmul_desc *d)
 // |f| <= 2^60, f finite): |f| is at most k 255 255 |sa sb|, with a factor of two for the chain's roundings
 static inline bool mm_fma_ok(const shl_mi355x_matmul_desc *d)
 {
-    if (!(d->out_scale >= 0x1p-40f && d->out_scale <= 0x1p40f)) return false;
-    const double bound = 2.0 * (double)d->k * 65025.0 * fabs((double)d->a_scale) * fabs((double)d->b_scale);
-    return bound <= 0x1p60;  // also NaN
+    return fma_div_ok(2.0 * (double)d->k * 65025.0 * fabs((double)d->a_scale) * fabs((double)d->b_scale), d->out_scale);
 }
 
 static inline void mm_plan(const void *a_dev, const void *b_dev, const shl_mi355x_matmul_desc *d, MmPlan *p)

@@ -33,8 +33,7 @@ struct PadArgs {
     int64_t oe[4], ie[4], bf[4];  // output extents, input extents, leading pads; the innermost in the form's unit
     int64_t items;
     uint32_t pad;  // the pad element, replicated over the dword
-    float si, zi, so, zo, inv_so;
-    int32_t mode;   // int8 vec: MOVE_RAW / MOVE_FMA / MOVE_DIV
+    MoveRec rec;
     int32_t small;  // the output has fewer than 2^32 elements: every index fits 32 bits
 };
 
@@ -59,11 +58,7 @@ __global__ __launch_bounds__(256) void pad_vec_kernel(PadArgs a)
     if (i >= a.items) return;
     const int64_t src = pad_source(i, a);
     uint4 v = make_uint4(a.pad, a.pad, a.pad, a.pad);
-    if (src >= 0) {
-        v = static_cast<const uint4 *>(a.in)[src];
-        v.x = move_word<F16>(v.x, a.mode, a.si, a.zi, a.so, a.zo, a.inv_so), v.y = move_word<F16>(v.y, a.mode, a.si, a.zi, a.so, a.zo, a.inv_so);
-        v.z = move_word<F16>(v.z, a.mode, a.si, a.zi, a.so, a.zo, a.inv_so), v.w = move_word<F16>(v.w, a.mode, a.si, a.zi, a.so, a.zo, a.inv_so);
-    }
+    if (src >= 0) v = move_piece<uint4, F16>(static_cast<const uint4 *>(a.in)[src], a.rec);
     static_cast<uint4 *>(a.out)[i] = v;
 }
 
@@ -77,8 +72,7 @@ __global__ __launch_bounds__(256) void pad_generic_kernel(PadArgs a)
         static_cast<uint16_t *>(a.out)[i] =
             src >= 0 ? float_to_f16_bits_ref(f16_bits_to_float(static_cast<const uint16_t *>(a.in)[src])) : (uint16_t)a.pad;
     } else {
-        static_cast<int8_t *>(a.out)[i] =
-            src >= 0 ? (int8_t)move_rq<false>(static_cast<const int8_t *>(a.in)[src], a.si, a.zi, a.so, a.zo, a.inv_so) : (int8_t)a.pad;
+        static_cast<int8_t *>(a.out)[i] = src >= 0 ? (int8_t)move_rq<false>(static_cast<const int8_t *>(a.in)[src], a.rec) : (int8_t)a.pad;
     }
 }
 
@@ -141,8 +135,7 @@ static const char *pad_invalid(const void *in_dev, const void *out_dev, const sh
     }
     if (no > INT64_MAX / 2) return "tensor too large";
     const int64_t es = d->dtype == SHL_MI355X_F16 ? 2 : 1;
-    const uintptr_t i0 = (uintptr_t)in_dev, i1 = i0 + (uintptr_t)(ni * es), o0 = (uintptr_t)out_dev, o1 = o0 + (uintptr_t)(no * es);
-    if (i0 < i1 && o0 < o1 && i0 < o1 && o0 < i1) return "the output overlaps the input";
+    if (ranges_overlap(in_dev, ni * es, out_dev, no * es)) return "the output overlaps the input";
     *in_elems = ni, *out_elems = no;
     return NULL;
 }
@@ -219,20 +212,10 @@ extern "C" int shl_mi355x_pad(const void *in_dev, void *out_dev, const struct sh
     }
     const uint32_t e = pad_element(d);
     a.pad = f16 ? e * 0x00010001u : e * 0x01010101u;
-    a.si = d->in_scale, a.zi = (float)d->in_zp;
-    a.so = d->out_scale, a.zo = (float)d->out_zp, a.inv_so = 1.0f / d->out_scale;
-    if (!f16) {
-        a.mode = move_fma_ok(d->in_scale, d->in_zp, d->out_scale) ? MOVE_FMA : MOVE_DIV;
-        if (form == PAD_VEC && d->in_zp == d->out_zp && memcmp(&d->in_scale, &d->out_scale, sizeof(float)) == 0 &&
-            requant_is_identity(d->in_scale, d->in_zp))
-            a.mode = MOVE_RAW;
-    }
+    a.rec = move_rec(d->in_scale, d->in_zp, d->out_scale, d->out_zp, !f16 && form == PAD_VEC);
     a.small = no < (1ll << 32);
     const int64_t groups = (a.items + 255) / 256;
-    if (groups > 0x7FFFFFFFll) {
-        set_error("pad: %lld workgroups exceed the grid", (long long)groups);
-        return SHL_MI355X_ENOTSUP;
-    }
+    if (grid_refused("pad", groups)) return SHL_MI355X_ENOTSUP;
     const dim3 grid((unsigned)groups), block(256);
     hipStream_t s = (hipStream_t)stream;
     if (form == PAD_VEC) hipLaunchKernelGGL(f16 ? pad_vec_kernel<true> : pad_vec_kernel<false>, grid, block, 0, s, a);

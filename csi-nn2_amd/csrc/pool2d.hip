@@ -393,8 +393,8 @@ static int pool_form(const shl_mi355x_pool_desc *d)
     return ((int64_t)d->c * esize) % 16 == 0 ? POOL_VEC : POOL_GENERIC;
 }
 
-// is requantising a dequantised value the identity for every int8 value?  (only asked for equal records; concat.hip
-// asks too)
+// is requantising a dequantised value the identity for every int8 value?  (only asked for equal records; the movers
+// ask too: requant_move.h:move_rec)
 bool requant_is_identity(float s, int32_t zp)
 {
     const float z = (float)zp;

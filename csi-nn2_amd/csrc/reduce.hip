@@ -44,7 +44,7 @@
 #include <type_traits>
 
 #include "reduce_canon.h"  // the host side: validation, canonicalisation, the form rule (a stand-alone program compiles it too)
-#include "requant_move.h"
+#include "common.h"
 
 namespace shl {
 

@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "fma_div_ok.h"
 #include "shl_mi355x.h"
 
 namespace shl {
@@ -114,9 +115,7 @@ static inline void rd_rows_plan(const RdCanon *c, int64_t es, RdRows *r)
 // largest element, with a factor of two for the chain's roundings
 static inline bool reduce_fma_ok(const shl_mi355x_reduce_desc *d, const RdCanon *c)
 {
-    if (!(d->out_scale >= 0x1p-40f && d->out_scale <= 0x1p40f)) return false;
-    const double bound = 2.0 * (double)c->inner_size * (128.0 + fabs((double)d->in_zp)) * fabs((double)d->in_scale);
-    return bound <= 0x1p60;  // also NaN
+    return fma_div_ok(2.0 * (double)c->inner_size * (128.0 + fabs((double)d->in_zp)) * fabs((double)d->in_scale), d->out_scale);
 }
 
 }  // namespace shl

@@ -352,9 +352,7 @@ static const char *const g_form_name[] = {"resize_nhwc_vec", "resize_nchw_row", 
 // conv_plan.hip:fma_division_ok admits: 2^-40 <= so <= 2^40, |x| <= 2^60, x finite)
 static bool resize_fma_ok(float s, int32_t zp, float so)
 {
-    if (!(so >= 0x1p-40f && so <= 0x1p40f)) return false;
-    const double bound = (128.0 + fabs((double)zp)) * fabs((double)s) * 4.0;  // four terms, weights in [0, 1]
-    return bound <= 0x1p60;  // also NaN
+    return fma_div_ok((128.0 + fabs((double)zp)) * fabs((double)s) * 4.0, so);  // four terms, weights in [0, 1]
 }
 
 template <bool F16, int OP>

@@ -41,22 +41,9 @@ struct ShuffleArgs {
     int32_t group, gc;
     int32_t row_bytes;  // pixel: C in bytes
     int32_t run;        // pixel: pixels per workgroup
-    float si, zi, so, zo, inv_so;
-    int32_t mode;   // int8: MOVE_RAW / MOVE_FMA / MOVE_DIV
+    MoveRec rec;
     int32_t small;  // the tensor has fewer than 2^32 elements: every index fits 32 bits
 };
-
-template <typename W, bool F16>
-__device__ __forceinline__ W shuffle_move(W v, const ShuffleArgs &a)
-{
-    if constexpr (sizeof(W) == 16) {
-        v.x = move_word<F16>(v.x, a.mode, a.si, a.zi, a.so, a.zo, a.inv_so), v.y = move_word<F16>(v.y, a.mode, a.si, a.zi, a.so, a.zo, a.inv_so);
-        v.z = move_word<F16>(v.z, a.mode, a.si, a.zi, a.so, a.zo, a.inv_so), v.w = move_word<F16>(v.w, a.mode, a.si, a.zi, a.so, a.zo, a.inv_so);
-        return v;
-    } else {
-        return move_word<F16>(v, a.mode, a.si, a.zi, a.so, a.zo, a.inv_so);
-    }
-}
 
 // the input plane that output plane `plane` = (image, output channel) shows
 __device__ __forceinline__ int64_t shuffle_source(int64_t plane, const ShuffleArgs &a)
@@ -75,7 +62,7 @@ __global__ __launch_bounds__(256) void shuffle_plane_kernel(ShuffleArgs a)
     int64_t piece;
     const int64_t plane = move_divmod(i, a.inner, a.small != 0, piece);
     const W v = static_cast<const W *>(a.in)[shuffle_source(plane, a) * a.inner + piece];
-    static_cast<W *>(a.out)[i] = shuffle_move<W, F16>(v, a);
+    static_cast<W *>(a.out)[i] = move_piece<W, F16>(v, a.rec);
 }
 
 template <typename W, bool F16>
@@ -109,7 +96,7 @@ __global__ __launch_bounds__(256) void shuffle_pixel_kernel(ShuffleArgs a)
                 word |= (uint32_t)px[k * a.gc + j] << (8 * (int)sizeof(E) * b);
                 if (++k == a.group) k = 0, ++j;
             }
-            w[q] = move_word<F16>(word, a.mode, a.si, a.zi, a.so, a.zo, a.inv_so);
+            w[q] = move_word<F16>(word, a.rec);
         }
         W v;
         if constexpr (sizeof(W) == 16) v.x = w[0], v.y = w[1], v.z = w[2], v.w = w[3];
@@ -129,8 +116,7 @@ __global__ __launch_bounds__(256) void shuffle_generic_kernel(ShuffleArgs a)
     if constexpr (F16) {
         static_cast<uint16_t *>(a.out)[i] = float_to_f16_bits_ref(f16_bits_to_float(static_cast<const uint16_t *>(a.in)[src]));
     } else {
-        static_cast<int8_t *>(a.out)[i] =
-            (int8_t)move_rq<false>(static_cast<const int8_t *>(a.in)[src], a.si, a.zi, a.so, a.zo, a.inv_so);
+        static_cast<int8_t *>(a.out)[i] = (int8_t)move_rq<false>(static_cast<const int8_t *>(a.in)[src], a.rec);
     }
 }
 
@@ -148,8 +134,7 @@ static const char *shuffle_invalid(const void *in_dev, const void *out_dev, cons
     if (__builtin_mul_overflow(d->outer, d->c, &n) || __builtin_mul_overflow(n, d->inner, &n) ||
         __builtin_mul_overflow(n, es, &bytes))
         return "tensor too large";
-    const uintptr_t i0 = (uintptr_t)in_dev, i1 = i0 + (uintptr_t)bytes, o0 = (uintptr_t)out_dev, o1 = o0 + (uintptr_t)bytes;
-    if (i0 < i1 && i0 < o1 && o0 < i1) return "the output overlaps the input";
+    if (ranges_overlap(in_dev, bytes, out_dev, bytes)) return "the output overlaps the input";
     *elems = n;
     return NULL;
 }
@@ -217,14 +202,7 @@ extern "C" int shl_mi355x_shuffle_channel(const void *in_dev, void *out_dev, con
     a.in = in_dev, a.out = out_dev;
     a.outer = d->outer, a.c = d->c;
     a.group = d->group, a.gc = (int32_t)(d->c / d->group);
-    a.si = d->in_scale, a.zi = (float)d->in_zp;
-    a.so = d->out_scale, a.zo = (float)d->out_zp, a.inv_so = 1.0f / d->out_scale;
-    if (!f16) {
-        a.mode = move_fma_ok(d->in_scale, d->in_zp, d->out_scale) ? MOVE_FMA : MOVE_DIV;
-        if (form != SHUFFLE_GENERIC && d->in_zp == d->out_zp && memcmp(&d->in_scale, &d->out_scale, sizeof(float)) == 0 &&
-            requant_is_identity(d->in_scale, d->in_zp))
-            a.mode = MOVE_RAW;
-    }
+    a.rec = move_rec(d->in_scale, d->in_zp, d->out_scale, d->out_zp, !f16 && form != SHUFFLE_GENERIC);
     a.small = elems < (1ll << 32);
     int64_t groups;
     if (form == SHUFFLE_PIXEL) {
@@ -240,10 +218,7 @@ extern "C" int shl_mi355x_shuffle_channel(const void *in_dev, void *out_dev, con
         a.items = d->outer * d->c * a.inner;
         groups = (a.items + 255) / 256;
     }
-    if (groups > 0x7FFFFFFFll) {
-        set_error("shuffle_channel: %lld workgroups exceed the grid", (long long)groups);
-        return SHL_MI355X_ENOTSUP;
-    }
+    if (grid_refused("shuffle_channel", groups)) return SHL_MI355X_ENOTSUP;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)groups), block(256);
     void (*kernel)(ShuffleArgs);  // (a template-id with a comma cannot be a macro argument)

@@ -66,44 +66,9 @@ struct TrArgs {
     int32_t bext[TR_DIMS - 2];
     int32_t ea, eb, ta, tb, nb;
     int32_t first;
-    float si, zi, so, zo, inv_so;
-    int32_t mode;   // int8: MOVE_RAW / MOVE_FMA / MOVE_DIV
+    MoveRec rec;
     int32_t small;  // the tensor has fewer than 2^32 elements: every index fits 32 bits
 };
-
-// one element by `mode`, in the low bits
-template <bool F16>
-__device__ __forceinline__ uint32_t move_elem(uint32_t v, const TrArgs &a)
-{
-    if constexpr (F16) {
-        return move_fix_f16x2(v & 0xFFFFu);
-    } else {
-        if (a.mode == MOVE_RAW) return v & 0xFFu;
-        const int q = (int8_t)v;
-        return (uint32_t)(a.mode == MOVE_FMA ? move_rq<true>(q, a.si, a.zi, a.so, a.zo, a.inv_so)
-                                             : move_rq<false>(q, a.si, a.zi, a.so, a.zo, a.inv_so)) & 0xFFu;
-    }
-}
-
-// the literal formula
-template <bool F16>
-__device__ __forceinline__ uint32_t move_literal(uint32_t v, const TrArgs &a)
-{
-    if constexpr (F16) return float_to_f16_bits_ref(f16_bits_to_float((uint16_t)v));
-    else return (uint32_t)move_rq<false>((int8_t)v, a.si, a.zi, a.so, a.zo, a.inv_so) & 0xFFu;
-}
-
-template <typename W, bool F16>
-__device__ __forceinline__ W move_piece(W v, const TrArgs &a)
-{
-    if constexpr (sizeof(W) == 16) {
-        v.x = move_word<F16>(v.x, a.mode, a.si, a.zi, a.so, a.zo, a.inv_so), v.y = move_word<F16>(v.y, a.mode, a.si, a.zi, a.so, a.zo, a.inv_so);
-        v.z = move_word<F16>(v.z, a.mode, a.si, a.zi, a.so, a.zo, a.inv_so), v.w = move_word<F16>(v.w, a.mode, a.si, a.zi, a.so, a.zo, a.inv_so);
-        return v;
-    } else {
-        return move_word<F16>(v, a.mode, a.si, a.zi, a.so, a.zo, a.inv_so);
-    }
-}
 
 template <bool F16>
 __global__ __launch_bounds__(256) void transpose_flat_kernel(TrArgs a)
@@ -113,14 +78,14 @@ __global__ __launch_bounds__(256) void transpose_flat_kernel(TrArgs a)
     if (i >= a.items) return;
     const int64_t at = i * 16;
     if (at + 16 <= a.bytes) {
-        static_cast<uint4 *>(a.out)[i] = move_piece<uint4, F16>(static_cast<const uint4 *>(a.in)[i], a);
+        static_cast<uint4 *>(a.out)[i] = move_piece<uint4, F16>(static_cast<const uint4 *>(a.in)[i], a.rec);
         return;
     }
     // the tail: fewer than 16 bytes, whole elements
     const E *src = reinterpret_cast<const E *>(static_cast<const uint8_t *>(a.in) + at);
     E *dst = reinterpret_cast<E *>(static_cast<uint8_t *>(a.out) + at);
     const int left = (int)((a.bytes - at) / (int64_t)sizeof(E));
-    for (int e = 0; e < left; ++e) dst[e] = (E)move_elem<F16>(src[e], a);
+    for (int e = 0; e < left; ++e) dst[e] = (E)move_elem<F16>(src[e], a.rec);
 }
 
 // rows (W = uint4 / uint32_t, LIT = false) and generic (W = the element, LIT = true): thread i owns output unit i and finds
@@ -139,8 +104,8 @@ __global__ __launch_bounds__(256) void transpose_walk_kernel(TrArgs a)
             src += c * a.is[k];
         }
     }
-    if constexpr (LIT) static_cast<W *>(a.out)[i] = (W)move_literal<F16>(static_cast<const W *>(a.in)[src], a);
-    else static_cast<W *>(a.out)[i] = move_piece<W, F16>(static_cast<const W *>(a.in)[src], a);
+    if constexpr (LIT) static_cast<W *>(a.out)[i] = (W)move_literal<F16>(static_cast<const W *>(a.in)[src], a.rec);
+    else static_cast<W *>(a.out)[i] = move_piece<W, F16>(static_cast<const W *>(a.in)[src], a.rec);
 }
 
 template <bool F16, bool VIN, bool VOUT>
@@ -173,11 +138,11 @@ __global__ __launch_bounds__(256) void transpose_tile_kernel(TrArgs a)
         if (ga < a.ea && gb < a.eb) {  // (VIN: eb is a multiple of EPV, so is gb: the whole access is inside)
             const int64_t at = in_base + (int64_t)ga * a.sa_in + gb;
             if constexpr (VIN) {
-                const uint32_t w = move_word<F16>(static_cast<const uint32_t *>(a.in)[at / EPV], a.mode, a.si, a.zi, a.so, a.zo, a.inv_so);
+                const uint32_t w = move_word<F16>(static_cast<const uint32_t *>(a.in)[at / EPV], a.rec);
 #pragma unroll
                 for (int j = 0; j < EPV; ++j) tile[(b + j) * PA + ar] = (E)(w >> (8 * (int)sizeof(E) * j));
             } else {
-                tile[b * PA + ar] = (E)move_elem<F16>(static_cast<const E *>(a.in)[at], a);
+                tile[b * PA + ar] = (E)move_elem<F16>(static_cast<const E *>(a.in)[at], a.rec);
             }
         }
     }
@@ -255,8 +220,7 @@ static void canon_flat(int64_t elems, Canon *c)
 static const char *buffers_invalid(const void *in_dev, const void *out_dev, int64_t bytes)
 {
     if (!in_dev || !out_dev) return "NULL argument";
-    const uintptr_t i0 = (uintptr_t)in_dev, i1 = i0 + (uintptr_t)bytes, o0 = (uintptr_t)out_dev, o1 = o0 + (uintptr_t)bytes;
-    if (i0 < i1 && i0 < o1 && o0 < i1) return "the output overlaps the input";
+    if (ranges_overlap(in_dev, bytes, out_dev, bytes)) return "the output overlaps the input";
     return NULL;
 }
 
@@ -311,14 +275,7 @@ static int canon_launch(const char *op, const void *in_dev, void *out_dev, const
     TrArgs a;
     memset(&a, 0, sizeof(a));
     a.in = in_dev, a.out = out_dev;
-    a.si = in_scale, a.zi = (float)in_zp;
-    a.so = out_scale, a.zo = (float)out_zp, a.inv_so = 1.0f / out_scale;
-    if (!f16) {
-        a.mode = move_fma_ok(in_scale, in_zp, out_scale) ? MOVE_FMA : MOVE_DIV;
-        if (form != TR_GENERIC && in_zp == out_zp && memcmp(&in_scale, &out_scale, sizeof(float)) == 0 &&
-            requant_is_identity(in_scale, in_zp))
-            a.mode = MOVE_RAW;
-    }
+    a.rec = move_rec(in_scale, in_zp, out_scale, out_zp, !f16 && form != TR_GENERIC);
     a.small = c->elems < (1ll << 32);
     int64_t groups;
     void (*kernel)(TrArgs);  // (a template-id with a comma cannot be a macro argument)
@@ -359,10 +316,7 @@ static int canon_launch(const char *op, const void *in_dev, void *out_dev, const
             kernel = f16 ? transpose_walk_kernel<uint16_t, true, true> : transpose_walk_kernel<uint8_t, false, true>;
         }
     }
-    if (groups > 0x7FFFFFFFll) {
-        set_error("%s: %lld workgroups exceed the grid", op, (long long)groups);
-        return SHL_MI355X_ENOTSUP;
-    }
+    if (grid_refused(op, groups)) return SHL_MI355X_ENOTSUP;
     const dim3 grid((unsigned)groups), block(256);
     hipLaunchKernelGGL(kernel, grid, block, 0, s, a);
     SHL_HIP(hipGetLastError());

@@ -32,6 +32,9 @@ RECORD_PAIRS = {
     "conv": ([Q_CONV[0], Q_A, Q_B, Q_CONV[1], Q_SAME], Q_CONV[1]),  # all differing but one
     "pow2": ([Q_POW2[0], Q_POW2[1]], Q_POW2[1]),
     "sat": ([Q_SAME, Q_CONV[0]], Q_OUT_SAT),
+    # (128 + |zp|) s = 2^61 for the 2^54 record, past the 2^60 that requant_move.h:move_fma_ok admits: one launch mixes
+    # inputs whose division may go through div_by_scale with one whose may not
+    "fma_mixed": ([Q_CONV[0], _q(2.0 ** 54, 0), Q_A], Q_SAME),
 }
 
 
@@ -125,6 +128,12 @@ def concat_cases():
     add("records_all_differ", "int8", three, 3, *differ)
     add("records_saturating", "int8", three, 3, [Q_SAME, Q_CONV[0], Q_SAME], Q_OUT_SAT)
     add("records_all_differ_generic", "int8", chans((1, 3, 3, 0), 3, (5, 16, 3)), 3, *differ)
+    fma_mixed = RECORD_PAIRS["fma_mixed"]                     # one wave spans all three inputs
+    add("records_fma_mixed_vec", "int8", chans((1, 2, 2, 0), 3, (16, 32, 16)), 3, *fma_mixed)
+    add("records_fma_mixed_generic", "int8", chans((1, 2, 2, 0), 3, (5, 16, 3)), 3, *fma_mixed)
+    nine = [recs[i % 3] for i in range(9)]
+    nine[3] = fma_mixed[0][1]                               # (input 8, an ordinary record, is the second launch)
+    add("count9_fma_mixed_vec", "int8", chans((1, 2, 2, 0), 3, [16] * 9), 3, nine, Q_SAME)
     every = np.arange(-128, 128, dtype=np.int16).astype(np.int8).reshape(1, 256)
     for key, (ins, outq) in RECORD_PAIRS.items():
         add("exhaustive_i8_" + key, "int8", [(1, 256)] * len(ins), 1, ins, outq, xs=[every] * len(ins),

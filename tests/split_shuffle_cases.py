@@ -35,6 +35,9 @@ RECORD_SETS = {
     "pow2": (Q_POW2[1], [Q_POW2[0], Q_POW2[1]]),
     "pow2_up": (Q_POW2[0], [Q_POW2[1]]),
     "sat": (Q_SAME, [Q_OUT_SAT, Q_CONV[0]]),
+    # the middle output's scale, 2^41, lies outside the [2^-40, 2^40] that requant_move.h:move_fma_ok admits: one launch
+    # mixes outputs whose division may go through div_by_scale with one whose may not
+    "fma_mixed": (Q_CONV[1], [Q_CONV[0], _q(2.0 ** 41, 0), Q_A]),
 }
 
 
@@ -133,6 +136,9 @@ def split_cases():
     add("records_all_differ", "int8", in_q=Q_CONV[1], out_qs=[Q_CONV[0], Q_A, Q_B], **three)
     add("records_saturating", "int8", in_q=Q_SAME, out_qs=[Q_SAME, Q_OUT_SAT, Q_CONV[0]], **three)
     add("records_all_differ_generic", "int8", (1, 3, 3, 24), 3, lens=(5, 16, 3), in_q=Q_CONV[1], out_qs=[Q_CONV[0], Q_A, Q_B])
+    fma_mixed = dict(in_q=RECORD_SETS["fma_mixed"][0], out_qs=RECORD_SETS["fma_mixed"][1])  # one wave spans all three outputs
+    add("records_fma_mixed_vec", "int8", (1, 2, 2, 64), 3, lens=(16, 32, 16), **fma_mixed)
+    add("records_fma_mixed_generic", "int8", (1, 2, 2, 24), 3, lens=(5, 16, 3), **fma_mixed)
     every = np.arange(-128, 128, dtype=np.int16).astype(np.int8)
     for key, (in_q, outs) in RECORD_SETS.items():
         add("exhaustive_i8_" + key, "int8", (1, 256 * len(outs)), 1, lens=[256] * len(outs), in_q=in_q, out_qs=outs,
