@@ -42,6 +42,7 @@ REDUCE_INIT_FLT_MAX, REDUCE_INIT_FIRST = 0, 1                   # .init
 REDUCE_GROUPS, REDUCE_CHUNK_BYTES = 4, 256
 OP_MATMUL = 95
 MATMUL_CHAIN, MATMUL_MFMA, MATMUL_MFMA_MAX_K = "matmul_chain", "matmul_mfma", 32768  # shl_mi355x_matmul's forms
+ATTENTION_MFMA, ATTENTION_MAX_KEYS = "attention_mfma", 1024  # shl_mi355x_attention's kernel and its cap on the keys
 OP_SIGMOID, OP_HARD_SIGMOID, OP_SILU, OP_LEAKY_RELU, OP_MUL = 154, 78, 190, 84, 107
 OP_RESIZE = 133
 OP_DECONV2D, OP_DEPTHWISE_DECONV2D, OP_GROUP_DECONV2D = 54, 55, 56
@@ -202,6 +203,15 @@ class MatmulDesc(C.Structure):
                 ("a_elems", C.c_int64), ("b_elems", C.c_int64), ("out_elems", C.c_int64),
                 ("a_scale", C.c_float), ("a_zp", C.c_int32), ("b_scale", C.c_float), ("b_zp", C.c_int32),
                 ("out_scale", C.c_float), ("out_zp", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class AttentionDesc(C.Structure):
+    """struct shl_mi355x_attention_desc (include/shl_mi355x.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("dtype", "batches", "s", "t", "d", "dv", "has_scale", "scale_is_first", "scale_raw",
+                                         "reserved0")] + \
+        [(n, C.c_float) for n in ("q_scale", "k_scale", "v_scale", "s_scale", "c_scale", "sc_scale", "p_scale", "out_scale")] + \
+        [(n, C.c_int32) for n in ("q_zp", "k_zp", "v_zp", "s_zp", "c_zp", "sc_zp", "p_zp", "out_zp")] + \
+        [("reserved", C.c_int32 * 4)]
 
 
 class ConvDesc(C.Structure):
@@ -404,6 +414,9 @@ def load_hip():
         "shl_mi355x_matmul_is_exact": (C.c_int, [C.POINTER(MatmulDesc)]),
         "shl_mi355x_matmul_bias": (C.c_int, [vp, vp, vp, vp, C.POINTER(MatmulDesc), f32, i32, f32, i32, i32, vp]),
         "shl_mi355x_matmul_bias_kernel_name": (C.c_char_p, [vp, vp, vp, vp, C.POINTER(MatmulDesc)]),
+        "shl_mi355x_attention": (C.c_int, [vp, vp, vp, vp, C.POINTER(AttentionDesc), vp]),
+        "shl_mi355x_attention_kernel_name": (C.c_char_p, [vp, vp, vp, vp, C.POINTER(AttentionDesc)]),
+        "shl_mi355x_attention_by_default": (C.c_int, [vp, vp, vp, vp, C.POINTER(AttentionDesc)]),
         "shl_mi355x_unary_lut_i8": (C.c_int, [vp, vp, sz, vp, vp]),
         "shl_mi355x_unary_lut_i8_kernel_name": (C.c_char_p, [vp, vp]),
         "shl_mi355x_unary_f16": (C.c_int, [vp, vp, sz, i32, f32, vp]),
@@ -521,6 +534,7 @@ def load_backend(frontend):
         opt.shl_mi355x_registry_get.argtypes = [C.c_void_p]
         opt.shl_mi355x_session_folded_activations.argtypes = [C.POINTER(Session)]
         opt.shl_mi355x_session_fused_linears.argtypes = [C.POINTER(Session)]
+        opt.shl_mi355x_session_fused_attentions.argtypes = [C.POINTER(Session)]
         opt.shl_mi355x_session_stream.argtypes = [C.POINTER(Session)]
         opt.shl_mi355x_session_stream.restype = C.c_void_p
         opt.shl_mi355x_session_set_stream.argtypes = [C.POINTER(Session), C.c_void_p]

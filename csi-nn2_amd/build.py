@@ -47,7 +47,8 @@ NO_SPILL_SOURCES = ("conv_igemm.hip", "conv_igemm_pp.hip", "conv_igemm_pc.hip",
                     "slab.hip", "shuffle.hip",  # (pure data movement: scratch traffic would be most of their memory traffic)
                     "transpose.hip", "pad.hip",
                     "reduce.hip",  # (its chains wait on one addition per element: a scratch reload in the loop would double that)
-                    "matmul.hip")  # (the chain likewise; the mfma form's K loop holds one slab's pieces in flight in registers)
+                    "matmul.hip",  # (the chain likewise; the mfma form's K loop holds one slab's pieces in flight in registers)
+                    "attention.hip")  # (the same K loops twice, and sixteen accumulators live across the softmax's f64 work)
 
 
 def spilled_kernels(usage_file):

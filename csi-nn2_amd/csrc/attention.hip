@@ -1,0 +1,347 @@
+// attention.hip -- the core of an attention block as ONE launch: scores = Q K^T, [scores * constant], softmax over the keys,
+// P V (shl_mi355x_attention; a session's STEP_ATTENTION).  Unfused that is four launches, and three intermediates -- the
+// [batches][S][T] scores twice, the probabilities once -- make a round trip through HBM.
+//
+// The launch equals shl_mi355x_matmul (mfma form) -> shl_mi355x_mul -> shl_mi355x_softmax -> shl_mi355x_matmul (mfma form) bit
+// for bit, by construction: every intermediate is computed exactly as the unfused kernel would STORE it -- the int8 byte under
+// its record, the rounded half with the NaN rule --, is kept in LDS and goes through the next layer's own element function:
+//   products  matmul_mfma's instructions on its fragment layout (matmul_step.h: 16 bytes of k per lane, [row][k] images with
+//             a zero-filled K tail, k ascending in 64-byte slabs into one accumulator), int8 on the raw bytes with the same
+//             correction by row and column sums, then mm_value.  That fixes the float32 summation order of binary16 as well
+//   multiply  mul_i8_one / mul_f16_one (mul_step.h) on the value the first product would have stored
+//   softmax   a row per wave.  The max is order-free, every element's exp(double(x - max)) is the same operation on the same
+//             operands (softmax_step.h), running_sum_exact is a one-wave routine over an LDS row padded with 256 zeros.  int8
+//             rows longer than 256 take the exponential and the requantised quotient from a per-row table of 256, as
+//             softmax_kernel does for every row: the same operations on the same operands, four f64 exp and divisions per lane
+//             and row instead of T / 64
+// A workgroup owns 32 query rows of one batch.  Its first four waves run the products; the softmax's f64 work is what a
+// small grid waits for, so there a workgroup brings four or twelve more waves for it (attention_canon.h:att_waves: 16, 8 or
+// 4 waves, as the grid and the LDS allow).  Q K^T: a pass covers 128 keys, a wave one 32 x 32 block of them;
+// the 32 x T tile of scores is written to LDS through mm_value + the mul step.  The probabilities overwrite the scores in
+// place, and P V reads them as its [row][k] operand directly; v goes through mm_put's transposing write, a pass covers 128
+// output columns.  LDS (attention_canon.h:att_lds) caps T at SHL_MI355X_ATTENTION_MAX_KEYS; d and dv are looped over.
+#include <stdlib.h>
+#include <string.h>
+
+#include <type_traits>
+
+#include "attention_canon.h"  // the host side: validation, the form rule, the LDS layout (a stand-alone program compiles it too)
+#include "matmul_step.h"
+#include "mul_step.h"
+#include "softmax_step.h"
+
+namespace shl {
+
+struct AttArgs {
+    const void *q, *k, *v;
+    void *out;
+    int32_t batches, S, T, D, DV, tiles;  // tiles: row tiles per batch
+    int32_t q_vec, k_vec, v_vec;
+    AttLds lds;
+    // Q K^T: the raw-byte correction's zero points, mult = fl(q_scale k_scale), the record the scores are stored under
+    int32_t izq, izk, s_div;
+    float mult1, s_so, s_zo, s_inv;
+    // the multiply by the constant craw (its raw element)
+    int32_t has_scale, craw;
+    MulRec mul;
+    // softmax: the record it reads (the scaled scores', else the scores') and the probabilities'
+    float x_si, x_zi, p_so, p_zo;
+    // P V
+    int32_t izp, izv, o_div;
+    float mult2, o_so, o_zo, o_inv;
+};
+
+// a wave's LDS writes are visible to its own later reads (the LDS serves one wave's instructions in order); this keeps the
+// compiler from moving either across the point
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <bool F16>
+__global__ __launch_bounds__(1024) void attention_mfma_kernel(AttArgs a)
+{
+    using Acc = typename AccT<!F16>::type;
+    using E = typename std::conditional<F16, uint16_t, uint8_t>::type;
+    constexpr int ES = F16 ? 2 : 1, KS = MM_KB / ES;  // elements of k per slab
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63, fr = lane & 31, fh = lane >> 5;
+    const int nw = (int)blockDim.x >> 6;  // 4, 8 or 16 waves: the first four run the products, all of them the softmax
+    const bool mover = tid < 256;         // (wave-uniform) the threads that load slabs and hold fragments
+    const int T = a.T, tp = a.lds.tile_pitch;
+    double *const e = reinterpret_cast<double *>(smem + a.lds.e) + wave * (T + 256);  // the wave's row of terms, 256 zeros behind
+    char *const tile = smem + a.lds.tile;
+    char *const lds_q = smem + a.lds.slab_q;
+    char *const lds_kv = smem + a.lds.slab_kv;
+    int32_t(*const row_sum)[32] = reinterpret_cast<int32_t(*)[32]>(smem + a.lds.row_sum);
+    const uint32_t bi = blockIdx.x / (uint32_t)a.tiles;
+    const int m0 = (int)(blockIdx.x - bi * (uint32_t)a.tiles) * ATT_ROWS;
+    // (every tensor holds fewer than 2^31 elements)
+    const void *pq = static_cast<const char *>(a.q) + (int64_t)bi * a.S * a.D * ES;
+    const void *pk = static_cast<const char *>(a.k) + (int64_t)bi * T * a.D * ES;
+    const void *pv = static_cast<const char *>(a.v) + (int64_t)bi * T * a.DV * ES;
+
+    // ---- scores = Q K^T, stored as matmul_mfma stores them, then the multiply -------------------------------------------------
+    for (int n0 = 0; n0 < T; n0 += ATT_KEYS) {
+        const bool active = mover && n0 + wave * 32 < T;  // (wave-uniform) the wave's block holds keys
+        Acc acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0;
+        int32_t rs = 0, cs = 0;
+        uint4 vq = make_uint4(0u, 0u, 0u, 0u), vk0 = vq, vk1 = vq;
+        if (tid < 4 * ATT_ROWS) vq = mm_piece<F16>(pq, a.D, m0, a.S, 0, a.D, 1, a.q_vec, tid);
+        if (mover) {
+            vk0 = mm_piece<F16>(pk, a.D, n0, T, 0, a.D, 1, a.k_vec, tid);
+            vk1 = mm_piece<F16>(pk, a.D, n0 + MM_T, T, 0, a.D, 1, a.k_vec, tid);
+        }
+        for (int k0 = 0; k0 < a.D; k0 += KS) {
+            __syncthreads();  // the previous slab's fragments were read
+            if (tid < 4 * ATT_ROWS) mm_put<F16>(lds_q, vq, 1, tid);
+            if (mover) {
+                mm_put<F16>(lds_kv, vk0, 1, tid);
+                mm_put<F16>(lds_kv + MM_T * MM_PITCH, vk1, 1, tid);
+            }
+            __syncthreads();
+            if (mover && k0 + KS < a.D) {  // the next slab's pieces travel while this slab's MFMAs run
+                if (tid < 4 * ATT_ROWS) vq = mm_piece<F16>(pq, a.D, m0, a.S, k0 + KS, a.D, 1, a.q_vec, tid);
+                vk0 = mm_piece<F16>(pk, a.D, n0, T, k0 + KS, a.D, 1, a.k_vec, tid);
+                vk1 = mm_piece<F16>(pk, a.D, n0 + MM_T, T, k0 + KS, a.D, 1, a.k_vec, tid);
+            }
+            if (!active) continue;
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const v4i fa = *reinterpret_cast<const v4i *>(lds_q + fr * MM_PITCH + s * 32 + fh * 16);
+                const v4i fb = *reinterpret_cast<const v4i *>(lds_kv + (wave * 32 + fr) * MM_PITCH + s * 32 + fh * 16);
+                acc = mfma<!F16>(fa, fb, acc);
+                if constexpr (!F16) {
+                    if (a.izk != 0) {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) rs = __builtin_amdgcn_sdot4(fa[j], 0x01010101, rs, false);
+                    }
+                    if (a.izq != 0) {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) cs = __builtin_amdgcn_sdot4(fb[j], 0x01010101, cs, false);
+                    }
+                }
+            }
+        }
+        if constexpr (!F16) {
+            // a lane holds half of its row's / column's k: the other half is 32 lanes away
+            rs += __shfl_xor(rs, 32);
+            cs += __shfl_xor(cs, 32);
+            if (mover && fh == 0) row_sum[wave][fr] = rs;
+            __syncthreads();
+        }
+        // C/D layout: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+        const int key = n0 + wave * 32 + fr;
+        const int32_t kzz = a.D * a.izq * a.izk;  // (D <= 32768, |zp| <= 128: below 2^30)
+        if (mover && key < T) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = (r & 3) + 8 * (r >> 2) + 4 * fh;
+                E *const dst = reinterpret_cast<E *>(tile + row * tp) + key;
+                if constexpr (F16) {
+                    uint16_t h = (uint16_t)mm_value<true>(acc[r], a.s_so, a.s_zo, a.s_inv, a.s_div);
+                    if (a.has_scale) h = mul_f16_one(h, (uint16_t)a.craw, a.mul);
+                    *dst = h;
+                } else {
+                    // (every term and the true sum fit 32 bits; unsigned arithmetic, so that no intermediate wrap is undefined)
+                    const uint32_t S = (uint32_t)acc[r] - (uint32_t)(a.izk * row_sum[wave][row]) - (uint32_t)(a.izq * cs) + (uint32_t)kzz;
+                    int qv = mm_value<false>(__fmul_rn((float)(int32_t)S, a.mult1), a.s_so, a.s_zo, a.s_inv, a.s_div);
+                    if (a.has_scale) qv = mul_i8_one(qv, a.craw, a.mul);
+                    *dst = (E)(int8_t)qv;
+                }
+            }
+        }
+    }
+    __syncthreads();  // the tile is complete
+
+    // ---- softmax along the keys, a row per wave; the probabilities overwrite the scores ---------------------------------------
+    {
+        const int tk = (T + KS - 1) / KS * KS;  // the keys of P V's whole slabs: those past T are zeros
+        double *const lut_e = reinterpret_cast<double *>(smem + a.lds.lut_e) + wave * 256;  // (a table per wave)
+        int8_t *const lut_q = reinterpret_cast<int8_t *>(smem + a.lds.lut_q) + wave * 256;
+        const bool table = !F16 && T > ATT_TABLE_ABOVE;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) e[T + 4 * lane + j] = 0.0;
+        for (int row = wave; row < ATT_ROWS; row += nw) {
+            E *const x = reinterpret_cast<E *>(tile + row * tp);
+            for (int j = T + lane; j < tk; j += 64) x[j] = 0;
+            if (m0 + row >= a.S) continue;  // (wave-uniform) a row past the last query: nothing of it is stored
+            // max (fmax over floats: exact whatever the order)
+            float m = -3.402823466e+38f;
+            for (int j = lane; j < T; j += 64) {
+                if constexpr (F16) m = fmaxf(m, f16_bits_to_float(x[j]));
+                else m = fmaxf(m, dequant_i8((int8_t)x[j], a.x_zi, a.x_si));
+            }
+#pragma unroll
+            for (int w = 32; w >= 1; w >>= 1) m = fmaxf(m, __shfl_xor(m, w));
+            if (table) {
+                // the row holds at most 256 distinct values: lane l evaluates the exponential (and, below, the quotient and its
+                // requantisation) of the values l - 128, l - 64, l, l + 64 once, the elements look theirs up
+                for (int v = lane; v < 256; v += 64) lut_e[v] = softmax_exp(dequant_i8(v - 128, a.x_zi, a.x_si), m);
+                wave_lds_sync();
+                for (int j = lane; j < T; j += 64) e[j] = lut_e[(int)(int8_t)x[j] + 128];
+            } else {
+                for (int j = lane; j < T; j += 64) {
+                    if constexpr (F16) e[j] = softmax_exp(f16_bits_to_float(x[j]), m);
+                    else e[j] = softmax_exp(dequant_i8((int8_t)x[j], a.x_zi, a.x_si), m);
+                }
+            }
+            wave_lds_sync();
+            const double acc = (double)running_sum_exact(e, T, lane);
+            if (table) {
+                for (int v = lane; v < 256; v += 64) lut_q[v] = (int8_t)requant_i8((float)(lut_e[v] / acc), a.p_so, a.p_zo);
+                wave_lds_sync();
+                for (int j = lane; j < T; j += 64) x[j] = (E)lut_q[(int)(int8_t)x[j] + 128];
+            } else {
+                for (int j = lane; j < T; j += 64) {
+                    const float pj = (float)(e[j] / acc);
+                    if constexpr (F16) x[j] = float_to_f16_bits_ref(pj);
+                    else x[j] = (E)(int8_t)requant_i8(pj, a.p_so, a.p_zo);
+                }
+            }
+            wave_lds_sync();  // the next row reuses e and the tables
+        }
+    }
+
+    // ---- out = P V: p from the tile as the [row][k] operand, v through the transposing write ---------------------------------
+    for (int c0 = 0; c0 < a.DV; c0 += ATT_KEYS) {
+        const bool active = mover && c0 + wave * 32 < a.DV;
+        Acc acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0;
+        int32_t rs = 0, cs = 0;
+        uint4 vv0 = make_uint4(0u, 0u, 0u, 0u), vv1 = vv0;
+        if (mover) {
+            vv0 = mm_piece<F16>(pv, a.DV, c0, a.DV, 0, T, 0, a.v_vec, tid);
+            vv1 = mm_piece<F16>(pv, a.DV, c0 + MM_T, a.DV, 0, T, 0, a.v_vec, tid);
+        }
+        for (int k0 = 0; k0 < T; k0 += KS) {
+            __syncthreads();  // the previous slab's fragments were read (first slab: every wave's probabilities are written)
+            if (mover) {
+                mm_put<F16>(lds_kv, vv0, 0, tid);
+                mm_put<F16>(lds_kv + MM_T * MM_PITCH, vv1, 0, tid);
+            }
+            __syncthreads();
+            if (mover && k0 + KS < T) {
+                vv0 = mm_piece<F16>(pv, a.DV, c0, a.DV, k0 + KS, T, 0, a.v_vec, tid);
+                vv1 = mm_piece<F16>(pv, a.DV, c0 + MM_T, a.DV, k0 + KS, T, 0, a.v_vec, tid);
+            }
+            if (!active) continue;
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const v4i fa = *reinterpret_cast<const v4i *>(tile + fr * tp + k0 * ES + s * 32 + fh * 16);
+                const v4i fb = *reinterpret_cast<const v4i *>(lds_kv + (wave * 32 + fr) * MM_PITCH + s * 32 + fh * 16);
+                acc = mfma<!F16>(fa, fb, acc);
+                if constexpr (!F16) {
+                    if (a.izv != 0) {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) rs = __builtin_amdgcn_sdot4(fa[j], 0x01010101, rs, false);
+                    }
+                    if (a.izp != 0) {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) cs = __builtin_amdgcn_sdot4(fb[j], 0x01010101, cs, false);
+                    }
+                }
+            }
+        }
+        if constexpr (!F16) {
+            rs += __shfl_xor(rs, 32);
+            cs += __shfl_xor(cs, 32);
+            if (mover && fh == 0) row_sum[wave][fr] = rs;
+            __syncthreads();
+        }
+        const int n = c0 + wave * 32 + fr;
+        const int32_t kzz = T * a.izp * a.izv;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = (r & 3) + 8 * (r >> 2) + 4 * fh;
+            const int m = m0 + row;
+            if (!mover || m >= a.S || n >= a.DV) continue;
+            const int64_t o = ((int64_t)bi * a.S + m) * a.DV + n;
+            if constexpr (F16) {
+                static_cast<uint16_t *>(a.out)[o] = (uint16_t)mm_value<true>(acc[r], a.o_so, a.o_zo, a.o_inv, a.o_div);
+            } else {
+                const uint32_t S = (uint32_t)acc[r] - (uint32_t)(a.izv * row_sum[wave][row]) - (uint32_t)(a.izp * cs) + (uint32_t)kzz;
+                static_cast<int8_t *>(a.out)[o] =
+                    (int8_t)mm_value<false>(__fmul_rn((float)(int32_t)S, a.mult2), a.o_so, a.o_zo, a.o_inv, a.o_div);
+            }
+        }
+    }
+}
+
+// NULL, or why the call is refused; *code: the status that goes with it
+static const char *attention_refusal(const void *q, const void *k, const void *v, const void *out, const shl_mi355x_attention_desc *d,
+                                     int *code)
+{
+    *code = SHL_MI355X_EINVAL;
+    const char *why = att_validate(q, k, v, out, d);
+    if (why) return why;
+    *code = SHL_MI355X_ENOTSUP;
+    return att_unsupported(d);
+}
+
+}  // namespace shl
+
+extern "C" const char *shl_mi355x_attention_kernel_name(const void *q_dev, const void *k_dev, const void *v_dev, const void *out_dev,
+                                                        const struct shl_mi355x_attention_desc *d)
+{
+    int code;
+    return shl::attention_refusal(q_dev, k_dev, v_dev, out_dev, d, &code) ? "" : SHL_MI355X_ATTENTION_MFMA;
+}
+
+extern "C" int shl_mi355x_attention_by_default(const void *q_dev, const void *k_dev, const void *v_dev, const void *out_dev,
+                                               const struct shl_mi355x_attention_desc *d)
+{
+    int code;
+    return !shl::attention_refusal(q_dev, k_dev, v_dev, out_dev, d, &code) && shl::att_default(d) ? 1 : 0;
+}
+
+extern "C" int shl_mi355x_attention(const void *q_dev, const void *k_dev, const void *v_dev, void *out_dev,
+                                    const struct shl_mi355x_attention_desc *d, void *stream)
+{
+    using namespace shl;
+    int code;
+    const char *why = attention_refusal(q_dev, k_dev, v_dev, out_dev, d, &code);
+    if (why) {
+        set_error("attention: %s", why);
+        return code;
+    }
+    const bool f16 = d->dtype == SHL_MI355X_F16;
+    const int64_t es = f16 ? 2 : 1;
+    shl_mi355x_matmul_desc qk, pv;
+    att_qk_desc(d, &qk);
+    att_pv_desc(d, &pv);
+    AttArgs a;
+    memset(&a, 0, sizeof(a));
+    a.q = q_dev, a.k = k_dev, a.v = v_dev, a.out = out_dev;
+    a.batches = d->batches, a.S = d->s, a.T = d->t, a.D = d->d, a.DV = d->dv;
+    a.tiles = (d->s + ATT_ROWS - 1) / ATT_ROWS;
+    a.q_vec = att_vec(q_dev, d->d, es), a.k_vec = att_vec(k_dev, d->d, es), a.v_vec = att_vec(v_dev, d->dv, es);
+    const int waves = att_waves(d);
+    a.lds = att_lds(d, waves);
+    // the products' constants as matmul_launch sets them
+    a.izq = d->q_zp, a.izk = d->k_zp, a.mult1 = d->q_scale * d->k_scale;  // rounded once, here
+    a.s_so = d->s_scale, a.s_zo = (float)d->s_zp, a.s_inv = 1.0f / d->s_scale, a.s_div = !f16 && mm_fma_ok(&qk);
+    a.izp = d->p_zp, a.izv = d->v_zp, a.mult2 = d->p_scale * d->v_scale;
+    a.o_so = d->out_scale, a.o_zo = (float)d->out_zp, a.o_inv = 1.0f / d->out_scale, a.o_div = !f16 && mm_fma_ok(&pv);
+    // the multiply's as bcast_launch sets them: a the scores, b the constant
+    a.has_scale = d->has_scale, a.craw = d->scale_raw;
+    a.mul.sa = d->s_scale, a.mul.za = (float)d->s_zp, a.mul.sb = d->c_scale, a.mul.zb = (float)d->c_zp;
+    a.mul.so = d->sc_scale, a.mul.zo = (float)d->sc_zp, a.mul.inv_so = 1.0f / d->sc_scale;
+    a.mul.fma_div = mul_fma_ok(d->s_scale, d->s_zp, d->c_scale, d->c_zp, d->sc_scale);
+    a.mul.a_second = d->scale_is_first ? 1 : 0;
+    a.x_si = d->has_scale ? d->sc_scale : d->s_scale, a.x_zi = (float)(d->has_scale ? d->sc_zp : d->s_zp);
+    a.p_so = d->p_scale, a.p_zo = (float)d->p_zp;
+    const int64_t groups = (int64_t)d->batches * a.tiles;  // (at most the output's element count)
+    static LdsOptIn opted_in[2];
+    if (a.lds.bytes > 48 * 1024)
+        lds_opt_in(opted_in[f16], reinterpret_cast<const void *>(f16 ? attention_mfma_kernel<true> : attention_mfma_kernel<false>));
+    hipLaunchKernelGGL(f16 ? attention_mfma_kernel<true> : attention_mfma_kernel<false>, dim3((unsigned)groups), dim3(64 * (unsigned)waves),
+                       (size_t)a.lds.bytes, (hipStream_t)stream, a);
+    SHL_HIP(hipGetLastError());
+    return SHL_MI355X_OK;
+}

@@ -1,0 +1,149 @@
+// attention_canon.h -- the host side of attention.hip: what is wrong with a descriptor, the two products as matmul descriptors,
+// the rule that decides whether the fused kernel exists for a shape, and its LDS layout.  Pure host code that touches no device
+// and includes no HIP header, so that a stand-alone program can compile it with the sanitizers (tests/test_attention_cpu.py).
+#pragma once
+#include <stdint.h>
+#include <string.h>
+
+#include "matmul_canon.h"
+
+namespace shl {
+
+constexpr int ATT_ROWS = 32;     // query rows per workgroup
+constexpr int ATT_KEYS = 128;    // keys (Q K^T) / output columns (P V) per pass: 32 per wave
+constexpr int ATT_TABLE_ABOVE = 256;  // int8 rows longer than this take the exponentials from a per-row table of 256
+
+// Q K^T: a = q [batches][s][d], b = k [batches][t][d] read with swapped strides (trans_b), stored under the s record
+static inline void att_qk_desc(const shl_mi355x_attention_desc *d, shl_mi355x_matmul_desc *m)
+{
+    memset(m, 0, sizeof(*m));
+    m->dtype = d->dtype, m->batches = d->batches, m->m = d->s, m->n = d->t, m->k = d->d;
+    m->a_batch_stride = (int64_t)d->s * d->d, m->a_row_stride = d->d, m->a_k_stride = 1;
+    m->b_batch_stride = (int64_t)d->t * d->d, m->b_col_stride = d->d, m->b_k_stride = 1;
+    m->a_elems = (int64_t)d->batches * d->s * d->d, m->b_elems = (int64_t)d->batches * d->t * d->d;
+    m->out_elems = (int64_t)d->batches * d->s * d->t;
+    m->a_scale = d->q_scale, m->a_zp = d->q_zp, m->b_scale = d->k_scale, m->b_zp = d->k_zp;
+    m->out_scale = d->s_scale, m->out_zp = d->s_zp;
+}
+
+// P V: a = p [batches][s][t], b = v [batches][t][dv], no transposes, stored under the output's record
+static inline void att_pv_desc(const shl_mi355x_attention_desc *d, shl_mi355x_matmul_desc *m)
+{
+    memset(m, 0, sizeof(*m));
+    m->dtype = d->dtype, m->batches = d->batches, m->m = d->s, m->n = d->dv, m->k = d->t;
+    m->a_batch_stride = (int64_t)d->s * d->t, m->a_row_stride = d->t, m->a_k_stride = 1;
+    m->b_batch_stride = (int64_t)d->t * d->dv, m->b_col_stride = 1, m->b_k_stride = d->dv;
+    m->a_elems = (int64_t)d->batches * d->s * d->t, m->b_elems = (int64_t)d->batches * d->t * d->dv;
+    m->out_elems = (int64_t)d->batches * d->s * d->dv;
+    m->a_scale = d->p_scale, m->a_zp = d->p_zp, m->b_scale = d->v_scale, m->b_zp = d->v_zp;
+    m->out_scale = d->out_scale, m->out_zp = d->out_zp;
+}
+
+// NULL, or what is wrong with the call (SHL_MI355X_EINVAL).  Nothing is enqueued and no device is touched
+static inline const char *att_validate(const void *q_dev, const void *k_dev, const void *v_dev, const void *out_dev,
+                                       const shl_mi355x_attention_desc *d)
+{
+    if (!d || !q_dev || !k_dev || !v_dev || !out_dev) return "NULL argument";
+    if (d->dtype != SHL_MI355X_I8 && d->dtype != SHL_MI355X_F16) return "dtype is neither int8 nor binary16";
+    if (d->batches < 1 || d->s < 1 || d->t < 1 || d->d < 1 || d->dv < 1) return "batches, s, t, d or dv below 1";
+    if (d->t > SHL_MI355X_ATTENTION_MAX_KEYS) return "t exceeds SHL_MI355X_ATTENTION_MAX_KEYS";
+    if (d->reserved0 != 0 || d->reserved[0] != 0 || d->reserved[1] != 0 || d->reserved[2] != 0 || d->reserved[3] != 0)
+        return "a reserved field that is not zero";
+    if ((d->has_scale != 0 && d->has_scale != 1) || (d->scale_is_first != 0 && d->scale_is_first != 1))
+        return "has_scale or scale_is_first is neither 0 nor 1";
+    if (d->has_scale && (d->dtype == SHL_MI355X_I8 ? (d->scale_raw < -128 || d->scale_raw > 127) : (d->scale_raw < 0 || d->scale_raw > 0xFFFF)))
+        return "scale_raw is no element of the dtype";
+    // (three factors below 2^31 each: the first product fits 64 bits, the second is taken only when the first is below 2^31)
+    const int64_t lim = 0x7FFFFFFFll;
+    const int64_t ext[5][2] = {{d->s, d->d}, {d->t, d->d}, {d->t, d->dv}, {d->s, d->dv}, {d->s, d->t}};
+    int64_t elems[5];
+    for (int i = 0; i < 5; ++i) {
+        const int64_t first = (int64_t)d->batches * ext[i][0];
+        if (first > lim || first * ext[i][1] > lim) return "a tensor of 2^31 or more elements";
+        elems[i] = first * ext[i][1];
+    }
+    const int64_t es = d->dtype == SHL_MI355X_F16 ? 2 : 1;
+    const uintptr_t o0 = (uintptr_t)out_dev, o1 = o0 + (uintptr_t)(elems[3] * es);
+    const uintptr_t in0[3] = {(uintptr_t)q_dev, (uintptr_t)k_dev, (uintptr_t)v_dev};
+    if ((in0[0] | in0[1] | in0[2] | o0) & (uintptr_t)(es - 1)) return "a pointer that is not aligned to its elements";
+    if (o1 < o0) return "a buffer that wraps around the address space";
+    for (int i = 0; i < 3; ++i) {
+        const uintptr_t i1 = in0[i] + (uintptr_t)(elems[i] * es);
+        if (i1 < in0[i]) return "a buffer that wraps around the address space";
+        if (in0[i] < o1 && o0 < i1) return "the output overlaps an operand";
+    }
+    return NULL;
+}
+
+// The fused kernel exists where shl_mi355x_matmul would run BOTH products in its mfma form: only against that form does the
+// fused launch equal the unfused calls.  NULL, or why not (SHL_MI355X_ENOTSUP); for a descriptor att_validate has passed.
+// (The form does not depend on the pointers: they decide the width of the loads only.)
+// (What a session fuses WITHOUT being asked is narrower: att_default below.)
+static inline const char *att_unsupported(const shl_mi355x_attention_desc *d)
+{
+    shl_mi355x_matmul_desc m;
+    MmPlan p;
+    att_qk_desc(d, &m);
+    mm_plan(NULL, NULL, &m, &p);
+    if (mm_form(&m, &p) != MM_MFMA) return "the matmul form rule gives Q K^T the chain form: the fused kernel equals the mfma form only";
+    att_pv_desc(d, &m);
+    mm_plan(NULL, NULL, &m, &p);
+    if (mm_form(&m, &p) != MM_MFMA) return "the matmul form rule gives P V the chain form: the fused kernel equals the mfma form only";
+    return NULL;
+}
+
+// The shape classes a session fuses by default: those where the fused launch was MEASURED faster than the four launches it
+// replaces by more than the run-to-run spread (profiles/attention_notes.md; fused / unfused, int8 and binary16):
+//   heads of 64 and more are excluded:  197 keys 1.19 / 1.13 (12 heads), 1.40 / 1.35 (3 heads), 1.01 / 1.01 at batch 8;
+//                                        64 keys 1.38 / 1.39; 384 keys 1.39 / 1.39; 512 keys 1.47 / 1.35; 640 keys 1.33 / 1.39
+//   heads of 32 on 850 keys are in:     0.81 / 0.87 (spread 0 - 2 %)
+// Heads below 64 on fewer keys were not measured and stay out.  SHL_MI355X_ATTENTION=1 fuses every shape the kernel takes
+constexpr int ATT_DEFAULT_MAX_D = 32;
+constexpr int ATT_DEFAULT_MIN_KEYS = 768;
+
+static inline bool att_default(const shl_mi355x_attention_desc *d) { return d->d <= ATT_DEFAULT_MAX_D && d->t >= ATT_DEFAULT_MIN_KEYS; }
+
+// 16-byte global loads stay aligned for every batch, row and piece of a dense [..][rows][inner] operand
+static inline int att_vec(const void *p, int64_t inner, int64_t es) { return ((uintptr_t)p & 15) == 0 && (inner * es) % 16 == 0; }
+
+// the LDS image, in bytes from the start: e rows | exponential tables (int8) | score tile | q slab | k / v slab | row sums |
+// requantised tables (int8), the rows and tables one per wave.  Every offset is a multiple of 16
+struct AttLds {
+    int32_t tile_pitch;  // bytes per row of the 32 x t score tile: whole 64-byte slabs of k + 16 (the 32 rows of a fragment read
+                         // fall on different banks)
+    int32_t e, lut_e, tile, slab_q, slab_kv, row_sum, lut_q, bytes;
+};
+
+static inline AttLds att_lds(const shl_mi355x_attention_desc *d, int waves)
+{
+    const int32_t es = d->dtype == SHL_MI355X_F16 ? 2 : 1, i8 = d->dtype == SHL_MI355X_I8;
+    AttLds l;
+    l.tile_pitch = (d->t * es + 63) / 64 * 64 + 16;
+    int32_t at = 0;
+    l.e = at, at += waves * (d->t + 256) * 8;
+    l.lut_e = at, at += i8 ? waves * 256 * 8 : 0;
+    l.tile = at, at += ATT_ROWS * l.tile_pitch;
+    l.slab_q = at, at += ATT_ROWS * 80;
+    l.slab_kv = at, at += ATT_KEYS * 80;
+    l.row_sum = at, at += 4 * 32 * 4;
+    l.lut_q = at, at += i8 ? waves * 256 : 0;
+    l.bytes = at;
+    return l;
+}
+
+// The waves of a workgroup: four run the products, and all of them the softmax, a row each at a time.  The softmax's f64 work
+// (exp, the running sum, the quotient) is a chain per row, so a grid that leaves the chip's SIMDs idle -- batch 1: 84 workgroups
+// for ViT-B's 12 heads on 256 CUs -- brings more waves per workgroup: as many of 16, 8, 4 as keep the whole grid at or under four
+// waves per SIMD (256 CUs x 16) and fit the LDS (an e row and, int8, two tables per wave)
+constexpr int ATT_LDS_BYTES = 160 * 1024;
+constexpr int64_t ATT_CHIP_WAVES = 256 * 16;
+
+static inline int att_waves(const shl_mi355x_attention_desc *d)
+{
+    const int64_t groups = (int64_t)d->batches * ((d->s + ATT_ROWS - 1) / ATT_ROWS);
+    for (int waves = 16; waves > 4; waves /= 2)
+        if (groups * waves <= ATT_CHIP_WAVES && att_lds(d, waves).bytes <= ATT_LDS_BYTES) return waves;
+    return 4;
+}
+
+}  // namespace shl

@@ -41,6 +41,7 @@
 
 #include "add_step.h"
 #include "common.h"
+#include "mul_step.h"
 
 namespace shl {
 
@@ -160,28 +161,7 @@ __device__ __forceinline__ uint64_t mul_b_index(const MulArgs &m, uint64_t e)
     return m.count <= 0xFFFFFFFFull ? mul_b_index<uint32_t>(m, (uint32_t)e) : mul_b_index<uint64_t>(m, e);
 }
 
-__device__ __forceinline__ int mul_i8_one(int qa, int qb, const MulArgs &m)
-{
-    const float x = __fmul_rn(__fsub_rn((float)qa, m.za), m.sa);  // int8_to_float_base (source/nn2/utils.c:499-502)
-    const float y = __fmul_rn(__fsub_rn((float)qb, m.zb), m.sb);
-    const float p = __fmul_rn(x, y);
-    const float d = m.fma_div ? div_by_scale(p, m.so, m.inv_so) : __fdiv_rn(p, m.so);
-    return sat8_from_float(__fadd_rn(rintf(d), m.zo));  // float_to_int8_base (:550-560)
-}
-
-// the product of two binary16 values as the reference's x86 build gives it.  Only NaNs need care: float32_to_float16_base
-// keeps a NaN's sign; the reference multiplies input1's element by input0's (mul.c:23 as compiled), so of two NaN operands
-// input1's goes through, with its own sign; inf * 0 makes the default NaN, whose sign bit is set on x86
-__device__ __forceinline__ uint16_t mul_f16_one(uint16_t ha, uint16_t hb, const MulArgs &m)
-{
-    const uint16_t h1 = m.a_second ? ha : hb, h0 = m.a_second ? hb : ha;  // the reference's input1, input0
-    if ((h1 & 0x7FFFu) > 0x7C00u) return (uint16_t)(0x7FFFu | (h1 & 0x8000u));
-    if ((h0 & 0x7FFFu) > 0x7C00u) return (uint16_t)(0x7FFFu | (h0 & 0x8000u));
-    const float p = __fmul_rn(f16_bits_to_float(ha), f16_bits_to_float(hb));
-    if (p != p) return (uint16_t)0xFFFFu;
-    return float_to_f16_bits_ref(p);
-}
-
+// mul: mul_i8_one / mul_f16_one of mul_step.h, which the fused attention kernel's scale step (attention.hip) applies as well
 // add: the element function of add_step.h, which the fused matmul + bias store (matmul.hip) applies as well
 __device__ __forceinline__ int add_i8_one(int qa, int qb, const MulArgs &m)
 {
@@ -386,10 +366,8 @@ static int bcast_launch(const char *what, const void *a_dev, const void *b_dev, 
     }
     m.sa = d->a_scale, m.za = (float)d->a_zp, m.sb = d->b_scale, m.zb = (float)d->b_zp;
     m.so = d->out_scale, m.zo = (float)d->out_zp, m.inv_so = 1.0f / d->out_scale;
-    // div_by_scale(p, so, RN(1 / so)) == p / so for every product (sum) these records can give (common.h; the range
-    // conv_plan.hip:fma_division_ok admits: 2^-40 <= so <= 2^40, |p| <= 2^60, p finite)
-    const double bound = (128.0 + fabs((double)d->a_zp)) * fabs((double)d->a_scale) * (128.0 + fabs((double)d->b_zp)) * fabs((double)d->b_scale);
-    m.fma_div = fma_div_ok(bound, d->out_scale);
+    // div_by_scale(p, so, RN(1 / so)) == p / so for every product (sum) these records can give (mul_step.h, add_step.h)
+    m.fma_div = mul_fma_ok(d->a_scale, d->a_zp, d->b_scale, d->b_zp, d->out_scale);
     if (OP == OP_ADD) m.fma_div = add_rec(d->a_scale, d->a_zp, d->b_scale, d->b_zp, d->out_scale, d->out_zp).fma_div;  // (the sum's bound)
     m.a_second = d->a_is_second ? 1 : 0;
     const int form = mul_form(OP, a_dev, b_dev, out_dev, d, &m.b_mode);

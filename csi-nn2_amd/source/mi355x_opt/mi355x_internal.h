@@ -167,6 +167,16 @@ int shl_mi355x_matmul_bias_forward(struct csinn_tensor *mat0, struct csinn_tenso
                                    struct csinn_tensor *bias, struct csinn_tensor *output, struct csinn_matmul_params *params,
                                    int bias_is_first, const void *a_dev, const void *b_dev, const void *bias_dev, void *out_dev,
                                    void *stream);
+/* attention.c, for session.c: matmul(q, k, trans_b) -> [mul by the one-element constant c, output sc] -> softmax (output p) ->
+ * matmul(p, v) as one descriptor (prepare: CSINN_TRUE when shl_mi355x_attention takes it and, unless `force`, fuses it by
+ * default) and as one launch on device buffers */
+int shl_mi355x_attention_prepare(struct csinn_tensor *q, struct csinn_tensor *k, struct csinn_tensor *s,
+                                 struct csinn_matmul_params *qk_params, struct csinn_tensor *c, struct csinn_tensor *sc,
+                                 int const_first, struct csinn_tensor *p, int axis, struct csinn_tensor *v,
+                                 struct csinn_tensor *out, struct csinn_matmul_params *pv_params, int force,
+                                 struct shl_mi355x_attention_desc *d);
+int shl_mi355x_attention_forward(const struct shl_mi355x_attention_desc *d, const void *q_dev, const void *k_dev, const void *v_dev,
+                                 void *out_dev, void *stream);
 int shl_mi355x_concat_perf(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params,
                            struct csinn_perf_info *info);
 int shl_mi355x_split_init(struct csinn_tensor *input, struct csinn_tensor **output, struct csinn_split_params *params);

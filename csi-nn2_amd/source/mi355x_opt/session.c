@@ -34,7 +34,7 @@ struct dev_tensor {
     int probe_dev;
 };
 
-/* one unit the session enqueues: a layer, or two layers that run as one launch.  A relu / relu6 layer folded into the
+/* one unit the session enqueues: a layer, or two layers (an attention core: three or four) that run as one launch.  A relu / relu6 layer folded into the
  * convolution in front of it is no step and no layer of a step: the convolution's step writes the activation's output */
 enum step_kind {
     STEP_LAYER,     /* layer a, through its exec callback */
@@ -42,11 +42,12 @@ enum step_kind {
     STEP_POOL_CONV, /* global_avgpool2d a + the convolution / fullyconnected layer b on the pooled map */
     STEP_CONV_POOL, /* 1x1 convolution a + global_avgpool2d b */
     STEP_MATMUL_BIAS, /* matmul a + the add b of a constant bias [N] to its output (shl_mi355x_matmul_bias) */
+    STEP_ATTENTION, /* matmul(q, k^T) a -> [mul by a constant] -> softmax -> matmul(p, v): b, c, d (shl_mi355x_attention) */
 };
 
 struct step {
     enum step_kind kind;
-    int a, b;             /* layer indices; b = -1 for STEP_LAYER */
+    int a, b, c, d;       /* layer indices in order; -1 from the first unused one on (STEP_LAYER: b, a pair: c) */
     struct shl_node *out; /* the tensor node the step finally writes (a split: the first of them) */
 };
 
@@ -63,6 +64,7 @@ struct dev_session {
     int nfused, nfolded;
     int npool; /* global_avgpool2d layers that run inside their consumer's launch */
     int nlinear; /* matmul layers that add the constant bias behind them in their own launch */
+    int nattention; /* Q K^T -> [scale] -> softmax -> P V chains that run as one launch */
     struct dev_session *next;
 };
 
@@ -207,6 +209,43 @@ static int linear_bias_input(struct shl_node *a, struct shl_node *b, struct shl_
     return shl_mi355x_bcast_prepare("add", b->in[0]->data, b->in[1]->data, out, &full, &small, &d) == CSINN_TRUE && small == c ? k : -1;
 }
 
+/* layers[0 .. n-1] (consecutive, each still a step of its own): matmul(q, k, trans_b; two activations) -> [mul by a one-element
+ * constant, on either side] -> softmax over the last axis -> matmul(p, v; v an activation, no transposes), every intermediate
+ * read once, by the next layer, and no graph output.  The number of layers the chain takes (3, or 4 with the mul) and its
+ * descriptor in *d; 0 when the layers run one by one -- also where shl_mi355x_attention has no kernel for the shape or, unless
+ * `force`, the shape is none it was measured faster on (shl_mi355x_attention_by_default) */
+static int attention_chain(struct shl_ref_graph *g, const int *layers, int n, int force, struct shl_mi355x_attention_desc *d)
+{
+    if (n < 3) return 0;
+    struct shl_node *qk = g->layer[layers[0]];
+    if (qk->type != CSINN_OP_MATMUL || session_op(qk) == NULL || qk->in_num != 2) return 0;
+    struct csinn_tensor *tq = qk->in[0]->data, *tk = qk->in[1]->data;
+    if (tq->is_const || tk->is_const || consumers_of(g, qk->out[0]) != 1) return 0;
+    struct shl_node *cur = qk->out[0], *cst = NULL, *sc = NULL;
+    int at = 1, const_first = 0;
+    struct shl_node *mul = g->layer[layers[1]];
+    if (mul->type == CSINN_OP_MUL) {
+        if (n < 4 || session_op(mul) == NULL || mul->in_num != 2 || (mul->in[0] == cur) == (mul->in[1] == cur)) return 0;
+        const_first = mul->in[1] == cur;
+        cst = mul->in[const_first ? 0 : 1];
+        sc = mul->out[0];
+        if (consumers_of(g, sc) != 1) return 0;
+        cur = sc;
+        at = 2;
+    }
+    struct shl_node *sm = g->layer[layers[at]], *pv = g->layer[layers[at + 1]];
+    if (sm->type != CSINN_OP_SOFTMAX || session_op(sm) == NULL || sm->in[0] != cur || consumers_of(g, sm->out[0]) != 1) return 0;
+    struct shl_node *p = sm->out[0];
+    if (pv->type != CSINN_OP_MATMUL || session_op(pv) == NULL || pv->in_num != 2 || pv->in[0] != p || pv->in[1] == p) return 0;
+    struct csinn_tensor *tv = pv->in[1]->data;
+    if (tv->is_const) return 0;
+    struct csinn_softmax_params *sp = sm->data;
+    if (shl_mi355x_attention_prepare(tq, tk, qk->out[0]->data, qk->data, cst ? cst->data : NULL, sc ? sc->data : NULL, const_first,
+                                     p->data, sp->axis, tv, pv->out[0]->data, pv->data, force, d) != CSINN_TRUE)
+        return 0;
+    return at + 2;
+}
+
 /* can steps `s` and `next` (adjacent, each still one layer) run as one launch, and as which?  STEP_LAYER: no */
 static enum step_kind merged_kind(struct shl_ref_graph *g, const struct step *s, const struct step *next)
 {
@@ -258,6 +297,11 @@ static enum step_kind merged_kind(struct shl_ref_graph *g, const struct step *s,
  *   matmul -> add of a constant bias [N], the matmul's only consumer   one launch of csrc/matmul.hip's BIAS instantiation
  *        (STEP_MATMUL_BIAS): the linear layer a converter exports as MatMul + Add; the add's arithmetic runs on the value the
  *        matmul would have stored, so the step equals the two layers bit for bit
+ *   matmul(q, k, trans_b) -> [mul by a one-element constant] -> softmax over the last axis -> matmul(p, v), every intermediate
+ *        read by the next layer only   one launch of csrc/attention.hip (STEP_ATTENTION) where both products take matmul's mfma
+ *        form: the scores and the probabilities stay in LDS, each computed as its own kernel would store it, so the step equals
+ *        the layers bit for bit.  By default only shape classes it was measured faster on (csrc/attention_canon.h:att_default);
+ *        SHL_MI355X_ATTENTION=1 merges every chain the kernel takes, =0 keeps the layers apart
  * Fills ds->steps. */
 static int plan_fusion(struct dev_session *ds, struct shl_ref_graph *g)
 {
@@ -270,7 +314,7 @@ static int plan_fusion(struct dev_session *ds, struct shl_ref_graph *g)
     for (int i = 0; i < g->layer_index; i++) {
         struct shl_node *a = g->layer[i], *b = i + 1 < g->layer_index ? g->layer[i + 1] : NULL;
         struct step *s = &steps[ns++];
-        *s = (struct step){STEP_LAYER, i, -1, a->out[0]};
+        *s = (struct step){STEP_LAYER, i, -1, -1, -1, a->out[0]};
         const int plain = a->type == CSINN_OP_CONV2D || a->type == CSINN_OP_DEPTHWISE_CONV2D;
         const int deconv = a->type == CSINN_OP_DECONV2D || a->type == CSINN_OP_DEPTHWISE_DECONV2D;
         if (!fold || !(plain || deconv) || b == NULL || (b->type != CSINN_OP_RELU && b->type != CSINN_OP_RELU6)) continue;
@@ -302,13 +346,28 @@ static int plan_fusion(struct dev_session *ds, struct shl_ref_graph *g)
     }
     /* merge adjacent steps greedily from the front; a merged step is not the first half of another merge
      * (SHL_MI355X_NO_FUSION=1 also keeps a matmul and its bias add apart: the switch of the linear fusion's A/B runs) */
+    /* SHL_MI355X_ATTENTION, read here, at plan time: "0" keeps the chain's layers apart, "1" merges every chain the kernel takes
+     * (A/B runs), unset merges the shape classes the fused launch was measured faster on */
+    const char *att = getenv("SHL_MI355X_ATTENTION");
+    const int attention = fold && !(att && att[0] == '0'), force = att && att[0] == '1';
     for (int k = 0; k < ns; k++) {
         struct step s = steps[k];
+        /* the core of an attention block first: its matmuls then are no longer candidates for a pair */
+        int chain[4] = {-1, -1, -1, -1}, avail = 0;
+        for (; avail < 4 && k + avail < ns; avail++) chain[avail] = steps[k + avail].a;
+        struct shl_mi355x_attention_desc ad;
+        const int taken = attention ? attention_chain(g, chain, avail, force, &ad) : 0;
+        if (taken > 0) {
+            steps[ds->nsteps++] = (struct step){STEP_ATTENTION, chain[0], chain[1], chain[2], taken == 4 ? chain[3] : -1, steps[k + taken - 1].out};
+            ds->nattention++;
+            k += taken - 1; /* the chain's other steps are taken */
+            continue;
+        }
         enum step_kind kind = k + 1 < ns ? merged_kind(g, &s, &steps[k + 1]) : STEP_LAYER;
         if (kind == STEP_MATMUL_BIAS && !fold) kind = STEP_LAYER;
         if (kind != STEP_LAYER) {
             k++; /* the second step is taken */
-            s = (struct step){kind, s.a, steps[k].a, steps[k].out};
+            s = (struct step){kind, s.a, steps[k].a, -1, -1, steps[k].out};
             if (kind == STEP_PWDW) ds->nfused++;
             else if (kind == STEP_MATMUL_BIAS) ds->nlinear++;
             else ds->npool++;
@@ -392,6 +451,16 @@ static int enqueue_layers(struct dev_session *ds, struct shl_ref_graph *g)
                                                                 nx->out[0]->data, n->data, kb == 0, in->dev, b->dev, bias->dev,
                                                                 out->dev, ds->stream)
                                : CSINN_FALSE;
+                break;
+            }
+            case STEP_ATTENTION: {
+                const int chain[4] = {s->a, s->b, s->c, s->d}, len = s->d >= 0 ? 4 : 3;
+                struct shl_node *pv = g->layer[chain[len - 1]];
+                struct shl_mi355x_attention_desc ad;
+                struct dev_tensor *kk = lookup(ds, n->in[1]), *v = lookup(ds, pv->in[1]);
+                rc = kk && v && attention_chain(g, chain, len, 1, &ad) == len /* (the plan has decided) */
+                         ? shl_mi355x_attention_forward(&ad, in->dev, kk->dev, v->dev, out->dev, ds->stream)
+                         : CSINN_FALSE;
                 break;
             }
             case STEP_PWDW:
@@ -638,6 +707,13 @@ int shl_mi355x_session_fused_linears(struct csinn_session *sess)
 {
     struct dev_session *ds = find_session(sess);
     return ds ? ds->nlinear : 0;
+}
+
+/* number of Q K^T -> [scale] -> softmax -> P V chains of `sess` that run as one launch */
+int shl_mi355x_session_fused_attentions(struct csinn_session *sess)
+{
+    struct dev_session *ds = find_session(sess);
+    return ds ? ds->nattention : 0;
 }
 
 /* 2 when `sess` executes as one device-resident hipGraph, 1 when device-resident with every run enqueueing its layers

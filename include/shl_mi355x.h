@@ -704,6 +704,63 @@ int shl_mi355x_matmul_bias(const void *a_dev, const void *b_dev, const void *bia
 const char *shl_mi355x_matmul_bias_kernel_name(const void *a_dev, const void *b_dev, const void *bias_dev, const void *out_dev,
                                                const struct shl_mi355x_matmul_desc *d);
 
+/* The core of an attention block -- scores = Q K^T, [scores * constant], softmax over the keys, P V -- as ONE launch.  All
+ * four tensors are dense, int8 or binary16: q[batches][s][d], k[batches][t][d] (the trans_b operand of Q K^T),
+ * v[batches][t][dv], out[batches][s][dv]; a head is a batch.  The result equals, bit for bit and in both dtypes, the calls it
+ * replaces: shl_mi355x_matmul (q, k with swapped strides; output record s_*) in its mfma form, then -- has_scale --
+ * shl_mi355x_mul by a one-element constant (raw element scale_raw under c_*; output record sc_*), then shl_mi355x_softmax
+ * along the last axis (output record p_*), then shl_mi355x_matmul (p, v; output record out_*) in its mfma form.  Equality is
+ * by construction, as for shl_mi355x_matmul_bias: every intermediate is computed exactly as the unfused kernel would store it
+ * -- the int8 byte under its record, the rounded half with the NaN rule --, stays in LDS and goes through the next layer's own
+ * element function; both products run the mfma form's instructions on its fragment layout, k ascending in 64-byte slabs,
+ * so binary16 sums are added in matmul_mfma's order.  scale_is_first: the constant is the mul layer's FIRST input (of two
+ * binary16 NaNs the second input's goes through).  binary16 ignores every record.
+ * A workgroup owns 32 query rows of one batch: four waves run the products, and 4, 8 or 16 -- as many as the grid leaves
+ * room for on the chip and the LDS holds -- share the softmax, a row per wave at a time.  The 32 x t scores live in LDS, so t
+ * is capped: SHL_MI355X_ATTENTION_MAX_KEYS.  At the cap in binary16 the kernel holds, in bytes: 32 rows x (2048 + 16) of
+ * scores 66048 + a running-sum row of (1024 + 256) doubles per wave, 40960 for four + operand slabs (32 + 128) x 80 12800 +
+ * row sums 512 = 120320 with four waves, 161280 of 163840 with the eight a small grid gets there (int8: 33280 + 40960 + 12800 +
+ * 512 + per wave an exponential table of 256 doubles and one of 256 bytes, 9216 for four = 96768; with eight waves 146944).
+ * d and dv are bounded by matmul's own rules only (int8: d <= 32768, zero points inside int8).
+ * SHL_MI355X_EINVAL before anything is enqueued: a NULL argument; a dtype that is neither; batches, s, t, d or dv below 1; t
+ * above the cap; a tensor (the scores included) of 2^31 or more elements; pointers not aligned to their elements; the output
+ * overlapping an operand; has_scale / scale_is_first other than 0 or 1; a scale_raw that is no element of the dtype; non-zero
+ * reserved fields.  SHL_MI355X_ENOTSUP when shl_mi355x_matmul's form rule gives either product the chain form (fewer than 64
+ * steps of k with at most 65536 outputs, what the mfma form cannot take, SHL_MI355X_MATMUL_FORM=chain): equality holds
+ * against the mfma form only, so the fused kernel exists only there.  Enqueues only: no allocation, no upload, no
+ * synchronisation (capturable in a hipGraph). */
+#define SHL_MI355X_ATTENTION_MFMA "attention_mfma"
+#define SHL_MI355X_ATTENTION_MAX_KEYS 1024
+
+struct shl_mi355x_attention_desc {
+    int32_t dtype; /* SHL_MI355X_I8 / SHL_MI355X_F16 */
+    int32_t batches;
+    int32_t s, t, d, dv;
+    int32_t has_scale;      /* 0: softmax reads the stored scores; 1: the scores times the constant */
+    int32_t scale_is_first; /* the constant is the mul layer's first input */
+    int32_t scale_raw;      /* the constant's raw element: an int8 value, or the 16 bits of a binary16 */
+    int32_t reserved0;      /* must be zero */
+    float q_scale, k_scale, v_scale;
+    float s_scale;  /* the scores as Q K^T stores them */
+    float c_scale;  /* the constant */
+    float sc_scale; /* the scaled scores */
+    float p_scale;  /* the probabilities */
+    float out_scale;
+    int32_t q_zp, k_zp, v_zp, s_zp, c_zp, sc_zp, p_zp, out_zp;
+    int32_t reserved[4]; /* must be zero */
+};
+
+int shl_mi355x_attention(const void *q_dev, const void *k_dev, const void *v_dev, void *out_dev,
+                         const struct shl_mi355x_attention_desc *d, void *stream);
+/* "attention_mfma", or "" for what the call refuses.  Pure host code, touches no device */
+const char *shl_mi355x_attention_kernel_name(const void *q_dev, const void *k_dev, const void *v_dev, const void *out_dev,
+                                             const struct shl_mi355x_attention_desc *d);
+/* 1 when the call names a kernel AND the shape belongs to a class in which the fused launch was measured faster than the four
+ * launches it replaces (profiles/attention_notes.md: heads of at most 32 on at least 768 keys): what a session fuses without
+ * being asked.  The call itself serves every shape that names a kernel.  Pure host code */
+int shl_mi355x_attention_by_default(const void *q_dev, const void *k_dev, const void *v_dev, const void *out_dev,
+                                    const struct shl_mi355x_attention_desc *d);
+
 /* nearest-neighbour / bilinear resize of a 4-d int8 / binary16 tensor: shl_ref_resize_quant
  * (source/reference/resize.c:464-468), bit for bit.  height_scale / width_scale are the reference's own floats, computed by
  * the CALLER as ONE float division each: (float)in / out, with align_corners (float)(in - 1) / (out - 1)

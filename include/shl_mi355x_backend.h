@@ -194,6 +194,11 @@ int shl_mi355x_session_fused_pools(struct csinn_session *sess);
 int shl_mi355x_session_folded_activations(struct csinn_session *sess);
 /* matmul layers of `sess` that run the add of a constant bias behind them inside their own launch (shl_mi355x_matmul_bias) */
 int shl_mi355x_session_fused_linears(struct csinn_session *sess);
+/* chains matmul(q, k, trans_b) -> [mul by a one-element constant] -> softmax over the last axis -> matmul(p, v) of `sess` that
+ * run as one launch (shl_mi355x_attention).  By default those of a shape class the fused launch was measured faster on
+ * (shl_mi355x_attention_by_default); at setup SHL_MI355X_ATTENTION=1 merges every chain the kernel takes, SHL_MI355X_ATTENTION=0
+ * or SHL_MI355X_NO_FUSION=1 keeps the layers apart */
+int shl_mi355x_session_fused_attentions(struct csinn_session *sess);
 
 #ifdef __cplusplus
 }
