@@ -214,6 +214,12 @@ class AttentionDesc(C.Structure):
         [("reserved", C.c_int32 * 4)]
 
 
+class ResidualDesc(C.Structure):
+    """struct shl_mi355x_residual_desc (include/shl_mi355x.h)"""
+    _fields_ = [("conv_first", C.c_int32), ("skip_scale", C.c_float), ("skip_zp", C.c_int32), ("sum_scale", C.c_float),
+                ("sum_zp", C.c_int32), ("act", C.c_int32), ("out_scale", C.c_float), ("out_zp", C.c_int32)]
+
+
 class ConvDesc(C.Structure):
     """struct shl_mi355x_conv_desc (include/shl_mi355x.h)"""
     _fields_ = [(n, C.c_int32) for n in (
@@ -380,6 +386,10 @@ def load_hip():
         "shl_mi355x_pool_conv_forward": (C.c_int, [vp, vp, vp, i32, i32, f32, i32, f32, i32, vp]),
         "shl_mi355x_conv_pool_fusable": (C.c_int, [vp, i32]),
         "shl_mi355x_conv_pool_forward": (C.c_int, [vp, vp, vp, vp, i32, f32, i32, f32, i32, vp]),
+        "shl_mi355x_conv_add_fusable": (C.c_int, [vp, i32]),
+        "shl_mi355x_conv_add_forward": (C.c_int, [vp, vp, vp, vp, i32, C.POINTER(ResidualDesc), vp]),
+        "shl_mi355x_conv_add_kernel_name": (C.c_char_p, [vp, i32]),
+        "shl_mi355x_conv_add_by_default": (C.c_int, [vp, i32]),
         "shl_mi355x_conv_plan_set_no_stream_consumer": (C.c_int, [vp, i32]),
         "shl_mi355x_pwdw_forward": (C.c_int, [vp, vp, vp, vp, i32, vp]),
         "shl_mi355x_relu_i8": (C.c_int, [vp, vp, sz, f32, i32, f32, i32, i32, vp]),
@@ -535,6 +545,7 @@ def load_backend(frontend):
         opt.shl_mi355x_session_folded_activations.argtypes = [C.POINTER(Session)]
         opt.shl_mi355x_session_fused_linears.argtypes = [C.POINTER(Session)]
         opt.shl_mi355x_session_fused_attentions.argtypes = [C.POINTER(Session)]
+        opt.shl_mi355x_session_fused_residuals.argtypes = [C.POINTER(Session)]
         opt.shl_mi355x_session_stream.argtypes = [C.POINTER(Session)]
         opt.shl_mi355x_session_stream.restype = C.c_void_p
         opt.shl_mi355x_session_set_stream.argtypes = [C.POINTER(Session), C.c_void_p]

@@ -42,6 +42,7 @@
 #include <type_traits>
 
 #include "igemm_common.h"
+#include "residual_step.h"
 
 namespace shl {
 
@@ -118,16 +119,37 @@ __device__ __forceinline__ const char *chunk_addr(const ConvArgs &a, const Pixel
     return ok ? p : pad;
 }
 
+// the four skip bytes behind output offset (p, oc): one dword where the channel count keeps every group of four aligned, else
+// the bytes that exist.  Nothing is read for a pixel or a channel past the tensor (the skip tensor has the output's extent)
+__device__ __forceinline__ uint32_t load_skip4(const ConvArgs &a, const void *skip_dev, int p, int oc, bool vec_ok)
+{
+    if (p >= a.M || oc >= a.Co) return 0;
+    const int8_t *skip = static_cast<const int8_t *>(skip_dev) + (int64_t)p * a.Co + oc;
+    if (vec_ok) return *reinterpret_cast<const uint32_t *>(skip);
+    uint32_t v = 0;
+    for (int e = 0; e < 4 && oc + e < a.Co; ++e) v |= (uint32_t)(uint8_t)skip[e] << (8 * e);
+    return v;
+}
+
 // ---- epilogue of one 32x32 MFMA tile (A rows = output channels, B column = pixel) ---------------
 // C/D layout: column = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5).
 // `tab_*` point at the table entries of the tile's first output channel (LDS or global).
+// EPI & EPI_RESIDUAL (int8): the skip connection's tail `tail` runs on the packed bytes (residual_step.h)
 template <bool kI8, int EPI, typename Acc>
 __device__ __forceinline__ void store_tile(const ConvArgs &a, const Acc &acc, int p, int oc_tile,
                                            int lhalf, const int32_t *tab_acc, const float *tab_mult,
-                                           const float *tab_bias)
+                                           const float *tab_bias, const ResidualTail *tail = nullptr)
 {
     if (p >= a.M) return;
+    constexpr int RQ = EPI & (EPI_RESIDUAL - 1);
+    constexpr bool kPost = kI8 && (EPI & EPI_RESIDUAL) != 0;
     const bool vec_ok = (a.Co & 3) == 0;
+    // the skip operand sits at the output's own offsets: requested in front of the requantisation chains
+    uint32_t skip4[4] = {0, 0, 0, 0};
+    if constexpr (kPost) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) skip4[g] = load_skip4(a, tail->skip, p, oc_tile + 8 * g + 4 * lhalf, vec_ok);
+    }
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
         const int r0 = 8 * g + 4 * lhalf;  // first of this lane's 4 consecutive channels
@@ -138,11 +160,12 @@ __device__ __forceinline__ void store_tile(const ConvArgs &a, const Acc &acc, in
         if constexpr (kI8) {
             const int4 ai = *reinterpret_cast<const int4 *>(tab_acc + r0);
             const float4 mu = *reinterpret_cast<const float4 *>(tab_mult + r0);
-            const int q0 = requant_i8_t<EPI>(acc[4 * g + 0] + ai.x, mu.x, bi.x, a);
-            const int q1 = requant_i8_t<EPI>(acc[4 * g + 1] + ai.y, mu.y, bi.y, a);
-            const int q2 = requant_i8_t<EPI>(acc[4 * g + 2] + ai.z, mu.z, bi.z, a);
-            const int q3 = requant_i8_t<EPI>(acc[4 * g + 3] + ai.w, mu.w, bi.w, a);
-            const uint32_t packed = pack4_i8(q0, q1, q2, q3);
+            const int q0 = requant_i8_t<RQ>(acc[4 * g + 0] + ai.x, mu.x, bi.x, a);
+            const int q1 = requant_i8_t<RQ>(acc[4 * g + 1] + ai.y, mu.y, bi.y, a);
+            const int q2 = requant_i8_t<RQ>(acc[4 * g + 2] + ai.z, mu.z, bi.z, a);
+            const int q3 = requant_i8_t<RQ>(acc[4 * g + 3] + ai.w, mu.w, bi.w, a);
+            uint32_t packed = pack4_i8(q0, q1, q2, q3);
+            if constexpr (kPost) packed = residual4_i8(packed, skip4[g], tail->post);
             int8_t *out = static_cast<int8_t *>(a.out);
             if (vec_ok) {
                 *reinterpret_cast<uint32_t *>(out + o) = packed;
@@ -214,10 +237,12 @@ struct TileGeom {                            //       N > 0 = producer / consume
 };
 
 template <bool kI8, int EPI, int MI, int WR, int WC, bool kUniformTap, int PIPE>
-__global__ __launch_bounds__(64 * WR * WC * (PIPE ? 2 : 1)) void conv_igemm_tile_kernel(ConvArgs a)
+__global__ __launch_bounds__(64 * WR * WC * (PIPE ? 2 : 1)) void conv_igemm_tile_kernel(typename IgemmArgs<EPI>::type a)
 {
     using G = TileGeom<MI, WR, WC, PIPE>;
     constexpr int ESIZE = kI8 ? 1 : 2;
+    constexpr int RQ = EPI & (EPI_RESIDUAL - 1);                   // the requantisation's code (common.h:epi_code)
+    constexpr bool kPost = kI8 && (EPI & EPI_RESIDUAL) != 0;       // ... and the residual tail behind it (residual_step.h)
     constexpr int NST = G::NST;
     constexpr int LA = NST - 1;  // look-ahead in K steps
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -511,6 +536,49 @@ __global__ __launch_bounds__(64 * WR * WC * (PIPE ? 2 : 1)) void conv_igemm_tile
         constexpr int RPI = 64 / CPR;    // rows per store instruction
         const int srow = lane / CPR, schunk = lane % CPR;
         char *out = static_cast<char *>(a.out);
+        if constexpr (kPost) {
+            // The residual tail (int8 NHWC): the same staging, and between the read-back and the store the add's and the
+            // activation's element functions on the staged bytes.  The 16 skip bytes behind each of the lane's four stores are
+            // requested in front of the requantisation chains.  (A compile-time loop: the body is past what a pragma unrolls.)
+            const ResidualTail tail = late_tail(a);
+            static_for<MI / 2>([&](auto ihc) {
+                constexpr int ih = decltype(ihc)::value;
+                const int oc_first = co0 + wr * 32 * MI + ih * 64 + schunk * 16;
+                uint4 skipv[64 / RPI];
+#pragma unroll
+                for (int it = 0; it < 64 / RPI; ++it) {
+                    const int p = pix0 + wc * 64 + it * RPI + srow;
+                    skipv[it] = make_uint4(0, 0, 0, 0);
+                    if (p < a.M && oc_first < a.Co)
+                        skipv[it] = *reinterpret_cast<const uint4 *>(static_cast<const char *>(tail.skip) + (int64_t)p * a.Co + oc_first);
+                }
+#pragma unroll
+                for (int i2 = 0; i2 < 2; ++i2)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) {
+                            constexpr int i = ih * 2;
+                            const int c = i2 * 32 + 8 * g + 4 * fhalf;
+                            const int ch = wr * 32 * MI + ih * 64 + c;
+                            const float4 bi = *reinterpret_cast<const float4 *>(tab_bias + ch);
+                            const int4 ai = *reinterpret_cast<const int4 *>(tab_acc + ch);
+                            const float4 mu = *reinterpret_cast<const float4 *>(tab_mult + ch);
+                            const auto &t = acc[i + i2][j];
+                            *reinterpret_cast<uint32_t *>(ws + (j * 32 + frow) * PITCH + c) =
+                                requant4_i8_t<RQ>(t[4 * g + 0] + ai.x, t[4 * g + 1] + ai.y, t[4 * g + 2] + ai.z, t[4 * g + 3] + ai.w, mu, bi, a);
+                        }
+#pragma unroll
+                for (int it = 0; it < 64 / RPI; ++it) {
+                    const int row = it * RPI + srow;
+                    const int p = pix0 + wc * 64 + row;
+                    uint4 v = *reinterpret_cast<const uint4 *>(ws + row * PITCH + schunk * 16);
+                    v.x = residual4_i8(v.x, skipv[it].x, tail.post), v.y = residual4_i8(v.y, skipv[it].y, tail.post);
+                    v.z = residual4_i8(v.z, skipv[it].z, tail.post), v.w = residual4_i8(v.w, skipv[it].w, tail.post);
+                    if (p < a.M && oc_first < a.Co) *reinterpret_cast<uint4 *>(out + (int64_t)p * a.Co + oc_first) = v;
+                }
+            });
+        } else
 #pragma unroll
         for (int ih = 0; ih < MI / 2; ++ih) {  // 64 channels at a time; the region is wave-private
 #pragma unroll
@@ -529,8 +597,8 @@ __global__ __launch_bounds__(64 * WR * WC * (PIPE ? 2 : 1)) void conv_igemm_tile
                         if constexpr (kI8) {
                             const int4 ai = *reinterpret_cast<const int4 *>(tab_acc + ch);
                             const float4 mu = *reinterpret_cast<const float4 *>(tab_mult + ch);
-                            const uint32_t pk = requant4_i8_t<EPI>(acc[i][j][4 * g + 0] + ai.x, acc[i][j][4 * g + 1] + ai.y,
-                                                                   acc[i][j][4 * g + 2] + ai.z, acc[i][j][4 * g + 3] + ai.w, mu, bi, a);
+                            const uint32_t pk = requant4_i8_t<RQ>(acc[i][j][4 * g + 0] + ai.x, acc[i][j][4 * g + 1] + ai.y,
+                                                                  acc[i][j][4 * g + 2] + ai.z, acc[i][j][4 * g + 3] + ai.w, mu, bi, a);
                             const int q0 = (int8_t)pk, q1 = (int8_t)(pk >> 8), q2 = (int8_t)(pk >> 16), q3 = (int8_t)(pk >> 24);
                             if (a.out_nchw) {
                                 dst_t[0] = (char)q0;
@@ -607,6 +675,14 @@ __global__ __launch_bounds__(64 * WR * WC * (PIPE ? 2 : 1)) void conv_igemm_tile
                     *reinterpret_cast<uint4 *>(out + ((int64_t)p * a.Co + oc_first) * ESIZE) = v;
             }
         }
+    } else if constexpr (kPost) {
+        const ResidualTail tail = late_tail(a);
+        static_for<MI * 2>([&](auto ijc) {
+            constexpr int i = decltype(ijc)::value / 2, j = decltype(ijc)::value % 2;
+            const int ch = wr * 32 * MI + i * 32;
+            store_tile<kI8, EPI>(a, acc[i][j], pix0 + wc * 64 + j * 32 + frow, co0 + ch, fhalf,
+                                 tab_acc + ch, tab_mult + ch, tab_bias + ch, &tail);
+        });
     } else {
 #pragma unroll
         for (int i = 0; i < MI; ++i)
@@ -740,9 +816,11 @@ __global__ __launch_bounds__(256) void conv_igemm_regs_kernel(ConvArgs a)
 constexpr int WU = 8;  // K sub-steps per pipeline group: 2 x 8 x 2 x 16 B = 512 B per lane in flight
 
 template <bool kI8, int EPI, int KS>
-__global__ __launch_bounds__(256) void conv_igemm_wave_kernel(ConvArgs a)
+__global__ __launch_bounds__(256) void conv_igemm_wave_kernel(typename IgemmArgs<EPI>::type a)
 {
     constexpr int ESIZE = kI8 ? 1 : 2;
+    constexpr int RQ = EPI & (EPI_RESIDUAL - 1);              // the requantisation's code (common.h:epi_code)
+    constexpr bool kPost = kI8 && (EPI & EPI_RESIDUAL) != 0;  // ... and the residual tail behind it (residual_step.h)
     __shared__ __attribute__((aligned(16))) int32_t red[KS == 4 ? 4 * 3 * 64 * 4 : 4];
     if (a.debug & 128) return;
     const int lane = threadIdx.x & 63;
@@ -825,12 +903,20 @@ __global__ __launch_bounds__(256) void conv_igemm_wave_kernel(ConvArgs a)
     // ---- finish
     const int p = tm * 32 + frow;
     const bool vec_ok = (a.Co & 3) == 0;
+    // residual tail: the skip bytes behind this lane's stores, requested before the reduction and the requantisation chains
+    // (KS == 1: its four groups; KS == 4: the one group this wave finishes)
+    uint32_t skip4[4] = {0, 0, 0, 0};
+    if constexpr (kPost) {
+#pragma unroll
+        for (int g = 0; g < (KS == 1 ? 4 : 1); ++g) skip4[g] = load_skip4(a, a.tail.skip, p, ch0 + 8 * (KS == 1 ? g : wave), vec_ok);
+    }
     auto finish4 = [&](const int (&v_i)[4], const float (&v_f)[4], int g_tab, int occ) {
         if (p >= a.M || occ >= a.Co) return;
         const int64_t o = (int64_t)p * a.Co + occ;
         if constexpr (kI8) {
-            const uint32_t packed = requant4_i8_t<EPI>(v_i[0] + ai[g_tab].x, v_i[1] + ai[g_tab].y, v_i[2] + ai[g_tab].z,
-                                                       v_i[3] + ai[g_tab].w, mu[g_tab], bi[g_tab], a);
+            uint32_t packed = requant4_i8_t<RQ>(v_i[0] + ai[g_tab].x, v_i[1] + ai[g_tab].y, v_i[2] + ai[g_tab].z,
+                                                v_i[3] + ai[g_tab].w, mu[g_tab], bi[g_tab], a);
+            if constexpr (kPost) packed = residual4_i8(packed, skip4[g_tab], a.tail.post);
             int8_t *out = static_cast<int8_t *>(a.out);
             if (vec_ok) {
                 *reinterpret_cast<uint32_t *>(out + o) = packed;
@@ -927,8 +1013,8 @@ bool igemm_supports(const shl_mi355x_conv_desc &d)
 
 // one launcher per kernel instantiation: kernels that need more than 64 KiB of dynamic LDS must be
 // opted in once through hipFuncSetAttribute
-template <void (*KERNEL)(ConvArgs)>
-static void launch_kernel(dim3 grid, size_t lds, hipStream_t s, const ConvArgs &a, int threads = 256)
+template <typename Args, void (*KERNEL)(Args)>
+static void launch_kernel(dim3 grid, size_t lds, hipStream_t s, const Args &a, int threads = 256)
 {
     static LdsOptIn opted_in;
     if (lds > 64 * 1024) lds_opt_in(opted_in, reinterpret_cast<const void *>(KERNEL));
@@ -1016,6 +1102,11 @@ const char *igemm_variant(int64_t M, int64_t Co, int64_t kbytes)
     if (ov[0]) return "tile";
     // LDS tile kernel once there is at least ~one 128x128 tile for every other CU; below that
     // (MobileNetV1 at batch 1: 1-98 tiles) latency dominates and the barrier-free wave kernel wins
+    return igemm_size_rule(M, Co, kbytes);
+}
+
+const char *igemm_size_rule(int64_t M, int64_t Co, int64_t kbytes)
+{
     const int64_t blocks128 = ((M + BM - 1) / BM) * ((Co + BN - 1) / BN);
     // ... from 96 tiles when K is deep (pointwise 512 -> 512 @14 at batch 16, 100 tiles: 7.6 us against 8.9; 1024 -> 1024 @7
     // at batch 32: 9.5 against 13.5; at 52 tiles the wave kernel is still ahead, 6.1 against 7.5), from 128 otherwise
@@ -1023,6 +1114,9 @@ const char *igemm_variant(int64_t M, int64_t Co, int64_t kbytes)
     // (K rows of 8 KiB and more -- binary16 512 -> 512 3x3 -- from 24: 47 us against 67 at batch 16, 28 tiles)
     return blocks128 >= (kbytes >= 8192 ? 24 : kbytes >= 512 ? 96 : 128) ? "tile" : "wave";
 }
+
+template <int POST, typename Args>
+static int launch_wave_regs_tile(const Args &a, int dtype, const char *v, hipStream_t s);
 
 int launch_conv_igemm(const ConvArgs &a, int dtype, int layout, hipStream_t s)
 {
@@ -1052,6 +1146,24 @@ int launch_conv_igemm(const ConvArgs &a, int dtype, int layout, hipStream_t s)
     if (!strcmp(v, "patch")) return launch_conv_igemm_patch(a, s);
     if (!strcmp(v, "pp")) return launch_conv_igemm_pp(a, dtype, ppf, s);
     if (!strcmp(v, "pc")) return launch_conv_igemm_pc(a, dtype, ppf, s);
+    return launch_wave_regs_tile<0>(a, dtype, v, s);
+}
+
+// a convolution with the residual tail in its stores: `family` is "wave" or "tile", the two that carry the post-op
+int launch_conv_igemm_residual(const ResidualConvArgs &a, const char *family, hipStream_t s)
+{
+    if (a.M == 0 || a.Co == 0) return SHL_MI355X_OK;
+    igemm_note_family(family);
+    return launch_wave_regs_tile<EPI_RESIDUAL>(a, SHL_MI355X_I8, family, s);
+}
+
+// the launch of problem `a` on the wave, regs or tile kernel (`v`).  POST = EPI_RESIDUAL: int8 with the residual tail
+// (Args = ResidualConvArgs), on the wave and tile kernels only -- instantiations of their own; POST = 0: the kernels as they were
+template <int POST, typename Args>
+static int launch_wave_regs_tile(const Args &a, int dtype, const char *v, hipStream_t s)
+{
+    const bool i8 = dtype == SHL_MI355X_I8;
+    const int esize = i8 ? 1 : 2;
     const int epi = i8 ? epi_code(a) : 0;
     dim3 grid;
     size_t lds = 0;
@@ -1115,35 +1227,41 @@ int launch_conv_igemm(const ConvArgs &a, int dtype, int layout, hipStream_t s)
         // to sit in the ring (ResNet-50 64->64 @56: 45 -> see notes), on unless SHL_MI355X_HALO=0
         if (!halo_env && tile == T256x64 && a.Kh * a.Kw * (a.C * esize / BKB) <= 10) want_halo = true;
         const int halo_tile = tile == T128 ? 0 : tile == T256x64 ? 1 : tile == T256x128 ? 2 : -1;
-        if (want_halo && halo_tile >= 0 && halo_eligible(a, esize)) {
+        if (POST == 0 && want_halo && halo_tile >= 0 && halo_eligible(a, esize)) {  // (the halo kernel carries no post-op)
             const int rc = launch_conv_igemm_halo(a, dtype, halo_tile, s);
             if (rc != SHL_MI355X_ENOTSUP) return rc;
         }
     }
-#define SHL_LAUNCH(...) launch_kernel<__VA_ARGS__>(grid, lds, s, a, threads)
-#define SHL_LAUNCH_EPI(KERNEL, ...)                                   \
-    switch (epi) {                                                    \
-        case 0: SHL_LAUNCH(KERNEL<true, 0 __VA_ARGS__>); break;       \
-        case 1: SHL_LAUNCH(KERNEL<true, 1 __VA_ARGS__>); break;       \
-        case 2: SHL_LAUNCH(KERNEL<true, 2 __VA_ARGS__>); break;       \
-        case 3: SHL_LAUNCH(KERNEL<true, 3 __VA_ARGS__>); break;       \
-        case 4: SHL_LAUNCH(KERNEL<true, 4 __VA_ARGS__>); break;       \
-        default: SHL_LAUNCH(KERNEL<true, 5 __VA_ARGS__>); break;      \
+#define SHL_LAUNCH(...) launch_kernel<Args, __VA_ARGS__>(grid, lds, s, a, threads)
+#define SHL_LAUNCH_F16(...) launch_kernel<ConvArgs, __VA_ARGS__>(grid, lds, s, a, threads)
+#define SHL_LAUNCH_EPI(KERNEL, ...)                                          \
+    switch (epi) {                                                           \
+        case 0: SHL_LAUNCH(KERNEL<true, POST + 0 __VA_ARGS__>); break;       \
+        case 1: SHL_LAUNCH(KERNEL<true, POST + 1 __VA_ARGS__>); break;       \
+        case 2: SHL_LAUNCH(KERNEL<true, POST + 2 __VA_ARGS__>); break;       \
+        case 3: SHL_LAUNCH(KERNEL<true, POST + 3 __VA_ARGS__>); break;       \
+        case 4: SHL_LAUNCH(KERNEL<true, POST + 4 __VA_ARGS__>); break;       \
+        default: SHL_LAUNCH(KERNEL<true, POST + 5 __VA_ARGS__>); break;      \
     }
 #define SHL_COMMA ,
 #define SHL_TILE_P(MI, WRV, WCV, UT, PP)                                                                              \
     if (i8) { SHL_LAUNCH_EPI(conv_igemm_tile_kernel, SHL_COMMA MI SHL_COMMA WRV SHL_COMMA WCV SHL_COMMA UT SHL_COMMA PP) } \
-    else { SHL_LAUNCH(conv_igemm_tile_kernel<false, 0, MI, WRV, WCV, UT, PP>); }
+    else { SHL_LAUNCH_F16(conv_igemm_tile_kernel<false, 0, MI, WRV, WCV, UT, PP>); }
 #define SHL_TILE(MI, WRV, WCV, UT) \
     if (pipe) { SHL_TILE_P(MI, WRV, WCV, UT, 4) } else { SHL_TILE_P(MI, WRV, WCV, UT, 0) }
     if (kind == 0) {
         if (splitk) {
-            if (i8) { SHL_LAUNCH_EPI(conv_igemm_wave_kernel, SHL_COMMA 4) } else { SHL_LAUNCH(conv_igemm_wave_kernel<false, 0, 4>); }
+            if (i8) { SHL_LAUNCH_EPI(conv_igemm_wave_kernel, SHL_COMMA 4) } else { SHL_LAUNCH_F16(conv_igemm_wave_kernel<false, 0, 4>); }
         } else {
-            if (i8) { SHL_LAUNCH_EPI(conv_igemm_wave_kernel, SHL_COMMA 1) } else { SHL_LAUNCH(conv_igemm_wave_kernel<false, 0, 1>); }
+            if (i8) { SHL_LAUNCH_EPI(conv_igemm_wave_kernel, SHL_COMMA 1) } else { SHL_LAUNCH_F16(conv_igemm_wave_kernel<false, 0, 1>); }
         }
     } else if (kind == 1) {
-        if (i8) { SHL_LAUNCH_EPI(conv_igemm_regs_kernel) } else { SHL_LAUNCH(conv_igemm_regs_kernel<false, 0>); }
+        if constexpr (POST == 0) {
+            if (i8) { SHL_LAUNCH_EPI(conv_igemm_regs_kernel) } else { SHL_LAUNCH_F16(conv_igemm_regs_kernel<false, 0>); }
+        } else {
+            set_error("conv_add_forward: the regs kernel carries no post-op");
+            return SHL_MI355X_ENOTSUP;
+        }
     } else if (tile == T256x256) {
         SHL_TILE_P(4, 2, 4, true, 0)
     } else if (tile == T256x128) {
@@ -1159,6 +1277,7 @@ int launch_conv_igemm(const ConvArgs &a, int dtype, int layout, hipStream_t s)
 #undef SHL_TILE_P
 #undef SHL_COMMA
 #undef SHL_LAUNCH_EPI
+#undef SHL_LAUNCH_F16
 #undef SHL_LAUNCH
     SHL_HIP(hipGetLastError());
     return SHL_MI355X_OK;

@@ -13,6 +13,8 @@
 #include <vector>
 
 #include "igemm_common.h"
+#include "residual_step.h"
+#include "residual_validate.h"
 
 struct shl_mi355x_conv_plan {
     shl_mi355x_conv_desc desc;
@@ -1219,6 +1221,80 @@ int shl_mi355x_conv_pool_forward(const shl_mi355x_conv_plan *plan, const void *i
     if (rc != SHL_MI355X_OK) return rc;
     if (a.M == 0) return SHL_MI355X_OK;
     return launch_conv1x1_pool(a, pool_dev, mid_scale, (float)mid_zp, out_scale, (float)out_zp, map_dev ? 1 : 0, (hipStream_t)stream);
+}
+
+/* conv2d -> add(conv_out, skip) -> [relu | relu6] in the convolution's launch (conv_igemm.hip, residual_step.h) */
+static ResidualPlanFacts residual_facts(const shl_mi355x_conv_plan *plan)
+{
+    ResidualPlanFacts f;
+    memset(&f, 0, sizeof(f));
+    if (!plan) return f;
+    const shl_mi355x_conv_desc &d = plan->desc;
+    f.present = 1, f.dtype = d.dtype, f.layout = d.layout, f.algo = plan->algo;
+    f.in_pixels = (int64_t)d.in_h * d.in_w, f.in_c = d.in_c;
+    f.out_pixels = (int64_t)d.out_h * d.out_w, f.out_c = d.out_c;
+    f.plan_batch = d.batch;
+    return f;
+}
+
+/* "wave" | "tile" for a fused launch of `plan` at `batch`, NULL where there is none */
+static const char *residual_family(const shl_mi355x_conv_plan *plan, int32_t batch)
+{
+    const ResidualPlanFacts f = residual_facts(plan);
+    static char far_in[1], far_skip[1], far_out[1];
+    shl_mi355x_residual_desc ok = {1, 1.0f, 0, 1.0f, 0, 0, 1.0f, 0};
+    const char *msg;
+    // (the pointers only have to be apart: ask with none of the buffers' extents)
+    ResidualPlanFacts shape = f;
+    shape.in_pixels = shape.out_pixels = 0;
+    if (residual_validate(&shape, far_in, far_skip, far_out, batch, &ok, &msg) != SHL_MI355X_OK) return nullptr;
+    const int64_t n = batch > 0 ? batch : f.plan_batch;
+    if (n * f.out_pixels > 0x7FFFFFFFll || igemm_env_override()) return nullptr;  // (SHL_MI355X_IGEMM: A/B runs of the unfused families)
+    const char *forced = residual_forced_form(getenv("SHL_MI355X_RESIDUAL_FORM"));
+    return forced ? forced : igemm_size_rule(n * f.out_pixels, f.out_c, plan->kstride);
+}
+
+int shl_mi355x_conv_add_fusable(const shl_mi355x_conv_plan *plan, int32_t batch) { return residual_family(plan, batch) ? 1 : 0; }
+
+const char *shl_mi355x_conv_add_kernel_name(const shl_mi355x_conv_plan *plan, int32_t batch)
+{
+    const char *v = residual_family(plan, batch);
+    return !v ? "" : !strcmp(v, "wave") ? "wave+add" : "tile+add";
+}
+
+int shl_mi355x_conv_add_by_default(const shl_mi355x_conv_plan *plan, int32_t batch)
+{
+    const char *v = residual_family(plan, batch);
+    if (!v) return 0;
+    const shl_mi355x_conv_desc &d = plan->desc;
+    const int64_t n = batch > 0 ? batch : d.batch;
+    return residual_default(n * d.out_h * d.out_w, d.out_c, plan->kstride, (int64_t)d.kernel_h * d.kernel_w, !strcmp(v, "tile")) ? 1 : 0;
+}
+
+int shl_mi355x_conv_add_forward(const shl_mi355x_conv_plan *plan, const void *input_dev, const void *skip_dev, void *output_dev,
+                                int32_t batch, const struct shl_mi355x_residual_desc *desc, void *stream)
+{
+    const ResidualPlanFacts f = residual_facts(plan);
+    const char *msg;
+    const int st = residual_validate(&f, input_dev, skip_dev, output_dev, batch, desc, &msg);
+    if (st != SHL_MI355X_OK) {
+        set_error("conv_add_forward: %s", msg);
+        return st;
+    }
+    const char *family = residual_family(plan, batch);
+    if (!family) {
+        set_error("conv_add_forward: no fused launch while SHL_MI355X_IGEMM forces a family");
+        return SHL_MI355X_ENOTSUP;
+    }
+    ResidualConvArgs a;
+    const int rc = fill_args(plan, input_dev, output_dev, batch, a);
+    if (rc != SHL_MI355X_OK) return rc;
+    if (a.M == 0) return SHL_MI355X_OK;
+    const shl_mi355x_conv_desc &d = plan->desc;
+    a.tail.skip = skip_dev;
+    a.tail.post = residual_rec(desc->conv_first, d.out_scale, d.out_zp, desc->skip_scale, desc->skip_zp, desc->sum_scale, desc->sum_zp,
+                               desc->act, desc->act ? desc->out_scale : desc->sum_scale, desc->act ? desc->out_zp : desc->sum_zp);
+    return launch_conv_igemm_residual(a, family, (hipStream_t)stream);
 }
 
 /* pointwise 1x1 + the depthwise 3x3 consuming it, fused into one launch */

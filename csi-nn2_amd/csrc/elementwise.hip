@@ -3,18 +3,17 @@
 // relu6.c:21-43): dequantise with the input record, clamp in fp32, requantise with the output
 // record.  HBM-bound: 16 bytes per lane per access.
 #include "common.h"
+#include "relu_step.h"
 
 namespace shl {
 
+// four packed elements through the layer's element function (relu_step.h)
 __device__ __forceinline__ uint32_t relu4(uint32_t v, float si, float zi, float so, float zo, int relu6)
 {
     uint32_t r = 0;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        float x = __fmul_rn(__fsub_rn((float)(int8_t)(v >> (8 * e)), zi), si);
-        x = x > 0.0f ? x : 0.0f;
-        if (relu6) x = fminf(x, 6.0f);
-        const int q = sat8_from_float(__fadd_rn(rintf(__fdiv_rn(x, so)), zo));
+        const int q = relu_i8_step((int8_t)(v >> (8 * e)), si, zi, so, zo, relu6);
         r |= (uint32_t)(q & 0xFF) << (8 * e);
     }
     return r;
@@ -35,12 +34,8 @@ __global__ __launch_bounds__(256) void relu_i8_kernel(const int8_t *in, int8_t *
         reinterpret_cast<uint4 *>(out)[i] = v;
     }
     // ragged tail
-    for (size_t i = nvec * 16 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
-        float x = __fmul_rn(__fsub_rn((float)in[i], zi), si);
-        x = x > 0.0f ? x : 0.0f;
-        if (relu6) x = fminf(x, 6.0f);
-        out[i] = (int8_t)sat8_from_float(__fadd_rn(rintf(__fdiv_rn(x, so)), zo));
-    }
+    for (size_t i = nvec * 16 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride)
+        out[i] = (int8_t)relu_i8_step(in[i], si, zi, so, zo, relu6);
 }
 
 // binary16: f16 -> f32 (exact), x > 0 ? x : 0, fmin(., 6), f32 -> f16 with the reference rounding

@@ -43,11 +43,13 @@ enum step_kind {
     STEP_CONV_POOL, /* 1x1 convolution a + global_avgpool2d b */
     STEP_MATMUL_BIAS, /* matmul a + the add b of a constant bias [N] to its output (shl_mi355x_matmul_bias) */
     STEP_ATTENTION, /* matmul(q, k^T) a -> [mul by a constant] -> softmax -> matmul(p, v): b, c, d (shl_mi355x_attention) */
+    STEP_CONV_ADD,  /* convolution a -> same-shape add b of its output and a skip tensor -> [relu | relu6 c] (shl_mi355x_conv_add_forward) */
 };
 
 struct step {
     enum step_kind kind;
-    int a, b, c, d;       /* layer indices in order; -1 from the first unused one on (STEP_LAYER: b, a pair: c) */
+    int a, b, c, d;       /* layer indices in order; -1 from the first unused one on (STEP_LAYER: b, a pair: c).  STEP_CONV_ADD:
+                           * a, b, [c], and d = which of the add's operands (0 or 1) is the skip tensor */
     struct shl_node *out; /* the tensor node the step finally writes (a split: the first of them) */
 };
 
@@ -65,6 +67,7 @@ struct dev_session {
     int npool; /* global_avgpool2d layers that run inside their consumer's launch */
     int nlinear; /* matmul layers that add the constant bias behind them in their own launch */
     int nattention; /* Q K^T -> [scale] -> softmax -> P V chains that run as one launch */
+    int nresidual; /* convolution -> add -> [relu | relu6] tails of skip connections that run as one launch */
     struct dev_session *next;
 };
 
@@ -246,12 +249,45 @@ static int attention_chain(struct shl_ref_graph *g, const int *layers, int n, in
     return at + 2;
 }
 
-/* can steps `s` and `next` (adjacent, each still one layer) run as one launch, and as which?  STEP_LAYER: no */
-static enum step_kind merged_kind(struct shl_ref_graph *g, const struct step *s, const struct step *next)
+static int one_record_i8(const struct csinn_tensor *t)
+{
+    return t->dtype == CSINN_DTYPE_INT8 && t->qinfo != NULL && t->quant_channel <= 1;
+}
+
+/* convolution a (its step writes `mid`, a folded activation included) -> add b: the index (0 or 1) of the add's OTHER operand, the
+ * skip tensor, -1 when the pair does not fuse.  The add is the same-shape one -- both operands and the sum int8 tensors of one
+ * record and equal dims -- and reads `mid` once; the plan must be one the fused launch takes (`force`) or was measured faster on */
+static int residual_skip_input(struct shl_node *a, struct shl_node *b, struct shl_node *mid, int force)
+{
+    if (!is_conv_op(a->type) || b->type != CSINN_OP_ADD || session_op(a) == NULL || session_op(b) == NULL) return -1;
+    if (b->in_num != 2 || (b->in[0] == mid) == (b->in[1] == mid)) return -1;
+    const int k = b->in[0] == mid ? 1 : 0;
+    struct csinn_tensor *tm = mid->data, *ts = b->in[k]->data, *to = b->out[0]->data, *in = a->in[0]->data;
+    if (!one_record_i8(tm) || !one_record_i8(ts) || !one_record_i8(to) || ts->is_const) return -1;
+    if (tm->dim_count != 4 || ts->dim_count != 4 || to->dim_count != 4) return -1;
+    for (int i = 0; i < 4; i++)
+        if (ts->dim[i] != tm->dim[i] || to->dim[i] != tm->dim[i]) return -1;
+    shl_mi355x_conv_plan *pa = shl_mi355x_registry_get(a->data);
+    if (pa == NULL) return -1;
+    return (force ? shl_mi355x_conv_add_fusable(pa, in->dim[0]) : shl_mi355x_conv_add_by_default(pa, in->dim[0])) ? k : -1;
+}
+
+/* the relu / relu6 layer `r` behind the sum of a fused residual tail joins it: it reads the sum, nothing else does */
+static int residual_takes_relu(struct shl_ref_graph *g, struct shl_node *sum, struct shl_node *r)
+{
+    if ((r->type != CSINN_OP_RELU && r->type != CSINN_OP_RELU6) || session_op(r) == NULL || r->in[0] != sum) return 0;
+    return consumers_of(g, sum) == 1 && one_record_i8(r->out[0]->data);
+}
+
+/* can steps `s` and `next` (adjacent, each still one layer) run as one launch, and as which?  STEP_LAYER: no.
+ * residual: 0 no residual tails, 1 those of the measured shape classes, 2 every one the kernel takes */
+static enum step_kind merged_kind(struct shl_ref_graph *g, const struct step *s, const struct step *next, int residual)
 {
     struct shl_node *a = g->layer[s->a], *b = g->layer[next->a], *mid = s->out;
     /* a linear layer as converters export it: MatMul(x, W) -> Add(., bias[N]), the bias on either side of the add */
     if (consumers_of(g, mid) == 1 && linear_bias_input(a, b, mid) >= 0) return STEP_MATMUL_BIAS;
+    /* the tail of a skip connection: convolution -> add(conv_out, skip), the convolution's output on either side of the add */
+    if (residual && consumers_of(g, mid) == 1 && residual_skip_input(a, b, mid, residual == 2) >= 0) return STEP_CONV_ADD;
     if (b->in[0] != mid || consumers_of(g, mid) != 1) return STEP_LAYER;
     /* global_avgpool2d -> the convolution / fullyconnected layer on the pooled map: one launch (csrc/conv_gemv.hip) */
     if (a->type == CSINN_OP_GLOBAL_AVGPOOL2D && (is_conv_op(b->type) || b->type == CSINN_OP_FULLYCONNECTED)) {
@@ -302,6 +338,12 @@ static enum step_kind merged_kind(struct shl_ref_graph *g, const struct step *s,
  *        form: the scores and the probabilities stay in LDS, each computed as its own kernel would store it, so the step equals
  *        the layers bit for bit.  By default only shape classes it was measured faster on (csrc/attention_canon.h:att_default);
  *        SHL_MI355X_ATTENTION=1 merges every chain the kernel takes, =0 keeps the layers apart
+ *   convolution (int8 NHWC, implicit GEMM; its folded activation included) -> add(conv_out, skip) of equal shapes, the convolution's
+ *        only consumer -> [relu | relu6, the sum's only consumer]   one launch of the convolution (STEP_CONV_ADD, csrc/conv_igemm.hip's
+ *        instantiations with the post-op): the add's and the activation's element functions run on the byte the convolution would
+ *        have stored, so the step equals the layers bit for bit.  A convolution that is already half of a pair or feeds a pool is
+ *        not taken (those merges come first).  By default only shape classes the fused launch was measured faster on
+ *        (csrc/residual_validate.h:residual_default); SHL_MI355X_RESIDUAL=1 merges every tail the kernel takes, =0 none
  * Fills ds->steps. */
 static int plan_fusion(struct dev_session *ds, struct shl_ref_graph *g)
 {
@@ -350,6 +392,9 @@ static int plan_fusion(struct dev_session *ds, struct shl_ref_graph *g)
      * (A/B runs), unset merges the shape classes the fused launch was measured faster on */
     const char *att = getenv("SHL_MI355X_ATTENTION");
     const int attention = fold && !(att && att[0] == '0'), force = att && att[0] == '1';
+    /* SHL_MI355X_RESIDUAL likewise: "0" none, "1" every tail the kernel takes, unset the measured shape classes */
+    const char *res = getenv("SHL_MI355X_RESIDUAL");
+    const int residual = !fold || (res && res[0] == '0') ? 0 : (res && res[0] == '1') ? 2 : 1;
     for (int k = 0; k < ns; k++) {
         struct step s = steps[k];
         /* the core of an attention block first: its matmuls then are no longer candidates for a pair */
@@ -363,13 +408,20 @@ static int plan_fusion(struct dev_session *ds, struct shl_ref_graph *g)
             k += taken - 1; /* the chain's other steps are taken */
             continue;
         }
-        enum step_kind kind = k + 1 < ns ? merged_kind(g, &s, &steps[k + 1]) : STEP_LAYER;
+        enum step_kind kind = k + 1 < ns ? merged_kind(g, &s, &steps[k + 1], residual) : STEP_LAYER;
         if (kind == STEP_MATMUL_BIAS && !fold) kind = STEP_LAYER;
         if (kind != STEP_LAYER) {
             k++; /* the second step is taken */
-            s = (struct step){kind, s.a, steps[k].a, -1, -1, steps[k].out};
+            const int skip_at = kind == STEP_CONV_ADD ? residual_skip_input(g->layer[s.a], g->layer[steps[k].a], s.out, residual == 2) : -1;
+            s = (struct step){kind, s.a, steps[k].a, -1, skip_at, steps[k].out};
+            if (kind == STEP_CONV_ADD && k + 1 < ns && residual_takes_relu(g, s.out, g->layer[steps[k + 1].a])) {
+                k++; /* ... and the activation behind the sum */
+                s.c = steps[k].a;
+                s.out = steps[k].out;
+            }
             if (kind == STEP_PWDW) ds->nfused++;
             else if (kind == STEP_MATMUL_BIAS) ds->nlinear++;
+            else if (kind == STEP_CONV_ADD) ds->nresidual++;
             else ds->npool++;
         }
         steps[ds->nsteps++] = s;
@@ -461,6 +513,22 @@ static int enqueue_layers(struct dev_session *ds, struct shl_ref_graph *g)
                 rc = kk && v && attention_chain(g, chain, len, 1, &ad) == len /* (the plan has decided) */
                          ? shl_mi355x_attention_forward(&ad, in->dev, kk->dev, v->dev, out->dev, ds->stream)
                          : CSINN_FALSE;
+                break;
+            }
+            case STEP_CONV_ADD: { /* the add and the activation read what the convolution (+ folded activation) would have written */
+                struct shl_node *relu = s->c >= 0 ? g->layer[s->c] : NULL;
+                const int ks = s->d; /* the add's operand that is the skip tensor */
+                struct dev_tensor *skip = ks == 0 || ks == 1 ? lookup(ds, nx->in[ks]) : NULL;
+                if (skip == NULL) {
+                    rc = CSINN_FALSE;
+                    break;
+                }
+                struct csinn_tensor *tskip = nx->in[ks]->data, *tsum = nx->out[0]->data, *tout = relu ? relu->out[0]->data : tsum;
+                struct shl_mi355x_residual_desc rd = {ks == 1, tskip->qinfo->scale, tskip->qinfo->zero_point, tsum->qinfo->scale,
+                                                      tsum->qinfo->zero_point, relu ? (relu->type == CSINN_OP_RELU6 ? 2 : 1) : 0,
+                                                      tout->qinfo->scale, tout->qinfo->zero_point};
+                rc = status_of(shl_mi355x_conv_add_forward(shl_mi355x_registry_get(n->data), in->dev, skip->dev, out->dev, batch, &rd,
+                                                           ds->stream));
                 break;
             }
             case STEP_PWDW:
@@ -714,6 +782,13 @@ int shl_mi355x_session_fused_attentions(struct csinn_session *sess)
 {
     struct dev_session *ds = find_session(sess);
     return ds ? ds->nattention : 0;
+}
+
+/* number of convolution -> add -> [relu | relu6] tails of skip connections of `sess` that run as one launch */
+int shl_mi355x_session_fused_residuals(struct csinn_session *sess)
+{
+    struct dev_session *ds = find_session(sess);
+    return ds ? ds->nresidual : 0;
 }
 
 /* 2 when `sess` executes as one device-resident hipGraph, 1 when device-resident with every run enqueueing its layers

@@ -327,6 +327,33 @@ int shl_mi355x_pool_conv_forward(const shl_mi355x_conv_plan *plan, const void *i
 int shl_mi355x_conv_pool_fusable(const shl_mi355x_conv_plan *plan, int32_t batch);
 int shl_mi355x_conv_pool_forward(const shl_mi355x_conv_plan *plan, const void *input_dev, void *map_dev, void *pool_dev, int32_t batch,
                                  float mid_scale, int32_t mid_zp, float out_scale, int32_t out_zp, void *stream);
+/* The tail of a skip connection -- conv2d [+ its folded activation] -> add(conv_out, skip) -> [relu | relu6] -- as ONE launch of
+ * the convolution (csrc/conv_igemm.hip, csrc/residual_step.h): int8, NHWC, plans of SHL_MI355X_ALGO_IGEMM.  `skip_dev` has the
+ * output's shape and layout.  Between requantisation and store the kernel applies the add's and the activation's element
+ * functions to the byte the convolution would have stored, so the launch equals shl_mi355x_conv_forward, shl_mi355x_add and
+ * shl_mi355x_relu_i8 one after the other bit for bit, for every record.  The convolution's own output record is the plan's.
+ * Two kernel families carry the post-op, the wave kernel and the tile kernels; a fused launch ignores the plan's tuned
+ * variant and picks between them by the size rule, SHL_MI355X_RESIDUAL_FORM=wave|tile (read per call) forces one.
+ * SHL_MI355X_EINVAL before anything is enqueued: a NULL argument, an `act` outside 0 .. 2, a scale that is no positive finite
+ * number, an output that overlaps the input or the skip tensor (the skip tensor may BE the input), a batch that gives 2^31 or
+ * more output pixels.  SHL_MI355X_ENOTSUP: a plan that is not int8 / NHWC / implicit GEMM, or a transposed convolution. */
+struct shl_mi355x_residual_desc {
+    int32_t conv_first;            /* the convolution's output is the add's first operand (else its second) */
+    float skip_scale;  int32_t skip_zp;  /* the other operand's record */
+    float sum_scale;   int32_t sum_zp;   /* the add's output record (= the activation's input record) */
+    int32_t act;                   /* 0 none (the sum is the result), 1 relu, 2 relu6 */
+    float out_scale;   int32_t out_zp;   /* the activation's output record; ignored when act == 0 */
+};
+/* 1 when the plan and the batch qualify (batch 0: the plan's) */
+int shl_mi355x_conv_add_fusable(const shl_mi355x_conv_plan *plan, int32_t batch);
+int shl_mi355x_conv_add_forward(const shl_mi355x_conv_plan *plan, const void *input_dev, const void *skip_dev, void *output_dev,
+                                int32_t batch, const struct shl_mi355x_residual_desc *desc, void *stream);
+/* the family a fused launch of this plan runs at `batch`, with the post-op behind it: "wave+add" or "tile+add" (the activation
+ * is a field of the record, not another kernel); "" where the fused launch is not supported.  Pure host code */
+const char *shl_mi355x_conv_add_kernel_name(const shl_mi355x_conv_plan *plan, int32_t batch);
+/* 1 for the shape classes where the fused launch was measured faster than the launches it replaces by more than their
+ * run-to-run spread (profiles/residual_notes.md): what a session fuses without being asked */
+int shl_mi355x_conv_add_by_default(const shl_mi355x_conv_plan *plan, int32_t batch);
 /* A hint from the owner of the graph: this depthwise layer's output does NOT feed a pointwise layer the bandwidth form
  * (depthwise -> pointwise in one launch, large batches) takes -- the latency form (pointwise -> depthwise) then keeps the
  * layer instead of yielding it (shl_mi355x_pwdw_fusable asks plan pairs, it cannot see a layer's consumer). */

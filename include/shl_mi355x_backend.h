@@ -199,6 +199,11 @@ int shl_mi355x_session_fused_linears(struct csinn_session *sess);
  * (shl_mi355x_attention_by_default); at setup SHL_MI355X_ATTENTION=1 merges every chain the kernel takes, SHL_MI355X_ATTENTION=0
  * or SHL_MI355X_NO_FUSION=1 keeps the layers apart */
 int shl_mi355x_session_fused_attentions(struct csinn_session *sess);
+/* tails of skip connections of `sess` -- convolution -> add(conv_out, skip) -> [relu | relu6] -- that run as one launch of the
+ * convolution (shl_mi355x_conv_add_forward; int8 NHWC implicit-GEMM plans, same-shape adds).  By default those of a shape class
+ * the fused launch was measured faster on (shl_mi355x_conv_add_by_default); at setup SHL_MI355X_RESIDUAL=1 merges every tail the
+ * kernel takes, SHL_MI355X_RESIDUAL=0 or SHL_MI355X_NO_FUSION=1 keeps the layers apart */
+int shl_mi355x_session_fused_residuals(struct csinn_session *sess);
 
 #ifdef __cplusplus
 }
