@@ -390,6 +390,10 @@ def load_hip():
         "shl_mi355x_conv_add_forward": (C.c_int, [vp, vp, vp, vp, i32, C.POINTER(ResidualDesc), vp]),
         "shl_mi355x_conv_add_kernel_name": (C.c_char_p, [vp, i32]),
         "shl_mi355x_conv_add_by_default": (C.c_int, [vp, i32]),
+        "shl_mi355x_conv_lut_fusable": (C.c_int, [vp, i32]),
+        "shl_mi355x_conv_lut_kernel_name": (C.c_char_p, [vp, i32]),
+        "shl_mi355x_conv_lut_by_default": (C.c_int, [vp, i32]),
+        "shl_mi355x_conv_lut_forward": (C.c_int, [vp, vp, vp, i32, vp, vp]),
         "shl_mi355x_conv_plan_set_no_stream_consumer": (C.c_int, [vp, i32]),
         "shl_mi355x_pwdw_forward": (C.c_int, [vp, vp, vp, vp, i32, vp]),
         "shl_mi355x_relu_i8": (C.c_int, [vp, vp, sz, f32, i32, f32, i32, i32, vp]),
@@ -546,6 +550,7 @@ def load_backend(frontend):
         opt.shl_mi355x_session_fused_linears.argtypes = [C.POINTER(Session)]
         opt.shl_mi355x_session_fused_attentions.argtypes = [C.POINTER(Session)]
         opt.shl_mi355x_session_fused_residuals.argtypes = [C.POINTER(Session)]
+        opt.shl_mi355x_session_fused_activations.argtypes = [C.POINTER(Session)]
         opt.shl_mi355x_session_stream.argtypes = [C.POINTER(Session)]
         opt.shl_mi355x_session_stream.restype = C.c_void_p
         opt.shl_mi355x_session_set_stream.argtypes = [C.POINTER(Session), C.c_void_p]
@@ -563,6 +568,9 @@ def load_backend(frontend):
         opt.shl_mi355x_resize_scale.argtypes = [C.c_int32, C.c_int32, C.c_int]
         opt.shl_mi355x_leaky_relu_table_i8.restype = None
         opt.shl_mi355x_leaky_relu_table_i8.argtypes = [C.c_float, C.c_int32, C.c_float, C.c_int32, C.c_float, table]
+        opt.shl_mi355x_gate_mul_table_i8.restype = None
+        opt.shl_mi355x_gate_mul_table_i8.argtypes = [C.c_int, C.c_float, C.c_int32, C.c_float, C.c_int32, C.c_int, C.c_float, C.c_int32,
+                                                     table]
         opt._typed = True
     # the dispatch tables exist after the first csinn_alloc_session (source/nn2/setup.c:77-84)
     s = frontend.csinn_alloc_session()

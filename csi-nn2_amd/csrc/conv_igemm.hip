@@ -42,6 +42,7 @@
 #include <type_traits>
 
 #include "igemm_common.h"
+#include "lut_step.h"
 #include "residual_step.h"
 
 namespace shl {
@@ -135,14 +136,17 @@ __device__ __forceinline__ uint32_t load_skip4(const ConvArgs &a, const void *sk
 // C/D layout: column = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5).
 // `tab_*` point at the table entries of the tile's first output channel (LDS or global).
 // EPI & EPI_RESIDUAL (int8): the skip connection's tail `tail` runs on the packed bytes (residual_step.h)
+// EPI & EPI_LUT (int8): the packed bytes go through the table `lut`, the calling wave's copy in LDS (lut_step.h)
 template <bool kI8, int EPI, typename Acc>
 __device__ __forceinline__ void store_tile(const ConvArgs &a, const Acc &acc, int p, int oc_tile,
                                            int lhalf, const int32_t *tab_acc, const float *tab_mult,
-                                           const float *tab_bias, const ResidualTail *tail = nullptr)
+                                           const float *tab_bias, const ResidualTail *tail = nullptr,
+                                           const uint8_t *lut = nullptr)
 {
     if (p >= a.M) return;
     constexpr int RQ = EPI & (EPI_RESIDUAL - 1);
     constexpr bool kPost = kI8 && (EPI & EPI_RESIDUAL) != 0;
+    constexpr bool kLut = kI8 && (EPI & EPI_LUT) != 0;
     const bool vec_ok = (a.Co & 3) == 0;
     // the skip operand sits at the output's own offsets: requested in front of the requantisation chains
     uint32_t skip4[4] = {0, 0, 0, 0};
@@ -166,6 +170,7 @@ __device__ __forceinline__ void store_tile(const ConvArgs &a, const Acc &acc, in
             const int q3 = requant_i8_t<RQ>(acc[4 * g + 3] + ai.w, mu.w, bi.w, a);
             uint32_t packed = pack4_i8(q0, q1, q2, q3);
             if constexpr (kPost) packed = residual4_i8(packed, skip4[g], tail->post);
+            if constexpr (kLut) packed = lut4(lut, packed);
             int8_t *out = static_cast<int8_t *>(a.out);
             if (vec_ok) {
                 *reinterpret_cast<uint32_t *>(out + o) = packed;
@@ -243,6 +248,7 @@ __global__ __launch_bounds__(64 * WR * WC * (PIPE ? 2 : 1)) void conv_igemm_tile
     constexpr int ESIZE = kI8 ? 1 : 2;
     constexpr int RQ = EPI & (EPI_RESIDUAL - 1);                   // the requantisation's code (common.h:epi_code)
     constexpr bool kPost = kI8 && (EPI & EPI_RESIDUAL) != 0;       // ... and the residual tail behind it (residual_step.h)
+    constexpr bool kLut = kI8 && (EPI & EPI_LUT) != 0;             // ... or the table post-op (lut_step.h)
     constexpr int NST = G::NST;
     constexpr int LA = NST - 1;  // look-ahead in K steps
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -526,6 +532,13 @@ __global__ __launch_bounds__(64 * WR * WC * (PIPE ? 2 : 1)) void conv_igemm_tile
     constexpr int ROW_B = 64 * ESIZE;  // one pixel's 64 channels (two MFMA row blocks)
     constexpr int PITCH = ROW_B + 16;  // padded LDS row: spreads the 4-byte writes over banks
     static_assert(G::NWAVES * 64 * PITCH <= NST * G::STAGE_B, "epilogue staging must fit in the ring");
+    // the table post-op: every MFMA wave copies the table into a slice of its own (all 64 lanes are active here; the array
+    // exists in the EPI_LUT instantiations only and lies outside the ring and the staging region)
+    const uint8_t *lut = nullptr;
+    if constexpr (kLut) {
+        __shared__ uint32_t lut_lds[G::NWAVES * 64];
+        lut = late_lut(lut_lds + wave * 64);
+    }
     if (staged) {
         // Stage 64 pixel x 64 channel blocks through LDS (the ring is free now) so that every lane
         // stores 16 contiguous bytes of one pixel: whole 64-byte (int8) / 128-byte (f16) channel
@@ -597,8 +610,9 @@ __global__ __launch_bounds__(64 * WR * WC * (PIPE ? 2 : 1)) void conv_igemm_tile
                         if constexpr (kI8) {
                             const int4 ai = *reinterpret_cast<const int4 *>(tab_acc + ch);
                             const float4 mu = *reinterpret_cast<const float4 *>(tab_mult + ch);
-                            const uint32_t pk = requant4_i8_t<RQ>(acc[i][j][4 * g + 0] + ai.x, acc[i][j][4 * g + 1] + ai.y,
-                                                                  acc[i][j][4 * g + 2] + ai.z, acc[i][j][4 * g + 3] + ai.w, mu, bi, a);
+                            uint32_t pk = requant4_i8_t<RQ>(acc[i][j][4 * g + 0] + ai.x, acc[i][j][4 * g + 1] + ai.y,
+                                                            acc[i][j][4 * g + 2] + ai.z, acc[i][j][4 * g + 3] + ai.w, mu, bi, a);
+                            if constexpr (kLut) pk = lut4(lut, pk);  // (on the packed bytes, in front of the staging)
                             const int q0 = (int8_t)pk, q1 = (int8_t)(pk >> 8), q2 = (int8_t)(pk >> 16), q3 = (int8_t)(pk >> 24);
                             if (a.out_nchw) {
                                 dst_t[0] = (char)q0;
@@ -682,6 +696,13 @@ __global__ __launch_bounds__(64 * WR * WC * (PIPE ? 2 : 1)) void conv_igemm_tile
             const int ch = wr * 32 * MI + i * 32;
             store_tile<kI8, EPI>(a, acc[i][j], pix0 + wc * 64 + j * 32 + frow, co0 + ch, fhalf,
                                  tab_acc + ch, tab_mult + ch, tab_bias + ch, &tail);
+        });
+    } else if constexpr (kLut) {
+        static_for<MI * 2>([&](auto ijc) {
+            constexpr int i = decltype(ijc)::value / 2, j = decltype(ijc)::value % 2;
+            const int ch = wr * 32 * MI + i * 32;
+            store_tile<kI8, EPI>(a, acc[i][j], pix0 + wc * 64 + j * 32 + frow, co0 + ch, fhalf,
+                                 tab_acc + ch, tab_mult + ch, tab_bias + ch, nullptr, lut);
         });
     } else {
 #pragma unroll
@@ -821,6 +842,7 @@ __global__ __launch_bounds__(256) void conv_igemm_wave_kernel(typename IgemmArgs
     constexpr int ESIZE = kI8 ? 1 : 2;
     constexpr int RQ = EPI & (EPI_RESIDUAL - 1);              // the requantisation's code (common.h:epi_code)
     constexpr bool kPost = kI8 && (EPI & EPI_RESIDUAL) != 0;  // ... and the residual tail behind it (residual_step.h)
+    constexpr bool kLut = kI8 && (EPI & EPI_LUT) != 0;        // ... or the table post-op (lut_step.h)
     __shared__ __attribute__((aligned(16))) int32_t red[KS == 4 ? 4 * 3 * 64 * 4 : 4];
     if (a.debug & 128) return;
     const int lane = threadIdx.x & 63;
@@ -910,6 +932,12 @@ __global__ __launch_bounds__(256) void conv_igemm_wave_kernel(typename IgemmArgs
 #pragma unroll
         for (int g = 0; g < (KS == 1 ? 4 : 1); ++g) skip4[g] = load_skip4(a, a.tail.skip, p, ch0 + 8 * (KS == 1 ? g : wave), vec_ok);
     }
+    // table post-op: the wave's own copy of the table, made here (all 64 lanes active, the K loop behind it) -- no block barrier
+    const uint8_t *lut = nullptr;
+    if constexpr (kLut) {
+        __shared__ uint32_t lut_lds[4 * 64];
+        lut = late_lut(lut_lds + wave * 64);
+    }
     auto finish4 = [&](const int (&v_i)[4], const float (&v_f)[4], int g_tab, int occ) {
         if (p >= a.M || occ >= a.Co) return;
         const int64_t o = (int64_t)p * a.Co + occ;
@@ -917,6 +945,7 @@ __global__ __launch_bounds__(256) void conv_igemm_wave_kernel(typename IgemmArgs
             uint32_t packed = requant4_i8_t<RQ>(v_i[0] + ai[g_tab].x, v_i[1] + ai[g_tab].y, v_i[2] + ai[g_tab].z,
                                                 v_i[3] + ai[g_tab].w, mu[g_tab], bi[g_tab], a);
             if constexpr (kPost) packed = residual4_i8(packed, skip4[g_tab], a.tail.post);
+            if constexpr (kLut) packed = lut4(lut, packed);
             int8_t *out = static_cast<int8_t *>(a.out);
             if (vec_ok) {
                 *reinterpret_cast<uint32_t *>(out + o) = packed;
@@ -1157,8 +1186,17 @@ int launch_conv_igemm_residual(const ResidualConvArgs &a, const char *family, hi
     return launch_wave_regs_tile<EPI_RESIDUAL>(a, SHL_MI355X_I8, family, s);
 }
 
+// a convolution with a table post-op in its stores: `family` is "wave" or "tile" likewise
+int launch_conv_igemm_lut(const LutConvArgs &a, const char *family, hipStream_t s)
+{
+    if (a.M == 0 || a.Co == 0) return SHL_MI355X_OK;
+    igemm_note_family(family);
+    return launch_wave_regs_tile<EPI_LUT>(a, SHL_MI355X_I8, family, s);
+}
+
 // the launch of problem `a` on the wave, regs or tile kernel (`v`).  POST = EPI_RESIDUAL: int8 with the residual tail
-// (Args = ResidualConvArgs), on the wave and tile kernels only -- instantiations of their own; POST = 0: the kernels as they were
+// (Args = ResidualConvArgs), POST = EPI_LUT: int8 with the table post-op (Args = LutConvArgs), on the wave and tile kernels
+// only -- instantiations of their own; POST = 0: the kernels as they were
 template <int POST, typename Args>
 static int launch_wave_regs_tile(const Args &a, int dtype, const char *v, hipStream_t s)
 {
@@ -1259,7 +1297,7 @@ static int launch_wave_regs_tile(const Args &a, int dtype, const char *v, hipStr
         if constexpr (POST == 0) {
             if (i8) { SHL_LAUNCH_EPI(conv_igemm_regs_kernel) } else { SHL_LAUNCH_F16(conv_igemm_regs_kernel<false, 0>); }
         } else {
-            set_error("conv_add_forward: the regs kernel carries no post-op");
+            set_error("the regs kernel carries no post-op");
             return SHL_MI355X_ENOTSUP;
         }
     } else if (tile == T256x256) {

@@ -13,6 +13,8 @@
 #include <vector>
 
 #include "igemm_common.h"
+#include "lut_step.h"
+#include "lut_validate.h"
 #include "residual_step.h"
 #include "residual_validate.h"
 
@@ -1295,6 +1297,79 @@ int shl_mi355x_conv_add_forward(const shl_mi355x_conv_plan *plan, const void *in
     a.tail.post = residual_rec(desc->conv_first, d.out_scale, d.out_zp, desc->skip_scale, desc->skip_zp, desc->sum_scale, desc->sum_zp,
                                desc->act, desc->act ? desc->out_scale : desc->sum_scale, desc->act ? desc->out_zp : desc->sum_zp);
     return launch_conv_igemm_residual(a, family, (hipStream_t)stream);
+}
+
+/* conv2d -> an int8 activation by table (or a swish / hard-swish gate, one table as well) in the convolution's launch
+ * (conv_igemm.hip, lut_step.h) */
+static LutPlanFacts lut_facts(const shl_mi355x_conv_plan *plan)
+{
+    LutPlanFacts f;
+    memset(&f, 0, sizeof(f));
+    if (!plan) return f;
+    const shl_mi355x_conv_desc &d = plan->desc;
+    f.present = 1, f.dtype = d.dtype, f.layout = d.layout, f.algo = plan->algo;
+    f.in_pixels = (int64_t)d.in_h * d.in_w, f.in_c = d.in_c;
+    f.out_pixels = (int64_t)d.out_h * d.out_w, f.out_c = d.out_c;
+    f.plan_batch = d.batch;
+    return f;
+}
+
+/* "wave" | "tile" for a fused launch of `plan` at `batch`, NULL where there is none */
+static const char *lut_family(const shl_mi355x_conv_plan *plan, int32_t batch)
+{
+    const LutPlanFacts f = lut_facts(plan);
+    static char far_in[1], far_out[1];
+    static const uint8_t any_table[256] = {0};
+    const char *msg;
+    // (the pointers only have to be apart: ask with none of the buffers' extents)
+    LutPlanFacts shape = f;
+    shape.in_pixels = shape.out_pixels = 0;
+    if (lut_validate(&shape, far_in, far_out, batch, any_table, &msg) != SHL_MI355X_OK) return nullptr;
+    const int64_t n = batch > 0 ? batch : f.plan_batch;
+    if (n * f.out_pixels > 0x7FFFFFFFll || igemm_env_override()) return nullptr;  // (SHL_MI355X_IGEMM: A/B runs of the unfused families)
+    const char *forced = lut_forced_form(getenv("SHL_MI355X_ACT_FORM"));
+    return forced ? forced : igemm_size_rule(n * f.out_pixels, f.out_c, plan->kstride);
+}
+
+int shl_mi355x_conv_lut_fusable(const shl_mi355x_conv_plan *plan, int32_t batch) { return lut_family(plan, batch) ? 1 : 0; }
+
+const char *shl_mi355x_conv_lut_kernel_name(const shl_mi355x_conv_plan *plan, int32_t batch)
+{
+    const char *v = lut_family(plan, batch);
+    return !v ? "" : !strcmp(v, "wave") ? "wave+lut" : "tile+lut";
+}
+
+int shl_mi355x_conv_lut_by_default(const shl_mi355x_conv_plan *plan, int32_t batch)
+{
+    const char *v = lut_family(plan, batch);
+    if (!v) return 0;
+    const shl_mi355x_conv_desc &d = plan->desc;
+    const int64_t n = batch > 0 ? batch : d.batch;
+    return lut_default(n * d.out_h * d.out_w, d.out_c, plan->kstride, (int64_t)d.kernel_h * d.kernel_w, d.stride_h > 1 || d.stride_w > 1,
+                       !strcmp(v, "tile")) ? 1 : 0;
+}
+
+int shl_mi355x_conv_lut_forward(const shl_mi355x_conv_plan *plan, const void *input_dev, void *output_dev, int32_t batch,
+                                const uint8_t table[256], void *stream)
+{
+    const LutPlanFacts f = lut_facts(plan);
+    const char *msg;
+    const int st = lut_validate(&f, input_dev, output_dev, batch, table, &msg);
+    if (st != SHL_MI355X_OK) {
+        set_error("conv_lut_forward: %s", msg);
+        return st;
+    }
+    const char *family = lut_family(plan, batch);
+    if (!family) {
+        set_error("conv_lut_forward: no fused launch while SHL_MI355X_IGEMM forces a family");
+        return SHL_MI355X_ENOTSUP;
+    }
+    LutConvArgs a;
+    const int rc = fill_args(plan, input_dev, output_dev, batch, a);
+    if (rc != SHL_MI355X_OK) return rc;
+    if (a.M == 0) return SHL_MI355X_OK;
+    memcpy(a.tab.w, table, 256);
+    return launch_conv_igemm_lut(a, family, (hipStream_t)stream);
 }
 
 /* pointwise 1x1 + the depthwise 3x3 consuming it, fused into one launch */

@@ -41,15 +41,13 @@
 
 #include "add_step.h"
 #include "common.h"
+#include "lut_step.h"
 #include "mul_step.h"
 
 namespace shl {
 
 // ------------------------------------------------------------------------------------------ int8 unary by table
-struct Lut256 {
-    uint32_t w[64];  // entry of byte value b (as uint8_t) = byte b & 3 of w[b >> 2]
-};
-
+// (Lut256 and lut4: lut_step.h, which the convolution's fused stores call as well)
 // the table is the FIRST kernel argument: lane t copies dword t of the argument block to LDS (indexing the by-value
 // struct with a lane id would send it through scratch)
 __device__ __forceinline__ void lut_to_lds(uint32_t *lds)
@@ -57,12 +55,6 @@ __device__ __forceinline__ void lut_to_lds(uint32_t *lds)
     typedef const __attribute__((address_space(4))) uint32_t *kernarg_words;
     if (threadIdx.x < 64) lds[threadIdx.x] = ((kernarg_words)__builtin_amdgcn_kernarg_segment_ptr())[threadIdx.x];
     __syncthreads();
-}
-
-__device__ __forceinline__ uint32_t lut4(const uint8_t *lut, uint32_t v)
-{
-    const uint32_t b0 = lut[v & 0xFFu], b1 = lut[(v >> 8) & 0xFFu], b2 = lut[(v >> 16) & 0xFFu], b3 = lut[v >> 24];
-    return b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
 }
 
 __global__ __launch_bounds__(256) void unary_lut_i8_vec_kernel(Lut256 tab, const int8_t *in, int8_t *out, size_t count)

@@ -60,12 +60,9 @@ __device__ __forceinline__ ResidualTail late_tail(const ResidualConvArgs &a)
 }
 
 // EPI of the implicit-GEMM kernels carries the post-op as one more bit above the requantisation's code (common.h:epi_code):
-// the instantiations without it are the ones there were
+// the instantiations without it are the ones there were.  (lut_step.h adds one more bit and holds IgemmArgs<EPI>, which picks
+// the kernel's argument type from the two.)
 constexpr int EPI_RESIDUAL = 8;
-template <int EPI>
-struct IgemmArgs {
-    using type = typename std::conditional<(EPI & EPI_RESIDUAL) != 0, ResidualConvArgs, ConvArgs>::type;
-};
 
 // four outputs at once: the bytes requant4_i8_* packed, the four skip bytes of the same offsets
 __device__ __forceinline__ uint32_t residual4_i8(uint32_t conv4, uint32_t skip4, const ResidualRec &m)

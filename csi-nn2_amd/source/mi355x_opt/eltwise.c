@@ -76,6 +76,28 @@ void shl_mi355x_leaky_relu_table_i8(float in_scale, int32_t in_zp, float out_sca
     build_table(f_leaky_relu, n, in_scale, in_zp, out_scale, out_zp, table);
 }
 
+/* The gate of a swish / hard-swish as converters export it, act(x) -> mul(x, gate): table[(uint8_t)b] is the byte the
+ * reference's mul gives for the operands (b, act(b)) in the layer's operand order.  The gate byte is the activation's own
+ * table entry; the product is source/reference/mul.c:23 behind shl_ref_diso_callback_base (utils.c:623-637): both operands
+ * dequantised (int8_to_float_base), ONE float32 product, float_to_int8_base.  Nothing contracted, as in build_table */
+void shl_mi355x_gate_mul_table_i8(int kind, float x_scale, int32_t x_zp, float gate_scale, int32_t gate_zp, int x_is_first,
+                                  float out_scale, int32_t out_zp, uint8_t table[256])
+{
+    uint8_t gate[256];
+    build_table(kind == SHL_MI355X_UNARY_HARD_SIGMOID ? f_hard_sigmoid : f_sigmoid, 0.0f, x_scale, x_zp, gate_scale, gate_zp, gate);
+    for (int q = -128; q < 128; q++) {
+        const float x = ((float)q - x_zp) * x_scale;
+        const float g = ((float)(int8_t)gate[(uint8_t)q] - gate_zp) * gate_scale;
+        const float p = x_is_first ? x * g : g * x; /* input0's element times input1's */
+        const float ret = nearbyint(p / out_scale) + out_zp;
+        int8_t r;
+        if (ret > 127) r = 127;
+        else if (ret < -128) r = -128;
+        else r = (int8_t)ret;
+        table[(uint8_t)q] = (uint8_t)r;
+    }
+}
+
 /* ---- unary callbacks ------------------------------------------------------------------------------------------ */
 static float (*const g_unary_f[])(float, float) = {f_sigmoid, f_hard_sigmoid, f_silu, f_leaky_relu}; /* by shl_mi355x_unary_kind */
 static const char *const g_unary_name[] = {"sigmoid", "hard_sigmoid", "silu", "leaky_relu"};

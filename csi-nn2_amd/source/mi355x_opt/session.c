@@ -44,6 +44,8 @@ enum step_kind {
     STEP_MATMUL_BIAS, /* matmul a + the add b of a constant bias [N] to its output (shl_mi355x_matmul_bias) */
     STEP_ATTENTION, /* matmul(q, k^T) a -> [mul by a constant] -> softmax -> matmul(p, v): b, c, d (shl_mi355x_attention) */
     STEP_CONV_ADD,  /* convolution a -> same-shape add b of its output and a skip tensor -> [relu | relu6 c] (shl_mi355x_conv_add_forward) */
+    STEP_CONV_LUT,  /* convolution a -> table activation b -> [mul c of the convolution's output and b's: a swish / hard-swish gate]
+                     * (shl_mi355x_conv_lut_forward) */
 };
 
 struct step {
@@ -51,6 +53,7 @@ struct step {
     int a, b, c, d;       /* layer indices in order; -1 from the first unused one on (STEP_LAYER: b, a pair: c).  STEP_CONV_ADD:
                            * a, b, [c], and d = which of the add's operands (0 or 1) is the skip tensor */
     struct shl_node *out; /* the tensor node the step finally writes (a split: the first of them) */
+    uint8_t lut[256];     /* STEP_CONV_LUT: the table of b (and c), built at plan time from the layers' records */
 };
 
 struct dev_session {
@@ -68,6 +71,7 @@ struct dev_session {
     int nlinear; /* matmul layers that add the constant bias behind them in their own launch */
     int nattention; /* Q K^T -> [scale] -> softmax -> P V chains that run as one launch */
     int nresidual; /* convolution -> add -> [relu | relu6] tails of skip connections that run as one launch */
+    int nactivation; /* table activations (gates included) that run inside their convolution's launch */
     struct dev_session *next;
 };
 
@@ -279,6 +283,54 @@ static int residual_takes_relu(struct shl_ref_graph *g, struct shl_node *sum, st
     return consumers_of(g, sum) == 1 && one_record_i8(r->out[0]->data);
 }
 
+static int same_dims(const struct csinn_tensor *x, const struct csinn_tensor *y)
+{
+    if (x->dim_count != y->dim_count) return 0;
+    for (int i = 0; i < x->dim_count; i++)
+        if (x->dim[i] != y->dim[i]) return 0;
+    return 1;
+}
+
+/* steps[0 .. n-1] (consecutive, each still one layer; steps[0] a convolution with its folded activation) begin with a table
+ * activation folded into the convolution's launch: the number of steps it takes and the table in `lut`; 0: the layers stay apart.
+ *   2  convolution -> sigmoid | hard_sigmoid | silu | leaky_relu, which alone reads the convolution's output
+ *   3  convolution -> sigmoid | hard_sigmoid -> mul(conv_out, gate), the convolution's output on either side of a same-shape mul
+ *      and read by exactly those two layers, the gate read by the mul alone: a swish / hard-swish as converters export it
+ * (consumers_of counts a graph output as a reader, so no intermediate tensor is one).  Every tensor is an int8 tensor of one
+ * record and the convolution's output dims; the plan must be one the fused launch takes (`force`) or was measured faster on */
+static int lut_chain(struct shl_ref_graph *g, const struct step *steps, int n, int force, uint8_t lut[256])
+{
+    if (n < 2) return 0;
+    struct shl_node *a = g->layer[steps[0].a], *b = g->layer[steps[1].a], *mid = steps[0].out;
+    if (!is_conv_op(a->type) || session_op(a) == NULL || session_op(b) == NULL || b->in_num < 1 || b->in[0] != mid) return 0;
+    const int gate_kind = b->type == CSINN_OP_SIGMOID || b->type == CSINN_OP_HARD_SIGMOID;
+    if (!gate_kind && b->type != CSINN_OP_SILU && b->type != CSINN_OP_LEAKY_RELU) return 0;
+    struct csinn_tensor *tm = mid->data, *tb = b->out[0]->data, *in = a->in[0]->data;
+    if (!one_record_i8(tm) || !one_record_i8(tb) || tm->dim_count != 4 || !same_dims(tm, tb)) return 0;
+    shl_mi355x_conv_plan *pa = shl_mi355x_registry_get(a->data);
+    if (pa == NULL || !(force ? shl_mi355x_conv_lut_fusable(pa, in->dim[0]) : shl_mi355x_conv_lut_by_default(pa, in->dim[0]))) return 0;
+    const float si = tm->qinfo->scale, so = tb->qinfo->scale;
+    const int32_t zi = tm->qinfo->zero_point, zo = tb->qinfo->zero_point;
+    const int readers = consumers_of(g, mid);
+    if (readers == 1) {
+        if (b->type == CSINN_OP_SIGMOID) shl_mi355x_sigmoid_table_i8(si, zi, so, zo, lut);
+        else if (b->type == CSINN_OP_HARD_SIGMOID) shl_mi355x_hard_sigmoid_table_i8(si, zi, so, zo, lut);
+        else if (b->type == CSINN_OP_SILU) shl_mi355x_silu_table_i8(si, zi, so, zo, lut);
+        else shl_mi355x_leaky_relu_table_i8(si, zi, so, zo, ((struct csinn_relu_params *)b->data)->n, lut);
+        return 2;
+    }
+    if (readers != 2 || !gate_kind || n < 3) return 0;
+    struct shl_node *c = g->layer[steps[2].a], *gate = b->out[0];
+    if (c->type != CSINN_OP_MUL || session_op(c) == NULL || c->in_num != 2 || consumers_of(g, gate) != 1) return 0;
+    const int x_first = c->in[0] == mid && c->in[1] == gate;
+    if (!x_first && !(c->in[0] == gate && c->in[1] == mid)) return 0;
+    struct csinn_tensor *tc = c->out[0]->data;
+    if (!one_record_i8(tc) || !same_dims(tm, tc)) return 0; /* (the same-shape mul: nothing is broadcast) */
+    shl_mi355x_gate_mul_table_i8(b->type == CSINN_OP_HARD_SIGMOID ? SHL_MI355X_UNARY_HARD_SIGMOID : SHL_MI355X_UNARY_SIGMOID, si, zi, so, zo,
+                                 x_first, tc->qinfo->scale, tc->qinfo->zero_point, lut);
+    return 3;
+}
+
 /* can steps `s` and `next` (adjacent, each still one layer) run as one launch, and as which?  STEP_LAYER: no.
  * residual: 0 no residual tails, 1 those of the measured shape classes, 2 every one the kernel takes */
 static enum step_kind merged_kind(struct shl_ref_graph *g, const struct step *s, const struct step *next, int residual)
@@ -344,6 +396,14 @@ static enum step_kind merged_kind(struct shl_ref_graph *g, const struct step *s,
  *        have stored, so the step equals the layers bit for bit.  A convolution that is already half of a pair or feeds a pool is
  *        not taken (those merges come first).  By default only shape classes the fused launch was measured faster on
  *        (csrc/residual_validate.h:residual_default); SHL_MI355X_RESIDUAL=1 merges every tail the kernel takes, =0 none
+ *   convolution (int8 NHWC, implicit GEMM; its folded activation included) -> sigmoid | hard_sigmoid | silu | leaky_relu, the
+ *        convolution's only consumer, or -> sigmoid | hard_sigmoid -> mul(conv_out, gate), a swish / hard-swish gate   one launch of
+ *        the convolution (STEP_CONV_LUT, csrc/conv_igemm.hip's instantiations with the table post-op): on int8 the layers are a
+ *        function of the byte the convolution would have stored, ONE 256-entry table built here from their records with the
+ *        layers' own builders, so the step equals the layers bit for bit.  Tried after the merges above: a convolution that is
+ *        half of a pair, feeds a pool or a residual tail is not taken, and the step is not the first half of a residual merge.
+ *        By default only shape classes the fused launch was measured faster on (csrc/lut_validate.h:lut_default);
+ *        SHL_MI355X_ACT_FUSE=1 merges every one the kernel takes, =0 none
  * Fills ds->steps. */
 static int plan_fusion(struct dev_session *ds, struct shl_ref_graph *g)
 {
@@ -395,6 +455,9 @@ static int plan_fusion(struct dev_session *ds, struct shl_ref_graph *g)
     /* SHL_MI355X_RESIDUAL likewise: "0" none, "1" every tail the kernel takes, unset the measured shape classes */
     const char *res = getenv("SHL_MI355X_RESIDUAL");
     const int residual = !fold || (res && res[0] == '0') ? 0 : (res && res[0] == '1') ? 2 : 1;
+    /* SHL_MI355X_ACT_FUSE likewise, for the table activations */
+    const char *af = getenv("SHL_MI355X_ACT_FUSE");
+    const int act_fuse = !fold || (af && af[0] == '0') ? 0 : (af && af[0] == '1') ? 2 : 1;
     for (int k = 0; k < ns; k++) {
         struct step s = steps[k];
         /* the core of an attention block first: its matmuls then are no longer candidates for a pair */
@@ -423,6 +486,16 @@ static int plan_fusion(struct dev_session *ds, struct shl_ref_graph *g)
             else if (kind == STEP_MATMUL_BIAS) ds->nlinear++;
             else if (kind == STEP_CONV_ADD) ds->nresidual++;
             else ds->npool++;
+        } else if (act_fuse) {
+            const int lut_taken = lut_chain(g, &steps[k], ns - k, act_fuse == 2, s.lut);
+            if (lut_taken > 0) {
+                s.kind = STEP_CONV_LUT;
+                s.b = steps[k + 1].a;
+                s.c = lut_taken == 3 ? steps[k + 2].a : -1;
+                s.out = steps[k + lut_taken - 1].out;
+                ds->nactivation++;
+                k += lut_taken - 1; /* the activation's (and the mul's) steps are taken */
+            }
         }
         steps[ds->nsteps++] = s;
     }
@@ -531,6 +604,9 @@ static int enqueue_layers(struct dev_session *ds, struct shl_ref_graph *g)
                                                            ds->stream));
                 break;
             }
+            case STEP_CONV_LUT: /* the table's input is what the convolution (+ folded activation) would have written */
+                rc = status_of(shl_mi355x_conv_lut_forward(shl_mi355x_registry_get(n->data), in->dev, out->dev, batch, s->lut, ds->stream));
+                break;
             case STEP_PWDW:
                 rc = status_of(shl_mi355x_pwdw_forward(shl_mi355x_registry_get(n->data), shl_mi355x_registry_get(nx->data), in->dev,
                                                        out->dev, batch, ds->stream));
@@ -789,6 +865,13 @@ int shl_mi355x_session_fused_residuals(struct csinn_session *sess)
 {
     struct dev_session *ds = find_session(sess);
     return ds ? ds->nresidual : 0;
+}
+
+/* number of table activations (gates included) of `sess` that run inside their convolution's launch */
+int shl_mi355x_session_fused_activations(struct csinn_session *sess)
+{
+    struct dev_session *ds = find_session(sess);
+    return ds ? ds->nactivation : 0;
 }
 
 /* 2 when `sess` executes as one device-resident hipGraph, 1 when device-resident with every run enqueueing its layers

@@ -354,6 +354,28 @@ const char *shl_mi355x_conv_add_kernel_name(const shl_mi355x_conv_plan *plan, in
 /* 1 for the shape classes where the fused launch was measured faster than the launches it replaces by more than their
  * run-to-run spread (profiles/residual_notes.md): what a session fuses without being asked */
 int shl_mi355x_conv_add_by_default(const shl_mi355x_conv_plan *plan, int32_t batch);
+/* An int8 activation that is a 256-entry table -- sigmoid / hard_sigmoid / silu / leaky_relu behind the convolution, or the
+ * gate of a swish / hard-swish, mul(x, act(x)), which depends on x's byte alone -- as ONE launch of the convolution
+ * (csrc/conv_igemm.hip, csrc/lut_step.h): int8, NHWC, plans of SHL_MI355X_ALGO_IGEMM.  `table` is HOST memory, 256 bytes,
+ * entry (uint8_t)q for input byte q, as shl_mi355x_unary_lut_i8 takes it; it travels by value in the kernel arguments, so the
+ * launch allocates nothing and is capturable.  Between requantisation and store the kernel looks up the byte the
+ * convolution would have stored (folded relu / relu6 and saturation included), so the launch equals shl_mi355x_conv_forward
+ * followed by shl_mi355x_unary_lut_i8 with the same table byte for byte, for ANY 256 bytes.
+ * Two kernel families carry the post-op, the wave kernel and the tile kernels; a fused launch ignores the plan's tuned
+ * variant and picks between them by the size rule, SHL_MI355X_ACT_FORM=wave|tile (read per call) forces one; there is no fused
+ * launch while SHL_MI355X_IGEMM forces a family.
+ * SHL_MI355X_EINVAL before anything is enqueued: a NULL argument, an output that overlaps the input, a batch that gives 2^31
+ * or more output pixels.  SHL_MI355X_ENOTSUP: a plan that is not int8 / NHWC / implicit GEMM, or a transposed convolution. */
+/* 1 when the plan and the batch qualify (batch 0: the plan's) */
+int shl_mi355x_conv_lut_fusable(const shl_mi355x_conv_plan *plan, int32_t batch);
+/* the family a fused launch of this plan runs at `batch`, with the post-op behind it: "wave+lut" or "tile+lut"; "" where the
+ * fused launch is not supported.  Pure host code */
+const char *shl_mi355x_conv_lut_kernel_name(const shl_mi355x_conv_plan *plan, int32_t batch);
+/* 1 for the shape classes where the fused launch was measured faster than the two launches it replaces by more than their
+ * run-to-run spread (profiles/act_fuse_notes.md): what a session fuses without being asked */
+int shl_mi355x_conv_lut_by_default(const shl_mi355x_conv_plan *plan, int32_t batch);
+int shl_mi355x_conv_lut_forward(const shl_mi355x_conv_plan *plan, const void *input_dev, void *output_dev, int32_t batch,
+                                const uint8_t table[256], void *stream);
 /* A hint from the owner of the graph: this depthwise layer's output does NOT feed a pointwise layer the bandwidth form
  * (depthwise -> pointwise in one launch, large batches) takes -- the latency form (pointwise -> depthwise) then keeps the
  * layer instead of yielding it (shl_mi355x_pwdw_fusable asks plan pairs, it cannot see a layer's consumer). */

@@ -161,6 +161,12 @@ void shl_mi355x_sigmoid_table_i8(float in_scale, int32_t in_zp, float out_scale,
 void shl_mi355x_hard_sigmoid_table_i8(float in_scale, int32_t in_zp, float out_scale, int32_t out_zp, uint8_t table[256]);
 void shl_mi355x_silu_table_i8(float in_scale, int32_t in_zp, float out_scale, int32_t out_zp, uint8_t table[256]);
 void shl_mi355x_leaky_relu_table_i8(float in_scale, int32_t in_zp, float out_scale, int32_t out_zp, float n, uint8_t table[256]);
+/* the gate of a swish / hard-swish, act(x) -> mul(x, gate), as ONE table: table[(uint8_t)b] = the byte the reference's mul gives
+ * for the operands (b, act(b)).  `kind`: SHL_MI355X_UNARY_SIGMOID or SHL_MI355X_UNARY_HARD_SIGMOID; x: the record of the tensor
+ * both layers read; gate: the activation's output record; `x_is_first`: x is the mul's first operand; out: the mul's output
+ * record.  Pure host code */
+void shl_mi355x_gate_mul_table_i8(int kind, float x_scale, int32_t x_zp, float gate_scale, int32_t gate_zp, int x_is_first,
+                                  float out_scale, int32_t out_zp, uint8_t table[256]);
 /* elementwise product; one operand has the output's shape, the other is broadcast to it by the reference's rule (either
  * order).  Both operands needing a broadcast, or shapes that break the rule, are refused */
 int shl_mi355x_mul_exec(struct csinn_tensor *input0, struct csinn_tensor *input1, struct csinn_tensor *output,
@@ -204,6 +210,12 @@ int shl_mi355x_session_fused_attentions(struct csinn_session *sess);
  * the fused launch was measured faster on (shl_mi355x_conv_add_by_default); at setup SHL_MI355X_RESIDUAL=1 merges every tail the
  * kernel takes, SHL_MI355X_RESIDUAL=0 or SHL_MI355X_NO_FUSION=1 keeps the layers apart */
 int shl_mi355x_session_fused_residuals(struct csinn_session *sess);
+/* table activations of `sess` that run inside their convolution's launch (shl_mi355x_conv_lut_forward; int8 NHWC
+ * implicit-GEMM plans): convolution -> sigmoid | hard_sigmoid | silu | leaky_relu, and the gates convolution -> sigmoid |
+ * hard_sigmoid -> mul(conv_out, gate), each counted once.  By default those of a shape class the fused launch was measured
+ * faster on (shl_mi355x_conv_lut_by_default); at setup SHL_MI355X_ACT_FUSE=1 merges every one the kernel takes,
+ * SHL_MI355X_ACT_FUSE=0 or SHL_MI355X_NO_FUSION=1 keeps the layers apart */
+int shl_mi355x_session_fused_activations(struct csinn_session *sess);
 
 #ifdef __cplusplus
 }
