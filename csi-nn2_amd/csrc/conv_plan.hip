@@ -1372,6 +1372,72 @@ int shl_mi355x_conv_lut_forward(const shl_mi355x_conv_plan *plan, const void *in
     return launch_conv_igemm_lut(a, family, (hipStream_t)stream);
 }
 
+/* the same post-op behind a depthwise layer, in the depthwise launch (dwconv.hip, dwconv_mfma.hip, lut_step.h) */
+/* DW_LUT_* of the kernel launch_dwconv runs for `plan` at `batch`; for a plan or a batch outside the scope, which dw_lut_validate
+ * refuses whatever the kernel, the generic one */
+static int dw_kernel_at(const shl_mi355x_conv_plan *plan, const LutPlanFacts &f, int32_t batch)
+{
+    const int64_t n = batch > 0 ? batch : f.plan_batch;
+    if (!f.present || f.dtype != SHL_MI355X_I8 || f.layout != SHL_MI355X_NHWC || f.algo != SHL_MI355X_ALGO_DW || n < 0 ||
+        n * f.out_pixels > 0x7FFFFFFFll)
+        return DW_LUT_NHWC;
+    ConvArgs a;
+    static char dummy[16];
+    return fill_args(plan, dummy, dummy, batch, a) == SHL_MI355X_OK ? dwconv_i8_kernel(a) : DW_LUT_NHWC;
+}
+
+/* ... -1 where there is no fused launch */
+static int dw_lut_kernel(const shl_mi355x_conv_plan *plan, int32_t batch)
+{
+    const LutPlanFacts f = lut_facts(plan);
+    const int kernel = dw_kernel_at(plan, f, batch);
+    static char far_in[1], far_out[1];
+    static const uint8_t any_table[256] = {0};
+    const char *msg;
+    // (the pointers only have to be apart: ask with none of the buffers' extents)
+    LutPlanFacts shape = f;
+    shape.in_pixels = shape.out_pixels = 0;
+    if (dw_lut_validate(&shape, plan ? plan->desc.out_w : 0, kernel, far_in, far_out, batch, any_table, &msg) != SHL_MI355X_OK) return -1;
+    const int64_t n = batch > 0 ? batch : f.plan_batch;
+    return n * f.out_pixels > 0x7FFFFFFFll ? -1 : kernel;
+}
+
+int shl_mi355x_dwconv_lut_fusable(const shl_mi355x_conv_plan *plan, int32_t batch) { return dw_lut_kernel(plan, batch) >= 0 ? 1 : 0; }
+
+const char *shl_mi355x_dwconv_lut_kernel_name(const shl_mi355x_conv_plan *plan, int32_t batch)
+{
+    const int k = dw_lut_kernel(plan, batch);
+    return k == DW_LUT_DOT4 ? "dwconv_dot4+lut" : k == DW_LUT_MFMA ? "dwconv_mfma+lut" : k == DW_LUT_NHWC ? "dwconv_nhwc+lut" : "";
+}
+
+int shl_mi355x_dwconv_lut_by_default(const shl_mi355x_conv_plan *plan, int32_t batch)
+{
+    const int k = dw_lut_kernel(plan, batch);
+    if (k < 0) return 0;
+    const shl_mi355x_conv_desc &d = plan->desc;
+    const int64_t n = batch > 0 ? batch : d.batch;
+    return dw_lut_default(n * d.out_h * d.out_w, d.out_c, (int64_t)d.kernel_h * d.kernel_w, d.stride_h > 1 || d.stride_w > 1, k) ? 1 : 0;
+}
+
+int shl_mi355x_dwconv_lut_forward(const shl_mi355x_conv_plan *plan, const void *input_dev, void *output_dev, int32_t batch,
+                                  const uint8_t table[256], void *stream)
+{
+    const LutPlanFacts f = lut_facts(plan);
+    const int kernel = dw_kernel_at(plan, f, batch);
+    const char *msg;
+    const int st = dw_lut_validate(&f, plan ? plan->desc.out_w : 0, kernel, input_dev, output_dev, batch, table, &msg);
+    if (st != SHL_MI355X_OK) {
+        set_error("dwconv_lut_forward: %s", msg);
+        return st;
+    }
+    LutConvArgs a;
+    const int rc = fill_args(plan, input_dev, output_dev, batch, a);
+    if (rc != SHL_MI355X_OK) return rc;
+    if (a.M == 0) return SHL_MI355X_OK;
+    memcpy(a.tab.w, table, 256);
+    return launch_dwconv_lut(a, (hipStream_t)stream);
+}
+
 /* pointwise 1x1 + the depthwise 3x3 consuming it, fused into one launch */
 int shl_mi355x_pwdw_form(const shl_mi355x_conv_plan *pw, const shl_mi355x_conv_plan *dw, int32_t batch)
 {

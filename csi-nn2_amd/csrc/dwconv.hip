@@ -19,8 +19,26 @@
 #include <type_traits>
 
 #include "common.h"
+#include "lut_step.h"
+#include "lut_validate.h"
 
 namespace shl {
+
+// the kernel argument: the convolution's block, in the instantiations with the table post-op the table behind it (lut_step.h)
+template <bool kLut>
+struct DwArgs {
+    using type = typename std::conditional<kLut, LutConvArgs, ConvArgs>::type;
+};
+
+// The table of a fused launch -> `tab` (256 bytes of LDS), visible to the whole workgroup on return.  EVERY thread of the
+// workgroup calls it, before any of them leaves: the first wave copies, one dword per lane, and the barrier publishes.  None of
+// the depthwise kernels has a K loop the 64 dwords would stay live across (late_lut's reason), so the copy sits at the entry
+__device__ __forceinline__ const uint8_t *entry_lut(uint32_t *tab)
+{
+    if (threadIdx.x < 64) late_lut(tab);
+    __syncthreads();
+    return reinterpret_cast<const uint8_t *>(tab);
+}
 
 template <bool kI8>
 struct DwVec {  // VEC = 4 channels: one dword of int8, two dwords of binary16
@@ -49,9 +67,16 @@ __device__ __forceinline__ void dw_accumulate(const typename DwVec<kI8>::type &i
 }
 
 // KS == 3: 3x3 taps fully unrolled, loads batched.  KS == 0: any kernel size, loop form.
-template <bool kI8, int KS>
-__global__ __launch_bounds__(256) void dwconv_nhwc_kernel(ConvArgs a)
+// kLut (int8): the packed bytes go through the table of a fused launch before the store
+template <bool kI8, int KS, bool kLut = false>
+__global__ __launch_bounds__(256) void dwconv_nhwc_kernel(typename DwArgs<kLut>::type a)
 {
+    static_assert(kI8 || !kLut, "binary16 gets no table");
+    const uint8_t *lut = nullptr;
+    if constexpr (kLut) {  // before the loop: a thread without work still reaches the barrier
+        __shared__ uint32_t lut_lds[64];
+        lut = entry_lut(lut_lds);
+    }
     constexpr int VEC = 4;
     constexpr int ESIZE = kI8 ? 1 : 2;
     using vec_t = typename DwVec<kI8>::type;
@@ -110,7 +135,9 @@ __global__ __launch_bounds__(256) void dwconv_nhwc_kernel(ConvArgs a)
             const int q1 = requant_i8_fast(acc_i[1], mu.y, bi.y, a);
             const int q2 = requant_i8_fast(acc_i[2], mu.z, bi.z, a);
             const int q3 = requant_i8_fast(acc_i[3], mu.w, bi.w, a);
-            *reinterpret_cast<uint32_t *>(static_cast<int8_t *>(a.out) + o) = pack4_i8(q0, q1, q2, q3);
+            uint32_t v = pack4_i8(q0, q1, q2, q3);
+            if constexpr (kLut) v = lut4(lut, v);
+            *reinterpret_cast<uint32_t *>(static_cast<int8_t *>(a.out) + o) = v;
         } else {
             *reinterpret_cast<uint2 *>(static_cast<uint16_t *>(a.out) + o) = finish4_f16(acc_f[0], acc_f[1], acc_f[2], acc_f[3], bi, a);
         }
@@ -128,9 +155,16 @@ __global__ __launch_bounds__(256) void dwconv_nhwc_kernel(ConvArgs a)
 //     sum (q - zp) w = sum q w - zp * sum_9 w = sum q w + acc_init[c] for every pixel;
 //   * blockIdx.x is the output row (n, oy) -- scalar decomposition -- and a thread only divides
 //     its 32-bit position in the row by the channel-group count.
-template <int EPI>
-__global__ __launch_bounds__(256) void dwconv3x3_i8_dot4_kernel(ConvArgs a)
+// kLut: the packed bytes go through the table of a fused launch before the store.  The last block of a row (blockIdx.y > 0 with a
+// few busy lanes, or a short row) has lanes past the row's end: they leave AFTER the table's barrier
+template <int EPI, bool kLut = false>
+__global__ __launch_bounds__(256) void dwconv3x3_i8_dot4_kernel(typename DwArgs<kLut>::type a)
 {
+    const uint8_t *lut = nullptr;
+    if constexpr (kLut) {
+        __shared__ uint32_t lut_lds[64];
+        lut = entry_lut(lut_lds);
+    }
     const int cgroups = a.C >> 2;
     const uint32_t e = blockIdx.y * 256u + threadIdx.x;  // position in the output row
     if (e >= (uint32_t)(a.Wo * cgroups)) return;
@@ -170,8 +204,9 @@ __global__ __launch_bounds__(256) void dwconv3x3_i8_dot4_kernel(ConvArgs a)
         acc[ch] = __builtin_amdgcn_sdot4((int)t2, (int)wk[3 * ch + 2], acc[ch], false);
     }
     const int64_t o = ((int64_t)row * a.Wo + ox) * a.C + c;
-    *reinterpret_cast<uint32_t *>(static_cast<int8_t *>(a.out) + o) =
-        requant4_i8_t<EPI>(acc[0], acc[1], acc[2], acc[3], mu, bi, a);
+    uint32_t v = requant4_i8_t<EPI>(acc[0], acc[1], acc[2], acc[3], mu, bi, a);
+    if constexpr (kLut) v = lut4(lut, v);
+    *reinterpret_cast<uint32_t *>(static_cast<int8_t *>(a.out) + o) = v;
 }
 
 bool dwconv_dot4_supports(const shl_mi355x_conv_desc &d)
@@ -202,7 +237,18 @@ bool dwconv_supports(const shl_mi355x_conv_desc &d)
            d.in_c % 4 == 0 && d.group > 1;
 }
 
-int launch_dwconv(const ConvArgs &a, int dtype, int layout, hipStream_t s)
+// The int8 NHWC kernel a launch of `a` runs (DW_LUT_*, lut_validate.h): ONE rule for launch_dwconv, the fused launch and the
+// name it reports
+int dwconv_i8_kernel(const ConvArgs &a)
+{
+    if (a.kstride != 12) return DW_LUT_NHWC;  // (12: the plan packed the weights for the dot4 kernel)
+    if (a.dh == 1 && a.dw == 1 && a.C == a.Co && dwconv_mfma_pick(a.M, a.C, a.H, a.W, a.Ho, a.Wo, a.sh, a.sw)) return DW_LUT_MFMA;
+    return DW_LUT_DOT4;
+}
+
+// kLut: `a` is a LutConvArgs and the kernels are the instantiations with the table post-op (int8 only)
+template <bool kLut>
+static int launch_dwconv_t(const typename DwArgs<kLut>::type &a, int dtype, int layout, hipStream_t s)
 {
     if (layout != SHL_MI355X_NHWC) {
         set_error("dwconv: only NHWC is handled by this kernel");
@@ -210,10 +256,12 @@ int launch_dwconv(const ConvArgs &a, int dtype, int layout, hipStream_t s)
     }
     const int64_t total = (int64_t)a.M * (a.C / 4);
     if (total == 0) return SHL_MI355X_OK;
-    if (dtype == SHL_MI355X_I8 && a.kstride == 12 && a.dh == 1 && a.dw == 1 && a.C == a.Co &&
-        dwconv_mfma_pick(a.M, a.C, a.H, a.W, a.Ho, a.Wo, a.sh, a.sw))
-        return launch_dwconv_mfma(a, s);
-    if (dtype == SHL_MI355X_I8 && a.kstride == 12) {  // plan packed the weights for the dot4 kernel
+    const int kernel = dtype == SHL_MI355X_I8 ? dwconv_i8_kernel(a) : DW_LUT_NHWC;
+    if (kernel == DW_LUT_MFMA) {
+        if constexpr (kLut) return launch_dwconv_mfma_lut(a, s);
+        else return launch_dwconv_mfma(a, s);
+    }
+    if (kernel == DW_LUT_DOT4) {
         const int64_t rows = (int64_t)a.N * a.Ho;
         const int64_t per_row = ((int64_t)a.Wo * (a.C / 4) + 255) / 256;
         if (rows > 0x7FFFFFFF || per_row > 65535) {
@@ -222,12 +270,12 @@ int launch_dwconv(const ConvArgs &a, int dtype, int layout, hipStream_t s)
         }
         const dim3 g2((unsigned)rows, (unsigned)per_row);
         switch (epi_code(a)) {
-            case 0: hipLaunchKernelGGL((dwconv3x3_i8_dot4_kernel<0>), g2, dim3(256), 0, s, a); break;
-            case 1: hipLaunchKernelGGL((dwconv3x3_i8_dot4_kernel<1>), g2, dim3(256), 0, s, a); break;
-            case 2: hipLaunchKernelGGL((dwconv3x3_i8_dot4_kernel<2>), g2, dim3(256), 0, s, a); break;
-            case 3: hipLaunchKernelGGL((dwconv3x3_i8_dot4_kernel<3>), g2, dim3(256), 0, s, a); break;
-            case 4: hipLaunchKernelGGL((dwconv3x3_i8_dot4_kernel<4>), g2, dim3(256), 0, s, a); break;
-            default: hipLaunchKernelGGL((dwconv3x3_i8_dot4_kernel<5>), g2, dim3(256), 0, s, a); break;
+            case 0: hipLaunchKernelGGL((dwconv3x3_i8_dot4_kernel<0, kLut>), g2, dim3(256), 0, s, a); break;
+            case 1: hipLaunchKernelGGL((dwconv3x3_i8_dot4_kernel<1, kLut>), g2, dim3(256), 0, s, a); break;
+            case 2: hipLaunchKernelGGL((dwconv3x3_i8_dot4_kernel<2, kLut>), g2, dim3(256), 0, s, a); break;
+            case 3: hipLaunchKernelGGL((dwconv3x3_i8_dot4_kernel<3, kLut>), g2, dim3(256), 0, s, a); break;
+            case 4: hipLaunchKernelGGL((dwconv3x3_i8_dot4_kernel<4, kLut>), g2, dim3(256), 0, s, a); break;
+            default: hipLaunchKernelGGL((dwconv3x3_i8_dot4_kernel<5, kLut>), g2, dim3(256), 0, s, a); break;
         }
         SHL_HIP(hipGetLastError());
         return SHL_MI355X_OK;
@@ -238,9 +286,12 @@ int launch_dwconv(const ConvArgs &a, int dtype, int layout, hipStream_t s)
     const bool k3 = a.Kh == 3 && a.Kw == 3;
     if (dtype == SHL_MI355X_I8) {
         if (k3)
-            hipLaunchKernelGGL((dwconv_nhwc_kernel<true, 3>), grid, block, 0, s, a);
+            hipLaunchKernelGGL((dwconv_nhwc_kernel<true, 3, kLut>), grid, block, 0, s, a);
         else
-            hipLaunchKernelGGL((dwconv_nhwc_kernel<true, 0>), grid, block, 0, s, a);
+            hipLaunchKernelGGL((dwconv_nhwc_kernel<true, 0, kLut>), grid, block, 0, s, a);
+    } else if constexpr (kLut) {
+        set_error("dwconv: the table post-op is int8 only");
+        return SHL_MI355X_ENOTSUP;
     } else {
         if (k3)
             hipLaunchKernelGGL((dwconv_nhwc_kernel<false, 3>), grid, block, 0, s, a);
@@ -250,5 +301,10 @@ int launch_dwconv(const ConvArgs &a, int dtype, int layout, hipStream_t s)
     SHL_HIP(hipGetLastError());
     return SHL_MI355X_OK;
 }
+
+int launch_dwconv(const ConvArgs &a, int dtype, int layout, hipStream_t s) { return launch_dwconv_t<false>(a, dtype, layout, s); }
+
+// the fused launch: the kernel launch_dwconv picks for the same arguments, with the table behind its requantisation
+int launch_dwconv_lut(const LutConvArgs &a, hipStream_t s) { return launch_dwconv_t<true>(a, SHL_MI355X_I8, SHL_MI355X_NHWC, s); }
 
 }  // namespace shl

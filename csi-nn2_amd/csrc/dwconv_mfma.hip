@@ -32,6 +32,7 @@
 
 #include "dw_mfma.h"
 #include "igemm_common.h"
+#include "lut_step.h"
 
 namespace shl {
 
@@ -44,8 +45,10 @@ struct DwmGeom {
     uint32_t pw_magic;   // j / pw == umulhi(j, pw_magic) for j < 2^16
 };
 
-template <int EPI>
-__global__ __launch_bounds__(256, 4) void dwconv3x3_i8_mfma_kernel(ConvArgs a, DwmGeom g)
+// kLut: `a` carries the table of a fused launch behind the convolution's block (lut_step.h); it goes into 256 bytes of LDS behind
+// the epilogue tables and the packed bytes go through it before the halves are swapped
+template <int EPI, bool kLut = false>
+__global__ __launch_bounds__(256, 4) void dwconv3x3_i8_mfma_kernel(typename std::conditional<kLut, LutConvArgs, ConvArgs>::type a, DwmGeom g)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -91,6 +94,12 @@ __global__ __launch_bounds__(256, 4) void dwconv3x3_i8_mfma_kernel(ConvArgs a, D
                               : which == 1 ? (const void *)(a.mult + cblk * g.cb) : (const void *)(a.bias + cblk * g.cb);
             reinterpret_cast<uint4 *>(tab)[which * q4 + i] = static_cast<const uint4 *>(src)[i];
         }
+    }
+    const uint8_t *lut = nullptr;
+    if constexpr (kLut) {  // the first wave copies, one dword per lane; the barrier below publishes
+        uint32_t *lut_lds = reinterpret_cast<uint32_t *>(tab + g.cb * 12);
+        if (tid < 64) late_lut(lut_lds);
+        lut = reinterpret_cast<const uint8_t *>(lut_lds);
     }
 
     // ---- this wave's channel group and its diagonal weight fragments
@@ -153,6 +162,7 @@ __global__ __launch_bounds__(256, 4) void dwconv3x3_i8_mfma_kernel(ConvArgs a, D
             const float4 mu = *reinterpret_cast<const float4 *>(tab_l + tab_stride + q * 32);
             const float4 bi = *reinterpret_cast<const float4 *>(tab_l + 2 * tab_stride + q * 32);
             pk[q] = requant4_i8_t<EPI>(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3], mu, bi, a);
+            if constexpr (kLut) pk[q] = lut4(lut, pk[q]);
         }
         const uint4 v = tile_channels_16(pk);  // 16 consecutive channels per lane (dw_mfma.h)
         const int oy = oy0 + py, ox = ox0 + px;
@@ -194,7 +204,8 @@ bool dwconv_mfma_pick(int64_t M, int C, int H, int W, int Ho, int Wo, int sh, in
     return M * (C >> 5) >= 80 * 1024;
 }
 
-int launch_dwconv_mfma(const ConvArgs &a, hipStream_t s)
+template <bool kLut>
+static int launch_dwconv_mfma_t(const typename std::conditional<kLut, LutConvArgs, ConvArgs>::type &a, hipStream_t s)
 {
     DwmGeom g;
     if (a.sh < 1 || a.sh > 2 || a.sw < 1 || a.sw > 2 || !dwm_geometry(a.C, a.sh, a.sw, a.Ho, a.Wo, a.N, g)) {
@@ -202,25 +213,29 @@ int launch_dwconv_mfma(const ConvArgs &a, hipStream_t s)
         return SHL_MI355X_ENOTSUP;
     }
     const dim3 grid((unsigned)(a.C / g.cb), (unsigned)g.tiles_x, (unsigned)(g.tiles_y * a.N));
-    const size_t lds = (size_t)g.npieces * 1024 + (size_t)g.cb * 12;
+    const size_t lds = (size_t)g.npieces * 1024 + (size_t)g.cb * 12 + (kLut ? sizeof(Lut256) : 0);
     static LdsOptIn opted[6];
     {
-        const void *fns[6] = {reinterpret_cast<const void *>(dwconv3x3_i8_mfma_kernel<0>), reinterpret_cast<const void *>(dwconv3x3_i8_mfma_kernel<1>),
-                              reinterpret_cast<const void *>(dwconv3x3_i8_mfma_kernel<2>), reinterpret_cast<const void *>(dwconv3x3_i8_mfma_kernel<3>),
-                              reinterpret_cast<const void *>(dwconv3x3_i8_mfma_kernel<4>), reinterpret_cast<const void *>(dwconv3x3_i8_mfma_kernel<5>)};
+        const void *fns[6] = {reinterpret_cast<const void *>(dwconv3x3_i8_mfma_kernel<0, kLut>), reinterpret_cast<const void *>(dwconv3x3_i8_mfma_kernel<1, kLut>),
+                              reinterpret_cast<const void *>(dwconv3x3_i8_mfma_kernel<2, kLut>), reinterpret_cast<const void *>(dwconv3x3_i8_mfma_kernel<3, kLut>),
+                              reinterpret_cast<const void *>(dwconv3x3_i8_mfma_kernel<4, kLut>), reinterpret_cast<const void *>(dwconv3x3_i8_mfma_kernel<5, kLut>)};
         const int e = epi_code(a);
         if (e >= 0 && e < 6) lds_opt_in(opted[e], fns[e]);
     }
     switch (epi_code(a)) {
-        case 0: hipLaunchKernelGGL((dwconv3x3_i8_mfma_kernel<0>), grid, dim3(256), lds, s, a, g); break;
-        case 1: hipLaunchKernelGGL((dwconv3x3_i8_mfma_kernel<1>), grid, dim3(256), lds, s, a, g); break;
-        case 2: hipLaunchKernelGGL((dwconv3x3_i8_mfma_kernel<2>), grid, dim3(256), lds, s, a, g); break;
-        case 3: hipLaunchKernelGGL((dwconv3x3_i8_mfma_kernel<3>), grid, dim3(256), lds, s, a, g); break;
-        case 4: hipLaunchKernelGGL((dwconv3x3_i8_mfma_kernel<4>), grid, dim3(256), lds, s, a, g); break;
-        default: hipLaunchKernelGGL((dwconv3x3_i8_mfma_kernel<5>), grid, dim3(256), lds, s, a, g); break;
+        case 0: hipLaunchKernelGGL((dwconv3x3_i8_mfma_kernel<0, kLut>), grid, dim3(256), lds, s, a, g); break;
+        case 1: hipLaunchKernelGGL((dwconv3x3_i8_mfma_kernel<1, kLut>), grid, dim3(256), lds, s, a, g); break;
+        case 2: hipLaunchKernelGGL((dwconv3x3_i8_mfma_kernel<2, kLut>), grid, dim3(256), lds, s, a, g); break;
+        case 3: hipLaunchKernelGGL((dwconv3x3_i8_mfma_kernel<3, kLut>), grid, dim3(256), lds, s, a, g); break;
+        case 4: hipLaunchKernelGGL((dwconv3x3_i8_mfma_kernel<4, kLut>), grid, dim3(256), lds, s, a, g); break;
+        default: hipLaunchKernelGGL((dwconv3x3_i8_mfma_kernel<5, kLut>), grid, dim3(256), lds, s, a, g); break;
     }
     SHL_HIP(hipGetLastError());
     return SHL_MI355X_OK;
 }
+
+int launch_dwconv_mfma(const ConvArgs &a, hipStream_t s) { return launch_dwconv_mfma_t<false>(a, s); }
+
+int launch_dwconv_mfma_lut(const LutConvArgs &a, hipStream_t s) { return launch_dwconv_mfma_t<true>(a, s); }
 
 }  // namespace shl

@@ -1,6 +1,7 @@
 // lut_step.h -- the 256-entry table of an int8 activation (sigmoid / hard_sigmoid / silu / leaky_relu, and a swish or hard-swish
 // gate: mul(x, act(x)) depends on x's byte alone), for the two places that look it up: the table kernels (eltwise.hip) and the
-// stores of a convolution with the activation folded into its launch (conv_igemm.hip).  One definition of the table and of the
+// stores of a convolution with the activation folded into its launch (conv_igemm.hip; dwconv.hip and dwconv_mfma.hip for a
+// depthwise layer).  One definition of the table and of the
 // lookup, so that the fused launch equals the layers by construction: its input is the byte the convolution's own
 // requantisation produced -- folded relu / relu6 and saturation included.
 #pragma once
@@ -59,5 +60,11 @@ __device__ __forceinline__ const uint8_t *late_lut(uint32_t *slice)
 
 // conv_igemm.hip: the fused launch on one of the two families that carry the post-op ("wave" | "tile")
 int launch_conv_igemm_lut(const LutConvArgs &a, const char *family, hipStream_t s);
+
+// dwconv.hip, dwconv_mfma.hip: the fused launch of a depthwise plan (int8, NHWC, depth multiplier 1) on the kernel launch_dwconv
+// picks for the same arguments, and which one that is (DW_LUT_* of lut_validate.h)
+int launch_dwconv_lut(const LutConvArgs &a, hipStream_t s);
+int launch_dwconv_mfma_lut(const LutConvArgs &a, hipStream_t s);
+int dwconv_i8_kernel(const ConvArgs &a);
 
 }  // namespace shl

@@ -44,8 +44,8 @@ enum step_kind {
     STEP_MATMUL_BIAS, /* matmul a + the add b of a constant bias [N] to its output (shl_mi355x_matmul_bias) */
     STEP_ATTENTION, /* matmul(q, k^T) a -> [mul by a constant] -> softmax -> matmul(p, v): b, c, d (shl_mi355x_attention) */
     STEP_CONV_ADD,  /* convolution a -> same-shape add b of its output and a skip tensor -> [relu | relu6 c] (shl_mi355x_conv_add_forward) */
-    STEP_CONV_LUT,  /* convolution a -> table activation b -> [mul c of the convolution's output and b's: a swish / hard-swish gate]
-                     * (shl_mi355x_conv_lut_forward) */
+    STEP_CONV_LUT,  /* convolution or depthwise layer a -> table activation b -> [mul c of a's output and b's: a swish / hard-swish
+                     * gate] (shl_mi355x_conv_lut_forward; a depthwise plan: shl_mi355x_dwconv_lut_forward) */
 };
 
 struct step {
@@ -291,24 +291,29 @@ static int same_dims(const struct csinn_tensor *x, const struct csinn_tensor *y)
     return 1;
 }
 
-/* steps[0 .. n-1] (consecutive, each still one layer; steps[0] a convolution with its folded activation) begin with a table
- * activation folded into the convolution's launch: the number of steps it takes and the table in `lut`; 0: the layers stay apart.
+/* steps[0 .. n-1] (consecutive, each still one layer; steps[0] a convolution or a depthwise layer with its folded activation) begin
+ * with a table activation folded into the convolution's launch: the number of steps it takes and the table in `lut`; 0: the layers stay apart.
  *   2  convolution -> sigmoid | hard_sigmoid | silu | leaky_relu, which alone reads the convolution's output
  *   3  convolution -> sigmoid | hard_sigmoid -> mul(conv_out, gate), the convolution's output on either side of a same-shape mul
  *      and read by exactly those two layers, the gate read by the mul alone: a swish / hard-swish as converters export it
  * (consumers_of counts a graph output as a reader, so no intermediate tensor is one).  Every tensor is an int8 tensor of one
- * record and the convolution's output dims; the plan must be one the fused launch takes (`force`) or was measured faster on */
+ * record and the convolution's output dims; the plan must be one the fused launch takes (`force`) or was measured faster on --
+ * asked of the entry points of the plan's algorithm, shl_mi355x_conv_lut_* (implicit GEMM) or shl_mi355x_dwconv_lut_* (depthwise) */
 static int lut_chain(struct shl_ref_graph *g, const struct step *steps, int n, int force, uint8_t lut[256])
 {
     if (n < 2) return 0;
     struct shl_node *a = g->layer[steps[0].a], *b = g->layer[steps[1].a], *mid = steps[0].out;
-    if (!is_conv_op(a->type) || session_op(a) == NULL || session_op(b) == NULL || b->in_num < 1 || b->in[0] != mid) return 0;
+    if (!(is_conv_op(a->type) || is_dw_op(a->type)) || session_op(a) == NULL || session_op(b) == NULL || b->in_num < 1 || b->in[0] != mid) return 0;
     const int gate_kind = b->type == CSINN_OP_SIGMOID || b->type == CSINN_OP_HARD_SIGMOID;
     if (!gate_kind && b->type != CSINN_OP_SILU && b->type != CSINN_OP_LEAKY_RELU) return 0;
     struct csinn_tensor *tm = mid->data, *tb = b->out[0]->data, *in = a->in[0]->data;
     if (!one_record_i8(tm) || !one_record_i8(tb) || tm->dim_count != 4 || !same_dims(tm, tb)) return 0;
     shl_mi355x_conv_plan *pa = shl_mi355x_registry_get(a->data);
-    if (pa == NULL || !(force ? shl_mi355x_conv_lut_fusable(pa, in->dim[0]) : shl_mi355x_conv_lut_by_default(pa, in->dim[0]))) return 0;
+    if (pa == NULL) return 0;
+    const int dw = shl_mi355x_conv_plan_algo(pa) == SHL_MI355X_ALGO_DW;
+    if (!(dw ? (force ? shl_mi355x_dwconv_lut_fusable(pa, in->dim[0]) : shl_mi355x_dwconv_lut_by_default(pa, in->dim[0]))
+             : (force ? shl_mi355x_conv_lut_fusable(pa, in->dim[0]) : shl_mi355x_conv_lut_by_default(pa, in->dim[0]))))
+        return 0;
     const float si = tm->qinfo->scale, so = tb->qinfo->scale;
     const int32_t zi = tm->qinfo->zero_point, zo = tb->qinfo->zero_point;
     const int readers = consumers_of(g, mid);
@@ -404,6 +409,11 @@ static enum step_kind merged_kind(struct shl_ref_graph *g, const struct step *s,
  *        half of a pair, feeds a pool or a residual tail is not taken, and the step is not the first half of a residual merge.
  *        By default only shape classes the fused launch was measured faster on (csrc/lut_validate.h:lut_default);
  *        SHL_MI355X_ACT_FUSE=1 merges every one the kernel takes, =0 none
+ *   depthwise layer (int8 NHWC, depth multiplier 1; its folded activation included) -> the same activations and gates   one launch
+ *        of the depthwise kernel (STEP_CONV_LUT as well, csrc/dwconv.hip's and csrc/dwconv_mfma.hip's instantiations with the
+ *        table post-op; the launch site picks the entry point by the plan's algorithm): MobileNetV3's depthwise -> hard-swish and
+ *        EfficientNet's depthwise -> swish.  Same patterns, reader counts, tables, order and switch; a depthwise layer that is
+ *        half of a pair is not taken.  The default classes: csrc/lut_validate.h:dw_lut_default
  * Fills ds->steps. */
 static int plan_fusion(struct dev_session *ds, struct shl_ref_graph *g)
 {
@@ -604,9 +614,13 @@ static int enqueue_layers(struct dev_session *ds, struct shl_ref_graph *g)
                                                            ds->stream));
                 break;
             }
-            case STEP_CONV_LUT: /* the table's input is what the convolution (+ folded activation) would have written */
-                rc = status_of(shl_mi355x_conv_lut_forward(shl_mi355x_registry_get(n->data), in->dev, out->dev, batch, s->lut, ds->stream));
+            case STEP_CONV_LUT: { /* the table's input is what the convolution (+ folded activation) would have written */
+                shl_mi355x_conv_plan *plan = shl_mi355x_registry_get(n->data);
+                rc = status_of(shl_mi355x_conv_plan_algo(plan) == SHL_MI355X_ALGO_DW
+                                   ? shl_mi355x_dwconv_lut_forward(plan, in->dev, out->dev, batch, s->lut, ds->stream)
+                                   : shl_mi355x_conv_lut_forward(plan, in->dev, out->dev, batch, s->lut, ds->stream));
                 break;
+            }
             case STEP_PWDW:
                 rc = status_of(shl_mi355x_pwdw_forward(shl_mi355x_registry_get(n->data), shl_mi355x_registry_get(nx->data), in->dev,
                                                        out->dev, batch, ds->stream));

@@ -376,6 +376,26 @@ const char *shl_mi355x_conv_lut_kernel_name(const shl_mi355x_conv_plan *plan, in
 int shl_mi355x_conv_lut_by_default(const shl_mi355x_conv_plan *plan, int32_t batch);
 int shl_mi355x_conv_lut_forward(const shl_mi355x_conv_plan *plan, const void *input_dev, void *output_dev, int32_t batch,
                                 const uint8_t table[256], void *stream);
+/* The same post-op behind a DEPTHWISE layer, as ONE launch of the depthwise kernel (csrc/dwconv.hip, csrc/dwconv_mfma.hip):
+ * int8, NHWC, plans of SHL_MI355X_ALGO_DW (depth multiplier 1).  The four entries above keep refusing such a plan; these
+ * four refuse every other one.  `table` as above, by value in the kernel arguments (nothing allocated, capturable) and 256
+ * bytes of LDS per workgroup.  The kernel is the one shl_mi355x_conv_forward runs for the same plan and batch -- the dot4
+ * kernel, the matrix-core kernel (its size rule and SHL_MI355X_DWMFMA honoured) or the generic one for kernels other than
+ * 3x3 -- and looks up the dword its unfused store would have written, so the launch equals shl_mi355x_conv_forward followed
+ * by shl_mi355x_unary_lut_i8 with the same table byte for byte, for ANY 256 bytes.
+ * SHL_MI355X_EINVAL before anything is enqueued: a NULL argument, an output that overlaps the input, a batch that gives 2^31
+ * or more output pixels.  SHL_MI355X_ENOTSUP: a plan that is not int8 / NHWC / depthwise (NCHW, binary16, implicit GEMM,
+ * depth multiplier above 1, per-channel depthwise, a transposed convolution), an output row beyond the dot4 kernel's grid. */
+/* 1 when the plan and the batch qualify (batch 0: the plan's) */
+int shl_mi355x_dwconv_lut_fusable(const shl_mi355x_conv_plan *plan, int32_t batch);
+/* the kernel a fused launch of this plan runs at `batch`, with the post-op behind it: "dwconv_dot4+lut", "dwconv_mfma+lut" or
+ * "dwconv_nhwc+lut"; "" where the fused launch is not supported.  Pure host code */
+const char *shl_mi355x_dwconv_lut_kernel_name(const shl_mi355x_conv_plan *plan, int32_t batch);
+/* 1 for the shape classes where the fused launch was measured faster than the two launches it replaces by more than their
+ * run-to-run spread (profiles/dw_act_fuse_notes.md): what a session fuses without being asked */
+int shl_mi355x_dwconv_lut_by_default(const shl_mi355x_conv_plan *plan, int32_t batch);
+int shl_mi355x_dwconv_lut_forward(const shl_mi355x_conv_plan *plan, const void *input_dev, void *output_dev, int32_t batch,
+                                  const uint8_t table[256], void *stream);
 /* A hint from the owner of the graph: this depthwise layer's output does NOT feed a pointwise layer the bandwidth form
  * (depthwise -> pointwise in one launch, large batches) takes -- the latency form (pointwise -> depthwise) then keeps the
  * layer instead of yielding it (shl_mi355x_pwdw_fusable asks plan pairs, it cannot see a layer's consumer). */

@@ -210,10 +210,10 @@ int shl_mi355x_session_fused_attentions(struct csinn_session *sess);
  * the fused launch was measured faster on (shl_mi355x_conv_add_by_default); at setup SHL_MI355X_RESIDUAL=1 merges every tail the
  * kernel takes, SHL_MI355X_RESIDUAL=0 or SHL_MI355X_NO_FUSION=1 keeps the layers apart */
 int shl_mi355x_session_fused_residuals(struct csinn_session *sess);
-/* table activations of `sess` that run inside their convolution's launch (shl_mi355x_conv_lut_forward; int8 NHWC
- * implicit-GEMM plans): convolution -> sigmoid | hard_sigmoid | silu | leaky_relu, and the gates convolution -> sigmoid |
+/* table activations of `sess` that run inside their convolution's launch (shl_mi355x_conv_lut_forward: int8 NHWC
+ * implicit-GEMM plans; shl_mi355x_dwconv_lut_forward: int8 NHWC depthwise plans): convolution -> sigmoid | hard_sigmoid | silu | leaky_relu, and the gates convolution -> sigmoid |
  * hard_sigmoid -> mul(conv_out, gate), each counted once.  By default those of a shape class the fused launch was measured
- * faster on (shl_mi355x_conv_lut_by_default); at setup SHL_MI355X_ACT_FUSE=1 merges every one the kernel takes,
+ * faster on (shl_mi355x_conv_lut_by_default, shl_mi355x_dwconv_lut_by_default); at setup SHL_MI355X_ACT_FUSE=1 merges every one the kernel takes,
  * SHL_MI355X_ACT_FUSE=0 or SHL_MI355X_NO_FUSION=1 keeps the layers apart */
 int shl_mi355x_session_fused_activations(struct csinn_session *sess);
 
