@@ -398,6 +398,7 @@ def load_hip():
         "shl_mi355x_dwconv_lut_kernel_name": (C.c_char_p, [vp, i32]),
         "shl_mi355x_dwconv_lut_by_default": (C.c_int, [vp, i32]),
         "shl_mi355x_dwconv_lut_forward": (C.c_int, [vp, vp, vp, i32, vp, vp]),
+        "shl_mi355x_last_igemm_flavour": (C.c_char_p, []),
         "shl_mi355x_conv_plan_set_no_stream_consumer": (C.c_int, [vp, i32]),
         "shl_mi355x_pwdw_forward": (C.c_int, [vp, vp, vp, vp, i32, vp]),
         "shl_mi355x_relu_i8": (C.c_int, [vp, vp, sz, f32, i32, f32, i32, i32, vp]),

@@ -1064,6 +1064,12 @@ static thread_local const char *g_last_family = "";
 void igemm_note_family(const char *v) { g_last_family = v; }
 const char *igemm_last_family() { return g_last_family; }
 
+// ... and the instantiation launch_wave_regs_tile launched last on this thread, for tests that sweep the flavours:
+// "wave/ks4/epi4+add", "regs/epi0", "tile/128x128/pipe8/utap/epi1+lut" ("anytap": a K step may cross taps); "" before any launch
+// and after a launch that went to the halo kernel instead
+static thread_local char g_last_flavour[64] = "";
+const char *igemm_last_flavour() { return g_last_flavour; }
+
 static const char *variant_override()
 {
     static const char *v = getenv("SHL_MI355X_IGEMM");
@@ -1212,6 +1218,7 @@ static int launch_wave_regs_tile(const Args &a, int dtype, const char *v, hipStr
     const bool utap = (a.C * esize) % 64 == 0 && a.Kh * a.Kw <= 32;
     enum { T128, T256x64, T256x128, T256x256 } tile = T128;
     bool splitk = false;
+    g_last_flavour[0] = 0;
     if (!strcmp(v, "wave")) {
         const int64_t tiles = (int64_t)((a.M + 31) / 32) * ((a.Co + 31) / 32);
         // fewer tiles than CUs and at least 8 sub-steps of K: one tile per block, K split 4 ways
@@ -1270,6 +1277,12 @@ static int launch_wave_regs_tile(const Args &a, int dtype, const char *v, hipStr
             if (rc != SHL_MI355X_ENOTSUP) return rc;
         }
     }
+    // the flavour record is written where the instantiation is named, from the template arguments themselves
+    const char *post = POST == EPI_RESIDUAL ? "+add" : POST == EPI_LUT ? "+lut" : "";
+#define SHL_NOTE_TILE(MI, WRV, WCV, UT, PP)                                                                       \
+    snprintf(g_last_flavour, sizeof(g_last_flavour), "tile/%dx%d/pipe%d/%s/epi%d%s", TileGeom<MI, WRV, WCV, PP>::TBM, \
+             TileGeom<MI, WRV, WCV, PP>::TBN, PP, UT ? "utap" : "anytap", epi, post);
+#define SHL_NOTE_WAVE(KS) snprintf(g_last_flavour, sizeof(g_last_flavour), "wave/ks%d/epi%d%s", KS, epi, post);
 #define SHL_LAUNCH(...) launch_kernel<Args, __VA_ARGS__>(grid, lds, s, a, threads)
 #define SHL_LAUNCH_F16(...) launch_kernel<ConvArgs, __VA_ARGS__>(grid, lds, s, a, threads)
 #define SHL_LAUNCH_EPI(KERNEL, ...)                                          \
@@ -1283,18 +1296,19 @@ static int launch_wave_regs_tile(const Args &a, int dtype, const char *v, hipStr
     }
 #define SHL_COMMA ,
 #define SHL_TILE_P(MI, WRV, WCV, UT, PP)                                                                              \
+    SHL_NOTE_TILE(MI, WRV, WCV, UT, PP)                                                                               \
     if (i8) { SHL_LAUNCH_EPI(conv_igemm_tile_kernel, SHL_COMMA MI SHL_COMMA WRV SHL_COMMA WCV SHL_COMMA UT SHL_COMMA PP) } \
     else { SHL_LAUNCH_F16(conv_igemm_tile_kernel<false, 0, MI, WRV, WCV, UT, PP>); }
 #define SHL_TILE(MI, WRV, WCV, UT) \
     if (pipe) { SHL_TILE_P(MI, WRV, WCV, UT, 4) } else { SHL_TILE_P(MI, WRV, WCV, UT, 0) }
+#define SHL_WAVE(KS)  \
+    SHL_NOTE_WAVE(KS) \
+    if (i8) { SHL_LAUNCH_EPI(conv_igemm_wave_kernel, SHL_COMMA KS) } else { SHL_LAUNCH_F16(conv_igemm_wave_kernel<false, 0, KS>); }
     if (kind == 0) {
-        if (splitk) {
-            if (i8) { SHL_LAUNCH_EPI(conv_igemm_wave_kernel, SHL_COMMA 4) } else { SHL_LAUNCH_F16(conv_igemm_wave_kernel<false, 0, 4>); }
-        } else {
-            if (i8) { SHL_LAUNCH_EPI(conv_igemm_wave_kernel, SHL_COMMA 1) } else { SHL_LAUNCH_F16(conv_igemm_wave_kernel<false, 0, 1>); }
-        }
+        if (splitk) { SHL_WAVE(4) } else { SHL_WAVE(1) }
     } else if (kind == 1) {
         if constexpr (POST == 0) {
+            snprintf(g_last_flavour, sizeof(g_last_flavour), "regs/epi%d", epi);
             if (i8) { SHL_LAUNCH_EPI(conv_igemm_regs_kernel) } else { SHL_LAUNCH_F16(conv_igemm_regs_kernel<false, 0>); }
         } else {
             set_error("the regs kernel carries no post-op");
@@ -1311,8 +1325,11 @@ static int launch_wave_regs_tile(const Args &a, int dtype, const char *v, hipStr
     } else {
         if (utap) { SHL_TILE(2, 2, 2, true) } else { SHL_TILE(2, 2, 2, false) }
     }
+#undef SHL_WAVE
 #undef SHL_TILE
 #undef SHL_TILE_P
+#undef SHL_NOTE_WAVE
+#undef SHL_NOTE_TILE
 #undef SHL_COMMA
 #undef SHL_LAUNCH_EPI
 #undef SHL_LAUNCH_F16

@@ -904,6 +904,8 @@ const char *shl_mi355x_conv_plan_kernel_name(const shl_mi355x_conv_plan *plan)
     return plan ? plan->kernel_name : "";
 }
 
+const char *shl_mi355x_last_igemm_flavour(void) { return shl::igemm_last_flavour(); }
+
 size_t shl_mi355x_conv_plan_bytes(const shl_mi355x_conv_plan *plan)
 {
     if (!plan) return 0;

@@ -311,6 +311,7 @@ int pc_read_trace(unsigned long long *host, int count);
 const char *igemm_pick(const ConvArgs &a, int esize, int *flavour);
 void igemm_note_family(const char *v);       // the family a launch path ran (string literal)
 const char *igemm_last_family();             // ... of the last launch on this thread
+const char *igemm_last_flavour();            // the wave / regs / tile instantiation of the last launch on this thread ("": none)
 void igemm_set_plan_variant(const char *v);  // nullptr: the selection rules; else "wave" | "tile" | "pp" | "pc" | "patch"
 bool igemm_env_override();                   // SHL_MI355X_IGEMM is set (A/B runs, tests): no tuning
 int pp_read_trace(unsigned long long *host, int count);

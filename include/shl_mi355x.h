@@ -282,6 +282,12 @@ int shl_mi355x_conv_plan_destroy(shl_mi355x_conv_plan *plan);
 /* the algorithm the plan resolved to (enum shl_mi355x_algo) and its kernel name */
 int shl_mi355x_conv_plan_algo(const shl_mi355x_conv_plan *plan);
 const char *shl_mi355x_conv_plan_kernel_name(const shl_mi355x_conv_plan *plan);
+/* Which instantiation of the wave / regs / tile implicit-GEMM kernels the calling thread launched last, fused or not: the
+ * family, its flavour (the wave kernel's K split; the tile kernel's size, ring depth and tap addressing), the requantisation
+ * code and the post-op, e.g. "wave/ks4/epi4+add", "regs/epi0", "tile/128x128/pipe8/utap/epi1+lut", "tile/256x64/pipe0/anytap/epi3";
+ * "" before any such launch.  Host side; for tests that must know which kernel they ran.  The pointer is to a thread-local
+ * buffer that the thread's next such launch overwrites: read or copy it before launching again */
+const char *shl_mi355x_last_igemm_flavour(void);
 /* bytes of packed weights + tables resident in HBM for this plan */
 size_t shl_mi355x_conv_plan_bytes(const shl_mi355x_conv_plan *plan);
 /*
