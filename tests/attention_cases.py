@@ -14,6 +14,8 @@ softmax over the keys, P V as one launch.
   device_formula  int8 only: the chain with both products through matmul_cases.exact_ref -- what the mfma form computes
   both_exact      the plan-time proof (matmul_cases.is_exact) for both products
   desc / unfused_descs   the C ABI's descriptors: the fused call's, and the four unfused calls'
+  run_both        (-m gpu) the fused launch and the four unfused calls on the same device buffers, with every intermediate
+attention_sweeps.py builds its seeded strata on _add (a p record and byte offsets of the operands are its to choose).
 The records are chosen so that rows are peaked, not flat: the softmax's input has a standard deviation of one to three units,
 more for longer rows, and the case builder's conditions (test_attention_cpu.py) ask every row of p and the output for more than
 8 distinct values.
@@ -45,7 +47,7 @@ def _target_std(t):
     return 1.2 + 0.4 * max(0.0, math.log2(t / 64.0))
 
 
-def _i8_records(c, regime, zq, zk, zv):
+def _i8_records(c, regime, zq, zk, zv, p_q=P_Q):
     """records under which int8 data uniform over the whole range gives peaked rows: the true scores have a standard deviation
     of target * sqrt(d) with the multiply (the constant then is about 1 / sqrt(d)), of target without; the scores and the scaled
     scores spread over about 40 LSB each"""
@@ -73,7 +75,7 @@ def _i8_records(c, regime, zq, zk, zv):
         c["c"] = np.array([int(np.clip(round(c_real / c["c_q"][0]) + c["c_q"][1], -128, 127))], np.int8)
         std_sc = std_s * (float(c["c"][0]) - c["c_q"][1]) * c["c_q"][0]
         c["sc_q"] = _q(std_sc / 40.0, -7) if regime == "conv" else _q(2.0 ** round(math.log2(std_sc / 40.0)), 4)
-    c["p_q"] = P_Q
+    c["p_q"] = p_q
     sv = 0.0219 if regime == "conv" else 2.0 ** -5
     c["v_q"] = _q(sv, zv)
     # the output is a weighted mean of v: under v's own scale it spreads as v does
@@ -81,7 +83,9 @@ def _i8_records(c, regime, zq, zk, zv):
 
 
 def _add(out, name, dtype, s=64, t=64, d=64, dv=64, batches=1, has_scale=True, scale_first=False, regime="pow2", zq=0, zk=0, zv=0,
-         special=False):
+         special=False, p_q=None, offsets=None):
+    """p_q: the probabilities' int8 record (P_Q unless given).  offsets: bytes by which run_both moves q, k, v and the output
+    off the allocator's grid, {"q": 4, ...}; a case without them has no such key"""
     full = "%s_%s" % (name, "f16" if dtype == "f16" else "i8")
     rng = _rng("attention " + full)
     c = dict(name=full, dtype=dtype, batches=batches, s=s, t=t, d=d, dv=dv, has_scale=has_scale, scale_first=scale_first,
@@ -89,7 +93,7 @@ def _add(out, name, dtype, s=64, t=64, d=64, dv=64, batches=1, has_scale=True, s
     shapes = ((batches, s, d), (batches, t, d), (batches, t, dv))
     if dtype == "int8":
         c["q"], c["k"], c["v"] = (rng.integers(-128, 128, sh, dtype=np.int8) for sh in shapes)
-        _i8_records(c, regime, zq, zk, zv)
+        _i8_records(c, regime, zq, zk, zv, P_Q if p_q is None else p_q)
     else:
         # multiples of 2^-3 in [-2, 2] (without the multiply: of 2^-4 in [-3/4, 3/4]): every partial sum of q k^T is exact in
         # float32, so the scores are the same bits in any order of summation; v is non-negative, so nothing behind the softmax cancels
@@ -110,6 +114,9 @@ def _add(out, name, dtype, s=64, t=64, d=64, dv=64, batches=1, has_scale=True, s
             qu[0, SPECIAL_ROWS[0], 5], qu[0, SPECIAL_ROWS[1], 2] = INF_P, NAN_P
     if not has_scale:
         c["c"], c["c_q"], c["sc_q"] = None, _q(1.0, 0), _q(1.0, 0)
+    if offsets:
+        assert set(offsets) <= {"q", "k", "v", "out"} and all(0 <= o < 16 and o % c["q"].itemsize == 0 for o in offsets.values())
+        c["offsets"] = dict(offsets)
     out.append(c)
 
 
@@ -233,6 +240,66 @@ def unfused_descs(c):
         mul = eltwise_cases.mul_desc(dict(dtype=c["dtype"], in_q=c["s_q"], in1_q=c["c_q"], out_q=c["sc_q"], small_first=c["scale_first"]),
                                      (b, s, t), (1,))
     return qk, mul, pv
+
+
+POISON = 0x5A
+GUARD = 64
+SLACK = 16  # room behind every buffer for a case's byte offsets (below 16 each)
+
+
+def run_both(hip, dev, c):
+    """(the fused launch's output, the four unfused calls' output, their probabilities, their scores, their softmax's input),
+    all from the device; the bytes around the fused output are poisoned and must stay.  A case's "offsets" move q, k, v and
+    the output (the fused one and the chain's alike) that many bytes off the allocator's grid: the unfused calls receive the
+    same pointers"""
+    b, s, t, dv = c["batches"], c["s"], c["t"], c["dv"]
+    es = c["q"].itemsize
+    dt = pkg.SHL_I8 if c["dtype"] == "int8" else pkg.SHL_F16
+    off = c.get("offsets", {})
+    room, bufs = [], {}
+
+    def alloc(nbytes):
+        room.append(dev.alloc(nbytes + SLACK))
+        return room[-1]
+    for key in ("q", "k", "v") + (("c",) if c["has_scale"] else ()):
+        bufs[key] = alloc(c[key].nbytes) + off.get(key, 0)
+        dev.upload(bufs[key], c[key])
+    for key in ("s", "x", "p"):
+        bufs[key] = alloc(b * s * t * es)
+    out_bytes = b * s * dv * es
+    frame = np.full(out_bytes + 2 * GUARD + SLACK, POISON, np.uint8)
+    for key in ("chain", "fused"):
+        bufs[key] = alloc(frame.nbytes)
+        dev.upload(bufs[key], frame)
+    first = GUARD + off.get("out", 0)  # the output's first byte in its frame
+    p_chain, p_fused = bufs["chain"] + first, bufs["fused"] + first
+    qk, mul, pv = unfused_descs(c)
+    assert hip.shl_mi355x_matmul_kernel_name(bufs["q"], bufs["k"], bufs["s"], C.byref(qk)).decode() == pkg.MATMUL_MFMA
+    assert hip.shl_mi355x_matmul_kernel_name(bufs["p"], bufs["v"], p_chain, C.byref(pv)).decode() == pkg.MATMUL_MFMA
+    pkg.check(hip.shl_mi355x_matmul(bufs["q"], bufs["k"], bufs["s"], C.byref(qk), None), hip, "shl_mi355x_matmul (q k^T)")
+    x, x_q = bufs["s"], c["s_q"]
+    if c["has_scale"]:
+        pkg.check(hip.shl_mi355x_mul(bufs["s"], bufs["c"], bufs["x"], C.byref(mul), None), hip, "shl_mi355x_mul")
+        x, x_q = bufs["x"], c["sc_q"]
+    pkg.check(hip.shl_mi355x_softmax(x, bufs["p"], dt, b * s, t, 1, x_q[0], x_q[1], c["p_q"][0], c["p_q"][1], None), hip,
+              "shl_mi355x_softmax")
+    pkg.check(hip.shl_mi355x_matmul(bufs["p"], bufs["v"], p_chain, C.byref(pv), None), hip, "shl_mi355x_matmul (p v)")
+    d = desc(c)
+    assert hip.shl_mi355x_attention_kernel_name(bufs["q"], bufs["k"], bufs["v"], p_fused, C.byref(d)).decode() == pkg.ATTENTION_MFMA
+    pkg.check(hip.shl_mi355x_attention(bufs["q"], bufs["k"], bufs["v"], p_fused, C.byref(d), None), hip, "shl_mi355x_attention")
+    got = dev.download(bufs["fused"], frame.shape, np.uint8)
+    assert np.all(got[:first - GUARD] == POISON), "wrote in front of the output's guard"
+    got = got[first - GUARD:]  # from the guard on: the frame of a case without offsets
+    assert np.all(got[:GUARD] == POISON) and np.all(got[GUARD + out_bytes:] == POISON), "wrote outside the output"
+    view = lambda raw, shape: raw.view(c["q"].dtype)[:int(np.prod(shape))].reshape(shape)
+    fused = view(got[GUARD:GUARD + out_bytes].copy(), (b, s, dv))
+    chain = view(dev.download(bufs["chain"], frame.shape, np.uint8)[first:first + out_bytes].copy(), (b, s, dv))
+    p = dev.download(bufs["p"], (b, s, t), c["q"].dtype)
+    scores = dev.download(bufs["s"], (b, s, t), c["q"].dtype)
+    x_in = dev.download(x, (b, s, t), c["q"].dtype)
+    for ptr in room:
+        dev.free(ptr)
+    return fused, chain, p, scores, x_in
 
 
 def expect_fused(c, force=None):

@@ -11,12 +11,12 @@ import pytest
 import attention_cases as ac
 import cases
 import matmul_cases as mc
+from attention_cases import run_both
 from cases import pkg
 
 CASES = ac.all_cases()
 IDS = [ac.case_id(c) for c in CASES]
-POISON = 0x5A
-GUARD = 64
+POISON = ac.POISON
 EINVAL, ENOTSUP = -2, -3
 
 
@@ -35,49 +35,6 @@ def oracle():
     return {c["name"]: ac.oracle_chain(c) for c in CASES}
 
 
-def run_both(hip, dev, c):
-    """(the fused launch's output, the four unfused calls' output, their probabilities), all from the device; the bytes around
-    the fused output are poisoned and must stay"""
-    b, s, t, dv = c["batches"], c["s"], c["t"], c["dv"]
-    es = c["q"].itemsize
-    dt = pkg.SHL_I8 if c["dtype"] == "int8" else pkg.SHL_F16
-    bufs = {}
-    for key in ("q", "k", "v") + (("c",) if c["has_scale"] else ()):
-        bufs[key] = dev.alloc(c[key].nbytes)
-        dev.upload(bufs[key], c[key])
-    for key in ("s", "x", "p"):
-        bufs[key] = dev.alloc(b * s * t * es)
-    out_bytes = b * s * dv * es
-    frame = np.full(out_bytes + 2 * GUARD, POISON, np.uint8)
-    for key in ("chain", "fused"):
-        bufs[key] = dev.alloc(frame.nbytes)
-        dev.upload(bufs[key], frame)
-    p_fused = bufs["fused"] + GUARD
-    qk, mul, pv = ac.unfused_descs(c)
-    assert hip.shl_mi355x_matmul_kernel_name(bufs["q"], bufs["k"], bufs["s"], C.byref(qk)).decode() == pkg.MATMUL_MFMA
-    assert hip.shl_mi355x_matmul_kernel_name(bufs["p"], bufs["v"], bufs["chain"], C.byref(pv)).decode() == pkg.MATMUL_MFMA
-    pkg.check(hip.shl_mi355x_matmul(bufs["q"], bufs["k"], bufs["s"], C.byref(qk), None), hip, "shl_mi355x_matmul (q k^T)")
-    x, x_q = bufs["s"], c["s_q"]
-    if c["has_scale"]:
-        pkg.check(hip.shl_mi355x_mul(bufs["s"], bufs["c"], bufs["x"], C.byref(mul), None), hip, "shl_mi355x_mul")
-        x, x_q = bufs["x"], c["sc_q"]
-    pkg.check(hip.shl_mi355x_softmax(x, bufs["p"], dt, b * s, t, 1, x_q[0], x_q[1], c["p_q"][0], c["p_q"][1], None), hip,
-              "shl_mi355x_softmax")
-    pkg.check(hip.shl_mi355x_matmul(bufs["p"], bufs["v"], bufs["chain"], C.byref(pv), None), hip, "shl_mi355x_matmul (p v)")
-    d = ac.desc(c)
-    assert hip.shl_mi355x_attention_kernel_name(bufs["q"], bufs["k"], bufs["v"], p_fused, C.byref(d)).decode() == pkg.ATTENTION_MFMA
-    pkg.check(hip.shl_mi355x_attention(bufs["q"], bufs["k"], bufs["v"], p_fused, C.byref(d), None), hip, "shl_mi355x_attention")
-    got = dev.download(bufs["fused"], frame.shape, np.uint8)
-    assert np.all(got[:GUARD] == POISON) and np.all(got[GUARD + out_bytes:] == POISON), "wrote outside the output"
-    view = lambda raw, shape: raw.view(c["q"].dtype)[:int(np.prod(shape))].reshape(shape)
-    fused = view(got[GUARD:GUARD + out_bytes].copy(), (b, s, dv))
-    chain = view(dev.download(bufs["chain"], frame.shape, np.uint8)[:out_bytes].copy(), (b, s, dv))
-    p = dev.download(bufs["p"], (b, s, t), c["q"].dtype)
-    for ptr in bufs.values():
-        dev.free(ptr)
-    return fused, chain, p
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", CASES, ids=IDS)
 def test_fused_equals_the_unfused_calls_and_the_oracle_chain(gpu, oracle, case, monkeypatch):
@@ -85,7 +42,7 @@ def test_fused_equals_the_unfused_calls_and_the_oracle_chain(gpu, oracle, case, 
     for var in ("SHL_MI355X_MATMUL_FORM", "SHL_MI355X_MUL_FORM", "SHL_MI355X_SOFTMAX_SEQ"):
         monkeypatch.delenv(var, raising=False)
     name = ac.case_id(case)
-    fused, chain, p = run_both(hip, dev, case)
+    fused, chain, p = run_both(hip, dev, case)[:3]
     mc.assert_same(fused, chain, name + ": fused vs matmul, mul, softmax, matmul")
     want = oracle[case["name"]]
     if case["dtype"] == "int8":

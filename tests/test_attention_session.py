@@ -24,13 +24,15 @@ FORMATS = [("int8", "NHWC"), ("f16", "NCHW")]
 SWITCH = "SHL_MI355X_ATTENTION"
 
 
-def attention_net(dtype="int8", layout="NCHW", second_consumer=False, tokens=80, hd=64):
+def attention_net(dtype="int8", layout="NCHW", second_consumer=False, tokens=80, hd=64, records=None, p_is_output=False):
     """matmul_cases.attention_block's layers at S = 80, C = 128, 2 heads of 64 (K = 64 and 80: both products are the mfma
     form's).  int8: every record is a power of two inside the plan-time proof.  binary16: x is a multiple of 1/2 in [0, 2] and
     Wq, Wk are -1/8, 0 or 1/8, so q, k (multiples of 2^-4 up to 32) are exact in binary16 and every partial sum of q k^T (a
     multiple of 2^-8 below 2^16) is exact in float32: the scores and p are the same bits in any order of summation; Wv and Wo
     are 0, 1/16 or 1/8, so everything behind the softmax is a sum of non-negative terms.  second_consumer: the scaled scores
-    also feed a second softmax (a graph output), behind the chain"""
+    also feed a second softmax (a graph output), behind the chain.  records: int8 records by tensor or constant name that replace
+    the ones below (which suit 80 tokens: on 768 keys they leave p nearly flat).  p_is_output: p is a graph output as well, which
+    keeps the layers apart"""
     q = lambda s, z: _q(2.0 ** s, z)
     rng = np.random.default_rng(171)
     s, h = tokens, 2
@@ -48,6 +50,11 @@ def attention_net(dtype="int8", layout="NCHW", second_consumer=False, tokens=80,
     consts = {"Wq": (mc._weights(rng, (c, c), dtype, signed), q(-11, 0)), "Wk": (mc._weights(rng, (c, c), dtype, signed), q(-11, 5)),
               "Wv": (mc._weights(rng, (c, c), dtype, positive), q(-10, 0)), "Wo": (mc._weights(rng, (c, c), dtype, positive), q(-10, -128)),
               "scale": (np.array([64], np.int8) if dtype == "int8" else np.array([0.125], np.float16), q(-9, 0))}
+    for name, rec in (records or {}).items():
+        if name in consts:
+            consts[name] = (consts[name][0], rec)
+        else:
+            t[name] = (t[name][0], rec)
     L = []
     for n in "qkv":
         L += [("matmul", n, ("x", "W" + n), n, {}),
@@ -63,7 +70,7 @@ def attention_net(dtype="int8", layout="NCHW", second_consumer=False, tokens=80,
           ("reshape", "o_merge", "os", "o", {}),
           ("matmul", "proj", ("o", "Wo"), "proj", {}),
           ("add", "residual", ("proj", "x"), "out", {})]
-    return mc.MatmulNet(dtype, layout, 173, "x", t, L, ["out"] + (["p2"] if second_consumer else []), consts, x_grid=(0, 4, 1.0 / 2))
+    return mc.MatmulNet(dtype, layout, 173, "x", t, L, ["out"] + (["p2"] if second_consumer else []) + (["p"] if p_is_output else []), consts, x_grid=(0, 4, 1.0 / 2))
 
 
 @pytest.fixture(scope="module")
@@ -149,6 +156,53 @@ def test_unasked_the_planner_merges_only_the_shapes_measured_faster(gpu, monkeyp
         assert opt.shl_mi355x_session_is_device_resident(sess) == 2
         assert opt.shl_mi355x_session_fused_attentions(sess) == want, kw
         net.close(fe)
+
+
+# on 768 keys the 80-token net's constant of 64 x 2^-9 leaves the int8 probabilities nearly flat (the oracle chain: two to four
+# distinct values a row); twice the constant gives rows of 4 to 8 and 70 distinct values in all
+RECORDS_768 = {"scale": _q(2.0 ** -8, 0)}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype,layout", FORMATS)
+def test_the_class_fused_unasked_runs_and_equals_the_layers_apart(gpu, dtype, layout, monkeypatch):
+    """768 tokens on 2 heads of 32: what csrc/attention_canon.h:att_default fuses with SHL_MI355X_ATTENTION unset.  The session
+    is one captured graph with one fused attention, and every run of it equals, bit for bit, the same net under
+    SHL_MI355X_ATTENTION=0 -- and the net whose p is a graph output, which hands out the layers-apart probabilities.  The CPU
+    oracle is not the arbiter here (P V's proof cannot hold on 768 keys under p's record, and the gate does not compose through
+    the projection): test_attention_sweeps.py carries the CPU reference for this shape"""
+    fe, hip, opt = gpu
+    for var in ("SHL_MI355X_HOST_SESSION", "SHL_MI355X_MATMUL_FORM", "SHL_MI355X_NO_FUSION", SWITCH):
+        monkeypatch.delenv(var, raising=False)
+    kw = dict(tokens=768, hd=32, records=RECORDS_768)
+    net = attention_net(dtype, layout, **kw)
+    sess = net.build(fe, pkg.API_MI355X)
+    assert opt.shl_mi355x_session_is_device_resident(sess) == 2, "the session is not one captured hipGraph"
+    assert opt.shl_mi355x_session_fused_attentions(sess) == 1
+    got = [net.run(fe, net.input(k)) for k in (0, 1, 0)]  # the graph replay reads fresh data
+    assert not np.array_equal(mc.bits(got[0]["out"]), mc.bits(got[1]["out"])), "the two inputs must tell runs apart"
+    monkeypatch.setenv(SWITCH, "0")
+    apart = attention_net(dtype, layout, **kw)
+    apart_sess = apart.build(fe, pkg.API_MI355X)
+    monkeypatch.delenv(SWITCH)
+    assert opt.shl_mi355x_session_is_device_resident(apart_sess) == 2
+    assert opt.shl_mi355x_session_fused_attentions(apart_sess) == 0
+    assert planner_counts(opt, sess) == planner_counts(opt, apart_sess)
+    assert opt.shl_mi355x_session_fused_linears(sess) == opt.shl_mi355x_session_fused_linears(apart_sess)
+    for k, g in zip((0, 1, 0), got):
+        assert g["out"].shape == net.shape("out")
+        mc.assert_same(apart.run(fe, apart.input(k))["out"], g["out"], "%s input %d: fused by default vs the layers apart" % (dtype, k))
+    apart.close(fe)
+    # p as a graph output keeps the layers apart whatever the switch says: the same output again, and the probabilities themselves
+    shown = attention_net(dtype, layout, p_is_output=True, **kw)
+    shown_sess = shown.build(fe, pkg.API_MI355X)
+    assert opt.shl_mi355x_session_fused_attentions(shown_sess) == 0
+    res = shown.run(fe, shown.input(0))
+    mc.assert_same(res["out"], got[0]["out"], dtype + ": fused by default vs the net whose p is a graph output")
+    spread = np.unique(mc.bits(res["p"])).size
+    assert spread > 8, "the layers-apart p holds %d different values: it would tell nothing" % spread
+    shown.close(fe)
+    net.close(fe)
 
 
 DROPIN = r"""
