@@ -390,6 +390,10 @@ def load_hip():
         "shl_mi355x_conv_add_forward": (C.c_int, [vp, vp, vp, vp, i32, C.POINTER(ResidualDesc), vp]),
         "shl_mi355x_conv_add_kernel_name": (C.c_char_p, [vp, i32]),
         "shl_mi355x_conv_add_by_default": (C.c_int, [vp, i32]),
+        "shl_mi355x_conv_add_f16_fusable": (C.c_int, [vp, i32]),
+        "shl_mi355x_conv_add_f16_forward": (C.c_int, [vp, vp, vp, vp, i32, C.POINTER(ResidualDesc), vp]),
+        "shl_mi355x_conv_add_f16_kernel_name": (C.c_char_p, [vp, i32]),
+        "shl_mi355x_conv_add_f16_by_default": (C.c_int, [vp, i32]),
         "shl_mi355x_conv_lut_fusable": (C.c_int, [vp, i32]),
         "shl_mi355x_conv_lut_kernel_name": (C.c_char_p, [vp, i32]),
         "shl_mi355x_conv_lut_by_default": (C.c_int, [vp, i32]),

@@ -51,4 +51,15 @@ __device__ __forceinline__ uint16_t add_f16_step(uint16_t h0, uint16_t h1)
     return float_to_f16_bits_ref(r);
 }
 
+// The sum of two binary16 values as the SAME-SHAPE add gives it (shl_mi355x_add; a session runs it for a residual add,
+// source/mi355x_opt/pooling.c:shl_mi355x_add_exec); h0 / h1: the layer's first / second input.  This is NOT add_f16_step: here
+// the hardware's addition picks the NaN (of two NaN operands the one its operand order prefers, an inf + -inf its default one)
+// and float_to_f16_bits_ref keeps that NaN's sign, where the broadcasting add follows the x86 reference's NaN rule.  For the two
+// places that compute it: the stand-alone kernel (elementwise.hip) and the store of a binary16 convolution with a fused
+// residual tail (residual_step.h), which must reproduce the stand-alone layer, not the broadcasting one.
+__device__ __forceinline__ uint16_t add_same_f16_step(uint16_t h0, uint16_t h1)
+{
+    return float_to_f16_bits_ref(__fadd_rn(f16_bits_to_float(h0), f16_bits_to_float(h1)));
+}
+
 }  // namespace shl

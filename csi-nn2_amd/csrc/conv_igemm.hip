@@ -132,10 +132,22 @@ __device__ __forceinline__ uint32_t load_skip4(const ConvArgs &a, const void *sk
     return v;
 }
 
+// binary16: the four skip halves behind output offset (p, oc), 8 bytes where the channel count keeps every group of four
+// together, else the halves that exist
+__device__ __forceinline__ uint2 load_skip4_f16(const ConvArgs &a, const void *skip_dev, int p, int oc, bool vec_ok)
+{
+    if (p >= a.M || oc >= a.Co) return make_uint2(0, 0);
+    const uint16_t *skip = static_cast<const uint16_t *>(skip_dev) + (int64_t)p * a.Co + oc;
+    if (vec_ok) return *reinterpret_cast<const uint2 *>(skip);
+    uint32_t h[4] = {0, 0, 0, 0};
+    for (int e = 0; e < 4 && oc + e < a.Co; ++e) h[e] = skip[e];
+    return make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
+}
+
 // ---- epilogue of one 32x32 MFMA tile (A rows = output channels, B column = pixel) ---------------
 // C/D layout: column = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5).
 // `tab_*` point at the table entries of the tile's first output channel (LDS or global).
-// EPI & EPI_RESIDUAL (int8): the skip connection's tail `tail` runs on the packed bytes (residual_step.h)
+// EPI & EPI_RESIDUAL: the skip connection's tail `tail` runs on the packed bytes / halves (residual_step.h)
 // EPI & EPI_LUT (int8): the packed bytes go through the table `lut`, the calling wave's copy in LDS (lut_step.h)
 template <bool kI8, int EPI, typename Acc>
 __device__ __forceinline__ void store_tile(const ConvArgs &a, const Acc &acc, int p, int oc_tile,
@@ -145,14 +157,18 @@ __device__ __forceinline__ void store_tile(const ConvArgs &a, const Acc &acc, in
 {
     if (p >= a.M) return;
     constexpr int RQ = EPI & (EPI_RESIDUAL - 1);
-    constexpr bool kPost = kI8 && (EPI & EPI_RESIDUAL) != 0;
+    constexpr bool kPost = (EPI & EPI_RESIDUAL) != 0;
     constexpr bool kLut = kI8 && (EPI & EPI_LUT) != 0;
     const bool vec_ok = (a.Co & 3) == 0;
-    // the skip operand sits at the output's own offsets: requested in front of the requantisation chains
+    // the skip operand sits at the output's own offsets: requested in front of the requantisation / finish4_f16 chains
     uint32_t skip4[4] = {0, 0, 0, 0};
+    uint2 skiph[4] = {};
     if constexpr (kPost) {
 #pragma unroll
-        for (int g = 0; g < 4; ++g) skip4[g] = load_skip4(a, tail->skip, p, oc_tile + 8 * g + 4 * lhalf, vec_ok);
+        for (int g = 0; g < 4; ++g) {
+            if constexpr (kI8) skip4[g] = load_skip4(a, tail->skip, p, oc_tile + 8 * g + 4 * lhalf, vec_ok);
+            else skiph[g] = load_skip4_f16(a, tail->skip, p, oc_tile + 8 * g + 4 * lhalf, vec_ok);
+        }
     }
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -178,7 +194,8 @@ __device__ __forceinline__ void store_tile(const ConvArgs &a, const Acc &acc, in
                 for (int e = 0; e < 4 && oc + e < a.Co; ++e) out[o + e] = (int8_t)(packed >> (8 * e));
             }
         } else {
-            const uint2 h2 = finish4_f16(acc[4 * g + 0], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3], bi, a);
+            uint2 h2 = finish4_f16(acc[4 * g + 0], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3], bi, a);
+            if constexpr (kPost) h2 = residual4_f16(h2, skiph[g], tail->post.conv_first, tail->post.act);
             uint16_t *out = static_cast<uint16_t *>(a.out);
             if (vec_ok) {
                 *reinterpret_cast<uint2 *>(out + o) = h2;
@@ -247,7 +264,7 @@ __global__ __launch_bounds__(64 * WR * WC * (PIPE ? 2 : 1)) void conv_igemm_tile
     using G = TileGeom<MI, WR, WC, PIPE>;
     constexpr int ESIZE = kI8 ? 1 : 2;
     constexpr int RQ = EPI & (EPI_RESIDUAL - 1);                   // the requantisation's code (common.h:epi_code)
-    constexpr bool kPost = kI8 && (EPI & EPI_RESIDUAL) != 0;       // ... and the residual tail behind it (residual_step.h)
+    constexpr bool kPost = (EPI & EPI_RESIDUAL) != 0;              // ... and the residual tail behind it (residual_step.h; either dtype)
     constexpr bool kLut = kI8 && (EPI & EPI_LUT) != 0;             // ... or the table post-op (lut_step.h)
     constexpr int NST = G::NST;
     constexpr int LA = NST - 1;  // look-ahead in K steps
@@ -550,20 +567,21 @@ __global__ __launch_bounds__(64 * WR * WC * (PIPE ? 2 : 1)) void conv_igemm_tile
         const int srow = lane / CPR, schunk = lane % CPR;
         char *out = static_cast<char *>(a.out);
         if constexpr (kPost) {
-            // The residual tail (int8 NHWC): the same staging, and between the read-back and the store the add's and the
-            // activation's element functions on the staged bytes.  The 16 skip bytes behind each of the lane's four stores are
-            // requested in front of the requantisation chains.  (A compile-time loop: the body is past what a pragma unrolls.)
+            // The residual tail (NHWC): the same staging, and between the read-back and the store the add's and the
+            // activation's element functions on the staged bytes / halves.  The 16 skip bytes behind each of the lane's four
+            // (binary16: eight) stores are requested in front of the requantisation / finish4_f16 chains.  (A compile-time loop:
+            // the body is past what a pragma unrolls.)
             const ResidualTail tail = late_tail(a);
             static_for<MI / 2>([&](auto ihc) {
                 constexpr int ih = decltype(ihc)::value;
-                const int oc_first = co0 + wr * 32 * MI + ih * 64 + schunk * 16;
+                const int oc_first = co0 + wr * 32 * MI + ih * 64 + schunk * (16 / ESIZE);
                 uint4 skipv[64 / RPI];
 #pragma unroll
                 for (int it = 0; it < 64 / RPI; ++it) {
                     const int p = pix0 + wc * 64 + it * RPI + srow;
                     skipv[it] = make_uint4(0, 0, 0, 0);
                     if (p < a.M && oc_first < a.Co)
-                        skipv[it] = *reinterpret_cast<const uint4 *>(static_cast<const char *>(tail.skip) + (int64_t)p * a.Co + oc_first);
+                        skipv[it] = *reinterpret_cast<const uint4 *>(static_cast<const char *>(tail.skip) + ((int64_t)p * a.Co + oc_first) * ESIZE);
                 }
 #pragma unroll
                 for (int i2 = 0; i2 < 2; ++i2)
@@ -575,20 +593,31 @@ __global__ __launch_bounds__(64 * WR * WC * (PIPE ? 2 : 1)) void conv_igemm_tile
                             const int c = i2 * 32 + 8 * g + 4 * fhalf;
                             const int ch = wr * 32 * MI + ih * 64 + c;
                             const float4 bi = *reinterpret_cast<const float4 *>(tab_bias + ch);
-                            const int4 ai = *reinterpret_cast<const int4 *>(tab_acc + ch);
-                            const float4 mu = *reinterpret_cast<const float4 *>(tab_mult + ch);
                             const auto &t = acc[i + i2][j];
-                            *reinterpret_cast<uint32_t *>(ws + (j * 32 + frow) * PITCH + c) =
-                                requant4_i8_t<RQ>(t[4 * g + 0] + ai.x, t[4 * g + 1] + ai.y, t[4 * g + 2] + ai.z, t[4 * g + 3] + ai.w, mu, bi, a);
+                            if constexpr (kI8) {
+                                const int4 ai = *reinterpret_cast<const int4 *>(tab_acc + ch);
+                                const float4 mu = *reinterpret_cast<const float4 *>(tab_mult + ch);
+                                *reinterpret_cast<uint32_t *>(ws + (j * 32 + frow) * PITCH + c) =
+                                    requant4_i8_t<RQ>(t[4 * g + 0] + ai.x, t[4 * g + 1] + ai.y, t[4 * g + 2] + ai.z, t[4 * g + 3] + ai.w, mu, bi, a);
+                            } else {
+                                *reinterpret_cast<uint2 *>(ws + (j * 32 + frow) * PITCH + c * ESIZE) =
+                                    finish4_f16(t[4 * g + 0], t[4 * g + 1], t[4 * g + 2], t[4 * g + 3], bi, a);
+                            }
                         }
 #pragma unroll
                 for (int it = 0; it < 64 / RPI; ++it) {
                     const int row = it * RPI + srow;
                     const int p = pix0 + wc * 64 + row;
                     uint4 v = *reinterpret_cast<const uint4 *>(ws + row * PITCH + schunk * 16);
-                    v.x = residual4_i8(v.x, skipv[it].x, tail.post), v.y = residual4_i8(v.y, skipv[it].y, tail.post);
-                    v.z = residual4_i8(v.z, skipv[it].z, tail.post), v.w = residual4_i8(v.w, skipv[it].w, tail.post);
-                    if (p < a.M && oc_first < a.Co) *reinterpret_cast<uint4 *>(out + (int64_t)p * a.Co + oc_first) = v;
+                    if constexpr (kI8) {
+                        v.x = residual4_i8(v.x, skipv[it].x, tail.post), v.y = residual4_i8(v.y, skipv[it].y, tail.post);
+                        v.z = residual4_i8(v.z, skipv[it].z, tail.post), v.w = residual4_i8(v.w, skipv[it].w, tail.post);
+                    } else {
+                        const uint2 lo = residual4_f16(make_uint2(v.x, v.y), make_uint2(skipv[it].x, skipv[it].y), tail.post.conv_first, tail.post.act);
+                        const uint2 hi = residual4_f16(make_uint2(v.z, v.w), make_uint2(skipv[it].z, skipv[it].w), tail.post.conv_first, tail.post.act);
+                        v = make_uint4(lo.x, lo.y, hi.x, hi.y);
+                    }
+                    if (p < a.M && oc_first < a.Co) *reinterpret_cast<uint4 *>(out + ((int64_t)p * a.Co + oc_first) * ESIZE) = v;
                 }
             });
         } else
@@ -841,7 +870,7 @@ __global__ __launch_bounds__(256) void conv_igemm_wave_kernel(typename IgemmArgs
 {
     constexpr int ESIZE = kI8 ? 1 : 2;
     constexpr int RQ = EPI & (EPI_RESIDUAL - 1);              // the requantisation's code (common.h:epi_code)
-    constexpr bool kPost = kI8 && (EPI & EPI_RESIDUAL) != 0;  // ... and the residual tail behind it (residual_step.h)
+    constexpr bool kPost = (EPI & EPI_RESIDUAL) != 0;         // ... and the residual tail behind it (residual_step.h; either dtype)
     constexpr bool kLut = kI8 && (EPI & EPI_LUT) != 0;        // ... or the table post-op (lut_step.h)
     __shared__ __attribute__((aligned(16))) int32_t red[KS == 4 ? 4 * 3 * 64 * 4 : 4];
     if (a.debug & 128) return;
@@ -928,9 +957,13 @@ __global__ __launch_bounds__(256) void conv_igemm_wave_kernel(typename IgemmArgs
     // residual tail: the skip bytes behind this lane's stores, requested before the reduction and the requantisation chains
     // (KS == 1: its four groups; KS == 4: the one group this wave finishes)
     uint32_t skip4[4] = {0, 0, 0, 0};
+    uint2 skiph[4] = {};
     if constexpr (kPost) {
 #pragma unroll
-        for (int g = 0; g < (KS == 1 ? 4 : 1); ++g) skip4[g] = load_skip4(a, a.tail.skip, p, ch0 + 8 * (KS == 1 ? g : wave), vec_ok);
+        for (int g = 0; g < (KS == 1 ? 4 : 1); ++g) {
+            if constexpr (kI8) skip4[g] = load_skip4(a, a.tail.skip, p, ch0 + 8 * (KS == 1 ? g : wave), vec_ok);
+            else skiph[g] = load_skip4_f16(a, a.tail.skip, p, ch0 + 8 * (KS == 1 ? g : wave), vec_ok);
+        }
     }
     // table post-op: the wave's own copy of the table, made here (all 64 lanes active, the K loop behind it) -- no block barrier
     const uint8_t *lut = nullptr;
@@ -953,7 +986,8 @@ __global__ __launch_bounds__(256) void conv_igemm_wave_kernel(typename IgemmArgs
                 for (int e = 0; e < 4 && occ + e < a.Co; ++e) out[o + e] = (int8_t)(packed >> (8 * e));
             }
         } else {
-            const uint2 hp = finish4_f16(v_f[0], v_f[1], v_f[2], v_f[3], bi[g_tab], a);
+            uint2 hp = finish4_f16(v_f[0], v_f[1], v_f[2], v_f[3], bi[g_tab], a);
+            if constexpr (kPost) hp = residual4_f16(hp, skiph[g_tab], a.tail.post.conv_first, a.tail.post.act);
             uint16_t *out = static_cast<uint16_t *>(a.out);
             if (vec_ok) {
                 *reinterpret_cast<uint2 *>(out + o) = hp;
@@ -1192,6 +1226,14 @@ int launch_conv_igemm_residual(const ResidualConvArgs &a, const char *family, hi
     return launch_wave_regs_tile<EPI_RESIDUAL>(a, SHL_MI355X_I8, family, s);
 }
 
+// ... of a binary16 problem: the same two families, their binary16 instantiations with the tail
+int launch_conv_igemm_residual_f16(const ResidualConvArgs &a, const char *family, hipStream_t s)
+{
+    if (a.M == 0 || a.Co == 0) return SHL_MI355X_OK;
+    igemm_note_family(family);
+    return launch_wave_regs_tile<EPI_RESIDUAL>(a, SHL_MI355X_F16, family, s);
+}
+
 // a convolution with a table post-op in its stores: `family` is "wave" or "tile" likewise
 int launch_conv_igemm_lut(const LutConvArgs &a, const char *family, hipStream_t s)
 {
@@ -1200,7 +1242,7 @@ int launch_conv_igemm_lut(const LutConvArgs &a, const char *family, hipStream_t 
     return launch_wave_regs_tile<EPI_LUT>(a, SHL_MI355X_I8, family, s);
 }
 
-// the launch of problem `a` on the wave, regs or tile kernel (`v`).  POST = EPI_RESIDUAL: int8 with the residual tail
+// the launch of problem `a` on the wave, regs or tile kernel (`v`).  POST = EPI_RESIDUAL: int8 or binary16 with the residual tail
 // (Args = ResidualConvArgs), POST = EPI_LUT: int8 with the table post-op (Args = LutConvArgs), on the wave and tile kernels
 // only -- instantiations of their own; POST = 0: the kernels as they were
 template <int POST, typename Args>
@@ -1284,7 +1326,9 @@ static int launch_wave_regs_tile(const Args &a, int dtype, const char *v, hipStr
              TileGeom<MI, WRV, WCV, PP>::TBN, PP, UT ? "utap" : "anytap", epi, post);
 #define SHL_NOTE_WAVE(KS) snprintf(g_last_flavour, sizeof(g_last_flavour), "wave/ks%d/epi%d%s", KS, epi, post);
 #define SHL_LAUNCH(...) launch_kernel<Args, __VA_ARGS__>(grid, lds, s, a, threads)
-#define SHL_LAUNCH_F16(...) launch_kernel<ConvArgs, __VA_ARGS__>(grid, lds, s, a, threads)
+#define SHL_LAUNCH_F16(KERNEL, ...)                                                                           \
+    if constexpr (POST == EPI_RESIDUAL) { SHL_LAUNCH(KERNEL<false, EPI_RESIDUAL __VA_ARGS__>); }                  \
+    else { launch_kernel<ConvArgs, KERNEL<false, 0 __VA_ARGS__>>(grid, lds, s, a, threads); }
 #define SHL_LAUNCH_EPI(KERNEL, ...)                                          \
     switch (epi) {                                                           \
         case 0: SHL_LAUNCH(KERNEL<true, POST + 0 __VA_ARGS__>); break;       \
@@ -1298,18 +1342,18 @@ static int launch_wave_regs_tile(const Args &a, int dtype, const char *v, hipStr
 #define SHL_TILE_P(MI, WRV, WCV, UT, PP)                                                                              \
     SHL_NOTE_TILE(MI, WRV, WCV, UT, PP)                                                                               \
     if (i8) { SHL_LAUNCH_EPI(conv_igemm_tile_kernel, SHL_COMMA MI SHL_COMMA WRV SHL_COMMA WCV SHL_COMMA UT SHL_COMMA PP) } \
-    else { SHL_LAUNCH_F16(conv_igemm_tile_kernel<false, 0, MI, WRV, WCV, UT, PP>); }
+    else { SHL_LAUNCH_F16(conv_igemm_tile_kernel, SHL_COMMA MI SHL_COMMA WRV SHL_COMMA WCV SHL_COMMA UT SHL_COMMA PP) }
 #define SHL_TILE(MI, WRV, WCV, UT) \
     if (pipe) { SHL_TILE_P(MI, WRV, WCV, UT, 4) } else { SHL_TILE_P(MI, WRV, WCV, UT, 0) }
 #define SHL_WAVE(KS)  \
     SHL_NOTE_WAVE(KS) \
-    if (i8) { SHL_LAUNCH_EPI(conv_igemm_wave_kernel, SHL_COMMA KS) } else { SHL_LAUNCH_F16(conv_igemm_wave_kernel<false, 0, KS>); }
+    if (i8) { SHL_LAUNCH_EPI(conv_igemm_wave_kernel, SHL_COMMA KS) } else { SHL_LAUNCH_F16(conv_igemm_wave_kernel, SHL_COMMA KS) }
     if (kind == 0) {
         if (splitk) { SHL_WAVE(4) } else { SHL_WAVE(1) }
     } else if (kind == 1) {
         if constexpr (POST == 0) {
             snprintf(g_last_flavour, sizeof(g_last_flavour), "regs/epi%d", epi);
-            if (i8) { SHL_LAUNCH_EPI(conv_igemm_regs_kernel) } else { SHL_LAUNCH_F16(conv_igemm_regs_kernel<false, 0>); }
+            if (i8) { SHL_LAUNCH_EPI(conv_igemm_regs_kernel) } else { SHL_LAUNCH_F16(conv_igemm_regs_kernel) }
         } else {
             set_error("the regs kernel carries no post-op");
             return SHL_MI355X_ENOTSUP;

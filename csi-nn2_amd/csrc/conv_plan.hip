@@ -1241,17 +1241,19 @@ static ResidualPlanFacts residual_facts(const shl_mi355x_conv_plan *plan)
     return f;
 }
 
-/* "wave" | "tile" for a fused launch of `plan` at `batch`, NULL where there is none */
-static const char *residual_family(const shl_mi355x_conv_plan *plan, int32_t batch)
+/* "wave" | "tile" for a fused launch of `plan` at `batch`, NULL where there is none; f16: of the binary16 entry points */
+static const char *residual_family(const shl_mi355x_conv_plan *plan, int32_t batch, bool f16 = false)
 {
     const ResidualPlanFacts f = residual_facts(plan);
-    static char far_in[1], far_skip[1], far_out[1];
+    alignas(2) static char far_in[2], far_skip[2], far_out[2];
     shl_mi355x_residual_desc ok = {1, 1.0f, 0, 1.0f, 0, 0, 1.0f, 0};
     const char *msg;
     // (the pointers only have to be apart: ask with none of the buffers' extents)
     ResidualPlanFacts shape = f;
     shape.in_pixels = shape.out_pixels = 0;
-    if (residual_validate(&shape, far_in, far_skip, far_out, batch, &ok, &msg) != SHL_MI355X_OK) return nullptr;
+    if ((f16 ? residual_f16_validate(&shape, far_in, far_skip, far_out, batch, &ok, &msg)
+             : residual_validate(&shape, far_in, far_skip, far_out, batch, &ok, &msg)) != SHL_MI355X_OK)
+        return nullptr;
     const int64_t n = batch > 0 ? batch : f.plan_batch;
     if (n * f.out_pixels > 0x7FFFFFFFll || igemm_env_override()) return nullptr;  // (SHL_MI355X_IGEMM: A/B runs of the unfused families)
     const char *forced = residual_forced_form(getenv("SHL_MI355X_RESIDUAL_FORM"));
@@ -1299,6 +1301,49 @@ int shl_mi355x_conv_add_forward(const shl_mi355x_conv_plan *plan, const void *in
     a.tail.post = residual_rec(desc->conv_first, d.out_scale, d.out_zp, desc->skip_scale, desc->skip_zp, desc->sum_scale, desc->sum_zp,
                                desc->act, desc->act ? desc->out_scale : desc->sum_scale, desc->act ? desc->out_zp : desc->sum_zp);
     return launch_conv_igemm_residual(a, family, (hipStream_t)stream);
+}
+
+/* the same tail behind a binary16 / NHWC convolution: entry points of their own, which refuse every other plan (the int8 ones
+ * above keep refusing a binary16 plan).  Only conv_first and act of the descriptor are read */
+int shl_mi355x_conv_add_f16_fusable(const shl_mi355x_conv_plan *plan, int32_t batch) { return residual_family(plan, batch, true) ? 1 : 0; }
+
+const char *shl_mi355x_conv_add_f16_kernel_name(const shl_mi355x_conv_plan *plan, int32_t batch)
+{
+    const char *v = residual_family(plan, batch, true);
+    return !v ? "" : !strcmp(v, "wave") ? "wave+add" : "tile+add";
+}
+
+int shl_mi355x_conv_add_f16_by_default(const shl_mi355x_conv_plan *plan, int32_t batch)
+{
+    const char *v = residual_family(plan, batch, true);
+    if (!v) return 0;
+    const shl_mi355x_conv_desc &d = plan->desc;
+    const int64_t n = batch > 0 ? batch : d.batch;
+    return residual_f16_default(n * d.out_h * d.out_w, d.out_c, plan->kstride, (int64_t)d.kernel_h * d.kernel_w, !strcmp(v, "tile")) ? 1 : 0;
+}
+
+int shl_mi355x_conv_add_f16_forward(const shl_mi355x_conv_plan *plan, const void *input_dev, const void *skip_dev, void *output_dev,
+                                    int32_t batch, const struct shl_mi355x_residual_desc *desc, void *stream)
+{
+    const ResidualPlanFacts f = residual_facts(plan);
+    const char *msg;
+    const int st = residual_f16_validate(&f, input_dev, skip_dev, output_dev, batch, desc, &msg);
+    if (st != SHL_MI355X_OK) {
+        set_error("conv_add_f16_forward: %s", msg);
+        return st;
+    }
+    const char *family = residual_family(plan, batch, true);
+    if (!family) {
+        set_error("conv_add_f16_forward: no fused launch while SHL_MI355X_IGEMM forces a family");
+        return SHL_MI355X_ENOTSUP;
+    }
+    ResidualConvArgs a;
+    const int rc = fill_args(plan, input_dev, output_dev, batch, a);
+    if (rc != SHL_MI355X_OK) return rc;
+    if (a.M == 0) return SHL_MI355X_OK;
+    a.tail.skip = skip_dev;
+    a.tail.post = residual_rec(desc->conv_first, 1.0f, 0, 1.0f, 0, 1.0f, 0, desc->act, 1.0f, 0);  // (binary16 reads conv_first and act)
+    return launch_conv_igemm_residual_f16(a, family, (hipStream_t)stream);
 }
 
 /* conv2d -> an int8 activation by table (or a swish / hard-swish gate, one table as well) in the convolution's launch

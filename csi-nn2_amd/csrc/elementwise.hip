@@ -2,6 +2,7 @@
 // Replaces shl_ref_relu_quant / shl_ref_relu6_quant (source/reference/relu.c:21-43,
 // relu6.c:21-43): dequantise with the input record, clamp in fp32, requantise with the output
 // record.  HBM-bound: 16 bytes per lane per access.
+#include "add_step.h"
 #include "common.h"
 #include "relu_step.h"
 
@@ -38,17 +39,11 @@ __global__ __launch_bounds__(256) void relu_i8_kernel(const int8_t *in, int8_t *
         out[i] = (int8_t)relu_i8_step(in[i], si, zi, so, zo, relu6);
 }
 
-// binary16: f16 -> f32 (exact), x > 0 ? x : 0, fmin(., 6), f32 -> f16 with the reference rounding
-// (source/reference/relu.c:21-35, relu6.c:21-36 inside shl_ref_siso_callback_base)
+// binary16: the layer's element function (relu_step.h:relu_f16_step)
 __global__ __launch_bounds__(256) void relu_f16_kernel(const uint16_t *in, uint16_t *out, size_t count, int relu6)
 {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
-        float x = f16_bits_to_float(in[i]);
-        x = x > 0.0f ? x : 0.0f;
-        if (relu6) x = fminf(x, 6.0f);
-        out[i] = float_to_f16_bits_ref(x);
-    }
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) out[i] = relu_f16_step(in[i], relu6);
 }
 
 // elementwise add of two same-shape tensors (residual connections):
@@ -65,9 +60,7 @@ __global__ __launch_bounds__(256) void add_kernel(const void *a, const void *b, 
             const float r = __fadd_rn(x, y);
             static_cast<int8_t *>(out)[i] = (int8_t)sat8_from_float(__fadd_rn(rintf(__fdiv_rn(r, so)), zo));
         } else {
-            const float x = f16_bits_to_float(static_cast<const uint16_t *>(a)[i]);
-            const float y = f16_bits_to_float(static_cast<const uint16_t *>(b)[i]);
-            static_cast<uint16_t *>(out)[i] = float_to_f16_bits_ref(__fadd_rn(x, y));
+            static_cast<uint16_t *>(out)[i] = add_same_f16_step(static_cast<const uint16_t *>(a)[i], static_cast<const uint16_t *>(b)[i]);
         }
     }
 }

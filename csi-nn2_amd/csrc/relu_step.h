@@ -32,4 +32,15 @@ __device__ __forceinline__ int relu_i8_step(int q, float si, float zi, float so,
 
 __device__ __forceinline__ int relu_i8_step(int q, const ReluRec &m) { return relu_i8_step(q, m.si, m.zi, m.so, m.zo, m.relu6); }
 
+// binary16 (source/reference/relu.c:21-35, relu6.c:21-36 inside shl_ref_siso_callback_base): f16 -> f32 (exact), x > 0 ? x : 0
+// (a NaN becomes 0), fmin(., 6) for relu6, f32 -> f16 with the reference's rounding.  For the stand-alone kernel
+// (elementwise.hip) and the store of a binary16 convolution with a fused residual tail (residual_step.h)
+__device__ __forceinline__ uint16_t relu_f16_step(uint16_t h, int relu6)
+{
+    float x = f16_bits_to_float(h);
+    x = x > 0.0f ? x : 0.0f;
+    if (relu6) x = fminf(x, 6.0f);
+    return float_to_f16_bits_ref(x);
+}
+
 }  // namespace shl

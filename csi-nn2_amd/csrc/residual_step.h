@@ -78,9 +78,30 @@ __device__ __forceinline__ uint32_t residual4_i8(uint32_t conv4, uint32_t skip4,
     return r;
 }
 
+// binary16: the four halves finish4_f16 produced (the convolution's folded relu / relu6 and its rounding included) and the four
+// skip halves of the same offsets, through the same-shape add's and the relu's element functions (add_step.h:add_same_f16_step --
+// not the broadcasting add's --, relu_step.h:relu_f16_step).  The records are not read: a binary16 tensor of a fused tail has
+// scale 1.  conv_first is not decorative here: the hardware's addition picks between two NaNs by operand position, so the
+// operands go in the LAYER's order
+__device__ __forceinline__ uint2 residual4_f16(uint2 conv4, uint2 skip4, int conv_first, int act)
+{
+    const uint32_t c[4] = {conv4.x & 0xFFFFu, conv4.x >> 16, conv4.y & 0xFFFFu, conv4.y >> 16};
+    const uint32_t k[4] = {skip4.x & 0xFFFFu, skip4.x >> 16, skip4.y & 0xFFFFu, skip4.y >> 16};
+    uint32_t h[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        uint16_t v = add_same_f16_step((uint16_t)(conv_first ? c[e] : k[e]), (uint16_t)(conv_first ? k[e] : c[e]));
+        if (act) v = relu_f16_step(v, act == 2);
+        h[e] = v;
+    }
+    return make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
+}
+
 // conv_igemm.hip: the fused launch on one of the two families that carry the post-op ("wave" | "tile"), and the size rule
-// that picks between them (igemm_variant's, without the A/B switches of the unfused launch)
+// that picks between them (igemm_variant's, without the A/B switches of the unfused launch).  _f16: a binary16 problem, of
+// whose tail only conv_first and act are read
 int launch_conv_igemm_residual(const ResidualConvArgs &a, const char *family, hipStream_t s);
+int launch_conv_igemm_residual_f16(const ResidualConvArgs &a, const char *family, hipStream_t s);
 const char *igemm_size_rule(int64_t M, int64_t Co, int64_t kbytes);
 
 }  // namespace shl

@@ -258,21 +258,32 @@ static int one_record_i8(const struct csinn_tensor *t)
     return t->dtype == CSINN_DTYPE_INT8 && t->qinfo != NULL && t->quant_channel <= 1;
 }
 
+/* a binary16 tensor as the same-shape add and the relu layers take it: one record, scale 1 */
+static int one_record_f16(const struct csinn_tensor *t)
+{
+    return t->dtype == CSINN_DTYPE_FLOAT16 && t->qinfo != NULL && t->quant_channel <= 1 && t->qinfo->scale == 1.0f;
+}
+
 /* convolution a (its step writes `mid`, a folded activation included) -> add b: the index (0 or 1) of the add's OTHER operand, the
  * skip tensor, -1 when the pair does not fuse.  The add is the same-shape one -- both operands and the sum int8 tensors of one
- * record and equal dims -- and reads `mid` once; the plan must be one the fused launch takes (`force`) or was measured faster on */
+ * record, or all three binary16 tensors of scale 1, and equal dims -- and reads `mid` once; the plan must be one the fused launch
+ * of its dtype takes (`force`) or was measured faster on (shl_mi355x_conv_add_* / shl_mi355x_conv_add_f16_*) */
 static int residual_skip_input(struct shl_node *a, struct shl_node *b, struct shl_node *mid, int force)
 {
     if (!is_conv_op(a->type) || b->type != CSINN_OP_ADD || session_op(a) == NULL || session_op(b) == NULL) return -1;
     if (b->in_num != 2 || (b->in[0] == mid) == (b->in[1] == mid)) return -1;
     const int k = b->in[0] == mid ? 1 : 0;
     struct csinn_tensor *tm = mid->data, *ts = b->in[k]->data, *to = b->out[0]->data, *in = a->in[0]->data;
-    if (!one_record_i8(tm) || !one_record_i8(ts) || !one_record_i8(to) || ts->is_const) return -1;
+    const int f16 = tm->dtype == CSINN_DTYPE_FLOAT16;
+    if (f16 ? !one_record_f16(tm) || !one_record_f16(ts) || !one_record_f16(to) : !one_record_i8(tm) || !one_record_i8(ts) || !one_record_i8(to))
+        return -1;
+    if (ts->is_const) return -1;
     if (tm->dim_count != 4 || ts->dim_count != 4 || to->dim_count != 4) return -1;
     for (int i = 0; i < 4; i++)
         if (ts->dim[i] != tm->dim[i] || to->dim[i] != tm->dim[i]) return -1;
     shl_mi355x_conv_plan *pa = shl_mi355x_registry_get(a->data);
     if (pa == NULL) return -1;
+    if (f16) return (force ? shl_mi355x_conv_add_f16_fusable(pa, in->dim[0]) : shl_mi355x_conv_add_f16_by_default(pa, in->dim[0])) ? k : -1;
     return (force ? shl_mi355x_conv_add_fusable(pa, in->dim[0]) : shl_mi355x_conv_add_by_default(pa, in->dim[0])) ? k : -1;
 }
 
@@ -280,7 +291,8 @@ static int residual_skip_input(struct shl_node *a, struct shl_node *b, struct sh
 static int residual_takes_relu(struct shl_ref_graph *g, struct shl_node *sum, struct shl_node *r)
 {
     if ((r->type != CSINN_OP_RELU && r->type != CSINN_OP_RELU6) || session_op(r) == NULL || r->in[0] != sum) return 0;
-    return consumers_of(g, sum) == 1 && one_record_i8(r->out[0]->data);
+    const struct csinn_tensor *ts = sum->data;
+    return consumers_of(g, sum) == 1 && (ts->dtype == CSINN_DTYPE_FLOAT16 ? one_record_f16(r->out[0]->data) : one_record_i8(r->out[0]->data));
 }
 
 static int same_dims(const struct csinn_tensor *x, const struct csinn_tensor *y)
@@ -610,8 +622,12 @@ static int enqueue_layers(struct dev_session *ds, struct shl_ref_graph *g)
                 struct shl_mi355x_residual_desc rd = {ks == 1, tskip->qinfo->scale, tskip->qinfo->zero_point, tsum->qinfo->scale,
                                                       tsum->qinfo->zero_point, relu ? (relu->type == CSINN_OP_RELU6 ? 2 : 1) : 0,
                                                       tout->qinfo->scale, tout->qinfo->zero_point};
-                rc = status_of(shl_mi355x_conv_add_forward(shl_mi355x_registry_get(n->data), in->dev, skip->dev, out->dev, batch, &rd,
-                                                           ds->stream));
+                /* (the plan's dtype is the sum's: binary16 has entry points of its own, which read conv_first and act alone) */
+                rc = status_of(tsum->dtype == CSINN_DTYPE_FLOAT16
+                                   ? shl_mi355x_conv_add_f16_forward(shl_mi355x_registry_get(n->data), in->dev, skip->dev, out->dev, batch, &rd,
+                                                                     ds->stream)
+                                   : shl_mi355x_conv_add_forward(shl_mi355x_registry_get(n->data), in->dev, skip->dev, out->dev, batch, &rd,
+                                                                 ds->stream));
                 break;
             }
             case STEP_CONV_LUT: { /* the table's input is what the convolution (+ folded activation) would have written */

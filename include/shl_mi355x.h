@@ -360,6 +360,25 @@ const char *shl_mi355x_conv_add_kernel_name(const shl_mi355x_conv_plan *plan, in
 /* 1 for the shape classes where the fused launch was measured faster than the launches it replaces by more than their
  * run-to-run spread (profiles/residual_notes.md): what a session fuses without being asked */
 int shl_mi355x_conv_add_by_default(const shl_mi355x_conv_plan *plan, int32_t batch);
+/* The same tail behind a binary16 convolution, entry points of their own: binary16, NHWC, plans of SHL_MI355X_ALGO_IGEMM (the
+ * four above keep refusing a binary16 plan, these refuse every other one with SHL_MI355X_ENOTSUP, "", 0 and 0).  The descriptor
+ * is the same struct; only `conv_first` and `act` are read -- binary16 tensors of a fused tail have scale 1 and the scale fields
+ * are not validated.  On the four halves the convolution would have stored (its folded relu / relu6 and its rounding included)
+ * the kernel runs the element functions of shl_mi355x_add (the same-shape add, whose NaN is the hardware's pick -- `conv_first`
+ * decides which of two NaNs goes through) and shl_mi355x_relu_f16, so the launch equals shl_mi355x_conv_forward, shl_mi355x_add
+ * and shl_mi355x_relu_f16 one after the other bit for bit, NaNs and infinities included, wherever the convolution alone runs
+ * the same accumulation order: the wave and tile kernels add the K steps up in one order, the wave kernel's split-K form (few
+ * tiles, K rows of 256 bytes and more) in another, and the other binary16 families (row-patch, ping-pong, gemv) in theirs, as
+ * they always did among themselves -- fp32 sums of the same products, rounded once to binary16.
+ * SHL_MI355X_EINVAL before anything is enqueued: a NULL argument, an `act` outside 0 .. 2, a batch that gives 2^31 or more
+ * output pixels, a skip pointer that is not 2-byte aligned, a buffer that wraps around the address space, an output that
+ * overlaps the input or the skip tensor (sizes count 2-byte elements).  SHL_MI355X_RESIDUAL_FORM forces the family likewise;
+ * _by_default: the classes of profiles/residual_f16_notes.md */
+int shl_mi355x_conv_add_f16_fusable(const shl_mi355x_conv_plan *plan, int32_t batch);
+int shl_mi355x_conv_add_f16_forward(const shl_mi355x_conv_plan *plan, const void *input_dev, const void *skip_dev, void *output_dev,
+                                    int32_t batch, const struct shl_mi355x_residual_desc *desc, void *stream);
+const char *shl_mi355x_conv_add_f16_kernel_name(const shl_mi355x_conv_plan *plan, int32_t batch);
+int shl_mi355x_conv_add_f16_by_default(const shl_mi355x_conv_plan *plan, int32_t batch);
 /* An int8 activation that is a 256-entry table -- sigmoid / hard_sigmoid / silu / leaky_relu behind the convolution, or the
  * gate of a swish / hard-swish, mul(x, act(x)), which depends on x's byte alone -- as ONE launch of the convolution
  * (csrc/conv_igemm.hip, csrc/lut_step.h): int8, NHWC, plans of SHL_MI355X_ALGO_IGEMM.  `table` is HOST memory, 256 bytes,
