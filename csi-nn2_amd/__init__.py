@@ -43,6 +43,7 @@ REDUCE_GROUPS, REDUCE_CHUNK_BYTES = 4, 256
 OP_MATMUL = 95
 MATMUL_CHAIN, MATMUL_MFMA, MATMUL_MFMA_MAX_K = "matmul_chain", "matmul_mfma", 32768  # shl_mi355x_matmul's forms
 ATTENTION_MFMA, ATTENTION_MAX_KEYS = "attention_mfma", 1024  # shl_mi355x_attention's kernel and its cap on the keys
+ATTENTION_BIAS_MFMA = "attention_bias_mfma"  # shl_mi355x_attention_bias's kernel
 OP_SIGMOID, OP_HARD_SIGMOID, OP_SILU, OP_LEAKY_RELU, OP_MUL = 154, 78, 190, 84, 107
 OP_RESIZE = 133
 OP_DECONV2D, OP_DEPTHWISE_DECONV2D, OP_GROUP_DECONV2D = 54, 55, 56
@@ -212,6 +213,13 @@ class AttentionDesc(C.Structure):
         [(n, C.c_float) for n in ("q_scale", "k_scale", "v_scale", "s_scale", "c_scale", "sc_scale", "p_scale", "out_scale")] + \
         [(n, C.c_int32) for n in ("q_zp", "k_zp", "v_zp", "s_zp", "c_zp", "sc_zp", "p_zp", "out_zp")] + \
         [("reserved", C.c_int32 * 4)]
+
+
+class AttentionBiasDesc(C.Structure):
+    """struct shl_mi355x_attention_bias_desc (include/shl_mi355x.h)"""
+    _fields_ = [("b_ext1", C.c_int32), ("bias_is_first", C.c_int32), ("b_stride", C.c_int64 * 2), ("row_stride", C.c_int64),
+                ("key_stride", C.c_int64), ("b_scale", C.c_float), ("b_zp", C.c_int32), ("sb_scale", C.c_float), ("sb_zp", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
 
 
 class ResidualDesc(C.Structure):
@@ -440,6 +448,10 @@ def load_hip():
         "shl_mi355x_attention": (C.c_int, [vp, vp, vp, vp, C.POINTER(AttentionDesc), vp]),
         "shl_mi355x_attention_kernel_name": (C.c_char_p, [vp, vp, vp, vp, C.POINTER(AttentionDesc)]),
         "shl_mi355x_attention_by_default": (C.c_int, [vp, vp, vp, vp, C.POINTER(AttentionDesc)]),
+        "shl_mi355x_attention_bias": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(AttentionDesc), C.POINTER(AttentionBiasDesc), vp]),
+        "shl_mi355x_attention_bias_kernel_name": (C.c_char_p, [vp, vp, vp, vp, vp, C.POINTER(AttentionDesc), C.POINTER(AttentionBiasDesc)]),
+        "shl_mi355x_attention_bias_by_default": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(AttentionDesc), C.POINTER(AttentionBiasDesc)]),
+        "shl_mi355x_attention_bias_geometry": (C.c_int, [C.POINTER(MulDesc), i32, i32, i32, C.POINTER(AttentionBiasDesc)]),
         "shl_mi355x_unary_lut_i8": (C.c_int, [vp, vp, sz, vp, vp]),
         "shl_mi355x_unary_lut_i8_kernel_name": (C.c_char_p, [vp, vp]),
         "shl_mi355x_unary_f16": (C.c_int, [vp, vp, sz, i32, f32, vp]),
@@ -558,6 +570,7 @@ def load_backend(frontend):
         opt.shl_mi355x_session_folded_activations.argtypes = [C.POINTER(Session)]
         opt.shl_mi355x_session_fused_linears.argtypes = [C.POINTER(Session)]
         opt.shl_mi355x_session_fused_attentions.argtypes = [C.POINTER(Session)]
+        opt.shl_mi355x_session_fused_attention_biases.argtypes = [C.POINTER(Session)]
         opt.shl_mi355x_session_fused_residuals.argtypes = [C.POINTER(Session)]
         opt.shl_mi355x_session_fused_activations.argtypes = [C.POINTER(Session)]
         opt.shl_mi355x_session_stream.argtypes = [C.POINTER(Session)]

@@ -9,6 +9,11 @@
 //             a zero-filled K tail, k ascending in 64-byte slabs into one accumulator), int8 on the raw bytes with the same
 //             correction by row and column sums, then mm_value.  That fixes the float32 summation order of binary16 as well
 //   multiply  mul_i8_one / mul_f16_one (mul_step.h) on the value the first product would have stored
+//   add       (shl_mi355x_attention_bias, the BIAS instantiations: a bias or mask between the multiply and the softmax, which a
+//             session's planner finds as a broadcasting add) add_i8_step / add_f16_step (add_step.h) on the value the multiply
+//             -- or the first product -- would have stored and the bias element, read from global memory by the descriptor's
+//             strides; the sum goes into the tile under its own record, which is the one the softmax then reads.  That launch
+//             equals matmul -> [mul] -> shl_mi355x_add_bcast -> softmax -> matmul
 //   softmax   a row per wave.  The max is order-free, every element's exp(double(x - max)) is the same operation on the same
 //             operands (softmax_step.h), running_sum_exact is a one-wave routine over an LDS row padded with 256 zeros.  int8
 //             rows longer than 256 take the exponential and the requantised quotient from a per-row table of 256, as
@@ -25,6 +30,7 @@
 
 #include <type_traits>
 
+#include "add_step.h"
 #include "attention_canon.h"  // the host side: validation, the form rule, the LDS layout (a stand-alone program compiles it too)
 #include "matmul_step.h"
 #include "mul_step.h"
@@ -51,6 +57,15 @@ struct AttArgs {
     float mult2, o_so, o_zo, o_inv;
 };
 
+// the biased launch's further arguments (shl_mi355x_attention_bias).  A kernel without the bias takes AttArgs alone: its
+// arguments, and with them its instructions, are what they were before the bias existed
+struct AttBiasArgs : AttArgs {
+    const void *bias;
+    int32_t b_ext1, b_stride0, b_stride1, row_stride, key_stride;  // in elements; validated: every index fits 31 bits
+    int32_t bias_first;                                            // the bias is the add layer's first input
+    AddRec add;                                                    // a the (scaled) scores, b the bias, the sum's record
+};
+
 // a wave's LDS writes are visible to its own later reads (the LDS serves one wave's instructions in order); this keeps the
 // compiler from moving either across the point
 __device__ __forceinline__ void wave_lds_sync()
@@ -60,12 +75,40 @@ __device__ __forceinline__ void wave_lds_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <bool F16>
-__global__ __launch_bounds__(1024) void attention_mfma_kernel(AttArgs a)
+// The lane's sixteen bias elements for its block of scores.  C/D layout: a lane holds one key and sixteen rows; for a fixed r 32
+// adjacent lanes read 32 adjacent keys of one row -- coalesced where key_stride is 1, one address where it is 0.  The batch's
+// and the tile's part of the index is the same for the whole wave and stays in scalar registers; a lane adds 32-bit offsets
+// (validated: every index fits 31 bits).  A key past the last one and a row past the last query load nothing
+template <typename E>
+__device__ __forceinline__ void att_bias_load(E (&bv)[16], const AttBiasArgs &a, uint32_t bi, int m0, int key, int fh, bool active)
+{
+    const uint32_t i0 = bi / (uint32_t)a.b_ext1, i1 = bi - i0 * (uint32_t)a.b_ext1;
+    const E *const pb = static_cast<const E *>(a.bias) +
+                        (i0 * (uint32_t)a.b_stride0 + i1 * (uint32_t)a.b_stride1 + (uint32_t)m0 * (uint32_t)a.row_stride);
+    const bool in = active && key < a.T;
+    const uint32_t lane_off = (uint32_t)(in ? key : 0) * (uint32_t)a.key_stride + (uint32_t)(4 * fh) * (uint32_t)a.row_stride;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2);
+        bv[r] = in && m0 + row + 4 * fh < a.S ? pb[lane_off + (uint32_t)row * (uint32_t)a.row_stride] : (E)0;
+    }
+}
+
+// Where the biased kernel asks for the bias (profiles/attention_bias_notes.md).  binary16: EARLY, in front of the K loop, so
+// that the store behind the loop does not wait for it: measured 1 to 3 % faster than asking at the store (128 VGPRs, no
+// spill).  int8: at the head of the store, in front of the row sums' exchange -- sixteen more values across the loop spill
+// there (the kernel's scalar registers already overflow into vector ones).  -DATT_BIAS_EARLY=0 builds the late binary16 form
+#ifndef ATT_BIAS_EARLY
+#define ATT_BIAS_EARLY 1
+#endif
+
+template <bool F16, bool BIAS>
+__global__ __launch_bounds__(1024) void attention_mfma_kernel(typename std::conditional<BIAS, AttBiasArgs, AttArgs>::type a)
 {
     using Acc = typename AccT<!F16>::type;
     using E = typename std::conditional<F16, uint16_t, uint8_t>::type;
     constexpr int ES = F16 ? 2 : 1, KS = MM_KB / ES;  // elements of k per slab
+    [[maybe_unused]] constexpr bool BIAS_EARLY = F16 && ATT_BIAS_EARLY;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63, fr = lane & 31, fh = lane >> 5;
     const int nw = (int)blockDim.x >> 6;  // 4, 8 or 16 waves: the first four run the products, all of them the softmax
@@ -91,6 +134,8 @@ __global__ __launch_bounds__(1024) void attention_mfma_kernel(AttArgs a)
         for (int r = 0; r < 16; ++r) acc[r] = 0;
         int32_t rs = 0, cs = 0;
         uint4 vq = make_uint4(0u, 0u, 0u, 0u), vk0 = vq, vk1 = vq;
+        [[maybe_unused]] E bv[16];  // BIAS: the lane's sixteen bias elements
+        if constexpr (BIAS && BIAS_EARLY) att_bias_load<E>(bv, a, bi, m0, n0 + wave * 32 + fr, fh, active);
         if (tid < 4 * ATT_ROWS) vq = mm_piece<F16>(pq, a.D, m0, a.S, 0, a.D, 1, a.q_vec, tid);
         if (mover) {
             vk0 = mm_piece<F16>(pk, a.D, n0, T, 0, a.D, 1, a.k_vec, tid);
@@ -127,6 +172,8 @@ __global__ __launch_bounds__(1024) void attention_mfma_kernel(AttArgs a)
                 }
             }
         }
+        // (asked for in front of the row sums' exchange and its barrier, which the elements then travel behind)
+        if constexpr (BIAS && !BIAS_EARLY) att_bias_load<E>(bv, a, bi, m0, n0 + wave * 32 + fr, fh, active);
         if constexpr (!F16) {
             // a lane holds half of its row's / column's k: the other half is 32 lanes away
             rs += __shfl_xor(rs, 32);
@@ -145,12 +192,14 @@ __global__ __launch_bounds__(1024) void attention_mfma_kernel(AttArgs a)
                 if constexpr (F16) {
                     uint16_t h = (uint16_t)mm_value<true>(acc[r], a.s_so, a.s_zo, a.s_inv, a.s_div);
                     if (a.has_scale) h = mul_f16_one(h, (uint16_t)a.craw, a.mul);
+                    if constexpr (BIAS) h = a.bias_first ? add_f16_step(bv[r], h) : add_f16_step(h, bv[r]);
                     *dst = h;
                 } else {
                     // (every term and the true sum fit 32 bits; unsigned arithmetic, so that no intermediate wrap is undefined)
                     const uint32_t S = (uint32_t)acc[r] - (uint32_t)(a.izk * row_sum[wave][row]) - (uint32_t)(a.izq * cs) + (uint32_t)kzz;
                     int qv = mm_value<false>(__fmul_rn((float)(int32_t)S, a.mult1), a.s_so, a.s_zo, a.s_inv, a.s_div);
                     if (a.has_scale) qv = mul_i8_one(qv, a.craw, a.mul);
+                    if constexpr (BIAS) qv = add_i8_step(qv, (int)(int8_t)bv[r], a.add);
                     *dst = (E)(int8_t)qv;
                 }
             }
@@ -300,29 +349,23 @@ extern "C" int shl_mi355x_attention_by_default(const void *q_dev, const void *k_
     return !shl::attention_refusal(q_dev, k_dev, v_dev, out_dev, d, &code) && shl::att_default(d) ? 1 : 0;
 }
 
-extern "C" int shl_mi355x_attention(const void *q_dev, const void *k_dev, const void *v_dev, void *out_dev,
-                                    const struct shl_mi355x_attention_desc *d, void *stream)
+namespace shl {
+
+// the arguments both launches share, for a call attention_refusal has passed; *waves: the workgroup's
+static void attention_args(const void *q_dev, const void *k_dev, const void *v_dev, void *out_dev, const shl_mi355x_attention_desc *d,
+                           AttArgs &a, int *waves)
 {
-    using namespace shl;
-    int code;
-    const char *why = attention_refusal(q_dev, k_dev, v_dev, out_dev, d, &code);
-    if (why) {
-        set_error("attention: %s", why);
-        return code;
-    }
     const bool f16 = d->dtype == SHL_MI355X_F16;
     const int64_t es = f16 ? 2 : 1;
     shl_mi355x_matmul_desc qk, pv;
     att_qk_desc(d, &qk);
     att_pv_desc(d, &pv);
-    AttArgs a;
-    memset(&a, 0, sizeof(a));
     a.q = q_dev, a.k = k_dev, a.v = v_dev, a.out = out_dev;
     a.batches = d->batches, a.S = d->s, a.T = d->t, a.D = d->d, a.DV = d->dv;
     a.tiles = (d->s + ATT_ROWS - 1) / ATT_ROWS;
     a.q_vec = att_vec(q_dev, d->d, es), a.k_vec = att_vec(k_dev, d->d, es), a.v_vec = att_vec(v_dev, d->dv, es);
-    const int waves = att_waves(d);
-    a.lds = att_lds(d, waves);
+    *waves = att_waves(d);
+    a.lds = att_lds(d, *waves);
     // the products' constants as matmul_launch sets them
     a.izq = d->q_zp, a.izk = d->k_zp, a.mult1 = d->q_scale * d->k_scale;  // rounded once, here
     a.s_so = d->s_scale, a.s_zo = (float)d->s_zp, a.s_inv = 1.0f / d->s_scale, a.s_div = !f16 && mm_fma_ok(&qk);
@@ -336,12 +379,101 @@ extern "C" int shl_mi355x_attention(const void *q_dev, const void *k_dev, const 
     a.mul.a_second = d->scale_is_first ? 1 : 0;
     a.x_si = d->has_scale ? d->sc_scale : d->s_scale, a.x_zi = (float)(d->has_scale ? d->sc_zp : d->s_zp);
     a.p_so = d->p_scale, a.p_zo = (float)d->p_zp;
-    const int64_t groups = (int64_t)d->batches * a.tiles;  // (at most the output's element count)
-    static LdsOptIn opted_in[2];
-    if (a.lds.bytes > 48 * 1024)
-        lds_opt_in(opted_in[f16], reinterpret_cast<const void *>(f16 ? attention_mfma_kernel<true> : attention_mfma_kernel<false>));
-    hipLaunchKernelGGL(f16 ? attention_mfma_kernel<true> : attention_mfma_kernel<false>, dim3((unsigned)groups), dim3(64 * (unsigned)waves),
-                       (size_t)a.lds.bytes, (hipStream_t)stream, a);
+}
+
+template <typename Args>
+static int attention_enqueue(void (*kernel)(Args), LdsOptIn &opted_in, const Args &a, int waves, void *stream)
+{
+    const int64_t groups = (int64_t)a.batches * a.tiles;  // (at most the output's element count)
+    if (a.lds.bytes > 48 * 1024) lds_opt_in(opted_in, reinterpret_cast<const void *>(kernel));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)groups), dim3(64 * (unsigned)waves), (size_t)a.lds.bytes, (hipStream_t)stream, a);
     SHL_HIP(hipGetLastError());
     return SHL_MI355X_OK;
+}
+
+// NULL, or why the biased call is refused; *code: the status that goes with it
+static const char *attention_bias_refusal(const void *q, const void *k, const void *v, const void *bias, const void *out,
+                                          const shl_mi355x_attention_desc *d, const shl_mi355x_attention_bias_desc *bd, int *code)
+{
+    *code = SHL_MI355X_EINVAL;
+    const char *why = att_bias_validate(q, k, v, bias, out, d, bd);
+    if (why) return why;
+    *code = SHL_MI355X_ENOTSUP;
+    return att_unsupported(d);
+}
+
+}  // namespace shl
+
+extern "C" int shl_mi355x_attention(const void *q_dev, const void *k_dev, const void *v_dev, void *out_dev,
+                                    const struct shl_mi355x_attention_desc *d, void *stream)
+{
+    using namespace shl;
+    int code;
+    const char *why = attention_refusal(q_dev, k_dev, v_dev, out_dev, d, &code);
+    if (why) {
+        set_error("attention: %s", why);
+        return code;
+    }
+    AttArgs a;
+    memset(&a, 0, sizeof(a));
+    int waves;
+    attention_args(q_dev, k_dev, v_dev, out_dev, d, a, &waves);
+    static LdsOptIn opted_in[2];
+    const bool f16 = d->dtype == SHL_MI355X_F16;
+    return attention_enqueue(f16 ? attention_mfma_kernel<true, false> : attention_mfma_kernel<false, false>, opted_in[f16], a, waves, stream);
+}
+
+extern "C" const char *shl_mi355x_attention_bias_kernel_name(const void *q_dev, const void *k_dev, const void *v_dev, const void *bias_dev,
+                                                             const void *out_dev, const struct shl_mi355x_attention_desc *d,
+                                                             const struct shl_mi355x_attention_bias_desc *bd)
+{
+    int code;
+    return shl::attention_bias_refusal(q_dev, k_dev, v_dev, bias_dev, out_dev, d, bd, &code) ? "" : SHL_MI355X_ATTENTION_BIAS_MFMA;
+}
+
+extern "C" int shl_mi355x_attention_bias_by_default(const void *q_dev, const void *k_dev, const void *v_dev, const void *bias_dev,
+                                                    const void *out_dev, const struct shl_mi355x_attention_desc *d,
+                                                    const struct shl_mi355x_attention_bias_desc *bd)
+{
+    int code;
+    return !shl::attention_bias_refusal(q_dev, k_dev, v_dev, bias_dev, out_dev, d, bd, &code) && shl::att_bias_default(d) ? 1 : 0;
+}
+
+extern "C" int shl_mi355x_attention_bias_geometry(const struct shl_mi355x_mul_desc *m, int32_t batches, int32_t s, int32_t t,
+                                                  struct shl_mi355x_attention_bias_desc *bd)
+{
+    const int rc = shl::att_bias_geometry(m, batches, s, t, bd);
+    if (rc == 1) shl::set_error("attention_bias_geometry: the groups are not those of [batches][s][t]");
+    if (rc == 2) shl::set_error("attention_bias_geometry: a bias that i0, i1, row and key strides cannot express");
+    return rc == 0 ? SHL_MI355X_OK : rc == 1 ? SHL_MI355X_EINVAL : SHL_MI355X_ENOTSUP;
+}
+
+extern "C" int shl_mi355x_attention_bias(const void *q_dev, const void *k_dev, const void *v_dev, const void *bias_dev, void *out_dev,
+                                         const struct shl_mi355x_attention_desc *d, const struct shl_mi355x_attention_bias_desc *bd,
+                                         void *stream)
+{
+    using namespace shl;
+    int code;
+    const char *why = attention_bias_refusal(q_dev, k_dev, v_dev, bias_dev, out_dev, d, bd, &code);
+    if (why) {
+        set_error("attention_bias: %s", why);
+        return code;
+    }
+    AttBiasArgs a;
+    memset(&a, 0, sizeof(a));
+    int waves;
+    attention_args(q_dev, k_dev, v_dev, out_dev, d, a, &waves);
+    // the add's as bcast_launch sets them: a the (scaled) scores, b the bias; the softmax then reads the sum's record.  add_rec
+    // is the one rule that picks the int8 division for shl_mi355x_add_bcast as well
+    a.bias = bias_dev;
+    a.add = add_rec(a.x_si, d->has_scale ? d->sc_zp : d->s_zp, bd->b_scale, bd->b_zp, bd->sb_scale, bd->sb_zp);
+    a.x_si = bd->sb_scale, a.x_zi = (float)bd->sb_zp;
+    a.bias_first = bd->bias_is_first;
+    // (a stride along an extent of 1 is never used: att_bias_last has bounded the others)
+    a.b_ext1 = bd->b_ext1;
+    a.b_stride0 = d->batches / bd->b_ext1 > 1 ? (int32_t)bd->b_stride[0] : 0, a.b_stride1 = bd->b_ext1 > 1 ? (int32_t)bd->b_stride[1] : 0;
+    a.row_stride = d->s > 1 ? (int32_t)bd->row_stride : 0, a.key_stride = d->t > 1 ? (int32_t)bd->key_stride : 0;
+    static LdsOptIn opted_in[2];
+    const bool f16 = d->dtype == SHL_MI355X_F16;
+    return attention_enqueue(f16 ? attention_mfma_kernel<true, true> : attention_mfma_kernel<false, true>, opted_in[f16], a, waves, stream);
 }

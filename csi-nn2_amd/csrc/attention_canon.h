@@ -103,6 +103,122 @@ constexpr int ATT_DEFAULT_MIN_KEYS = 768;
 
 static inline bool att_default(const shl_mi355x_attention_desc *d) { return d->d <= ATT_DEFAULT_MAX_D && d->t >= ATT_DEFAULT_MIN_KEYS; }
 
+// ---- the biased launch (shl_mi355x_attention_bias) ---------------------------------------------------------------------------
+// the largest index the kernel forms in the bias, or -1 when it is 2^31 or more; for a descriptor whose strides are not negative
+// and whose b_ext1 divides batches.  (A stride along an extent of 1 is never multiplied by anything but 0)
+static inline int64_t att_bias_last(const shl_mi355x_attention_desc *d, const shl_mi355x_attention_bias_desc *b)
+{
+    const int64_t lim = 0x7FFFFFFFll;
+    const int64_t ext[4] = {d->batches / b->b_ext1, b->b_ext1, d->s, d->t};
+    const int64_t stride[4] = {b->b_stride[0], b->b_stride[1], b->row_stride, b->key_stride};
+    int64_t last = 0;
+    for (int i = 0; i < 4; ++i) {
+        if (ext[i] == 1) continue;
+        // (an extent below 2^31 times a stride below 2^31 fits 64 bits; so does the sum of four terms below 2^31)
+        if (stride[i] > lim || (ext[i] - 1) * stride[i] > lim) return -1;
+        last += (ext[i] - 1) * stride[i];
+    }
+    return last > lim ? -1 : last;
+}
+
+// NULL, or what is wrong with the call (SHL_MI355X_EINVAL): everything att_validate refuses, and the bias's own defects
+static inline const char *att_bias_validate(const void *q_dev, const void *k_dev, const void *v_dev, const void *bias_dev,
+                                            const void *out_dev, const shl_mi355x_attention_desc *d,
+                                            const shl_mi355x_attention_bias_desc *b)
+{
+    const char *why = att_validate(q_dev, k_dev, v_dev, out_dev, d);
+    if (why) return why;
+    if (!bias_dev || !b) return "NULL argument";
+    if (b->reserved[0] != 0 || b->reserved[1] != 0 || b->reserved[2] != 0 || b->reserved[3] != 0) return "a reserved field that is not zero";
+    if (b->bias_is_first != 0 && b->bias_is_first != 1) return "bias_is_first is neither 0 nor 1";
+    if (b->b_stride[0] < 0 || b->b_stride[1] < 0 || b->row_stride < 0 || b->key_stride < 0) return "a negative bias stride";
+    if (b->b_ext1 < 1 || d->batches % b->b_ext1 != 0) return "b_ext1 is below 1 or does not divide batches";
+    const int64_t last = att_bias_last(d, b);
+    if (last < 0) return "a bias index of 2^31 or more";
+    const int64_t es = d->dtype == SHL_MI355X_F16 ? 2 : 1;
+    const uintptr_t b0 = (uintptr_t)bias_dev, b1 = b0 + (uintptr_t)((last + 1) * es);
+    if (b0 & (uintptr_t)(es - 1)) return "a pointer that is not aligned to its elements";
+    if (b1 < b0) return "a buffer that wraps around the address space";
+    const uintptr_t o0 = (uintptr_t)out_dev, o1 = o0 + (uintptr_t)((int64_t)d->batches * d->s * d->dv * es);  // (att_validate: below 2^31)
+    if (b0 < o1 && o0 < b1) return "the output overlaps the bias";
+    return NULL;
+}
+
+// The strides of the biased launch from the add's collapsed groups (eltwise.c:shl_mi355x_bcast_prepare: groups of neighbouring
+// dims of the scores along which the bias varies or is broadcast, outermost first).  The groups are cut where they cross the
+// borders of [batches][s][t]; pieces that continue each other (the outer one's stride is the inner one's times its extent) are
+// one piece again.  The keys and the rows must come out as one piece each, the batches as at most two: i0 (outer) and i1.
+// 0: done; 1: the groups are not those of [batches][s][t]; 2: a bias the four strides cannot express
+static inline int att_bias_geometry(const shl_mi355x_mul_desc *m, int32_t batches, int32_t s, int32_t t, shl_mi355x_attention_bias_desc *b)
+{
+    if (!m || !b || m->ngroups < 1 || m->ngroups > 4 || batches < 1 || s < 1 || t < 1) return 1;
+    int64_t count = 1;
+    for (int g = 0; g < m->ngroups; ++g) {
+        if (m->dim[g] < 1 || m->b_stride[g] < 0 || m->dim[g] > 0x7FFFFFFFll) return 1;
+        count *= m->dim[g];
+        if (count > 0x7FFFFFFFll) return 1;
+    }
+    if (count != (int64_t)batches * s * t) return 1;
+    // pieces, innermost first: seg 0 the keys, 1 the rows, 2 the batches
+    struct Piece {
+        int seg;
+        int64_t ext, stride;
+    } piece[12];
+    int np = 0;
+    const int64_t seg_ext[3] = {t, s, batches};
+    int g = m->ngroups - 1, seg = 0;
+    int64_t grem = m->dim[g], gst = m->b_stride[g], srem = seg_ext[0];
+    for (;;) {
+        while (grem == 1 && g > 0) --g, grem = m->dim[g], gst = m->b_stride[g];
+        while (srem == 1 && seg < 2) ++seg, srem = seg_ext[seg];
+        if (grem == 1 || srem == 1) break;  // (the counts are equal: both are used up together)
+        int64_t take;
+        if (grem % srem == 0) take = srem;
+        else if (srem % grem == 0) take = grem;
+        else return 2;
+        // a piece that continues the one before it joins it
+        if (np > 0 && piece[np - 1].seg == seg && gst == piece[np - 1].stride * piece[np - 1].ext) piece[np - 1].ext *= take;
+        else {
+            if (np == 12) return 2;
+            piece[np].seg = seg, piece[np].ext = take, piece[np].stride = gst, ++np;
+        }
+        grem /= take, srem /= take, gst *= take;
+    }
+    if (grem != 1 || srem != 1) return 1;
+    int64_t stride[3][2] = {{0, 0}, {0, 0}, {0, 0}}, ext[3][2] = {{1, 1}, {1, 1}, {1, 1}};
+    int n[3] = {0, 0, 0};
+    for (int i = 0; i < np; ++i) {
+        const int sg = piece[i].seg;
+        if (n[sg] == (sg == 2 ? 2 : 1)) return 2;
+        stride[sg][n[sg]] = piece[i].stride, ext[sg][n[sg]] = piece[i].ext, ++n[sg];
+    }
+    b->key_stride = stride[0][0], b->row_stride = stride[1][0];
+    // one batch piece: all of the batch index is i1
+    b->b_ext1 = (int32_t)(n[2] == 2 ? ext[2][0] : batches);
+    b->b_stride[1] = stride[2][0], b->b_stride[0] = n[2] == 2 ? stride[2][1] : 0;
+    return 0;
+}
+
+// The shape classes a session fuses by default when the chain carries a bias: those where the biased launch was MEASURED
+// faster than the five launches it replaces, in int8 and in binary16, by more than the spread between windows on both sides
+// (profiles/attention_bias_notes.md; fused / unfused, int8 and binary16; a workgroup is 32 query rows of one batch):
+//   long rows on one round of the chip   heads of 32 on 850 keys, 216 workgroups: 0.82 / 0.93 -- but 1.64 / 1.84 on the 1728
+//                                        workgroups of batch 8, which hold a CU each for their 850 keys' LDS
+//   windows, many of them                heads of 32 on 49 keys, 3072 workgroups: 0.85 / 0.94 -- on 384 workgroups a tie
+// Heads of 64 on 128 keys (384 workgroups: 0.91 / 0.95) and on 197 keys (672: 0.98 / 0.96) win too, but by little, and lose
+// 17 to 38 % at batch 1 and on 384 keys: they stay behind the switch.  SHL_MI355X_ATTENTION=1 fuses every shape the kernel takes
+constexpr int ATT_BIAS_LONG_MAX_GROUPS = 256;    // (the chip's CUs)
+constexpr int ATT_BIAS_WINDOW_MAX_KEYS = 64;
+constexpr int ATT_BIAS_WINDOW_MIN_GROUPS = 3072;
+
+static inline bool att_bias_default(const shl_mi355x_attention_desc *d)
+{
+    const int64_t groups = (int64_t)d->batches * ((d->s + ATT_ROWS - 1) / ATT_ROWS);
+    if (d->d > ATT_DEFAULT_MAX_D) return false;
+    return (d->t >= ATT_DEFAULT_MIN_KEYS && groups <= ATT_BIAS_LONG_MAX_GROUPS) ||
+           (d->t <= ATT_BIAS_WINDOW_MAX_KEYS && groups >= ATT_BIAS_WINDOW_MIN_GROUPS);
+}
+
 // 16-byte global loads stay aligned for every batch, row and piece of a dense [..][rows][inner] operand
 static inline int att_vec(const void *p, int64_t inner, int64_t es) { return ((uintptr_t)p & 15) == 0 && (inner * es) % 16 == 0; }
 

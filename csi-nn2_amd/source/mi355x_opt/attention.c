@@ -78,6 +78,59 @@ int shl_mi355x_attention_prepare(struct csinn_tensor *q, struct csinn_tensor *k,
     return force || shl_mi355x_attention_by_default(a0, a1, a2, a3, d) ? CSINN_TRUE : CSINN_FALSE;
 }
 
+/* The add between the (scaled) scores and the softmax of a chain whose other layers shl_mi355x_attention_prepare has put into
+ * *d (asked with `force`: whether the biased chain is fused by default is decided here).  in0 / in1 / sum: the add layer's
+ * tensors; x: the chain's own tensor among its inputs, the other one is the bias (a mask, a relative position bias).
+ * CSINN_TRUE with *bd filled when shl_mi355x_attention_bias takes the chain and -- unless `force` -- fuses the shape by default.
+ * The add must be one shl_mi355x_add_exec hands to shl_mi355x_add_bcast with the bias as its broadcast operand: that is the
+ * launch the fused kernel equals.  Two operands of equal shape go to shl_mi355x_add there, whose binary16 NaN rule is another
+ * (csrc/add_step.h), so they stay apart.  A bias that varies along more than two groups of the batch dims, or whose groups cut
+ * through the rows or the keys, has no descriptor and stays apart as well */
+int shl_mi355x_attention_bias_prepare(struct csinn_tensor *in0, struct csinn_tensor *in1, struct csinn_tensor *sum,
+                                      struct csinn_tensor *x, const struct shl_mi355x_attention_desc *d, int force,
+                                      struct shl_mi355x_attention_bias_desc *bd)
+{
+    if (in0 == NULL || in1 == NULL || d == NULL || (x != in0 && x != in1) || in0 == in1) return CSINN_FALSE;
+    struct csinn_tensor *bias = x == in0 ? in1 : in0;
+    if (!plain(sum, d->dtype) || !is_shape(sum, d->batches, d->s, d->t) || sum->dim_count != x->dim_count) return CSINN_FALSE;
+    if (shl_mi355x_dtype_code(bias) != d->dtype || bias->qinfo == NULL || bias->quant_channel > 1 || bias->dim_count < 1 ||
+        bias->dim_count > sum->dim_count || (d->dtype == SHL_MI355X_F16 && bias->qinfo->scale != 1.0f))
+        return CSINN_FALSE;
+    int same = bias->dim_count == sum->dim_count;
+    for (int i = 0; i < sum->dim_count; i++) {
+        if (x->dim[i] != sum->dim[i]) return CSINN_FALSE;
+        const int j = i - (sum->dim_count - bias->dim_count);
+        const int32_t b = j >= 0 ? bias->dim[j] : 1;
+        if (b != sum->dim[i] && b != 1) return CSINN_FALSE; /* (asked here, so that bcast_prepare has nothing to complain about) */
+        if (j >= 0 && b != sum->dim[i]) same = 0;
+    }
+    if (same) return CSINN_FALSE;
+    struct csinn_tensor *full, *small;
+    struct shl_mi355x_mul_desc md;
+    if (shl_mi355x_bcast_prepare("add", in0, in1, sum, &full, &small, &md) != CSINN_TRUE || small != bias || full != x) return CSINN_FALSE;
+    memset(bd, 0, sizeof(*bd));
+    if (shl_mi355x_attention_bias_geometry(&md, d->batches, d->s, d->t, bd) != SHL_MI355X_OK) return CSINN_FALSE;
+    bd->bias_is_first = bias == in0;
+    bd->b_scale = bias->qinfo->scale, bd->b_zp = bias->qinfo->zero_point;
+    bd->sb_scale = sum->qinfo->scale, bd->sb_zp = sum->qinfo->zero_point;
+    const void *a0 = (const void *)((uintptr_t)1 << 56), *a1 = (const void *)((uintptr_t)1 << 57), *a2 = (const void *)((uintptr_t)1 << 58),
+               *a3 = (const void *)((uintptr_t)1 << 59), *a4 = (const void *)((uintptr_t)1 << 60);
+    if (shl_mi355x_attention_bias_kernel_name(a0, a1, a2, a4, a3, d, bd)[0] == '\0') return CSINN_FALSE;
+    return force || shl_mi355x_attention_bias_by_default(a0, a1, a2, a4, a3, d, bd) ? CSINN_TRUE : CSINN_FALSE;
+}
+
+int shl_mi355x_attention_bias_forward(const struct shl_mi355x_attention_desc *d, const struct shl_mi355x_attention_bias_desc *bd,
+                                      const void *q_dev, const void *k_dev, const void *v_dev, const void *bias_dev, void *out_dev,
+                                      void *stream)
+{
+    int st = shl_mi355x_attention_bias(q_dev, k_dev, v_dev, bias_dev, out_dev, d, bd, stream);
+    if (st != SHL_MI355X_OK) {
+        shl_debug_error("mi355x: attention with a bias failed (%d): %s\n", st, shl_mi355x_last_error());
+        return CSINN_FALSE;
+    }
+    return CSINN_TRUE;
+}
+
 int shl_mi355x_attention_forward(const struct shl_mi355x_attention_desc *d, const void *q_dev, const void *k_dev, const void *v_dev,
                                  void *out_dev, void *stream)
 {

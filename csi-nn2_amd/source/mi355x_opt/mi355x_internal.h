@@ -177,6 +177,14 @@ int shl_mi355x_attention_prepare(struct csinn_tensor *q, struct csinn_tensor *k,
                                  struct shl_mi355x_attention_desc *d);
 int shl_mi355x_attention_forward(const struct shl_mi355x_attention_desc *d, const void *q_dev, const void *k_dev, const void *v_dev,
                                  void *out_dev, void *stream);
+/* ... and the same chain with a broadcasting add (layer tensors in0, in1, sum; x: the chain's own operand of it) between the
+ * [scaled] scores and the softmax: the add's part of the descriptor, and the launch (shl_mi355x_attention_bias) */
+int shl_mi355x_attention_bias_prepare(struct csinn_tensor *in0, struct csinn_tensor *in1, struct csinn_tensor *sum,
+                                      struct csinn_tensor *x, const struct shl_mi355x_attention_desc *d, int force,
+                                      struct shl_mi355x_attention_bias_desc *bd);
+int shl_mi355x_attention_bias_forward(const struct shl_mi355x_attention_desc *d, const struct shl_mi355x_attention_bias_desc *bd,
+                                      const void *q_dev, const void *k_dev, const void *v_dev, const void *bias_dev, void *out_dev,
+                                      void *stream);
 int shl_mi355x_concat_perf(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params,
                            struct csinn_perf_info *info);
 int shl_mi355x_split_init(struct csinn_tensor *input, struct csinn_tensor **output, struct csinn_split_params *params);

@@ -34,7 +34,7 @@ struct dev_tensor {
     int probe_dev;
 };
 
-/* one unit the session enqueues: a layer, or two layers (an attention core: three or four) that run as one launch.  A relu / relu6 layer folded into the
+/* one unit the session enqueues: a layer, or two layers (an attention core: three to five) that run as one launch.  A relu / relu6 layer folded into the
  * convolution in front of it is no step and no layer of a step: the convolution's step writes the activation's output */
 enum step_kind {
     STEP_LAYER,     /* layer a, through its exec callback */
@@ -42,7 +42,8 @@ enum step_kind {
     STEP_POOL_CONV, /* global_avgpool2d a + the convolution / fullyconnected layer b on the pooled map */
     STEP_CONV_POOL, /* 1x1 convolution a + global_avgpool2d b */
     STEP_MATMUL_BIAS, /* matmul a + the add b of a constant bias [N] to its output (shl_mi355x_matmul_bias) */
-    STEP_ATTENTION, /* matmul(q, k^T) a -> [mul by a constant] -> softmax -> matmul(p, v): b, c, d (shl_mi355x_attention) */
+    STEP_ATTENTION, /* matmul(q, k^T) a -> [mul by a constant] -> [add of a bias or mask] -> softmax -> matmul(p, v): b, c, d, e
+                     * (shl_mi355x_attention; with the add shl_mi355x_attention_bias) */
     STEP_CONV_ADD,  /* convolution a -> same-shape add b of its output and a skip tensor -> [relu | relu6 c] (shl_mi355x_conv_add_forward) */
     STEP_CONV_LUT,  /* convolution or depthwise layer a -> table activation b -> [mul c of a's output and b's: a swish / hard-swish
                      * gate] (shl_mi355x_conv_lut_forward; a depthwise plan: shl_mi355x_dwconv_lut_forward) */
@@ -54,6 +55,7 @@ struct step {
                            * a, b, [c], and d = which of the add's operands (0 or 1) is the skip tensor */
     struct shl_node *out; /* the tensor node the step finally writes (a split: the first of them) */
     uint8_t lut[256];     /* STEP_CONV_LUT: the table of b (and c), built at plan time from the layers' records */
+    int e;                /* STEP_ATTENTION only: the chain's fifth layer, -1 when it has four or three */
 };
 
 struct dev_session {
@@ -69,7 +71,8 @@ struct dev_session {
     int nfused, nfolded;
     int npool; /* global_avgpool2d layers that run inside their consumer's launch */
     int nlinear; /* matmul layers that add the constant bias behind them in their own launch */
-    int nattention; /* Q K^T -> [scale] -> softmax -> P V chains that run as one launch */
+    int nattention; /* Q K^T -> [scale] -> [+ bias] -> softmax -> P V chains that run as one launch */
+    int nattention_bias; /* ... those of them with the add of a bias or mask */
     int nresidual; /* convolution -> add -> [relu | relu6] tails of skip connections that run as one launch */
     int nactivation; /* table activations (gates included) that run inside their convolution's launch */
     struct dev_session *next;
@@ -217,12 +220,17 @@ static int linear_bias_input(struct shl_node *a, struct shl_node *b, struct shl_
 }
 
 /* layers[0 .. n-1] (consecutive, each still a step of its own): matmul(q, k, trans_b; two activations) -> [mul by a one-element
- * constant, on either side] -> softmax over the last axis -> matmul(p, v; v an activation, no transposes), every intermediate
- * read once, by the next layer, and no graph output.  The number of layers the chain takes (3, or 4 with the mul) and its
- * descriptor in *d; 0 when the layers run one by one -- also where shl_mi355x_attention has no kernel for the shape or, unless
- * `force`, the shape is none it was measured faster on (shl_mi355x_attention_by_default) */
-static int attention_chain(struct shl_ref_graph *g, const int *layers, int n, int force, struct shl_mi355x_attention_desc *d)
+ * constant, on either side] -> [add of a bias or mask, on either side: a constant or an activation an earlier step wrote, broadcast
+ * to the scores] -> softmax over the last axis -> matmul(p, v; v an activation, no transposes), every intermediate
+ * read once, by the next layer, and no graph output.  The number of layers the chain takes (3, one more with the mul, one more
+ * with the add) and its descriptor in *d; with the add *bias is its other operand's node and *bd the add's part of the
+ * descriptor, without it *bias is NULL.  0 when the layers run one by one -- also where the launch has no kernel for the
+ * shape or, unless `force`, the shape is none it was measured faster on (shl_mi355x_attention_by_default, with the add
+ * shl_mi355x_attention_bias_by_default).  A mul BEHIND the add is no part of the chain */
+static int attention_chain(struct shl_ref_graph *g, const int *layers, int n, int force, struct shl_mi355x_attention_desc *d,
+                           struct shl_mi355x_attention_bias_desc *bd, struct shl_node **bias)
 {
+    *bias = NULL;
     if (n < 3) return 0;
     struct shl_node *qk = g->layer[layers[0]];
     if (qk->type != CSINN_OP_MATMUL || session_op(qk) == NULL || qk->in_num != 2) return 0;
@@ -240,6 +248,17 @@ static int attention_chain(struct shl_ref_graph *g, const int *layers, int n, in
         cur = sc;
         at = 2;
     }
+    struct shl_node *add = g->layer[layers[at]], *x = cur;
+    if (add->type == CSINN_OP_ADD) {
+        if (session_op(add) == NULL || add->in_num != 2 || (add->in[0] == cur) == (add->in[1] == cur)) return 0;
+        *bias = add->in[add->in[0] == cur ? 1 : 0];
+        cur = add->out[0];
+        if (consumers_of(g, cur) != 1) return 0;
+        at++;
+    } else {
+        add = NULL;
+    }
+    if (n < at + 2) return 0;
     struct shl_node *sm = g->layer[layers[at]], *pv = g->layer[layers[at + 1]];
     if (sm->type != CSINN_OP_SOFTMAX || session_op(sm) == NULL || sm->in[0] != cur || consumers_of(g, sm->out[0]) != 1) return 0;
     struct shl_node *p = sm->out[0];
@@ -248,7 +267,10 @@ static int attention_chain(struct shl_ref_graph *g, const int *layers, int n, in
     if (tv->is_const) return 0;
     struct csinn_softmax_params *sp = sm->data;
     if (shl_mi355x_attention_prepare(tq, tk, qk->out[0]->data, qk->data, cst ? cst->data : NULL, sc ? sc->data : NULL, const_first,
-                                     p->data, sp->axis, tv, pv->out[0]->data, pv->data, force, d) != CSINN_TRUE)
+                                     p->data, sp->axis, tv, pv->out[0]->data, pv->data, force || add != NULL, d) != CSINN_TRUE)
+        return 0;
+    /* (with the add the default is the biased launch's own) */
+    if (add != NULL && shl_mi355x_attention_bias_prepare(add->in[0]->data, add->in[1]->data, add->out[0]->data, x->data, d, force, bd) != CSINN_TRUE)
         return 0;
     return at + 2;
 }
@@ -402,11 +424,12 @@ static enum step_kind merged_kind(struct shl_ref_graph *g, const struct step *s,
  *   matmul -> add of a constant bias [N], the matmul's only consumer   one launch of csrc/matmul.hip's BIAS instantiation
  *        (STEP_MATMUL_BIAS): the linear layer a converter exports as MatMul + Add; the add's arithmetic runs on the value the
  *        matmul would have stored, so the step equals the two layers bit for bit
- *   matmul(q, k, trans_b) -> [mul by a one-element constant] -> softmax over the last axis -> matmul(p, v), every intermediate
+ *   matmul(q, k, trans_b) -> [mul by a one-element constant] -> [add of a bias or mask broadcast to the scores] -> softmax over
+ *        the last axis -> matmul(p, v), every intermediate
  *        read by the next layer only   one launch of csrc/attention.hip (STEP_ATTENTION) where both products take matmul's mfma
  *        form: the scores and the probabilities stay in LDS, each computed as its own kernel would store it, so the step equals
- *        the layers bit for bit.  By default only shape classes it was measured faster on (csrc/attention_canon.h:att_default);
- *        SHL_MI355X_ATTENTION=1 merges every chain the kernel takes, =0 keeps the layers apart
+ *        the layers bit for bit.  By default only shape classes it was measured faster on (csrc/attention_canon.h:att_default,
+ *        with the add att_bias_default); SHL_MI355X_ATTENTION=1 merges every chain the kernel takes, =0 keeps the layers apart
  *   convolution (int8 NHWC, implicit GEMM; its folded activation included) -> add(conv_out, skip) of equal shapes, the convolution's
  *        only consumer -> [relu | relu6, the sum's only consumer]   one launch of the convolution (STEP_CONV_ADD, csrc/conv_igemm.hip's
  *        instantiations with the post-op): the add's and the activation's element functions run on the byte the convolution would
@@ -483,13 +506,17 @@ static int plan_fusion(struct dev_session *ds, struct shl_ref_graph *g)
     for (int k = 0; k < ns; k++) {
         struct step s = steps[k];
         /* the core of an attention block first: its matmuls then are no longer candidates for a pair */
-        int chain[4] = {-1, -1, -1, -1}, avail = 0;
-        for (; avail < 4 && k + avail < ns; avail++) chain[avail] = steps[k + avail].a;
+        int chain[5] = {-1, -1, -1, -1, -1}, avail = 0;
+        for (; avail < 5 && k + avail < ns; avail++) chain[avail] = steps[k + avail].a;
         struct shl_mi355x_attention_desc ad;
-        const int taken = attention ? attention_chain(g, chain, avail, force, &ad) : 0;
+        struct shl_mi355x_attention_bias_desc abd;
+        struct shl_node *bias = NULL;
+        const int taken = attention ? attention_chain(g, chain, avail, force, &ad, &abd, &bias) : 0;
         if (taken > 0) {
-            steps[ds->nsteps++] = (struct step){STEP_ATTENTION, chain[0], chain[1], chain[2], taken == 4 ? chain[3] : -1, steps[k + taken - 1].out};
+            steps[ds->nsteps] = (struct step){STEP_ATTENTION, chain[0], chain[1], chain[2], taken >= 4 ? chain[3] : -1, steps[k + taken - 1].out};
+            steps[ds->nsteps++].e = taken == 5 ? chain[4] : -1;
             ds->nattention++;
+            if (bias != NULL) ds->nattention_bias++;
             k += taken - 1; /* the chain's other steps are taken */
             continue;
         }
@@ -601,13 +628,19 @@ static int enqueue_layers(struct dev_session *ds, struct shl_ref_graph *g)
                 break;
             }
             case STEP_ATTENTION: {
-                const int chain[4] = {s->a, s->b, s->c, s->d}, len = s->d >= 0 ? 4 : 3;
-                struct shl_node *pv = g->layer[chain[len - 1]];
+                const int chain[5] = {s->a, s->b, s->c, s->d, s->e}, len = s->d < 0 ? 3 : s->e < 0 ? 4 : 5;
+                struct shl_node *pv = g->layer[chain[len - 1]], *bias = NULL;
                 struct shl_mi355x_attention_desc ad;
+                struct shl_mi355x_attention_bias_desc abd;
                 struct dev_tensor *kk = lookup(ds, n->in[1]), *v = lookup(ds, pv->in[1]);
-                rc = kk && v && attention_chain(g, chain, len, 1, &ad) == len /* (the plan has decided) */
-                         ? shl_mi355x_attention_forward(&ad, in->dev, kk->dev, v->dev, out->dev, ds->stream)
-                         : CSINN_FALSE;
+                if (!kk || !v || attention_chain(g, chain, len, 1, &ad, &abd, &bias) != len) { /* (the plan has decided) */
+                    rc = CSINN_FALSE;
+                } else if (bias != NULL) { /* a constant bias is resident like any constant operand of an add */
+                    struct dev_tensor *b = lookup(ds, bias);
+                    rc = b ? shl_mi355x_attention_bias_forward(&ad, &abd, in->dev, kk->dev, v->dev, b->dev, out->dev, ds->stream) : CSINN_FALSE;
+                } else {
+                    rc = shl_mi355x_attention_forward(&ad, in->dev, kk->dev, v->dev, out->dev, ds->stream);
+                }
                 break;
             }
             case STEP_CONV_ADD: { /* the add and the activation read what the convolution (+ folded activation) would have written */
@@ -883,11 +916,18 @@ int shl_mi355x_session_fused_linears(struct csinn_session *sess)
     return ds ? ds->nlinear : 0;
 }
 
-/* number of Q K^T -> [scale] -> softmax -> P V chains of `sess` that run as one launch */
+/* number of Q K^T -> [scale] -> [+ bias] -> softmax -> P V chains of `sess` that run as one launch */
 int shl_mi355x_session_fused_attentions(struct csinn_session *sess)
 {
     struct dev_session *ds = find_session(sess);
     return ds ? ds->nattention : 0;
+}
+
+/* ... and how many of those carry the add of a bias or mask (shl_mi355x_attention_bias) */
+int shl_mi355x_session_fused_attention_biases(struct csinn_session *sess)
+{
+    struct dev_session *ds = find_session(sess);
+    return ds ? ds->nattention_bias : 0;
 }
 
 /* number of convolution -> add -> [relu | relu6] tails of skip connections of `sess` that run as one launch */

@@ -855,6 +855,62 @@ const char *shl_mi355x_attention_kernel_name(const void *q_dev, const void *k_de
 int shl_mi355x_attention_by_default(const void *q_dev, const void *k_dev, const void *v_dev, const void *out_dev,
                                     const struct shl_mi355x_attention_desc *d);
 
+/* The same core with an additive bias or mask on the scores -- Q K^T, [scores * constant], + bias, softmax, P V -- as ONE
+ * launch: a padding mask [B,1,1,T], a relative position bias [1,H,S,T], a causal mask [1,1,S,T].  `d` is the descriptor
+ * above, unchanged; has_scale says whether the add reads the scaled scores (record sc_*) or the stored ones (s_*).  The bias
+ * is int8 or binary16 like the rest, under the record b_*; the sum is stored -- in LDS -- under sb_*, and the softmax reads
+ * that record.  The bias element of batch bi = i0 * b_ext1 + i1, query row and key is
+ *     bias[i0 * b_stride[0] + i1 * b_stride[1] + row * row_stride + key * key_stride],
+ * every stride in elements and 0 where the bias is broadcast (a stride along an extent of 1 is not read).
+ * shl_mi355x_attention_bias_geometry derives these fields from the collapsed groups of the add's own descriptor.
+ * The result equals, bit for bit, shl_mi355x_matmul -> [shl_mi355x_mul] -> shl_mi355x_add_bcast (a: the scores, b: the
+ * bias, a_is_second = bias_is_first, the geometry the strides state) -> shl_mi355x_softmax -> shl_mi355x_matmul on the same
+ * buffers: the sum is add_step.h's element function on the value the multiply (or the product) would have stored, in the
+ * int8 variant (one fused multiply-add or the hardware's division) that shl_mi355x_add_bcast takes for the same three
+ * records; binary16: of two NaNs the layer's second input's goes through, inf + -inf is 0xFFFF.
+ * The bias pointer needs its element's alignment only; q, k, v and the output keep the rules above.  No LDS beyond
+ * shl_mi355x_attention's.  SHL_MI355X_EINVAL before anything is enqueued: whatever shl_mi355x_attention refuses so; a NULL
+ * bias or bias descriptor; a negative stride; b_ext1 below 1 or not dividing batches; a largest bias index of 2^31 or more;
+ * bias_is_first other than 0 or 1; non-zero reserved fields; a bias pointer not aligned to its elements; the output
+ * overlapping the bias.  SHL_MI355X_ENOTSUP where shl_mi355x_attention returns it.  Enqueues only: no allocation, no upload,
+ * no synchronisation (capturable in a hipGraph). */
+#define SHL_MI355X_ATTENTION_BIAS_MFMA "attention_bias_mfma"
+
+struct shl_mi355x_attention_bias_desc {
+    int32_t b_ext1;        /* the inner extent of the batch index: bi = i0 * b_ext1 + i1; divides batches */
+    int32_t bias_is_first; /* the bias is the add layer's first input */
+    int64_t b_stride[2];   /* what one step of i0 / i1 moves in the bias, in elements */
+    int64_t row_stride;    /* ... one query row */
+    int64_t key_stride;    /* ... one key */
+    float b_scale;         /* the bias */
+    int32_t b_zp;
+    float sb_scale;        /* the sum: the softmax's input */
+    int32_t sb_zp;
+    int32_t reserved[4];   /* must be zero */
+};
+
+int shl_mi355x_attention_bias(const void *q_dev, const void *k_dev, const void *v_dev, const void *bias_dev, void *out_dev,
+                              const struct shl_mi355x_attention_desc *d, const struct shl_mi355x_attention_bias_desc *bd,
+                              void *stream);
+/* "attention_bias_mfma", or "" for what the call refuses.  Pure host code, touches no device */
+const char *shl_mi355x_attention_bias_kernel_name(const void *q_dev, const void *k_dev, const void *v_dev, const void *bias_dev,
+                                                  const void *out_dev, const struct shl_mi355x_attention_desc *d,
+                                                  const struct shl_mi355x_attention_bias_desc *bd);
+/* 1 when the call names a kernel AND the shape belongs to a class in which the biased launch was measured faster than the
+ * five launches it replaces (profiles/attention_bias_notes.md: heads of at most 32 on at least 768 keys when the grid is at
+ * most 256 workgroups of 32 query rows, and on at most 64 keys when it is at least 3072): what a session fuses without being
+ * asked.  Pure host code */
+int shl_mi355x_attention_bias_by_default(const void *q_dev, const void *k_dev, const void *v_dev, const void *bias_dev,
+                                         const void *out_dev, const struct shl_mi355x_attention_desc *d,
+                                         const struct shl_mi355x_attention_bias_desc *bd);
+struct shl_mi355x_mul_desc;
+/* b_ext1 and the four strides of *bd from the collapsed groups of the add's descriptor `m` (its a the scores
+ * [batches][s][t], its b the bias); the other fields of *bd are left alone.  SHL_MI355X_OK, SHL_MI355X_EINVAL when the
+ * groups do not describe [batches][s][t], SHL_MI355X_ENOTSUP for a bias that varies in a way i0, i1, row and key cannot
+ * express (a group boundary inside the rows or the keys, more than two batch groups).  Pure host code */
+int shl_mi355x_attention_bias_geometry(const struct shl_mi355x_mul_desc *m, int32_t batches, int32_t s, int32_t t,
+                                       struct shl_mi355x_attention_bias_desc *bd);
+
 /* nearest-neighbour / bilinear resize of a 4-d int8 / binary16 tensor: shl_ref_resize_quant
  * (source/reference/resize.c:464-468), bit for bit.  height_scale / width_scale are the reference's own floats, computed by
  * the CALLER as ONE float division each: (float)in / out, with align_corners (float)(in - 1) / (out - 1)

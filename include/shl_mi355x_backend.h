@@ -205,6 +205,11 @@ int shl_mi355x_session_fused_linears(struct csinn_session *sess);
  * (shl_mi355x_attention_by_default); at setup SHL_MI355X_ATTENTION=1 merges every chain the kernel takes, SHL_MI355X_ATTENTION=0
  * or SHL_MI355X_NO_FUSION=1 keeps the layers apart */
 int shl_mi355x_session_fused_attentions(struct csinn_session *sess);
+/* ... those of them that carry an add of a bias or mask between the [scaled] scores and the softmax, on either side, its other
+ * operand a constant or an earlier activation broadcast to the scores (shl_mi355x_attention_bias; counted in the number above
+ * as well).  Their default is shl_mi355x_attention_bias_by_default; the switches are the same.  Operands of equal shape, a
+ * bias that needs more than two groups of the batch dims, and a mul behind the add stay apart */
+int shl_mi355x_session_fused_attention_biases(struct csinn_session *sess);
 /* tails of skip connections of `sess` -- convolution -> add(conv_out, skip) -> [relu | relu6] -- that run as one launch of the
  * convolution (shl_mi355x_conv_add_forward; int8 NHWC implicit-GEMM plans, same-shape adds).  By default those of a shape class
  * the fused launch was measured faster on (shl_mi355x_conv_add_by_default); at setup SHL_MI355X_RESIDUAL=1 merges every tail the
