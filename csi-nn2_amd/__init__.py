@@ -44,6 +44,7 @@ OP_MATMUL = 95
 MATMUL_CHAIN, MATMUL_MFMA, MATMUL_MFMA_MAX_K = "matmul_chain", "matmul_mfma", 32768  # shl_mi355x_matmul's forms
 ATTENTION_MFMA, ATTENTION_MAX_KEYS = "attention_mfma", 1024  # shl_mi355x_attention's kernel and its cap on the keys
 ATTENTION_BIAS_MFMA = "attention_bias_mfma"  # shl_mi355x_attention_bias's kernel
+ATTENTION_LAYOUT_MFMA, ATTENTION_BIAS_LAYOUT_MFMA = "attention_layout_mfma", "attention_bias_layout_mfma"  # shl_mi355x_attention_layout's
 OP_SIGMOID, OP_HARD_SIGMOID, OP_SILU, OP_LEAKY_RELU, OP_MUL = 154, 78, 190, 84, 107
 OP_RESIZE = 133
 OP_DECONV2D, OP_DEPTHWISE_DECONV2D, OP_GROUP_DECONV2D = 54, 55, 56
@@ -257,6 +258,12 @@ class SplitDesc(C.Structure):
                 ("in_zp", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
+class AttentionLayoutDesc(C.Structure):
+    """struct shl_mi355x_attention_layout_desc (include/shl_mi355x.h)"""
+    _fields_ = [("heads", C.c_int32), ("moved", C.c_int32), ("q_stride", C.c_int32 * 3), ("k_stride", C.c_int32 * 3),
+                ("v_stride", C.c_int32 * 3), ("out_stride", C.c_int32 * 3), ("reserved", C.c_int32 * 2)]
+
+
 class ShuffleDesc(C.Structure):
     """struct shl_mi355x_shuffle_desc (include/shl_mi355x.h)"""
     _fields_ = [("dtype", C.c_int32), ("group", C.c_int32), ("outer", C.c_int64), ("c", C.c_int64), ("inner", C.c_int64),
@@ -452,6 +459,14 @@ def load_hip():
         "shl_mi355x_attention_bias_kernel_name": (C.c_char_p, [vp, vp, vp, vp, vp, C.POINTER(AttentionDesc), C.POINTER(AttentionBiasDesc)]),
         "shl_mi355x_attention_bias_by_default": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(AttentionDesc), C.POINTER(AttentionBiasDesc)]),
         "shl_mi355x_attention_bias_geometry": (C.c_int, [C.POINTER(MulDesc), i32, i32, i32, C.POINTER(AttentionBiasDesc)]),
+        "shl_mi355x_attention_layout": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(AttentionDesc), C.POINTER(AttentionBiasDesc),
+                                                  C.POINTER(AttentionLayoutDesc), vp]),
+        "shl_mi355x_attention_layout_kernel_name": (C.c_char_p, [vp, vp, vp, vp, vp, C.POINTER(AttentionDesc), C.POINTER(AttentionBiasDesc),
+                                                                 C.POINTER(AttentionLayoutDesc)]),
+        "shl_mi355x_attention_layout_by_default": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(AttentionDesc), C.POINTER(AttentionBiasDesc),
+                                                             C.POINTER(AttentionLayoutDesc)]),
+        "shl_mi355x_attention_layout_strides": (C.c_int, [C.POINTER(i32), i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32,
+                                                          C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "shl_mi355x_unary_lut_i8": (C.c_int, [vp, vp, sz, vp, vp]),
         "shl_mi355x_unary_lut_i8_kernel_name": (C.c_char_p, [vp, vp]),
         "shl_mi355x_unary_f16": (C.c_int, [vp, vp, sz, i32, f32, vp]),
@@ -571,6 +586,7 @@ def load_backend(frontend):
         opt.shl_mi355x_session_fused_linears.argtypes = [C.POINTER(Session)]
         opt.shl_mi355x_session_fused_attentions.argtypes = [C.POINTER(Session)]
         opt.shl_mi355x_session_fused_attention_biases.argtypes = [C.POINTER(Session)]
+        opt.shl_mi355x_session_folded_head_moves.argtypes = [C.POINTER(Session)]
         opt.shl_mi355x_session_fused_residuals.argtypes = [C.POINTER(Session)]
         opt.shl_mi355x_session_fused_activations.argtypes = [C.POINTER(Session)]
         opt.shl_mi355x_session_stream.argtypes = [C.POINTER(Session)]

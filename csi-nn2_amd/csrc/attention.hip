@@ -25,6 +25,17 @@
 // the 32 x T tile of scores is written to LDS through mm_value + the mul step.  The probabilities overwrite the scores in
 // place, and P V reads them as its [row][k] operand directly; v goes through mm_put's transposing write, a pass covers 128
 // output columns.  LDS (attention_canon.h:att_lds) caps T at SHL_MI355X_ATTENTION_MAX_KEYS; d and dv are looped over.
+//
+// The LAYOUT instantiations (shl_mi355x_attention_layout) take the operands where a model's projections left them -- q, k, v
+// inside [B, S, H d], the output into one -- instead of behind a reshape and a transpose(0,2,1,3) each: per operand three
+// element strides {outer, head, row} and `heads`, the batch index bi = i0 heads + i1, the base i0 outer + i1 head computed
+// once per workgroup in scalar registers, mm_piece given the row stride where the dense form gives d / dv, the store's index
+// base + row out_row + col.  The innermost dim keeps stride 1.  That launch equals the movers (shl_mi355x_move,
+// shl_mi355x_transpose) around the dense launch bit for bit: int8 movers under one record copy bytes; binary16 movers turn an
+// infinity into +-65504 and a NaN into 0x7FFF with its sign (requant_move.h:move_fix_f16x2), which the kernel applies to the
+// pieces of an input whose `moved` bit is set.  The dense instantiations take their old argument blocks and keep their
+// registers (profiles/attention_layout_notes.md); every combination of dtype, bias and layout compiles without a spill, so
+// none is refused for its registers.
 #include <stdlib.h>
 #include <string.h>
 
@@ -34,6 +45,7 @@
 #include "attention_canon.h"  // the host side: validation, the form rule, the LDS layout (a stand-alone program compiles it too)
 #include "matmul_step.h"
 #include "mul_step.h"
+#include "requant_move.h"
 #include "softmax_step.h"
 
 namespace shl {
@@ -65,6 +77,31 @@ struct AttBiasArgs : AttArgs {
     int32_t bias_first;                                            // the bias is the add layer's first input
     AddRec add;                                                    // a the (scaled) scores, b the bias, the sum's record
 };
+
+// the layout launch's further arguments (shl_mi355x_attention_layout), appended to either struct as AttBiasArgs' are to AttArgs:
+// a kernel without them takes what it took before the layout form existed.  Strides in elements; validated: every index an
+// operand forms fits 31 bits
+struct AttLayoutPart {
+    int32_t heads, moved;  // bi = i0 * heads + i1; moved: ATT_MOVED_* (binary16: the movers' rule for special values on what is loaded)
+    int32_t q_outer, q_head, q_row, k_outer, k_head, k_row, v_outer, v_head, v_row, o_outer, o_head, o_row;
+};
+struct AttLayoutArgs : AttArgs {
+    AttLayoutPart lay;
+};
+struct AttBiasLayoutArgs : AttBiasArgs {
+    AttLayoutPart lay;
+};
+template <bool BIAS, bool LAYOUT>
+using AttArgsOf = typename std::conditional<LAYOUT, typename std::conditional<BIAS, AttBiasLayoutArgs, AttLayoutArgs>::type,
+                                            typename std::conditional<BIAS, AttBiasArgs, AttArgs>::type>::type;
+
+// a piece as the movers would have delivered it (requant_move.h: an infinity as +-65504, a NaN as 0x7FFF with its sign; idempotent,
+// so once stands for a reshape and a transpose; the zeros of a piece's tail stay zeros)
+__device__ __forceinline__ uint4 att_moved(uint4 v)
+{
+    v.x = move_fix_f16x2(v.x), v.y = move_fix_f16x2(v.y), v.z = move_fix_f16x2(v.z), v.w = move_fix_f16x2(v.w);
+    return v;
+}
 
 // a wave's LDS writes are visible to its own later reads (the LDS serves one wave's instructions in order); this keeps the
 // compiler from moving either across the point
@@ -102,8 +139,8 @@ __device__ __forceinline__ void att_bias_load(E (&bv)[16], const AttBiasArgs &a,
 #define ATT_BIAS_EARLY 1
 #endif
 
-template <bool F16, bool BIAS>
-__global__ __launch_bounds__(1024) void attention_mfma_kernel(typename std::conditional<BIAS, AttBiasArgs, AttArgs>::type a)
+template <bool F16, bool BIAS, bool LAYOUT>
+__global__ __launch_bounds__(1024) void attention_mfma_kernel(AttArgsOf<BIAS, LAYOUT> a)
 {
     using Acc = typename AccT<!F16>::type;
     using E = typename std::conditional<F16, uint16_t, uint8_t>::type;
@@ -122,9 +159,27 @@ __global__ __launch_bounds__(1024) void attention_mfma_kernel(typename std::cond
     const uint32_t bi = blockIdx.x / (uint32_t)a.tiles;
     const int m0 = (int)(blockIdx.x - bi * (uint32_t)a.tiles) * ATT_ROWS;
     // (every tensor holds fewer than 2^31 elements)
-    const void *pq = static_cast<const char *>(a.q) + (int64_t)bi * a.S * a.D * ES;
-    const void *pk = static_cast<const char *>(a.k) + (int64_t)bi * T * a.D * ES;
-    const void *pv = static_cast<const char *>(a.v) + (int64_t)bi * T * a.DV * ES;
+    const void *pq, *pk, *pv;
+    int q_row, k_row, v_row;  // the stride of the dimension a piece does not walk
+    [[maybe_unused]] bool fix_q = false, fix_k = false, fix_v = false;
+    [[maybe_unused]] uint32_t o_base = 0;
+    if constexpr (LAYOUT) {
+        // (wave-uniform, in scalar registers; validated: every operand's largest index fits 31 bits)
+        const uint32_t i0 = bi / (uint32_t)a.lay.heads, i1 = bi - i0 * (uint32_t)a.lay.heads;
+        pq = static_cast<const E *>(a.q) + (i0 * (uint32_t)a.lay.q_outer + i1 * (uint32_t)a.lay.q_head);
+        pk = static_cast<const E *>(a.k) + (i0 * (uint32_t)a.lay.k_outer + i1 * (uint32_t)a.lay.k_head);
+        pv = static_cast<const E *>(a.v) + (i0 * (uint32_t)a.lay.v_outer + i1 * (uint32_t)a.lay.v_head);
+        o_base = i0 * (uint32_t)a.lay.o_outer + i1 * (uint32_t)a.lay.o_head;
+        q_row = a.lay.q_row, k_row = a.lay.k_row, v_row = a.lay.v_row;
+        if constexpr (F16) {
+            fix_q = a.lay.moved & ATT_MOVED_Q, fix_k = a.lay.moved & ATT_MOVED_K, fix_v = a.lay.moved & ATT_MOVED_V;
+        }
+    } else {
+        pq = static_cast<const char *>(a.q) + (int64_t)bi * a.S * a.D * ES;
+        pk = static_cast<const char *>(a.k) + (int64_t)bi * T * a.D * ES;
+        pv = static_cast<const char *>(a.v) + (int64_t)bi * T * a.DV * ES;
+        q_row = a.D, k_row = a.D, v_row = a.DV;
+    }
 
     // ---- scores = Q K^T, stored as matmul_mfma stores them, then the multiply -------------------------------------------------
     for (int n0 = 0; n0 < T; n0 += ATT_KEYS) {
@@ -136,13 +191,17 @@ __global__ __launch_bounds__(1024) void attention_mfma_kernel(typename std::cond
         uint4 vq = make_uint4(0u, 0u, 0u, 0u), vk0 = vq, vk1 = vq;
         [[maybe_unused]] E bv[16];  // BIAS: the lane's sixteen bias elements
         if constexpr (BIAS && BIAS_EARLY) att_bias_load<E>(bv, a, bi, m0, n0 + wave * 32 + fr, fh, active);
-        if (tid < 4 * ATT_ROWS) vq = mm_piece<F16>(pq, a.D, m0, a.S, 0, a.D, 1, a.q_vec, tid);
+        if (tid < 4 * ATT_ROWS) vq = mm_piece<F16>(pq, q_row, m0, a.S, 0, a.D, 1, a.q_vec, tid);
         if (mover) {
-            vk0 = mm_piece<F16>(pk, a.D, n0, T, 0, a.D, 1, a.k_vec, tid);
-            vk1 = mm_piece<F16>(pk, a.D, n0 + MM_T, T, 0, a.D, 1, a.k_vec, tid);
+            vk0 = mm_piece<F16>(pk, k_row, n0, T, 0, a.D, 1, a.k_vec, tid);
+            vk1 = mm_piece<F16>(pk, k_row, n0 + MM_T, T, 0, a.D, 1, a.k_vec, tid);
         }
         for (int k0 = 0; k0 < a.D; k0 += KS) {
             __syncthreads();  // the previous slab's fragments were read
+            if constexpr (LAYOUT && F16) {  // (between mm_piece and mm_put: the operand as its movers would have left it)
+                if (fix_q) vq = att_moved(vq);
+                if (fix_k) vk0 = att_moved(vk0), vk1 = att_moved(vk1);
+            }
             if (tid < 4 * ATT_ROWS) mm_put<F16>(lds_q, vq, 1, tid);
             if (mover) {
                 mm_put<F16>(lds_kv, vk0, 1, tid);
@@ -150,9 +209,9 @@ __global__ __launch_bounds__(1024) void attention_mfma_kernel(typename std::cond
             }
             __syncthreads();
             if (mover && k0 + KS < a.D) {  // the next slab's pieces travel while this slab's MFMAs run
-                if (tid < 4 * ATT_ROWS) vq = mm_piece<F16>(pq, a.D, m0, a.S, k0 + KS, a.D, 1, a.q_vec, tid);
-                vk0 = mm_piece<F16>(pk, a.D, n0, T, k0 + KS, a.D, 1, a.k_vec, tid);
-                vk1 = mm_piece<F16>(pk, a.D, n0 + MM_T, T, k0 + KS, a.D, 1, a.k_vec, tid);
+                if (tid < 4 * ATT_ROWS) vq = mm_piece<F16>(pq, q_row, m0, a.S, k0 + KS, a.D, 1, a.q_vec, tid);
+                vk0 = mm_piece<F16>(pk, k_row, n0, T, k0 + KS, a.D, 1, a.k_vec, tid);
+                vk1 = mm_piece<F16>(pk, k_row, n0 + MM_T, T, k0 + KS, a.D, 1, a.k_vec, tid);
             }
             if (!active) continue;
 #pragma unroll
@@ -265,19 +324,22 @@ __global__ __launch_bounds__(1024) void attention_mfma_kernel(typename std::cond
         int32_t rs = 0, cs = 0;
         uint4 vv0 = make_uint4(0u, 0u, 0u, 0u), vv1 = vv0;
         if (mover) {
-            vv0 = mm_piece<F16>(pv, a.DV, c0, a.DV, 0, T, 0, a.v_vec, tid);
-            vv1 = mm_piece<F16>(pv, a.DV, c0 + MM_T, a.DV, 0, T, 0, a.v_vec, tid);
+            vv0 = mm_piece<F16>(pv, v_row, c0, a.DV, 0, T, 0, a.v_vec, tid);
+            vv1 = mm_piece<F16>(pv, v_row, c0 + MM_T, a.DV, 0, T, 0, a.v_vec, tid);
         }
         for (int k0 = 0; k0 < T; k0 += KS) {
             __syncthreads();  // the previous slab's fragments were read (first slab: every wave's probabilities are written)
+            if constexpr (LAYOUT && F16) {
+                if (fix_v) vv0 = att_moved(vv0), vv1 = att_moved(vv1);
+            }
             if (mover) {
                 mm_put<F16>(lds_kv, vv0, 0, tid);
                 mm_put<F16>(lds_kv + MM_T * MM_PITCH, vv1, 0, tid);
             }
             __syncthreads();
             if (mover && k0 + KS < T) {
-                vv0 = mm_piece<F16>(pv, a.DV, c0, a.DV, k0 + KS, T, 0, a.v_vec, tid);
-                vv1 = mm_piece<F16>(pv, a.DV, c0 + MM_T, a.DV, k0 + KS, T, 0, a.v_vec, tid);
+                vv0 = mm_piece<F16>(pv, v_row, c0, a.DV, k0 + KS, T, 0, a.v_vec, tid);
+                vv1 = mm_piece<F16>(pv, v_row, c0 + MM_T, a.DV, k0 + KS, T, 0, a.v_vec, tid);
             }
             if (!active) continue;
 #pragma unroll
@@ -310,7 +372,12 @@ __global__ __launch_bounds__(1024) void attention_mfma_kernel(typename std::cond
             const int row = (r & 3) + 8 * (r >> 2) + 4 * fh;
             const int m = m0 + row;
             if (!mover || m >= a.S || n >= a.DV) continue;
-            const int64_t o = ((int64_t)bi * a.S + m) * a.DV + n;
+            // LAYOUT: the movers behind the core would change nothing of what is stored here -- mm_value<true> gives a NaN as
+            // 0x7FFF / 0xFFFF and float_to_f16_bits_ref saturates everything else to at most 0x7BFF in magnitude, and
+            // move_fix_f16x2 leaves exactly those halves alone --, so the output's moved bit needs no work
+            int64_t o;
+            if constexpr (LAYOUT) o = (int64_t)(o_base + (uint32_t)m * (uint32_t)a.lay.o_row + (uint32_t)n);
+            else o = ((int64_t)bi * a.S + m) * a.DV + n;
             if constexpr (F16) {
                 static_cast<uint16_t *>(a.out)[o] = (uint16_t)mm_value<true>(acc[r], a.o_so, a.o_zo, a.o_inv, a.o_div);
             } else {
@@ -391,6 +458,22 @@ static int attention_enqueue(void (*kernel)(Args), LdsOptIn &opted_in, const Arg
     return SHL_MI355X_OK;
 }
 
+// the biased launches' further arguments, behind attention_args
+static void attention_bias_args(const void *bias_dev, const shl_mi355x_attention_desc *d, const shl_mi355x_attention_bias_desc *bd,
+                                AttBiasArgs &a)
+{
+    // the add's as bcast_launch sets them: a the (scaled) scores, b the bias; the softmax then reads the sum's record.  add_rec
+    // is the one rule that picks the int8 division for shl_mi355x_add_bcast as well
+    a.bias = bias_dev;
+    a.add = add_rec(a.x_si, d->has_scale ? d->sc_zp : d->s_zp, bd->b_scale, bd->b_zp, bd->sb_scale, bd->sb_zp);
+    a.x_si = bd->sb_scale, a.x_zi = (float)bd->sb_zp;
+    a.bias_first = bd->bias_is_first;
+    // (a stride along an extent of 1 is never used: att_bias_last has bounded the others)
+    a.b_ext1 = bd->b_ext1;
+    a.b_stride0 = d->batches / bd->b_ext1 > 1 ? (int32_t)bd->b_stride[0] : 0, a.b_stride1 = bd->b_ext1 > 1 ? (int32_t)bd->b_stride[1] : 0;
+    a.row_stride = d->s > 1 ? (int32_t)bd->row_stride : 0, a.key_stride = d->t > 1 ? (int32_t)bd->key_stride : 0;
+}
+
 // NULL, or why the biased call is refused; *code: the status that goes with it
 static const char *attention_bias_refusal(const void *q, const void *k, const void *v, const void *bias, const void *out,
                                           const shl_mi355x_attention_desc *d, const shl_mi355x_attention_bias_desc *bd, int *code)
@@ -420,7 +503,7 @@ extern "C" int shl_mi355x_attention(const void *q_dev, const void *k_dev, const 
     attention_args(q_dev, k_dev, v_dev, out_dev, d, a, &waves);
     static LdsOptIn opted_in[2];
     const bool f16 = d->dtype == SHL_MI355X_F16;
-    return attention_enqueue(f16 ? attention_mfma_kernel<true, false> : attention_mfma_kernel<false, false>, opted_in[f16], a, waves, stream);
+    return attention_enqueue(f16 ? attention_mfma_kernel<true, false, false> : attention_mfma_kernel<false, false, false>, opted_in[f16], a, waves, stream);
 }
 
 extern "C" const char *shl_mi355x_attention_bias_kernel_name(const void *q_dev, const void *k_dev, const void *v_dev, const void *bias_dev,
@@ -463,17 +546,109 @@ extern "C" int shl_mi355x_attention_bias(const void *q_dev, const void *k_dev, c
     memset(&a, 0, sizeof(a));
     int waves;
     attention_args(q_dev, k_dev, v_dev, out_dev, d, a, &waves);
-    // the add's as bcast_launch sets them: a the (scaled) scores, b the bias; the softmax then reads the sum's record.  add_rec
-    // is the one rule that picks the int8 division for shl_mi355x_add_bcast as well
-    a.bias = bias_dev;
-    a.add = add_rec(a.x_si, d->has_scale ? d->sc_zp : d->s_zp, bd->b_scale, bd->b_zp, bd->sb_scale, bd->sb_zp);
-    a.x_si = bd->sb_scale, a.x_zi = (float)bd->sb_zp;
-    a.bias_first = bd->bias_is_first;
-    // (a stride along an extent of 1 is never used: att_bias_last has bounded the others)
-    a.b_ext1 = bd->b_ext1;
-    a.b_stride0 = d->batches / bd->b_ext1 > 1 ? (int32_t)bd->b_stride[0] : 0, a.b_stride1 = bd->b_ext1 > 1 ? (int32_t)bd->b_stride[1] : 0;
-    a.row_stride = d->s > 1 ? (int32_t)bd->row_stride : 0, a.key_stride = d->t > 1 ? (int32_t)bd->key_stride : 0;
+    attention_bias_args(bias_dev, d, bd, a);
     static LdsOptIn opted_in[2];
     const bool f16 = d->dtype == SHL_MI355X_F16;
-    return attention_enqueue(f16 ? attention_mfma_kernel<true, true> : attention_mfma_kernel<false, true>, opted_in[f16], a, waves, stream);
+    return attention_enqueue(f16 ? attention_mfma_kernel<true, true, false> : attention_mfma_kernel<false, true, false>, opted_in[f16], a, waves, stream);
+}
+
+// ---- the layout form: the operands where the projections left them (shl_mi355x_attention_layout) ------------------------------
+namespace shl {
+
+// NULL, or why the layout call is refused; *code: the status that goes with it
+static const char *attention_layout_refusal(const void *q, const void *k, const void *v, const void *bias, const void *out,
+                                            const shl_mi355x_attention_desc *d, const shl_mi355x_attention_bias_desc *bd,
+                                            const shl_mi355x_attention_layout_desc *ld, int *code)
+{
+    *code = SHL_MI355X_EINVAL;
+    const char *why = att_layout_validate(q, k, v, bias, out, d, bd, ld);
+    if (why) return why;
+    *code = SHL_MI355X_ENOTSUP;
+    return att_unsupported(d);
+}
+
+static void attention_layout_args(const void *q_dev, const void *k_dev, const void *v_dev, const shl_mi355x_attention_desc *d,
+                                  const shl_mi355x_attention_layout_desc *ld, AttArgs &a, AttLayoutPart &lay)
+{
+    const int64_t es = d->dtype == SHL_MI355X_F16 ? 2 : 1;
+    const int64_t ext_q[3] = {d->batches / ld->heads, ld->heads, d->s}, ext_kv[3] = {d->batches / ld->heads, ld->heads, d->t};
+    a.q_vec = att_vec_layout(q_dev, ld->q_stride, ext_q, d->d, es), a.k_vec = att_vec_layout(k_dev, ld->k_stride, ext_kv, d->d, es);
+    a.v_vec = att_vec_layout(v_dev, ld->v_stride, ext_kv, d->dv, es);
+    lay.heads = ld->heads, lay.moved = ld->moved;
+    lay.q_outer = ld->q_stride[0], lay.q_head = ld->q_stride[1], lay.q_row = ld->q_stride[2];
+    lay.k_outer = ld->k_stride[0], lay.k_head = ld->k_stride[1], lay.k_row = ld->k_stride[2];
+    lay.v_outer = ld->v_stride[0], lay.v_head = ld->v_stride[1], lay.v_row = ld->v_stride[2];
+    lay.o_outer = ld->out_stride[0], lay.o_head = ld->out_stride[1], lay.o_row = ld->out_stride[2];
+}
+
+}  // namespace shl
+
+extern "C" const char *shl_mi355x_attention_layout_kernel_name(const void *q_dev, const void *k_dev, const void *v_dev, const void *bias_dev,
+                                                               const void *out_dev, const struct shl_mi355x_attention_desc *d,
+                                                               const struct shl_mi355x_attention_bias_desc *bd,
+                                                               const struct shl_mi355x_attention_layout_desc *ld)
+{
+    int code;
+    if (shl::attention_layout_refusal(q_dev, k_dev, v_dev, bias_dev, out_dev, d, bd, ld, &code)) return "";
+    return bias_dev ? SHL_MI355X_ATTENTION_BIAS_LAYOUT_MFMA : SHL_MI355X_ATTENTION_LAYOUT_MFMA;
+}
+
+extern "C" int shl_mi355x_attention_layout_by_default(const void *q_dev, const void *k_dev, const void *v_dev, const void *bias_dev,
+                                                      const void *out_dev, const struct shl_mi355x_attention_desc *d,
+                                                      const struct shl_mi355x_attention_bias_desc *bd,
+                                                      const struct shl_mi355x_attention_layout_desc *ld)
+{
+    int code;
+    return !shl::attention_layout_refusal(q_dev, k_dev, v_dev, bias_dev, out_dev, d, bd, ld, &code) && shl::att_layout_default(d, ld) ? 1 : 0;
+}
+
+extern "C" int shl_mi355x_attention_layout_strides(const int32_t *src_dim, int32_t src_rank, int32_t nsteps, const int32_t *step_is_transpose,
+                                                   const int32_t *step_rank, const int32_t *step_v, int32_t swap_last2, int32_t *batches,
+                                                   int32_t *rows, int32_t *cols, int32_t *heads, int32_t stride[3])
+{
+    using namespace shl;
+    constexpr int MAX_STEPS = 8;
+    AttViewStep step[MAX_STEPS];
+    int rc = 1;
+    if (nsteps >= 0 && nsteps <= MAX_STEPS && (nsteps == 0 || (step_is_transpose && step_rank && step_v))) {
+        for (int i = 0; i < nsteps; ++i) {
+            step[i].is_transpose = step_is_transpose[i], step[i].rank = step_rank[i];
+            for (int j = 0; j < SHL_MI355X_MAX_DIM; ++j) step[i].v[j] = j < step_rank[i] ? step_v[i * SHL_MI355X_MAX_DIM + j] : 0;
+        }
+        rc = att_layout_strides(src_dim, src_rank, step, nsteps, swap_last2, batches, rows, cols, heads, stride);
+    }
+    if (rc == 1) set_error("attention_layout_strides: the arguments describe no view of the source");
+    if (rc == 2) set_error("attention_layout_strides: a view that outer, head and row strides cannot express");
+    return rc == 0 ? SHL_MI355X_OK : rc == 1 ? SHL_MI355X_EINVAL : SHL_MI355X_ENOTSUP;
+}
+
+extern "C" int shl_mi355x_attention_layout(const void *q_dev, const void *k_dev, const void *v_dev, const void *bias_dev, void *out_dev,
+                                           const struct shl_mi355x_attention_desc *d, const struct shl_mi355x_attention_bias_desc *bd,
+                                           const struct shl_mi355x_attention_layout_desc *ld, void *stream)
+{
+    using namespace shl;
+    int code;
+    const char *why = attention_layout_refusal(q_dev, k_dev, v_dev, bias_dev, out_dev, d, bd, ld, &code);
+    if (why) {
+        set_error("attention_layout: %s", why);
+        return code;
+    }
+    const bool f16 = d->dtype == SHL_MI355X_F16;
+    int waves;
+    static LdsOptIn opted_in[4];
+    if (!bias_dev) {
+        AttLayoutArgs a;
+        memset(&a, 0, sizeof(a));
+        attention_args(q_dev, k_dev, v_dev, out_dev, d, a, &waves);
+        attention_layout_args(q_dev, k_dev, v_dev, d, ld, a, a.lay);
+        return attention_enqueue(f16 ? attention_mfma_kernel<true, false, true> : attention_mfma_kernel<false, false, true>, opted_in[f16], a,
+                                 waves, stream);
+    }
+    AttBiasLayoutArgs a;
+    memset(&a, 0, sizeof(a));
+    attention_args(q_dev, k_dev, v_dev, out_dev, d, a, &waves);
+    attention_bias_args(bias_dev, d, bd, a);
+    attention_layout_args(q_dev, k_dev, v_dev, d, ld, a, a.lay);
+    return attention_enqueue(f16 ? attention_mfma_kernel<true, true, true> : attention_mfma_kernel<false, true, true>, opted_in[2 + f16], a,
+                             waves, stream);
 }

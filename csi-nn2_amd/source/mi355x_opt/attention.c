@@ -141,3 +141,16 @@ int shl_mi355x_attention_forward(const struct shl_mi355x_attention_desc *d, cons
     }
     return CSINN_TRUE;
 }
+
+/* the same chains on operands where the projections left them (bd NULL: without a bias) */
+int shl_mi355x_attention_layout_forward(const struct shl_mi355x_attention_desc *d, const struct shl_mi355x_attention_bias_desc *bd,
+                                        const struct shl_mi355x_attention_layout_desc *ld, const void *q_dev, const void *k_dev,
+                                        const void *v_dev, const void *bias_dev, void *out_dev, void *stream)
+{
+    int st = shl_mi355x_attention_layout(q_dev, k_dev, v_dev, bd ? bias_dev : NULL, out_dev, d, bd, ld, stream);
+    if (st != SHL_MI355X_OK) {
+        shl_debug_error("mi355x: attention through strides failed (%d): %s\n", st, shl_mi355x_last_error());
+        return CSINN_FALSE;
+    }
+    return CSINN_TRUE;
+}

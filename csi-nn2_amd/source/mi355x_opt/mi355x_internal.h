@@ -185,6 +185,10 @@ int shl_mi355x_attention_bias_prepare(struct csinn_tensor *in0, struct csinn_ten
 int shl_mi355x_attention_bias_forward(const struct shl_mi355x_attention_desc *d, const struct shl_mi355x_attention_bias_desc *bd,
                                       const void *q_dev, const void *k_dev, const void *v_dev, const void *bias_dev, void *out_dev,
                                       void *stream);
+/* ... and either chain on operands where the projections left them (shl_mi355x_attention_layout; bd NULL: without a bias) */
+int shl_mi355x_attention_layout_forward(const struct shl_mi355x_attention_desc *d, const struct shl_mi355x_attention_bias_desc *bd,
+                                        const struct shl_mi355x_attention_layout_desc *ld, const void *q_dev, const void *k_dev,
+                                        const void *v_dev, const void *bias_dev, void *out_dev, void *stream);
 int shl_mi355x_concat_perf(struct csinn_tensor **input, struct csinn_tensor *output, struct csinn_concat_params *params,
                            struct csinn_perf_info *info);
 int shl_mi355x_split_init(struct csinn_tensor *input, struct csinn_tensor **output, struct csinn_split_params *params);

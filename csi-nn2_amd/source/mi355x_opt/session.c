@@ -19,6 +19,7 @@
  * shl_gref.h (include/shl_gref.h), so the same code walks graphs built by the genuine
  * libshl's gref or by this repository's stand-in.
  */
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -56,6 +57,8 @@ struct step {
     struct shl_node *out; /* the tensor node the step finally writes (a split: the first of them) */
     uint8_t lut[256];     /* STEP_CONV_LUT: the table of b (and c), built at plan time from the layers' records */
     int e;                /* STEP_ATTENTION only: the chain's fifth layer, -1 when it has four or three */
+    int fold[4];          /* STEP_ATTENTION only: the reshape / transpose layers in front of q, k, v and behind the output that the
+                           * launch stands for (shl_mi355x_attention_layout); all 0: the dense launch */
 };
 
 struct dev_session {
@@ -73,6 +76,7 @@ struct dev_session {
     int nlinear; /* matmul layers that add the constant bias behind them in their own launch */
     int nattention; /* Q K^T -> [scale] -> [+ bias] -> softmax -> P V chains that run as one launch */
     int nattention_bias; /* ... those of them with the add of a bias or mask */
+    int nhead_moves; /* reshape / transpose layers around attention cores that those launches read and write through strides */
     int nresidual; /* convolution -> add -> [relu | relu6] tails of skip connections that run as one launch */
     int nactivation; /* table activations (gates included) that run inside their convolution's launch */
     struct dev_session *next;
@@ -228,9 +232,10 @@ static int linear_bias_input(struct shl_node *a, struct shl_node *b, struct shl_
  * shape or, unless `force`, the shape is none it was measured faster on (shl_mi355x_attention_by_default, with the add
  * shl_mi355x_attention_bias_by_default).  A mul BEHIND the add is no part of the chain */
 static int attention_chain(struct shl_ref_graph *g, const int *layers, int n, int force, struct shl_mi355x_attention_desc *d,
-                           struct shl_mi355x_attention_bias_desc *bd, struct shl_node **bias)
+                           struct shl_mi355x_attention_bias_desc *bd, struct shl_node **bias, int *k_swapped)
 {
     *bias = NULL;
+    *k_swapped = 0;
     if (n < 3) return 0;
     struct shl_node *qk = g->layer[layers[0]];
     if (qk->type != CSINN_OP_MATMUL || session_op(qk) == NULL || qk->in_num != 2) return 0;
@@ -266,13 +271,157 @@ static int attention_chain(struct shl_ref_graph *g, const int *layers, int n, in
     struct csinn_tensor *tv = pv->in[1]->data;
     if (tv->is_const) return 0;
     struct csinn_softmax_params *sp = sm->data;
-    if (shl_mi355x_attention_prepare(tq, tk, qk->out[0]->data, qk->data, cst ? cst->data : NULL, sc ? sc->data : NULL, const_first,
+    /* K as ONNX exports it: [.., d, t] into a product without trans_b.  The chain is described as if K were [.., t, d] read with
+     * trans_b; the caller takes it only where the moves in front of K fold into strides (head_moves: swap_last2) */
+    struct csinn_matmul_params *qp = qk->data, qp_view;
+    struct csinn_tensor k_view;
+    if (!qp->trans_a && !qp->trans_b && tk->dim_count >= 2 && tk->dim_count <= MAX_DIM) {
+        k_view = *tk;
+        k_view.dim[tk->dim_count - 2] = tk->dim[tk->dim_count - 1], k_view.dim[tk->dim_count - 1] = tk->dim[tk->dim_count - 2];
+        qp_view = *qp;
+        qp_view.trans_b = true;
+        tk = &k_view, qp = &qp_view;
+        *k_swapped = 1;
+    }
+    if (shl_mi355x_attention_prepare(tq, tk, qk->out[0]->data, qp, cst ? cst->data : NULL, sc ? sc->data : NULL, const_first,
                                      p->data, sp->axis, tv, pv->out[0]->data, pv->data, force || add != NULL, d) != CSINN_TRUE)
         return 0;
     /* (with the add the default is the biased launch's own) */
     if (add != NULL && shl_mi355x_attention_bias_prepare(add->in[0]->data, add->in[1]->data, add->out[0]->data, x->data, d, force, bd) != CSINN_TRUE)
         return 0;
     return at + 2;
+}
+
+static int one_record_i8(const struct csinn_tensor *t);
+static int one_record_f16(const struct csinn_tensor *t);
+
+/* ---- the head split and merge moves around an attention core (shl_mi355x_attention_layout) ------------------------------------- */
+#define FOLD_MAX 4 /* layers of one run */
+
+/* a reshape or a transpose that this backend runs and that copies its elements unchanged by the movers' own rule: int8 under
+ * equal records whose requantisation is the identity on all 256 values (csrc/requant_move.h:move_rec chooses MOVE_RAW where the
+ * form may copy, and the other modes give the same bytes then); binary16 at scale 1 on both sides, where the movers change
+ * infinities and NaNs only -- the launch applies that rule to an operand whose `moved` bit is set */
+static int pure_move(struct shl_node *n)
+{
+    if ((n->type != CSINN_OP_RESHAPE && n->type != CSINN_OP_TRANSPOSE) || session_op(n) == NULL || n->in_num != 1 || n->out_num != 1) return 0;
+    const struct csinn_tensor *in = n->in[0]->data, *out = n->out[0]->data;
+    if (in->is_const || in->dtype != out->dtype || in->dim_count < 1 || in->dim_count > MAX_DIM || out->dim_count < 1 || out->dim_count > MAX_DIM)
+        return 0;
+    if (one_record_f16(in)) return one_record_f16(out);
+    if (!one_record_i8(in) || !one_record_i8(out)) return 0;
+    const float s = in->qinfo->scale, z = (float)in->qinfo->zero_point;
+    if (in->qinfo->zero_point != out->qinfo->zero_point || memcmp(&in->qinfo->scale, &out->qinfo->scale, sizeof(float)) != 0) return 0;
+    for (int q = -128; q < 128; q++) { /* (csrc/pool2d.hip:requant_is_identity) */
+        const float x = ((float)q - z) * s; /* (this file is compiled without contraction) */
+        float r = rintf(x / s) + z;
+        r = r > 127.0f ? 127.0f : r;
+        r = r < -128.0f ? -128.0f : r;
+        if (!(r == r) || (int)r != q) return 0;
+    }
+    return 1;
+}
+
+/* The run of pure moves, with at most one transpose among them, that ends in `x` (out = 0: the layers that make x, each read by
+ * exactly one consumer and no graph output) or starts from it (out = 1: the layers that consume x and each other).  want > 0: a
+ * run of exactly that many layers (the plan has decided), else the longest the strides express.  Returns the run's length, its
+ * layers in graph order in `run`, the tensor at its far end in *far (the source the launch reads / the tensor it writes) and
+ * the view's heads and strides; 0 when nothing folds.  rows / cols / batches: what the view must come out as; swap: x is
+ * [.., cols, rows] (K without trans_b) */
+static int head_moves(struct shl_ref_graph *g, struct shl_node *x, int out, int swap, int want, int32_t batches, int32_t rows,
+                      int32_t cols, int *run, struct shl_node **far, int32_t *heads, int32_t stride[3])
+{
+    int seen[FOLD_MAX], n = 0, transposes = 0;
+    struct shl_node *cur = x;
+    while (n < FOLD_MAX) {
+        if (consumers_of(g, cur) != 1) break; /* (a graph output counts as a consumer) */
+        int at = -1;
+        for (int k = 0; at < 0 && k < g->layer_index; k++) {
+            struct shl_node *l = g->layer[k];
+            if (out ? (l->in_num >= 1 && l->in[0] == cur) : (l->out_num == 1 && l->out[0] == cur)) at = k;
+        }
+        if (at < 0 || !pure_move(g->layer[at])) break;
+        if (g->layer[at]->type == CSINN_OP_TRANSPOSE && ++transposes > 1) break;
+        seen[n++] = at;
+        cur = out ? g->layer[at]->out[0] : g->layer[at]->in[0];
+    }
+    for (int len = want > 0 ? want : n; len >= 1 && len <= n; len--) {
+        /* the chain from the far end towards the core: for the output the destination and the layers inverted */
+        struct shl_node *end = out ? g->layer[seen[len - 1]]->out[0] : g->layer[seen[len - 1]]->in[0];
+        const struct csinn_tensor *te = end->data;
+        int32_t is_t[FOLD_MAX], rank[FOLD_MAX], v[FOLD_MAX * MAX_DIM];
+        int ok = 1;
+        memset(v, 0, sizeof(v));
+        for (int i = 0; ok && i < len; i++) {
+            struct shl_node *l = g->layer[seen[len - 1 - i]];
+            const struct csinn_tensor *to = out ? l->in[0]->data : l->out[0]->data; /* what the step makes */
+            is_t[i] = l->type == CSINN_OP_TRANSPOSE;
+            rank[i] = to->dim_count;
+            if (is_t[i]) {
+                const struct csinn_transpose_params *tp = l->data;
+                if (tp->permute_num != to->dim_count || tp->permute_num > MAX_DIM) ok = 0;
+                for (int k = 0; ok && k < tp->permute_num; k++) {
+                    if (tp->permute[k] < 0 || tp->permute[k] >= tp->permute_num) ok = 0;
+                    else if (out) v[i * MAX_DIM + tp->permute[k]] = k; /* the inverse permutation */
+                    else v[i * MAX_DIM + k] = tp->permute[k];
+                }
+            } else {
+                for (int k = 0; k < to->dim_count; k++) v[i * MAX_DIM + k] = to->dim[k];
+            }
+        }
+        int32_t b, r, c;
+        if (ok && !te->is_const &&
+            shl_mi355x_attention_layout_strides(te->dim, te->dim_count, len, is_t, rank, v, swap, &b, &r, &c, heads, stride) == SHL_MI355X_OK &&
+            b == batches && r == rows && c == cols) {
+            for (int i = 0; i < len; i++) run[i] = seen[out ? i : len - 1 - i];
+            *far = end;
+            return len;
+        }
+        if (want > 0) break;
+    }
+    return 0;
+}
+
+/* The layout descriptor of a chain attention_chain has described (layers, len, *d; k_swapped: its K is [.., d, t]): which moves
+ * around it fold (want: NULL for the longest runs, else the counts the plan stored), the tensors the launch then reads and
+ * writes (src[0..2], *dst; the chain's own where a side does not fold) and *ld.  Each side folds or stays on its own; sides
+ * whose views split the batch index differently cannot share `heads`, and the later of them stays.  Returns the layers folded */
+static int attention_layout(struct shl_ref_graph *g, const int *layers, int len, const struct shl_mi355x_attention_desc *d, int k_swapped,
+                            const int *want, int fold[4], int runs[4][FOLD_MAX], struct shl_node *src[3], struct shl_node **dst,
+                            struct shl_mi355x_attention_layout_desc *ld)
+{
+    struct shl_node *qk = g->layer[layers[0]], *pv = g->layer[layers[len - 1]];
+    struct shl_node *x[4] = {qk->in[0], qk->in[1], pv->in[1], pv->out[0]};
+    const int32_t rows[4] = {d->s, d->t, d->t, d->s}, cols[4] = {d->d, d->d, d->dv, d->dv};
+    int32_t *const st[4] = {ld->q_stride, ld->k_stride, ld->v_stride, ld->out_stride};
+    int32_t heads[4];
+    int total = 0;
+    memset(ld, 0, sizeof(*ld));
+    ld->heads = d->batches;
+    for (int i = 0; i < 4; i++) {
+        struct shl_node *far = x[i];
+        fold[i] = want != NULL && want[i] == 0 ? 0
+                                                : head_moves(g, x[i], i == 3, i == 1 && k_swapped, want ? want[i] : 0, d->batches, rows[i], cols[i],
+                                                             runs[i], &far, &heads[i], st[i]);
+        if (fold[i] > 0 && heads[i] != d->batches) { /* two pieces: the split every other side must share */
+            if (ld->heads == d->batches) ld->heads = heads[i];
+            else if (ld->heads != heads[i]) fold[i] = 0, far = x[i];
+        }
+        if (fold[i] == 0) heads[i] = d->batches, st[i][0] = 0, st[i][1] = rows[i] * cols[i], st[i][2] = cols[i]; /* dense */
+        if (i < 3) src[i] = far;
+        else *dst = far;
+        total += fold[i];
+    }
+    if (want != NULL)
+        for (int i = 0; i < 4; i++)
+            if (fold[i] != want[i]) return -1;
+    /* one piece (heads = batches: the index is bi * head) is two pieces under any split */
+    for (int i = 0; i < 4; i++)
+        if (heads[i] == d->batches && ld->heads != d->batches) st[i][0] = ld->heads * st[i][1];
+    /* (an int8 mover under these records copies bytes; a binary16 one applies its rule for infinities and NaNs) */
+    for (int i = 0; i < 4; i++)
+        if (fold[i] > 0) ld->moved |= 1 << i;
+    return total;
 }
 
 static int one_record_i8(const struct csinn_tensor *t)
@@ -503,18 +652,53 @@ static int plan_fusion(struct dev_session *ds, struct shl_ref_graph *g)
     /* SHL_MI355X_ACT_FUSE likewise, for the table activations */
     const char *af = getenv("SHL_MI355X_ACT_FUSE");
     const int act_fuse = !fold || (af && af[0] == '0') ? 0 : (af && af[0] == '1') ? 2 : 1;
+    /* SHL_MI355X_ATTENTION_LAYOUT likewise, for the reshape / transpose runs around a merged core: "0" folds none, "1" every run
+     * the kernel takes, unset the classes one layout launch was measured faster on (shl_mi355x_attention_layout_by_default) --
+     * unset, a core the dense default leaves apart merges too when all four sides fold and its class was measured faster */
+    const char *lay = getenv("SHL_MI355X_ATTENTION_LAYOUT");
+    const int layout = !attention || (lay && lay[0] == '0') ? 0 : (lay && lay[0] == '1') ? 2 : 1;
+    char *gone = calloc((size_t)g->layer_index + 1, 1); /* layers an attention launch stands for */
+    if (gone == NULL) return 0;
     for (int k = 0; k < ns; k++) {
         struct step s = steps[k];
+        if (s.kind == STEP_LAYER && gone[s.a]) continue; /* a move behind a core that took it */
         /* the core of an attention block first: its matmuls then are no longer candidates for a pair */
         int chain[5] = {-1, -1, -1, -1, -1}, avail = 0;
         for (; avail < 5 && k + avail < ns; avail++) chain[avail] = steps[k + avail].a;
         struct shl_mi355x_attention_desc ad;
         struct shl_mi355x_attention_bias_desc abd;
-        struct shl_node *bias = NULL;
-        const int taken = attention ? attention_chain(g, chain, avail, force, &ad, &abd, &bias) : 0;
+        struct shl_mi355x_attention_layout_desc ld;
+        struct shl_node *bias = NULL, *src[3], *dst = NULL;
+        int k_swapped = 0, fold4[4] = {0, 0, 0, 0}, runs[4][FOLD_MAX], folded = 0;
+        int taken = attention ? attention_chain(g, chain, avail, force, &ad, &abd, &bias, &k_swapped) : 0;
+        int promoted = 0;
+        if (taken == 0 && layout == 1 && !force) { /* (with the moves on the scales the dense default's verdict may change) */
+            taken = attention_chain(g, chain, avail, 1, &ad, &abd, &bias, &k_swapped);
+            promoted = taken > 0;
+        }
+        if (taken > 0 && layout) {
+            folded = attention_layout(g, chain, taken, &ad, k_swapped, NULL, fold4, runs, src, &dst, &ld);
+            /* the last word belongs to the kernel's own rules, asked with made-up addresses that do not overlap */
+            const void *a0 = (const void *)((uintptr_t)1 << 56), *a1 = (const void *)((uintptr_t)1 << 57), *a2 = (const void *)((uintptr_t)1 << 58),
+                       *a3 = (const void *)((uintptr_t)1 << 59), *a4 = bias ? (const void *)((uintptr_t)1 << 60) : NULL;
+            const struct shl_mi355x_attention_bias_desc *pb = bias ? &abd : NULL;
+            if (folded > 0 && shl_mi355x_attention_layout_kernel_name(a0, a1, a2, a4, a3, &ad, pb, &ld)[0] == '\0') folded = 0;
+            if (folded > 0 && layout == 1 && !shl_mi355x_attention_layout_by_default(a0, a1, a2, a4, a3, &ad, pb, &ld)) folded = 0;
+            if (promoted && !(folded > 0 && fold4[0] && fold4[1] && fold4[2] && fold4[3])) folded = 0;
+        }
+        if ((promoted || k_swapped) && (folded <= 0 || (k_swapped && fold4[1] == 0))) taken = 0; /* the layers run one by one */
         if (taken > 0) {
             steps[ds->nsteps] = (struct step){STEP_ATTENTION, chain[0], chain[1], chain[2], taken >= 4 ? chain[3] : -1, steps[k + taken - 1].out};
-            steps[ds->nsteps++].e = taken == 5 ? chain[4] : -1;
+            steps[ds->nsteps].e = taken == 5 ? chain[4] : -1;
+            if (folded > 0) {
+                for (int i = 0; i < 4; i++) {
+                    steps[ds->nsteps].fold[i] = fold4[i];
+                    for (int j = 0; j < fold4[i]; j++) gone[runs[i][j]] = 1;
+                }
+                steps[ds->nsteps].out = dst;
+                ds->nhead_moves += folded;
+            }
+            ds->nsteps++;
             ds->nattention++;
             if (bias != NULL) ds->nattention_bias++;
             k += taken - 1; /* the chain's other steps are taken */
@@ -548,6 +732,14 @@ static int plan_fusion(struct dev_session *ds, struct shl_ref_graph *g)
         }
         steps[ds->nsteps++] = s;
     }
+    /* the moves in FRONT of a core were steps before the core was found: mark and compact.  (This relies on a reshape or a
+     * transpose never being part of a merged step -- no step kind above takes one --: a folded move inside a merged step would
+     * still run, and nhead_moves would count a layer that did) */
+    int kept = 0;
+    for (int k = 0; k < ds->nsteps; k++)
+        if (!(steps[k].kind == STEP_LAYER && gone[steps[k].a])) steps[kept++] = steps[k];
+    ds->nsteps = kept;
+    free(gone);
     return 1;
 }
 
@@ -633,8 +825,22 @@ static int enqueue_layers(struct dev_session *ds, struct shl_ref_graph *g)
                 struct shl_mi355x_attention_desc ad;
                 struct shl_mi355x_attention_bias_desc abd;
                 struct dev_tensor *kk = lookup(ds, n->in[1]), *v = lookup(ds, pv->in[1]);
-                if (!kk || !v || attention_chain(g, chain, len, 1, &ad, &abd, &bias) != len) { /* (the plan has decided) */
+                int k_swapped = 0;
+                if (!kk || !v || attention_chain(g, chain, len, 1, &ad, &abd, &bias, &k_swapped) != len) { /* (the plan has decided) */
                     rc = CSINN_FALSE;
+                } else if (s->fold[0] || s->fold[1] || s->fold[2] || s->fold[3]) { /* through strides: the sources' buffers, the last folded layer's output */
+                    struct shl_mi355x_attention_layout_desc ld;
+                    struct shl_node *src[3], *dst = NULL;
+                    int fold4[4], runs[4][FOLD_MAX];
+                    struct dev_tensor *b = bias ? lookup(ds, bias) : NULL, *sq, *sk, *sv;
+                    if (attention_layout(g, chain, len, &ad, k_swapped, s->fold, fold4, runs, src, &dst, &ld) <= 0 || dst != s->out ||
+                        (bias && !b) || !(sq = lookup(ds, src[0])) || !(sk = lookup(ds, src[1])) || !(sv = lookup(ds, src[2])))
+                        rc = CSINN_FALSE;
+                    else
+                        rc = shl_mi355x_attention_layout_forward(&ad, bias ? &abd : NULL, &ld, sq->dev, sk->dev, sv->dev, b ? b->dev : NULL,
+                                                                 out->dev, ds->stream);
+                } else if (k_swapped) {
+                    rc = CSINN_FALSE; /* (a K without trans_b is merged only with its moves folded) */
                 } else if (bias != NULL) { /* a constant bias is resident like any constant operand of an add */
                     struct dev_tensor *b = lookup(ds, bias);
                     rc = b ? shl_mi355x_attention_bias_forward(&ad, &abd, in->dev, kk->dev, v->dev, b->dev, out->dev, ds->stream) : CSINN_FALSE;
@@ -921,6 +1127,13 @@ int shl_mi355x_session_fused_attentions(struct csinn_session *sess)
 {
     struct dev_session *ds = find_session(sess);
     return ds ? ds->nattention : 0;
+}
+
+/* how many reshape / transpose layers around those cores run inside their launches (shl_mi355x_attention_layout) */
+int shl_mi355x_session_folded_head_moves(struct csinn_session *sess)
+{
+    struct dev_session *ds = find_session(sess);
+    return ds ? ds->nhead_moves : 0;
 }
 
 /* ... and how many of those carry the add of a bias or mask (shl_mi355x_attention_bias) */

@@ -911,6 +911,71 @@ struct shl_mi355x_mul_desc;
 int shl_mi355x_attention_bias_geometry(const struct shl_mi355x_mul_desc *m, int32_t batches, int32_t s, int32_t t,
                                        struct shl_mi355x_attention_bias_desc *bd);
 
+/* The same core -- with a bias (bias_dev and bd given) or without (both NULL) -- on operands where the projections left
+ * them: a model's q, k and v are [B, S, H D], split into heads by a reshape and a transpose(0,2,1,3) each, and the output is
+ * merged again by the inverse pair.  Those eight layers do no arithmetic; this launch reads and writes through strides
+ * instead.  `d` (and `bd`) are the descriptors above, unchanged: batches = B H.  For each of q, k, v and out the layout
+ * descriptor holds three strides in elements, {outer, head, row}: with the batch index bi = i0 * heads + i1, element
+ * (bi, row, col) of an operand is at
+ *     base[i0 * outer + i1 * head + row * row_stride + col],
+ * the innermost dim (d, d, dv, dv) keeps stride 1.  [B, S, H D] read as [B H][S][D] is {S H D, D, H D} with heads = H; the
+ * dense layout is {0, rows * inner, inner} with heads = batches.  Inputs may have any strides that are not negative -- 0, rows
+ * that overlap, q, k and v inside one packed [B, S, 3, H, D] projection.  The output's elements must be distinct (its four
+ * (extent, stride) pairs, sorted by stride, each stride at least the extent times the stride below it; extents of 1 do not
+ * count); gaps between them are allowed and are not written.
+ * `moved` (bit 0 q, 1 k, 2 v, 3 out) says which operands replace a chain of shl_mi355x_move / shl_mi355x_transpose.  Those
+ * are not the identity in binary16: an infinity arrives as +-65504, every NaN as 0x7FFF with its sign.  Where an input's bit
+ * is set the kernel applies that rule to what it loads, so that the launch equals the movers followed by the dense call for
+ * any bits; with the bit clear the operand is read raw, and the launch equals the dense call on a copy permuted by the
+ * host.  The output's bit changes nothing: a stored half is finite or one of those two NaNs already.  int8 operands are
+ * always read raw (a mover whose two records differ requantises: such a layer is not a layout).
+ * 16-byte loads serve an operand whose pointer is 16-byte aligned and whose inner extent and strides (those along an extent
+ * above 1) are multiples of 16 bytes; every other operand is read by elements.  The kernel, its LDS and its cap on t are shl_mi355x_attention's.
+ * SHL_MI355X_EINVAL before anything is enqueued: whatever the descriptor or the bias makes shl_mi355x_attention[_bias] refuse
+ * (the dense ranges aside: an operand's range here is that of its strides); a NULL layout descriptor; one of bias_dev and bd
+ * NULL and the other not; heads below 1 or not dividing batches; a negative stride; an operand whose largest index is 2^31 or
+ * more; moved bits beyond the four; non-zero reserved fields; output elements that overlap each other; the output's range
+ * overlapping an operand's or the bias's.  SHL_MI355X_ENOTSUP exactly where shl_mi355x_attention returns it.  Enqueues only:
+ * no allocation, no upload, no synchronisation (capturable in a hipGraph). */
+#define SHL_MI355X_ATTENTION_LAYOUT_MFMA "attention_layout_mfma"
+#define SHL_MI355X_ATTENTION_BIAS_LAYOUT_MFMA "attention_bias_layout_mfma"
+
+struct shl_mi355x_attention_layout_desc {
+    int32_t heads; /* the inner extent of the batch index: bi = i0 * heads + i1; divides batches */
+    int32_t moved; /* bit 0 q, 1 k, 2 v, 3 out: the operand stands for a chain of movers (binary16: their special-value rule) */
+    int32_t q_stride[3], k_stride[3], v_stride[3], out_stride[3]; /* {outer, head, row}, in elements */
+    int32_t reserved[2]; /* must be zero */
+};
+
+int shl_mi355x_attention_layout(const void *q_dev, const void *k_dev, const void *v_dev, const void *bias_dev, void *out_dev,
+                                const struct shl_mi355x_attention_desc *d, const struct shl_mi355x_attention_bias_desc *bd,
+                                const struct shl_mi355x_attention_layout_desc *ld, void *stream);
+/* "attention_layout_mfma", with a bias "attention_bias_layout_mfma", or "" for what the call refuses.  Pure host code */
+const char *shl_mi355x_attention_layout_kernel_name(const void *q_dev, const void *k_dev, const void *v_dev, const void *bias_dev,
+                                                    const void *out_dev, const struct shl_mi355x_attention_desc *d,
+                                                    const struct shl_mi355x_attention_bias_desc *bd,
+                                                    const struct shl_mi355x_attention_layout_desc *ld);
+/* 1 when the call names a kernel AND the shape belongs to a class in which one layout launch was measured faster, in int8
+ * and in binary16, than the eight mover launches and the core they surround (profiles/attention_layout_notes.md; dv = d:
+ * heads of 32 to 64 on 49 to 197 keys from 21 workgroups of 32 query rows on, and heads of at most 32 on at least 768 keys while the grid is at most 256 workgroups
+ * of 32 query rows): what a session folds without being asked.  Pure host code */
+int shl_mi355x_attention_layout_by_default(const void *q_dev, const void *k_dev, const void *v_dev, const void *bias_dev,
+                                           const void *out_dev, const struct shl_mi355x_attention_desc *d,
+                                           const struct shl_mi355x_attention_bias_desc *bd,
+                                           const struct shl_mi355x_attention_layout_desc *ld);
+/* The three strides of the [batches][rows][cols] view that a chain of movers makes of a dense tensor: src_dim[src_rank], then
+ * nsteps steps in order.  Step i has step_rank[i] values at step_v + i * SHL_MI355X_MAX_DIM: with step_is_transpose[i] the
+ * permutation (output dim k is input dim perm[k]; at most one step may be one), else a reshape's target dims.  swap_last2
+ * exchanges the last two dims of the result once more (a K that reaches Q K^T as [..][d][t] and is read without trans_b).  The
+ * last two dims are the rows and the columns, the product of the others is *batches; *heads and stride[3] = {outer, head, row}
+ * are the layout descriptor's.  For the output, describe the DESTINATION and the chain behind the core inverted.
+ * SHL_MI355X_OK; SHL_MI355X_EINVAL for arguments that describe no view; SHL_MI355X_ENOTSUP for a view the strides cannot
+ * express (an inner stride other than 1, rows or columns in more than one piece, batch dims in more than two).  Pure host
+ * code */
+int shl_mi355x_attention_layout_strides(const int32_t *src_dim, int32_t src_rank, int32_t nsteps, const int32_t *step_is_transpose,
+                                        const int32_t *step_rank, const int32_t *step_v, int32_t swap_last2, int32_t *batches,
+                                        int32_t *rows, int32_t *cols, int32_t *heads, int32_t stride[3]);
+
 /* nearest-neighbour / bilinear resize of a 4-d int8 / binary16 tensor: shl_ref_resize_quant
  * (source/reference/resize.c:464-468), bit for bit.  height_scale / width_scale are the reference's own floats, computed by
  * the CALLER as ONE float division each: (float)in / out, with align_corners (float)(in - 1) / (out - 1)

@@ -210,6 +210,17 @@ int shl_mi355x_session_fused_attentions(struct csinn_session *sess);
  * as well).  Their default is shl_mi355x_attention_bias_by_default; the switches are the same.  Operands of equal shape, a
  * bias that needs more than two groups of the batch dims, and a mul behind the add stay apart */
 int shl_mi355x_session_fused_attention_biases(struct csinn_session *sess);
+/* The reshape / transpose layers around those cores -- a model's head split in front of q, k and v (reshape [B,S,H,D],
+ * transpose(0,2,1,3); K also as transpose(0,2,3,1) into a product without trans_b) and the merge behind the output -- that run
+ * inside the core's launch, which reads the sources' buffers and writes the last folded layer's output through strides
+ * (shl_mi355x_attention_layout).  A run folds when every layer in it is this backend's, is read by one consumer and is no graph
+ * output (the last one behind the core may be read by any), copies its elements unchanged (int8: equal records whose
+ * requantisation is the identity; binary16: scale 1, with the movers' rule for infinities and NaNs applied by the launch), and the
+ * strides express the view; each of the four sides folds or stays on its own.  At setup SHL_MI355X_ATTENTION_LAYOUT=0 folds
+ * nothing, =1 every run the kernel takes around every chain that SHL_MI355X_ATTENTION lets merge; unset, the classes one layout
+ * launch was measured faster on (shl_mi355x_attention_layout_by_default) -- a core the dense default leaves apart then merges
+ * too when all four sides fold.  SHL_MI355X_ATTENTION=0 keeps everything apart */
+int shl_mi355x_session_folded_head_moves(struct csinn_session *sess);
 /* tails of skip connections of `sess` -- convolution -> add(conv_out, skip) -> [relu | relu6] -- that run as one launch of the
  * convolution (shl_mi355x_conv_add_forward; int8 NHWC implicit-GEMM plans, same-shape adds).  By default those of a shape class
  * the fused launch was measured faster on (shl_mi355x_conv_add_by_default); at setup SHL_MI355X_RESIDUAL=1 merges every tail the
