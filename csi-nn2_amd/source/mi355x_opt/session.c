@@ -20,6 +20,7 @@
  * libshl's gref or by this repository's stand-in.
  */
 #include <math.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -35,31 +36,40 @@ struct dev_tensor {
     int probe_dev;
 };
 
-/* one unit the session enqueues: a layer, or two layers (an attention core: three to five) that run as one launch.  A relu / relu6 layer folded into the
- * convolution in front of it is no step and no layer of a step: the convolution's step writes the activation's output */
-enum step_kind {
-    STEP_LAYER,     /* layer a, through its exec callback */
-    STEP_PWDW,      /* a pointwise and a depthwise layer, in either order (shl_mi355x_pwdw_forward) */
-    STEP_POOL_CONV, /* global_avgpool2d a + the convolution / fullyconnected layer b on the pooled map */
-    STEP_CONV_POOL, /* 1x1 convolution a + global_avgpool2d b */
-    STEP_MATMUL_BIAS, /* matmul a + the add b of a constant bias [N] to its output (shl_mi355x_matmul_bias) */
-    STEP_ATTENTION, /* matmul(q, k^T) a -> [mul by a constant] -> [add of a bias or mask] -> softmax -> matmul(p, v): b, c, d, e
-                     * (shl_mi355x_attention; with the add shl_mi355x_attention_bias) */
-    STEP_CONV_ADD,  /* convolution a -> same-shape add b of its output and a skip tensor -> [relu | relu6 c] (shl_mi355x_conv_add_forward) */
-    STEP_CONV_LUT,  /* convolution or depthwise layer a -> table activation b -> [mul c of a's output and b's: a swish / hard-swish
-                     * gate] (shl_mi355x_conv_lut_forward; a depthwise plan: shl_mi355x_dwconv_lut_forward) */
-};
+/* one unit the session enqueues: a plain layer through its exec callback, or the layers a rule of the planner's table (rules[],
+ * above plan_fusion) merged into one launch.  A relu / relu6 layer folded into the convolution in front of it is no step and no
+ * layer of a step: the convolution's step writes the activation's output.  A step carries all its launch needs: enqueue_layers
+ * looks up the device buffers of `src` and `out` and calls the rule's launch, nothing is matched again */
+#define STEP_LAYERS 5 /* the longest chain: an attention core with its mul and its add */
+#define STEP_SOURCES 4
+#define FOLD_MAX 4 /* layers of one run of moves around an attention core */
+struct rule;
 
 struct step {
-    enum step_kind kind;
-    int a, b, c, d;       /* layer indices in order; -1 from the first unused one on (STEP_LAYER: b, a pair: c).  STEP_CONV_ADD:
-                           * a, b, [c], and d = which of the add's operands (0 or 1) is the skip tensor */
-    struct shl_node *out; /* the tensor node the step finally writes (a split: the first of them) */
-    uint8_t lut[256];     /* STEP_CONV_LUT: the table of b (and c), built at plan time from the layers' records */
-    int e;                /* STEP_ATTENTION only: the chain's fifth layer, -1 when it has four or three */
-    int fold[4];          /* STEP_ATTENTION only: the reshape / transpose layers in front of q, k, v and behind the output that the
-                           * launch stands for (shl_mi355x_attention_layout); all 0: the dense launch */
+    const struct rule *rule; /* NULL: the plain layer layer[0] */
+    int layer[STEP_LAYERS], nlayers; /* the layers it stands for, in graph order (an attention step's folded moves are not among them) */
+    struct shl_node *out;    /* the tensor node the step finally writes (a split: the first of them) */
+    struct shl_node *src[STEP_SOURCES]; /* the tensor nodes the launch reads, NULL from the first unused one on.  [0]: the first
+                              * layer's input.  linear: the matmul's second operand, the bias.  residual: the skip tensor.
+                              * attention: q, k, v (behind folded moves: the tensors the moves read), the bias or NULL */
+    union {
+        uint8_t lut[256]; /* table: the activation (and the gate's mul), built from the layers' records */
+        int bias_at;      /* linear: which of the add's operands (0 or 1) is the bias */
+        struct {
+            int skip_at; /* which of the add's operands (0 or 1) is the skip tensor */
+            int act;     /* the activation behind the sum: 0 none, 1 relu, 2 relu6 */
+        } residual;
+        struct {
+            struct shl_mi355x_attention_desc ad;
+            struct shl_mi355x_attention_bias_desc abd; /* with src[3] */
+            struct shl_mi355x_attention_layout_desc ld; /* with a fold: the launch goes through strides */
+            int fold[4]; /* the reshape / transpose layers in front of q, k, v and behind the output that the launch stands
+                          * for (shl_mi355x_attention_layout); all 0: the dense launch */
+        } attention;
+    } u;
 };
+
+enum { R_ATTENTION, R_LINEAR, R_RESIDUAL, R_POOL_CONV, R_CONV_POOL, R_PAIR, R_TABLE, N_RULES }; /* rules[], in priority order */
 
 struct dev_session {
     struct csinn_session *sess;
@@ -71,14 +81,10 @@ struct dev_session {
     void *graph_exec;
     struct step *steps; /* what enqueue_layers runs, in order (plan_fusion); kept for the re-capture after a rebind */
     int nsteps;
-    int nfused, nfolded;
-    int npool; /* global_avgpool2d layers that run inside their consumer's launch */
-    int nlinear; /* matmul layers that add the constant bias behind them in their own launch */
-    int nattention; /* Q K^T -> [scale] -> [+ bias] -> softmax -> P V chains that run as one launch */
-    int nattention_bias; /* ... those of them with the add of a bias or mask */
-    int nhead_moves; /* reshape / transpose layers around attention cores that those launches read and write through strides */
-    int nresidual; /* convolution -> add -> [relu | relu6] tails of skip connections that run as one launch */
-    int nactivation; /* table activations (gates included) that run inside their convolution's launch */
+    int count[N_RULES];  /* steps of each rule */
+    int nfolded;         /* relu / relu6 layers that run in the epilogue of the convolution in front of them */
+    int nattention_bias; /* attention steps with the add of a bias or mask */
+    int nhead_moves;     /* reshape / transpose layers around attention cores that those launches read and write through strides */
     struct dev_session *next;
 };
 
@@ -198,6 +204,25 @@ static int consumers_of(struct shl_ref_graph *g, struct shl_node *tensor)
     return consumers;
 }
 
+static int one_record_i8(const struct csinn_tensor *t)
+{
+    return t->dtype == CSINN_DTYPE_INT8 && t->qinfo != NULL && t->quant_channel <= 1;
+}
+
+/* a binary16 tensor as the same-shape add and the relu layers take it: one record, scale 1 */
+static int one_record_f16(const struct csinn_tensor *t)
+{
+    return t->dtype == CSINN_DTYPE_FLOAT16 && t->qinfo != NULL && t->quant_channel <= 1 && t->qinfo->scale == 1.0f;
+}
+
+static int same_dims(const struct csinn_tensor *x, const struct csinn_tensor *y)
+{
+    if (x->dim_count != y->dim_count) return 0;
+    for (int i = 0; i < x->dim_count; i++)
+        if (x->dim[i] != y->dim[i]) return 0;
+    return 1;
+}
+
 /* matmul a -> add b, the add's other operand a constant whose only dim that is not 1 is the last and equals N ([N], [1,N],
  * [1,1,N], ...): the index (0 or 1) of that constant among the add's inputs, -1 when the pair does not fuse.  The add must be
  * a broadcasting one that the backend takes (one record per tensor, equal dtypes) and reads `mid` once */
@@ -207,16 +232,13 @@ static int linear_bias_input(struct shl_node *a, struct shl_node *b, struct shl_
     if (a->in_num != 2 || b->in_num != 2 || (b->in[0] == mid) == (b->in[1] == mid)) return -1;
     const int k = b->in[0] == mid ? 1 : 0;
     struct csinn_tensor *c = b->in[k]->data, *tm = mid->data, *out = b->out[0]->data;
-    if (!c->is_const || c->data == NULL || c->dim_count < 1 || tm->dim_count < 2 || out->dim_count != tm->dim_count) return -1;
+    if (!c->is_const || c->data == NULL || c->dim_count < 1 || tm->dim_count < 2 || !same_dims(out, tm)) return -1;
     const int32_t n = tm->dim[tm->dim_count - 1];
     if (c->dim[c->dim_count - 1] != n || n < 2) return -1;
     for (int i = 0; i < c->dim_count - 1; i++)
         if (c->dim[i] != 1) return -1;
     int64_t rows = 1;
-    for (int i = 0; i < tm->dim_count; i++) {
-        if (out->dim[i] != tm->dim[i]) return -1;
-        if (i < tm->dim_count - 1) rows *= tm->dim[i];
-    }
+    for (int i = 0; i < tm->dim_count - 1; i++) rows *= tm->dim[i];
     if (rows < 2) return -1; /* (one row: a same-shape add, which has its own kernel) */
     struct csinn_tensor *full, *small;
     struct shl_mi355x_mul_desc d;
@@ -292,11 +314,7 @@ static int attention_chain(struct shl_ref_graph *g, const int *layers, int n, in
     return at + 2;
 }
 
-static int one_record_i8(const struct csinn_tensor *t);
-static int one_record_f16(const struct csinn_tensor *t);
-
 /* ---- the head split and merge moves around an attention core (shl_mi355x_attention_layout) ------------------------------------- */
-#define FOLD_MAX 4 /* layers of one run */
 
 /* a reshape or a transpose that this backend runs and that copies its elements unchanged by the movers' own rule: int8 under
  * equal records whose requantisation is the identity on all 256 values (csrc/requant_move.h:move_rec chooses MOVE_RAW where the
@@ -323,12 +341,12 @@ static int pure_move(struct shl_node *n)
 }
 
 /* The run of pure moves, with at most one transpose among them, that ends in `x` (out = 0: the layers that make x, each read by
- * exactly one consumer and no graph output) or starts from it (out = 1: the layers that consume x and each other).  want > 0: a
- * run of exactly that many layers (the plan has decided), else the longest the strides express.  Returns the run's length, its
+ * exactly one consumer and no graph output) or starts from it (out = 1: the layers that consume x and each other): the longest
+ * the strides express.  Returns the run's length, its
  * layers in graph order in `run`, the tensor at its far end in *far (the source the launch reads / the tensor it writes) and
  * the view's heads and strides; 0 when nothing folds.  rows / cols / batches: what the view must come out as; swap: x is
  * [.., cols, rows] (K without trans_b) */
-static int head_moves(struct shl_ref_graph *g, struct shl_node *x, int out, int swap, int want, int32_t batches, int32_t rows,
+static int head_moves(struct shl_ref_graph *g, struct shl_node *x, int out, int swap, int32_t batches, int32_t rows,
                       int32_t cols, int *run, struct shl_node **far, int32_t *heads, int32_t stride[3])
 {
     int seen[FOLD_MAX], n = 0, transposes = 0;
@@ -345,7 +363,7 @@ static int head_moves(struct shl_ref_graph *g, struct shl_node *x, int out, int 
         seen[n++] = at;
         cur = out ? g->layer[at]->out[0] : g->layer[at]->in[0];
     }
-    for (int len = want > 0 ? want : n; len >= 1 && len <= n; len--) {
+    for (int len = n; len >= 1; len--) {
         /* the chain from the far end towards the core: for the output the destination and the layers inverted */
         struct shl_node *end = out ? g->layer[seen[len - 1]]->out[0] : g->layer[seen[len - 1]]->in[0];
         const struct csinn_tensor *te = end->data;
@@ -377,17 +395,16 @@ static int head_moves(struct shl_ref_graph *g, struct shl_node *x, int out, int 
             *far = end;
             return len;
         }
-        if (want > 0) break;
     }
     return 0;
 }
 
 /* The layout descriptor of a chain attention_chain has described (layers, len, *d; k_swapped: its K is [.., d, t]): which moves
- * around it fold (want: NULL for the longest runs, else the counts the plan stored), the tensors the launch then reads and
- * writes (src[0..2], *dst; the chain's own where a side does not fold) and *ld.  Each side folds or stays on its own; sides
- * whose views split the batch index differently cannot share `heads`, and the later of them stays.  Returns the layers folded */
+ * around it fold (the longest runs), the tensors the launch then reads and writes (src[0..2], *dst; the chain's own where a side
+ * does not fold) and *ld.  Each side folds or stays on its own; sides whose views split the batch index differently cannot share
+ * `heads`, and the later of them stays.  Returns the layers folded */
 static int attention_layout(struct shl_ref_graph *g, const int *layers, int len, const struct shl_mi355x_attention_desc *d, int k_swapped,
-                            const int *want, int fold[4], int runs[4][FOLD_MAX], struct shl_node *src[3], struct shl_node **dst,
+                            int fold[4], int runs[4][FOLD_MAX], struct shl_node *src[3], struct shl_node **dst,
                             struct shl_mi355x_attention_layout_desc *ld)
 {
     struct shl_node *qk = g->layer[layers[0]], *pv = g->layer[layers[len - 1]];
@@ -400,9 +417,7 @@ static int attention_layout(struct shl_ref_graph *g, const int *layers, int len,
     ld->heads = d->batches;
     for (int i = 0; i < 4; i++) {
         struct shl_node *far = x[i];
-        fold[i] = want != NULL && want[i] == 0 ? 0
-                                                : head_moves(g, x[i], i == 3, i == 1 && k_swapped, want ? want[i] : 0, d->batches, rows[i], cols[i],
-                                                             runs[i], &far, &heads[i], st[i]);
+        fold[i] = head_moves(g, x[i], i == 3, i == 1 && k_swapped, d->batches, rows[i], cols[i], runs[i], &far, &heads[i], st[i]);
         if (fold[i] > 0 && heads[i] != d->batches) { /* two pieces: the split every other side must share */
             if (ld->heads == d->batches) ld->heads = heads[i];
             else if (ld->heads != heads[i]) fold[i] = 0, far = x[i];
@@ -412,9 +427,6 @@ static int attention_layout(struct shl_ref_graph *g, const int *layers, int len,
         else *dst = far;
         total += fold[i];
     }
-    if (want != NULL)
-        for (int i = 0; i < 4; i++)
-            if (fold[i] != want[i]) return -1;
     /* one piece (heads = batches: the index is bi * head) is two pieces under any split */
     for (int i = 0; i < 4; i++)
         if (heads[i] == d->batches && ld->heads != d->batches) st[i][0] = ld->heads * st[i][1];
@@ -422,17 +434,6 @@ static int attention_layout(struct shl_ref_graph *g, const int *layers, int len,
     for (int i = 0; i < 4; i++)
         if (fold[i] > 0) ld->moved |= 1 << i;
     return total;
-}
-
-static int one_record_i8(const struct csinn_tensor *t)
-{
-    return t->dtype == CSINN_DTYPE_INT8 && t->qinfo != NULL && t->quant_channel <= 1;
-}
-
-/* a binary16 tensor as the same-shape add and the relu layers take it: one record, scale 1 */
-static int one_record_f16(const struct csinn_tensor *t)
-{
-    return t->dtype == CSINN_DTYPE_FLOAT16 && t->qinfo != NULL && t->quant_channel <= 1 && t->qinfo->scale == 1.0f;
 }
 
 /* convolution a (its step writes `mid`, a folded activation included) -> add b: the index (0 or 1) of the add's OTHER operand, the
@@ -449,9 +450,7 @@ static int residual_skip_input(struct shl_node *a, struct shl_node *b, struct sh
     if (f16 ? !one_record_f16(tm) || !one_record_f16(ts) || !one_record_f16(to) : !one_record_i8(tm) || !one_record_i8(ts) || !one_record_i8(to))
         return -1;
     if (ts->is_const) return -1;
-    if (tm->dim_count != 4 || ts->dim_count != 4 || to->dim_count != 4) return -1;
-    for (int i = 0; i < 4; i++)
-        if (ts->dim[i] != tm->dim[i] || to->dim[i] != tm->dim[i]) return -1;
+    if (tm->dim_count != 4 || !same_dims(tm, ts) || !same_dims(tm, to)) return -1;
     shl_mi355x_conv_plan *pa = shl_mi355x_registry_get(a->data);
     if (pa == NULL) return -1;
     if (f16) return (force ? shl_mi355x_conv_add_f16_fusable(pa, in->dim[0]) : shl_mi355x_conv_add_f16_by_default(pa, in->dim[0])) ? k : -1;
@@ -466,14 +465,6 @@ static int residual_takes_relu(struct shl_ref_graph *g, struct shl_node *sum, st
     return consumers_of(g, sum) == 1 && (ts->dtype == CSINN_DTYPE_FLOAT16 ? one_record_f16(r->out[0]->data) : one_record_i8(r->out[0]->data));
 }
 
-static int same_dims(const struct csinn_tensor *x, const struct csinn_tensor *y)
-{
-    if (x->dim_count != y->dim_count) return 0;
-    for (int i = 0; i < x->dim_count; i++)
-        if (x->dim[i] != y->dim[i]) return 0;
-    return 1;
-}
-
 /* steps[0 .. n-1] (consecutive, each still one layer; steps[0] a convolution or a depthwise layer with its folded activation) begin
  * with a table activation folded into the convolution's launch: the number of steps it takes and the table in `lut`; 0: the layers stay apart.
  *   2  convolution -> sigmoid | hard_sigmoid | silu | leaky_relu, which alone reads the convolution's output
@@ -485,7 +476,7 @@ static int same_dims(const struct csinn_tensor *x, const struct csinn_tensor *y)
 static int lut_chain(struct shl_ref_graph *g, const struct step *steps, int n, int force, uint8_t lut[256])
 {
     if (n < 2) return 0;
-    struct shl_node *a = g->layer[steps[0].a], *b = g->layer[steps[1].a], *mid = steps[0].out;
+    struct shl_node *a = g->layer[steps[0].layer[0]], *b = g->layer[steps[1].layer[0]], *mid = steps[0].out;
     if (!(is_conv_op(a->type) || is_dw_op(a->type)) || session_op(a) == NULL || session_op(b) == NULL || b->in_num < 1 || b->in[0] != mid) return 0;
     const int gate_kind = b->type == CSINN_OP_SIGMOID || b->type == CSINN_OP_HARD_SIGMOID;
     if (!gate_kind && b->type != CSINN_OP_SILU && b->type != CSINN_OP_LEAKY_RELU) return 0;
@@ -508,7 +499,7 @@ static int lut_chain(struct shl_ref_graph *g, const struct step *steps, int n, i
         return 2;
     }
     if (readers != 2 || !gate_kind || n < 3) return 0;
-    struct shl_node *c = g->layer[steps[2].a], *gate = b->out[0];
+    struct shl_node *c = g->layer[steps[2].layer[0]], *gate = b->out[0];
     if (c->type != CSINN_OP_MUL || session_op(c) == NULL || c->in_num != 2 || consumers_of(g, gate) != 1) return 0;
     const int x_first = c->in[0] == mid && c->in[1] == gate;
     if (!x_first && !(c->in[0] == gate && c->in[1] == mid)) return 0;
@@ -517,230 +508,6 @@ static int lut_chain(struct shl_ref_graph *g, const struct step *steps, int n, i
     shl_mi355x_gate_mul_table_i8(b->type == CSINN_OP_HARD_SIGMOID ? SHL_MI355X_UNARY_HARD_SIGMOID : SHL_MI355X_UNARY_SIGMOID, si, zi, so, zo,
                                  x_first, tc->qinfo->scale, tc->qinfo->zero_point, lut);
     return 3;
-}
-
-/* can steps `s` and `next` (adjacent, each still one layer) run as one launch, and as which?  STEP_LAYER: no.
- * residual: 0 no residual tails, 1 those of the measured shape classes, 2 every one the kernel takes */
-static enum step_kind merged_kind(struct shl_ref_graph *g, const struct step *s, const struct step *next, int residual)
-{
-    struct shl_node *a = g->layer[s->a], *b = g->layer[next->a], *mid = s->out;
-    /* a linear layer as converters export it: MatMul(x, W) -> Add(., bias[N]), the bias on either side of the add */
-    if (consumers_of(g, mid) == 1 && linear_bias_input(a, b, mid) >= 0) return STEP_MATMUL_BIAS;
-    /* the tail of a skip connection: convolution -> add(conv_out, skip), the convolution's output on either side of the add */
-    if (residual && consumers_of(g, mid) == 1 && residual_skip_input(a, b, mid, residual == 2) >= 0) return STEP_CONV_ADD;
-    if (b->in[0] != mid || consumers_of(g, mid) != 1) return STEP_LAYER;
-    /* global_avgpool2d -> the convolution / fullyconnected layer on the pooled map: one launch (csrc/conv_gemv.hip) */
-    if (a->type == CSINN_OP_GLOBAL_AVGPOOL2D && (is_conv_op(b->type) || b->type == CSINN_OP_FULLYCONNECTED)) {
-        struct csinn_tensor *pin = a->in[0]->data, *pmid = mid->data;
-        struct csinn_pool_params *pp = a->data;
-        shl_mi355x_conv_plan *pb = shl_mi355x_registry_get(b->data);
-        const int nhwc = pp->base.layout == CSINN_LAYOUT_NHWC;
-        if (pb && nhwc && pin->dim_count == 4 && pin->dtype == CSINN_DTYPE_INT8 && pin->qinfo && pmid->qinfo &&
-            pin->quant_channel <= 1 && pmid->quant_channel <= 1 &&
-            shl_mi355x_pool_conv_fusable(pb, pin->dim[0], pin->dim[1] * pin->dim[2]))
-            return STEP_POOL_CONV;
-    }
-    /* 1x1 convolution -> global_avgpool2d, the pooled tensor being all anything reads of it: one launch
-     * (csrc/conv1x1_latency.hip: the workgroup of a channel slice holds the whole map) */
-    if (is_conv_op(a->type) && b->type == CSINN_OP_GLOBAL_AVGPOOL2D) {
-        struct csinn_tensor *cin = a->in[0]->data, *pmid = mid->data, *pout = b->out[0]->data;
-        struct csinn_pool_params *pp = b->data;
-        shl_mi355x_conv_plan *pa = shl_mi355x_registry_get(a->data);
-        if (pa && pp->base.layout == CSINN_LAYOUT_NHWC && pmid->dim_count == 4 && pmid->dtype == CSINN_DTYPE_INT8 && pmid->qinfo &&
-            pout->qinfo && pmid->quant_channel <= 1 && pout->quant_channel <= 1 &&
-            shl_mi355x_conv_pool_fusable(pa, cin->dim[0]))
-            return STEP_CONV_POOL;
-    }
-    /* pointwise -> depthwise (latency form, small batches) or depthwise -> pointwise (bandwidth form, large
-     * batches: csrc/dwpw_stream.hip); shl_mi355x_pwdw_fusable tells the orders apart by the plans */
-    if ((is_conv_op(a->type) && is_dw_op(b->type)) || (is_dw_op(a->type) && is_conv_op(b->type))) {
-        shl_mi355x_conv_plan *pa = shl_mi355x_registry_get(a->data), *pb = shl_mi355x_registry_get(b->data);
-        struct csinn_tensor *in = a->in[0]->data;
-        if (pa && pb && shl_mi355x_pwdw_fusable(pa, pb, in->dim[0])) return STEP_PWDW;
-    }
-    return STEP_LAYER;
-}
-
-/* Graph-level rewrites; the intermediate tensors then never exist in HBM:
- *   conv / depthwise / deconv2d (no activation) -> relu | relu6, the convolution's only consumer, same output record
- *        the activation moves into the convolution's epilogue (the relu layer gets no step, the convolution's step writes
- *        the relu's output): what a converter emits for a RISC-V target -- example/c906_mobilenetv1_f16.c is
- *        28 csinn_conv2d + 27 csinn_relu -- runs as 28 launches, not 55
- *   1x1 convolution -> depthwise 3x3   one launch of csrc/pwdw_fused.hip (int8 NHWC) / pwdw_f16_nchw.hip (STEP_PWDW)
- *   depthwise 3x3 -> 1x1 convolution   one launch of csrc/dwpw_stream.hip at throughput batches (32 / 64 / 128 / 256 channels:
- *        the requantised depthwise tile is the pointwise MFMA operand); the latency form of this pairing recomputed the
- *        depthwise tile in every channel slice and is parked (attic/README.md)
- *   matmul -> add of a constant bias [N], the matmul's only consumer   one launch of csrc/matmul.hip's BIAS instantiation
- *        (STEP_MATMUL_BIAS): the linear layer a converter exports as MatMul + Add; the add's arithmetic runs on the value the
- *        matmul would have stored, so the step equals the two layers bit for bit
- *   matmul(q, k, trans_b) -> [mul by a one-element constant] -> [add of a bias or mask broadcast to the scores] -> softmax over
- *        the last axis -> matmul(p, v), every intermediate
- *        read by the next layer only   one launch of csrc/attention.hip (STEP_ATTENTION) where both products take matmul's mfma
- *        form: the scores and the probabilities stay in LDS, each computed as its own kernel would store it, so the step equals
- *        the layers bit for bit.  By default only shape classes it was measured faster on (csrc/attention_canon.h:att_default,
- *        with the add att_bias_default); SHL_MI355X_ATTENTION=1 merges every chain the kernel takes, =0 keeps the layers apart
- *   convolution (int8 NHWC, implicit GEMM; its folded activation included) -> add(conv_out, skip) of equal shapes, the convolution's
- *        only consumer -> [relu | relu6, the sum's only consumer]   one launch of the convolution (STEP_CONV_ADD, csrc/conv_igemm.hip's
- *        instantiations with the post-op): the add's and the activation's element functions run on the byte the convolution would
- *        have stored, so the step equals the layers bit for bit.  A convolution that is already half of a pair or feeds a pool is
- *        not taken (those merges come first).  By default only shape classes the fused launch was measured faster on
- *        (csrc/residual_validate.h:residual_default); SHL_MI355X_RESIDUAL=1 merges every tail the kernel takes, =0 none
- *   convolution (int8 NHWC, implicit GEMM; its folded activation included) -> sigmoid | hard_sigmoid | silu | leaky_relu, the
- *        convolution's only consumer, or -> sigmoid | hard_sigmoid -> mul(conv_out, gate), a swish / hard-swish gate   one launch of
- *        the convolution (STEP_CONV_LUT, csrc/conv_igemm.hip's instantiations with the table post-op): on int8 the layers are a
- *        function of the byte the convolution would have stored, ONE 256-entry table built here from their records with the
- *        layers' own builders, so the step equals the layers bit for bit.  Tried after the merges above: a convolution that is
- *        half of a pair, feeds a pool or a residual tail is not taken, and the step is not the first half of a residual merge.
- *        By default only shape classes the fused launch was measured faster on (csrc/lut_validate.h:lut_default);
- *        SHL_MI355X_ACT_FUSE=1 merges every one the kernel takes, =0 none
- *   depthwise layer (int8 NHWC, depth multiplier 1; its folded activation included) -> the same activations and gates   one launch
- *        of the depthwise kernel (STEP_CONV_LUT as well, csrc/dwconv.hip's and csrc/dwconv_mfma.hip's instantiations with the
- *        table post-op; the launch site picks the entry point by the plan's algorithm): MobileNetV3's depthwise -> hard-swish and
- *        EfficientNet's depthwise -> swish.  Same patterns, reader counts, tables, order and switch; a depthwise layer that is
- *        half of a pair is not taken.  The default classes: csrc/lut_validate.h:dw_lut_default
- * Fills ds->steps. */
-static int plan_fusion(struct dev_session *ds, struct shl_ref_graph *g)
-{
-    struct step *steps = ds->steps = calloc((size_t)g->layer_index, sizeof(*steps));
-    if (steps == NULL) return 0;
-    const char *off = getenv("SHL_MI355X_NO_FUSION");
-    const int fold = !(off && off[0] == '1');
-    int ns = 0;
-    /* one step per layer; an activation that folds joins the convolution's step */
-    for (int i = 0; i < g->layer_index; i++) {
-        struct shl_node *a = g->layer[i], *b = i + 1 < g->layer_index ? g->layer[i + 1] : NULL;
-        struct step *s = &steps[ns++];
-        *s = (struct step){STEP_LAYER, i, -1, -1, -1, a->out[0]};
-        const int plain = a->type == CSINN_OP_CONV2D || a->type == CSINN_OP_DEPTHWISE_CONV2D;
-        const int deconv = a->type == CSINN_OP_DECONV2D || a->type == CSINN_OP_DEPTHWISE_DECONV2D;
-        if (!fold || !(plain || deconv) || b == NULL || (b->type != CSINN_OP_RELU && b->type != CSINN_OP_RELU6)) continue;
-        if (b->in[0] != a->out[0] || consumers_of(g, a->out[0]) != 1) continue;
-        int (*const fold_activation)(struct csinn_tensor *, struct csinn_tensor *, struct csinn_tensor *, struct csinn_tensor *,
-                                     struct csinn_tensor *, struct csinn_conv2d_params *, int) =
-            deconv ? shl_mi355x_deconv2d_fold_activation : shl_mi355x_conv2d_fold_activation;
-        if (fold_activation(a->in[0]->data, a->out[0]->data, b->out[0]->data, a->in[1]->data, a->in[2]->data, a->data,
-                            b->type == CSINN_OP_RELU6) == CSINN_TRUE) {
-            s->out = b->out[0];
-            ds->nfolded++;
-            i++; /* the activation layer is taken */
-        }
-    }
-    /* a depthwise layer whose output does not feed ONE pointwise layer that the bandwidth form takes keeps its latency pair
-     * (the plan pair test below cannot see a layer's consumer: ADVICE r05 -- dw 32 -> pw 16 of MobileNetV2, two consumers, ...) */
-    for (int k = 0; k < ns; k++) {
-        struct shl_node *a = g->layer[steps[k].a], *b = k + 1 < ns ? g->layer[steps[k + 1].a] : NULL;
-        if (!is_dw_op(a->type)) continue;
-        shl_mi355x_conv_plan *pa = shl_mi355x_registry_get(a->data);
-        if (pa == NULL) continue;
-        struct csinn_tensor *in = a->in[0]->data;
-        int streams = 0;
-        if (b && b->in[0] == steps[k].out && is_conv_op(b->type) && consumers_of(g, steps[k].out) == 1) {
-            shl_mi355x_conv_plan *pb = shl_mi355x_registry_get(b->data);
-            streams = pb != NULL && shl_mi355x_pwdw_fusable(pa, pb, in->dim[0]);
-        }
-        shl_mi355x_conv_plan_set_no_stream_consumer(pa, !streams);
-    }
-    /* merge adjacent steps greedily from the front; a merged step is not the first half of another merge
-     * (SHL_MI355X_NO_FUSION=1 also keeps a matmul and its bias add apart: the switch of the linear fusion's A/B runs) */
-    /* SHL_MI355X_ATTENTION, read here, at plan time: "0" keeps the chain's layers apart, "1" merges every chain the kernel takes
-     * (A/B runs), unset merges the shape classes the fused launch was measured faster on */
-    const char *att = getenv("SHL_MI355X_ATTENTION");
-    const int attention = fold && !(att && att[0] == '0'), force = att && att[0] == '1';
-    /* SHL_MI355X_RESIDUAL likewise: "0" none, "1" every tail the kernel takes, unset the measured shape classes */
-    const char *res = getenv("SHL_MI355X_RESIDUAL");
-    const int residual = !fold || (res && res[0] == '0') ? 0 : (res && res[0] == '1') ? 2 : 1;
-    /* SHL_MI355X_ACT_FUSE likewise, for the table activations */
-    const char *af = getenv("SHL_MI355X_ACT_FUSE");
-    const int act_fuse = !fold || (af && af[0] == '0') ? 0 : (af && af[0] == '1') ? 2 : 1;
-    /* SHL_MI355X_ATTENTION_LAYOUT likewise, for the reshape / transpose runs around a merged core: "0" folds none, "1" every run
-     * the kernel takes, unset the classes one layout launch was measured faster on (shl_mi355x_attention_layout_by_default) --
-     * unset, a core the dense default leaves apart merges too when all four sides fold and its class was measured faster */
-    const char *lay = getenv("SHL_MI355X_ATTENTION_LAYOUT");
-    const int layout = !attention || (lay && lay[0] == '0') ? 0 : (lay && lay[0] == '1') ? 2 : 1;
-    char *gone = calloc((size_t)g->layer_index + 1, 1); /* layers an attention launch stands for */
-    if (gone == NULL) return 0;
-    for (int k = 0; k < ns; k++) {
-        struct step s = steps[k];
-        if (s.kind == STEP_LAYER && gone[s.a]) continue; /* a move behind a core that took it */
-        /* the core of an attention block first: its matmuls then are no longer candidates for a pair */
-        int chain[5] = {-1, -1, -1, -1, -1}, avail = 0;
-        for (; avail < 5 && k + avail < ns; avail++) chain[avail] = steps[k + avail].a;
-        struct shl_mi355x_attention_desc ad;
-        struct shl_mi355x_attention_bias_desc abd;
-        struct shl_mi355x_attention_layout_desc ld;
-        struct shl_node *bias = NULL, *src[3], *dst = NULL;
-        int k_swapped = 0, fold4[4] = {0, 0, 0, 0}, runs[4][FOLD_MAX], folded = 0;
-        int taken = attention ? attention_chain(g, chain, avail, force, &ad, &abd, &bias, &k_swapped) : 0;
-        int promoted = 0;
-        if (taken == 0 && layout == 1 && !force) { /* (with the moves on the scales the dense default's verdict may change) */
-            taken = attention_chain(g, chain, avail, 1, &ad, &abd, &bias, &k_swapped);
-            promoted = taken > 0;
-        }
-        if (taken > 0 && layout) {
-            folded = attention_layout(g, chain, taken, &ad, k_swapped, NULL, fold4, runs, src, &dst, &ld);
-            /* the last word belongs to the kernel's own rules, asked with made-up addresses that do not overlap */
-            const void *a0 = (const void *)((uintptr_t)1 << 56), *a1 = (const void *)((uintptr_t)1 << 57), *a2 = (const void *)((uintptr_t)1 << 58),
-                       *a3 = (const void *)((uintptr_t)1 << 59), *a4 = bias ? (const void *)((uintptr_t)1 << 60) : NULL;
-            const struct shl_mi355x_attention_bias_desc *pb = bias ? &abd : NULL;
-            if (folded > 0 && shl_mi355x_attention_layout_kernel_name(a0, a1, a2, a4, a3, &ad, pb, &ld)[0] == '\0') folded = 0;
-            if (folded > 0 && layout == 1 && !shl_mi355x_attention_layout_by_default(a0, a1, a2, a4, a3, &ad, pb, &ld)) folded = 0;
-            if (promoted && !(folded > 0 && fold4[0] && fold4[1] && fold4[2] && fold4[3])) folded = 0;
-        }
-        if ((promoted || k_swapped) && (folded <= 0 || (k_swapped && fold4[1] == 0))) taken = 0; /* the layers run one by one */
-        if (taken > 0) {
-            steps[ds->nsteps] = (struct step){STEP_ATTENTION, chain[0], chain[1], chain[2], taken >= 4 ? chain[3] : -1, steps[k + taken - 1].out};
-            steps[ds->nsteps].e = taken == 5 ? chain[4] : -1;
-            if (folded > 0) {
-                for (int i = 0; i < 4; i++) {
-                    steps[ds->nsteps].fold[i] = fold4[i];
-                    for (int j = 0; j < fold4[i]; j++) gone[runs[i][j]] = 1;
-                }
-                steps[ds->nsteps].out = dst;
-                ds->nhead_moves += folded;
-            }
-            ds->nsteps++;
-            ds->nattention++;
-            if (bias != NULL) ds->nattention_bias++;
-            k += taken - 1; /* the chain's other steps are taken */
-            continue;
-        }
-        enum step_kind kind = k + 1 < ns ? merged_kind(g, &s, &steps[k + 1], residual) : STEP_LAYER;
-        if (kind == STEP_MATMUL_BIAS && !fold) kind = STEP_LAYER;
-        if (kind != STEP_LAYER) {
-            k++; /* the second step is taken */
-            const int skip_at = kind == STEP_CONV_ADD ? residual_skip_input(g->layer[s.a], g->layer[steps[k].a], s.out, residual == 2) : -1;
-            s = (struct step){kind, s.a, steps[k].a, -1, skip_at, steps[k].out};
-            if (kind == STEP_CONV_ADD && k + 1 < ns && residual_takes_relu(g, s.out, g->layer[steps[k + 1].a])) {
-                k++; /* ... and the activation behind the sum */
-                s.c = steps[k].a;
-                s.out = steps[k].out;
-            }
-            if (kind == STEP_PWDW) ds->nfused++;
-            else if (kind == STEP_MATMUL_BIAS) ds->nlinear++;
-            else if (kind == STEP_CONV_ADD) ds->nresidual++;
-            else ds->npool++;
-        } else if (act_fuse) {
-            const int lut_taken = lut_chain(g, &steps[k], ns - k, act_fuse == 2, s.lut);
-            if (lut_taken > 0) {
-                s.kind = STEP_CONV_LUT;
-                s.b = steps[k + 1].a;
-                s.c = lut_taken == 3 ? steps[k + 2].a : -1;
-                s.out = steps[k + lut_taken - 1].out;
-                ds->nactivation++;
-                k += lut_taken - 1; /* the activation's (and the mul's) steps are taken */
-            }
-        }
-        steps[ds->nsteps++] = s;
-    }
-    /* the moves in FRONT of a core were steps before the core was found: mark and compact.  (This relies on a reshape or a
-     * transpose never being part of a merged step -- no step kind above takes one --: a folded move inside a merged step would
-     * still run, and nhead_moves would count a layer that did) */
-    int kept = 0;
-    for (int k = 0; k < ds->nsteps; k++)
-        if (!(steps[k].kind == STEP_LAYER && gone[steps[k].a])) steps[kept++] = steps[k];
-    ds->nsteps = kept;
-    free(gone);
-    return 1;
 }
 
 /* layer `n` through its exec callback, writing `out` */
@@ -786,105 +553,373 @@ static int run_layer(struct dev_session *ds, struct shl_node *n, struct dev_tens
 
 static int status_of(int st) { return st == SHL_MI355X_OK ? CSINN_TRUE : CSINN_FALSE; }
 
+/* ---- the planner's rules: what merges into one launch, and the launch ---------------------------------------------------------- */
+
+/* what a rule's match sees.  The switches as levels: 0 off, 1 the shape classes the fused launch was measured faster on, 2 every
+ * shape the kernel takes (A/B runs) -- see switch_level */
+struct planner {
+    struct dev_session *ds;
+    struct shl_ref_graph *g;
+    struct step *steps; /* from position k on: one step per layer, activations folded */
+    int ns;
+    int fuse;      /* SHL_MI355X_NO_FUSION is not 1; 0 also zeroes every level below (but not the pair and the pool rules) */
+    int attention; /* SHL_MI355X_ATTENTION */
+    int layout;    /* SHL_MI355X_ATTENTION_LAYOUT; 0 where no core merges */
+    int residual;  /* SHL_MI355X_RESIDUAL */
+    int act_fuse;  /* SHL_MI355X_ACT_FUSE */
+    char *gone;    /* by layer: a move that an attention step stands for (written by the attention rule) */
+};
+
+/* One row per fusion, in priority order: at a position the first rule that matches wins, and the steps it takes are no
+ * candidates for a later rule -- a merged step is never the first half of another merge.
+ *   match   can steps k, k + 1, ... (each still one layer) run as one launch?  The number of steps taken, with *s -- which
+ *           arrives as steps[k] -- filled (take(), src[1..], u); 0 with nothing but s->u touched when they stay apart
+ *   launch  enqueues the step: in[i] is the device tensor of s->src[i], out that of s->out */
+struct rule {
+    const char *name; /* as shl_mi355x_session_describe prints it */
+    int (*match)(struct planner *p, int k, struct step *s);
+    int (*launch)(struct dev_session *ds, struct shl_ref_graph *g, const struct step *s, struct dev_tensor *const *in, struct dev_tensor *out);
+};
+
+/* *s stands for steps k .. k + n - 1 */
+static int take(const struct planner *p, int k, int n, struct step *s)
+{
+    for (int i = 0; i < n; i++) s->layer[i] = p->steps[k + i].layer[0];
+    s->nlayers = n;
+    s->out = p->steps[k + n - 1].out;
+    return n;
+}
+
+/* steps k and k + 1 as a candidate pair: the layers and the tensor between them, which has one reader */
+static int adjacent(const struct planner *p, int k, struct shl_node **a, struct shl_node **b, struct shl_node **mid)
+{
+    if (k + 1 >= p->ns) return 0;
+    *a = p->g->layer[p->steps[k].layer[0]];
+    *b = p->g->layer[p->steps[k + 1].layer[0]];
+    *mid = p->steps[k].out;
+    return consumers_of(p->g, *mid) == 1;
+}
+
+/* attention: matmul(q, k, trans_b) -> [mul by a one-element constant] -> [add of a bias or mask broadcast to the scores] ->
+ * softmax over the last axis -> matmul(p, v), every intermediate read by the next layer only (attention_chain): one launch of
+ * csrc/attention.hip where both products take matmul's mfma form.  The scores and the probabilities stay in LDS, each computed
+ * as its own kernel would store it, so the step equals the layers bit for bit.  First in the table: the core's matmuls then are
+ * no candidates for a linear step.  With the layout level on, the reshape / transpose runs around the core fold into the launch
+ * as strides (attention_layout), the kernel's own rules having the last word; at level 1 a core the dense default leaves apart
+ * is "promoted" when all four sides fold and its class was measured faster.  A K without trans_b merges only when its moves fold.
+ * Moves behind the core are marked gone and skipped by the loop; those in front were already emitted and are compacted away */
+static int match_attention(struct planner *p, int k, struct step *s)
+{
+    struct shl_ref_graph *g = p->g;
+    struct shl_mi355x_attention_desc *ad = &s->u.attention.ad;
+    struct shl_mi355x_attention_bias_desc *abd = &s->u.attention.abd;
+    struct shl_mi355x_attention_layout_desc *ld = &s->u.attention.ld;
+    struct shl_node *bias = NULL, *src[3], *dst = NULL;
+    int chain[STEP_LAYERS], avail = 0, k_swapped = 0, fold4[4] = {0, 0, 0, 0}, runs[4][FOLD_MAX], folded = 0, promoted = 0;
+    for (; avail < STEP_LAYERS && k + avail < p->ns; avail++) chain[avail] = p->steps[k + avail].layer[0];
+    const int force = p->attention == 2;
+    int taken = p->attention ? attention_chain(g, chain, avail, force, ad, abd, &bias, &k_swapped) : 0;
+    if (taken == 0 && p->layout == 1 && !force) { /* (with the moves on the scales the dense default's verdict may change) */
+        taken = attention_chain(g, chain, avail, 1, ad, abd, &bias, &k_swapped);
+        promoted = taken > 0;
+    }
+    if (taken > 0 && p->layout) {
+        folded = attention_layout(g, chain, taken, ad, k_swapped, fold4, runs, src, &dst, ld);
+        /* the last word belongs to the kernel's own rules, asked with made-up addresses that do not overlap */
+        const void *a0 = (const void *)((uintptr_t)1 << 56), *a1 = (const void *)((uintptr_t)1 << 57), *a2 = (const void *)((uintptr_t)1 << 58),
+                   *a3 = (const void *)((uintptr_t)1 << 59), *a4 = bias ? (const void *)((uintptr_t)1 << 60) : NULL;
+        const struct shl_mi355x_attention_bias_desc *pb = bias ? abd : NULL;
+        if (folded > 0 && shl_mi355x_attention_layout_kernel_name(a0, a1, a2, a4, a3, ad, pb, ld)[0] == '\0') folded = 0;
+        if (folded > 0 && p->layout == 1 && !shl_mi355x_attention_layout_by_default(a0, a1, a2, a4, a3, ad, pb, ld)) folded = 0;
+        if (promoted && !(fold4[0] && fold4[1] && fold4[2] && fold4[3])) folded = 0;
+    }
+    if (taken == 0 || ((promoted || k_swapped) && (folded <= 0 || (k_swapped && fold4[1] == 0)))) return 0; /* the layers run one by one */
+    struct shl_node *qk = g->layer[chain[0]], *pv = g->layer[chain[taken - 1]];
+    take(p, k, taken, s);
+    s->src[0] = qk->in[0], s->src[1] = qk->in[1], s->src[2] = pv->in[1], s->src[3] = bias;
+    memset(s->u.attention.fold, 0, sizeof(s->u.attention.fold));
+    if (folded > 0) { /* through strides: the sources' buffers, the last folded layer's output */
+        for (int i = 0; i < 4; i++) {
+            s->u.attention.fold[i] = fold4[i];
+            for (int j = 0; j < fold4[i]; j++) p->gone[runs[i][j]] = 1;
+            if (i < 3) s->src[i] = src[i];
+        }
+        s->out = dst;
+        p->ds->nhead_moves += folded;
+    }
+    if (bias != NULL) p->ds->nattention_bias++;
+    return taken;
+}
+
+static int launch_attention(struct dev_session *ds, struct shl_ref_graph *g, const struct step *s, struct dev_tensor *const *in, struct dev_tensor *out)
+{
+    (void)g;
+    const int *fold = s->u.attention.fold;
+    const struct shl_mi355x_attention_desc *ad = &s->u.attention.ad;
+    const struct shl_mi355x_attention_bias_desc *abd = in[3] ? &s->u.attention.abd : NULL;
+    if (fold[0] || fold[1] || fold[2] || fold[3])
+        return shl_mi355x_attention_layout_forward(ad, abd, &s->u.attention.ld, in[0]->dev, in[1]->dev, in[2]->dev, in[3] ? in[3]->dev : NULL,
+                                                   out->dev, ds->stream);
+    if (abd) /* a constant bias is resident like any constant operand of an add */
+        return shl_mi355x_attention_bias_forward(ad, abd, in[0]->dev, in[1]->dev, in[2]->dev, in[3]->dev, out->dev, ds->stream);
+    return shl_mi355x_attention_forward(ad, in[0]->dev, in[1]->dev, in[2]->dev, out->dev, ds->stream);
+}
+
+/* linear: matmul -> add of a constant bias [N], the bias on either side of the add (linear_bias_input): the linear layer a
+ * converter exports as MatMul + Add, one launch of csrc/matmul.hip's BIAS instantiation.  The add's arithmetic runs on the value
+ * the matmul would have stored, so the step equals the two layers bit for bit.  It has no switch of its own:
+ * SHL_MI355X_NO_FUSION=1 keeps the two apart (the linear fusion's A/B runs) */
+static int match_linear(struct planner *p, int k, struct step *s)
+{
+    struct shl_node *a, *b, *mid;
+    if (!p->fuse || !adjacent(p, k, &a, &b, &mid)) return 0;
+    const int kb = linear_bias_input(a, b, mid);
+    if (kb < 0) return 0;
+    s->u.bias_at = kb;
+    s->src[1] = a->in[1], s->src[2] = b->in[kb];
+    return take(p, k, 2, s);
+}
+
+static int launch_linear(struct dev_session *ds, struct shl_ref_graph *g, const struct step *s, struct dev_tensor *const *in, struct dev_tensor *out)
+{
+    struct shl_node *n = g->layer[s->layer[0]], *nx = g->layer[s->layer[1]];
+    return shl_mi355x_matmul_bias_forward(n->in[0]->data, n->in[1]->data, n->out[0]->data, s->src[2]->data, nx->out[0]->data, n->data,
+                                          s->u.bias_at == 0, in[0]->dev, in[1]->dev, in[2]->dev, out->dev, ds->stream);
+}
+
+/* residual: convolution (implicit GEMM, int8 or binary16 NHWC; its folded activation included) -> add(conv_out, skip) of equal
+ * shapes, the convolution's output on either side (residual_skip_input) -> [relu | relu6, taken only when the sum has that one
+ * reader]: the tail of a skip connection as one launch of the convolution (csrc/conv_igemm.hip's instantiations with the
+ * post-op).  The add's and the activation's element functions run on the value the convolution would have stored, so the step
+ * equals the layers bit for bit.  Level 1: csrc/residual_validate.h:residual_default */
+static int match_residual(struct planner *p, int k, struct step *s)
+{
+    struct shl_node *a, *b, *mid;
+    if (!p->residual || !adjacent(p, k, &a, &b, &mid)) return 0;
+    const int ks = residual_skip_input(a, b, mid, p->residual == 2);
+    if (ks < 0) return 0;
+    struct shl_node *r = k + 2 < p->ns ? p->g->layer[p->steps[k + 2].layer[0]] : NULL;
+    const int relu = r != NULL && residual_takes_relu(p->g, p->steps[k + 1].out, r);
+    s->u.residual.skip_at = ks;
+    s->u.residual.act = relu ? (r->type == CSINN_OP_RELU6 ? 2 : 1) : 0;
+    s->src[1] = b->in[ks];
+    return take(p, k, relu ? 3 : 2, s);
+}
+
+/* the add and the activation read what the convolution (+ folded activation) would have written */
+static int launch_residual(struct dev_session *ds, struct shl_ref_graph *g, const struct step *s, struct dev_tensor *const *in, struct dev_tensor *out)
+{
+    struct shl_node *n = g->layer[s->layer[0]], *add = g->layer[s->layer[1]];
+    struct csinn_tensor *tskip = s->src[1]->data, *tsum = add->out[0]->data, *tout = s->out->data;
+    struct shl_mi355x_residual_desc rd = {s->u.residual.skip_at == 1, tskip->qinfo->scale, tskip->qinfo->zero_point, tsum->qinfo->scale,
+                                          tsum->qinfo->zero_point, s->u.residual.act, tout->qinfo->scale, tout->qinfo->zero_point};
+    /* (the plan's dtype is the sum's: binary16 has entry points of its own, which read conv_first and act alone) */
+    int (*const forward)(const shl_mi355x_conv_plan *, const void *, const void *, void *, int32_t, const struct shl_mi355x_residual_desc *, void *) =
+        tsum->dtype == CSINN_DTYPE_FLOAT16 ? shl_mi355x_conv_add_f16_forward : shl_mi355x_conv_add_forward;
+    return status_of(forward(shl_mi355x_registry_get(n->data), in[0]->dev, in[1]->dev, out->dev, in[0]->shadow.dim[0], &rd, ds->stream));
+}
+
+/* pool_conv: global_avgpool2d -> the convolution / fullyconnected layer on the pooled map: one launch (csrc/conv_gemv.hip) */
+static int match_pool_conv(struct planner *p, int k, struct step *s)
+{
+    struct shl_node *a, *b, *mid;
+    if (!adjacent(p, k, &a, &b, &mid) || b->in[0] != mid) return 0;
+    if (a->type != CSINN_OP_GLOBAL_AVGPOOL2D || !(is_conv_op(b->type) || b->type == CSINN_OP_FULLYCONNECTED)) return 0;
+    struct csinn_tensor *pin = a->in[0]->data, *pmid = mid->data;
+    struct csinn_pool_params *pp = a->data;
+    shl_mi355x_conv_plan *pb = shl_mi355x_registry_get(b->data);
+    if (!(pb && pp->base.layout == CSINN_LAYOUT_NHWC && pin->dim_count == 4 && pin->dtype == CSINN_DTYPE_INT8 && pin->qinfo && pmid->qinfo &&
+          pin->quant_channel <= 1 && pmid->quant_channel <= 1 && shl_mi355x_pool_conv_fusable(pb, pin->dim[0], pin->dim[1] * pin->dim[2])))
+        return 0;
+    return take(p, k, 2, s);
+}
+
+static int launch_pool_conv(struct dev_session *ds, struct shl_ref_graph *g, const struct step *s, struct dev_tensor *const *in, struct dev_tensor *out)
+{
+    struct shl_node *n = g->layer[s->layer[0]], *nx = g->layer[s->layer[1]];
+    struct csinn_tensor *pin = n->in[0]->data, *pmid = n->out[0]->data;
+    return status_of(shl_mi355x_pool_conv_forward(shl_mi355x_registry_get(nx->data), in[0]->dev, out->dev, in[0]->shadow.dim[0],
+                                                  pin->dim[1] * pin->dim[2], pin->qinfo->scale, pin->qinfo->zero_point, pmid->qinfo->scale,
+                                                  pmid->qinfo->zero_point, ds->stream));
+}
+
+/* conv_pool: 1x1 convolution -> global_avgpool2d, the pooled tensor being all anything reads of it: one launch
+ * (csrc/conv1x1_latency.hip: the workgroup of a channel slice holds the whole map) */
+static int match_conv_pool(struct planner *p, int k, struct step *s)
+{
+    struct shl_node *a, *b, *mid;
+    if (!adjacent(p, k, &a, &b, &mid) || b->in[0] != mid || !is_conv_op(a->type) || b->type != CSINN_OP_GLOBAL_AVGPOOL2D) return 0;
+    struct csinn_tensor *cin = a->in[0]->data, *pmid = mid->data, *pout = b->out[0]->data;
+    struct csinn_pool_params *pp = b->data;
+    shl_mi355x_conv_plan *pa = shl_mi355x_registry_get(a->data);
+    if (!(pa && pp->base.layout == CSINN_LAYOUT_NHWC && pmid->dim_count == 4 && pmid->dtype == CSINN_DTYPE_INT8 && pmid->qinfo && pout->qinfo &&
+          pmid->quant_channel <= 1 && pout->quant_channel <= 1 && shl_mi355x_conv_pool_fusable(pa, cin->dim[0])))
+        return 0;
+    return take(p, k, 2, s);
+}
+
+/* the pool reads what the convolution (+ folded activation) would have written */
+static int launch_conv_pool(struct dev_session *ds, struct shl_ref_graph *g, const struct step *s, struct dev_tensor *const *in, struct dev_tensor *out)
+{
+    struct shl_node *n = g->layer[s->layer[0]], *nx = g->layer[s->layer[1]];
+    struct csinn_tensor *pmid = nx->in[0]->data, *pout = nx->out[0]->data;
+    return status_of(shl_mi355x_conv_pool_forward(shl_mi355x_registry_get(n->data), in[0]->dev, NULL, out->dev, in[0]->shadow.dim[0],
+                                                  pmid->qinfo->scale, pmid->qinfo->zero_point, pout->qinfo->scale, pout->qinfo->zero_point,
+                                                  ds->stream));
+}
+
+/* pair: pointwise -> depthwise 3x3 (latency form, small batches: csrc/pwdw_fused.hip, pwdw_f16_nchw.hip) or depthwise 3x3 ->
+ * pointwise (bandwidth form at throughput batches, csrc/dwpw_stream.hip: the requantised depthwise tile is the pointwise MFMA
+ * operand; the latency form of this order is parked, attic/README.md); shl_mi355x_pwdw_fusable tells the orders apart by the plans */
+static int match_pair(struct planner *p, int k, struct step *s)
+{
+    struct shl_node *a, *b, *mid;
+    if (!adjacent(p, k, &a, &b, &mid) || b->in[0] != mid) return 0;
+    if (!((is_conv_op(a->type) && is_dw_op(b->type)) || (is_dw_op(a->type) && is_conv_op(b->type)))) return 0;
+    shl_mi355x_conv_plan *pa = shl_mi355x_registry_get(a->data), *pb = shl_mi355x_registry_get(b->data);
+    struct csinn_tensor *in = a->in[0]->data;
+    return pa && pb && shl_mi355x_pwdw_fusable(pa, pb, in->dim[0]) ? take(p, k, 2, s) : 0;
+}
+
+static int launch_pair(struct dev_session *ds, struct shl_ref_graph *g, const struct step *s, struct dev_tensor *const *in, struct dev_tensor *out)
+{
+    return status_of(shl_mi355x_pwdw_forward(shl_mi355x_registry_get(g->layer[s->layer[0]]->data), shl_mi355x_registry_get(g->layer[s->layer[1]]->data),
+                                             in[0]->dev, out->dev, in[0]->shadow.dim[0], ds->stream));
+}
+
+/* table: convolution or depthwise layer (int8 NHWC; its folded activation included) -> sigmoid | hard_sigmoid | silu |
+ * leaky_relu, or -> sigmoid | hard_sigmoid -> mul(conv_out, gate), a swish / hard-swish gate (lut_chain): one launch of the
+ * convolution with the table post-op (csrc/conv_igemm.hip; depthwise: csrc/dwconv.hip, csrc/dwconv_mfma.hip -- MobileNetV3's
+ * depthwise -> hard-swish, EfficientNet's depthwise -> swish).  On int8 the layers are a function of the byte the convolution
+ * would have stored, ONE 256-entry table built from their records with the layers' own builders, so the step equals the layers
+ * bit for bit.  Last in the table: a convolution that is half of a pair, feeds a pool or a residual tail is not taken, and the
+ * step is not the first half of a residual merge.  Level 1: csrc/lut_validate.h:lut_default, dw_lut_default */
+static int match_table(struct planner *p, int k, struct step *s)
+{
+    const int n = p->act_fuse ? lut_chain(p->g, &p->steps[k], p->ns - k, p->act_fuse == 2, s->u.lut) : 0;
+    return n > 0 ? take(p, k, n, s) : 0;
+}
+
+/* the table's input is what the convolution (+ folded activation) would have written */
+static int launch_table(struct dev_session *ds, struct shl_ref_graph *g, const struct step *s, struct dev_tensor *const *in, struct dev_tensor *out)
+{
+    shl_mi355x_conv_plan *plan = shl_mi355x_registry_get(g->layer[s->layer[0]]->data);
+    return status_of(shl_mi355x_conv_plan_algo(plan) == SHL_MI355X_ALGO_DW
+                         ? shl_mi355x_dwconv_lut_forward(plan, in[0]->dev, out->dev, in[0]->shadow.dim[0], s->u.lut, ds->stream)
+                         : shl_mi355x_conv_lut_forward(plan, in[0]->dev, out->dev, in[0]->shadow.dim[0], s->u.lut, ds->stream));
+}
+
+static const struct rule rules[N_RULES] = {
+    [R_ATTENTION] = {"attention", match_attention, launch_attention},
+    [R_LINEAR] = {"linear", match_linear, launch_linear},
+    [R_RESIDUAL] = {"residual", match_residual, launch_residual},
+    [R_POOL_CONV] = {"pool_conv", match_pool_conv, launch_pool_conv},
+    [R_CONV_POOL] = {"conv_pool", match_conv_pool, launch_conv_pool},
+    [R_PAIR] = {"pair", match_pair, launch_pair},
+    [R_TABLE] = {"table", match_table, launch_table},
+};
+
+/* a planner switch, read at plan time: 0 for "0", 2 for "1", 1 when unset (or anything else) */
+static int switch_level(const char *name)
+{
+    const char *v = getenv(name);
+    return v && v[0] == '0' ? 0 : v && v[0] == '1' ? 2 : 1;
+}
+
+/* Graph-level rewrites; the intermediate tensors then never exist in HBM.  Three passes:
+ *   1  conv / depthwise / deconv2d (no activation) -> relu | relu6, the convolution's only consumer, same output record: the
+ *      activation moves into the convolution's epilogue (the relu layer gets no step, the convolution's step writes the relu's
+ *      output).  What a converter emits for a RISC-V target -- example/c906_mobilenetv1_f16.c is 28 csinn_conv2d + 27
+ *      csinn_relu -- runs as 28 launches, not 55
+ *   2  depthwise plans learn whether the bandwidth pair takes their consumer
+ *   3  rules[], greedily from the front
+ * Fills ds->steps. */
+static int plan_fusion(struct dev_session *ds, struct shl_ref_graph *g)
+{
+    struct step *steps = ds->steps = calloc((size_t)g->layer_index, sizeof(*steps));
+    struct planner p = {.ds = ds, .g = g, .steps = steps, .gone = calloc((size_t)g->layer_index + 1, 1)};
+    if (steps == NULL || p.gone == NULL) {
+        free(p.gone);
+        return 0;
+    }
+    p.fuse = switch_level("SHL_MI355X_NO_FUSION") != 2;
+    p.attention = p.fuse ? switch_level("SHL_MI355X_ATTENTION") : 0;
+    p.layout = p.attention ? switch_level("SHL_MI355X_ATTENTION_LAYOUT") : 0;
+    p.residual = p.fuse ? switch_level("SHL_MI355X_RESIDUAL") : 0;
+    p.act_fuse = p.fuse ? switch_level("SHL_MI355X_ACT_FUSE") : 0;
+    /* one step per layer; an activation that folds joins the convolution's step */
+    for (int i = 0; i < g->layer_index; i++) {
+        struct shl_node *a = g->layer[i], *b = i + 1 < g->layer_index ? g->layer[i + 1] : NULL;
+        struct step *s = &steps[p.ns++];
+        *s = (struct step){.layer = {i}, .nlayers = 1, .out = a->out[0], .src = {a->in[0]}};
+        const int plain = a->type == CSINN_OP_CONV2D || a->type == CSINN_OP_DEPTHWISE_CONV2D;
+        const int deconv = a->type == CSINN_OP_DECONV2D || a->type == CSINN_OP_DEPTHWISE_DECONV2D;
+        if (!p.fuse || !(plain || deconv) || b == NULL || (b->type != CSINN_OP_RELU && b->type != CSINN_OP_RELU6)) continue;
+        if (b->in[0] != a->out[0] || consumers_of(g, a->out[0]) != 1) continue;
+        int (*const fold_activation)(struct csinn_tensor *, struct csinn_tensor *, struct csinn_tensor *, struct csinn_tensor *,
+                                     struct csinn_tensor *, struct csinn_conv2d_params *, int) =
+            deconv ? shl_mi355x_deconv2d_fold_activation : shl_mi355x_conv2d_fold_activation;
+        if (fold_activation(a->in[0]->data, a->out[0]->data, b->out[0]->data, a->in[1]->data, a->in[2]->data, a->data,
+                            b->type == CSINN_OP_RELU6) == CSINN_TRUE) {
+            s->out = b->out[0];
+            ds->nfolded++;
+            i++; /* the activation layer is taken */
+        }
+    }
+    /* a depthwise layer whose output does not feed ONE pointwise layer that the bandwidth form takes keeps its latency pair
+     * (the pair rule cannot see a layer's consumer: ADVICE r05 -- dw 32 -> pw 16 of MobileNetV2, two consumers, ...) */
+    for (int k = 0; k < p.ns; k++) {
+        struct shl_node *a = g->layer[steps[k].layer[0]], *b = k + 1 < p.ns ? g->layer[steps[k + 1].layer[0]] : NULL;
+        if (!is_dw_op(a->type)) continue;
+        shl_mi355x_conv_plan *pa = shl_mi355x_registry_get(a->data);
+        if (pa == NULL) continue;
+        struct csinn_tensor *in = a->in[0]->data;
+        int streams = 0;
+        if (b && b->in[0] == steps[k].out && is_conv_op(b->type) && consumers_of(g, steps[k].out) == 1) {
+            shl_mi355x_conv_plan *pb = shl_mi355x_registry_get(b->data);
+            streams = pb != NULL && shl_mi355x_pwdw_fusable(pa, pb, in->dim[0]);
+        }
+        shl_mi355x_conv_plan_set_no_stream_consumer(pa, !streams);
+    }
+    /* the merged steps overwrite the list in place: position nsteps never runs ahead of k */
+    for (int k = 0; k < p.ns; k++) {
+        struct step s = steps[k];
+        if (p.gone[s.layer[0]]) continue; /* a move behind a core that took it */
+        int taken = 0;
+        for (int r = 0; r < N_RULES && taken == 0; r++)
+            if ((taken = rules[r].match(&p, k, &s)) > 0) {
+                s.rule = &rules[r];
+                ds->count[r]++;
+                k += taken - 1;
+            }
+        steps[ds->nsteps++] = s;
+    }
+    /* the moves in FRONT of a core were steps before the core was found: compact.  (This relies on a reshape or a transpose
+     * never being part of a merged step -- no rule takes one --: a folded move inside a merged step would still run, and
+     * nhead_moves would count a layer that did) */
+    int kept = 0;
+    for (int k = 0; k < ds->nsteps; k++)
+        if (!(steps[k].rule == NULL && p.gone[steps[k].layer[0]])) steps[kept++] = steps[k];
+    ds->nsteps = kept;
+    free(p.gone);
+    return 1;
+}
+
 /* enqueue every step on the session stream, tensors resident in HBM */
 static int enqueue_layers(struct dev_session *ds, struct shl_ref_graph *g)
 {
     for (int k = 0; k < ds->nsteps; k++) {
         const struct step *s = &ds->steps[k];
-        struct shl_node *n = g->layer[s->a], *nx = s->b >= 0 ? g->layer[s->b] : NULL;
-        struct dev_tensor *in = lookup(ds, n->in[0]), *out = lookup(ds, s->out);
-        const int batch = in->shadow.dim[0];
-        int rc;
-        switch (s->kind) {
-            case STEP_POOL_CONV: {
-                struct csinn_tensor *pin = n->in[0]->data, *pmid = n->out[0]->data;
-                rc = status_of(shl_mi355x_pool_conv_forward(shl_mi355x_registry_get(nx->data), in->dev, out->dev, batch,
-                                                            pin->dim[1] * pin->dim[2], pin->qinfo->scale, pin->qinfo->zero_point,
-                                                            pmid->qinfo->scale, pmid->qinfo->zero_point, ds->stream));
-                break;
-            }
-            case STEP_CONV_POOL: { /* the pool reads what the convolution (+ folded activation) would have written */
-                struct csinn_tensor *pmid = nx->in[0]->data, *pout = nx->out[0]->data;
-                rc = status_of(shl_mi355x_conv_pool_forward(shl_mi355x_registry_get(n->data), in->dev, NULL, out->dev, batch,
-                                                            pmid->qinfo->scale, pmid->qinfo->zero_point, pout->qinfo->scale,
-                                                            pout->qinfo->zero_point, ds->stream));
-                break;
-            }
-            case STEP_MATMUL_BIAS: {
-                const int kb = linear_bias_input(n, nx, n->out[0]);
-                struct dev_tensor *b = lookup(ds, n->in[1]), *bias = kb >= 0 ? lookup(ds, nx->in[kb]) : NULL;
-                rc = b && bias ? shl_mi355x_matmul_bias_forward(n->in[0]->data, n->in[1]->data, n->out[0]->data, nx->in[kb]->data,
-                                                                nx->out[0]->data, n->data, kb == 0, in->dev, b->dev, bias->dev,
-                                                                out->dev, ds->stream)
-                               : CSINN_FALSE;
-                break;
-            }
-            case STEP_ATTENTION: {
-                const int chain[5] = {s->a, s->b, s->c, s->d, s->e}, len = s->d < 0 ? 3 : s->e < 0 ? 4 : 5;
-                struct shl_node *pv = g->layer[chain[len - 1]], *bias = NULL;
-                struct shl_mi355x_attention_desc ad;
-                struct shl_mi355x_attention_bias_desc abd;
-                struct dev_tensor *kk = lookup(ds, n->in[1]), *v = lookup(ds, pv->in[1]);
-                int k_swapped = 0;
-                if (!kk || !v || attention_chain(g, chain, len, 1, &ad, &abd, &bias, &k_swapped) != len) { /* (the plan has decided) */
-                    rc = CSINN_FALSE;
-                } else if (s->fold[0] || s->fold[1] || s->fold[2] || s->fold[3]) { /* through strides: the sources' buffers, the last folded layer's output */
-                    struct shl_mi355x_attention_layout_desc ld;
-                    struct shl_node *src[3], *dst = NULL;
-                    int fold4[4], runs[4][FOLD_MAX];
-                    struct dev_tensor *b = bias ? lookup(ds, bias) : NULL, *sq, *sk, *sv;
-                    if (attention_layout(g, chain, len, &ad, k_swapped, s->fold, fold4, runs, src, &dst, &ld) <= 0 || dst != s->out ||
-                        (bias && !b) || !(sq = lookup(ds, src[0])) || !(sk = lookup(ds, src[1])) || !(sv = lookup(ds, src[2])))
-                        rc = CSINN_FALSE;
-                    else
-                        rc = shl_mi355x_attention_layout_forward(&ad, bias ? &abd : NULL, &ld, sq->dev, sk->dev, sv->dev, b ? b->dev : NULL,
-                                                                 out->dev, ds->stream);
-                } else if (k_swapped) {
-                    rc = CSINN_FALSE; /* (a K without trans_b is merged only with its moves folded) */
-                } else if (bias != NULL) { /* a constant bias is resident like any constant operand of an add */
-                    struct dev_tensor *b = lookup(ds, bias);
-                    rc = b ? shl_mi355x_attention_bias_forward(&ad, &abd, in->dev, kk->dev, v->dev, b->dev, out->dev, ds->stream) : CSINN_FALSE;
-                } else {
-                    rc = shl_mi355x_attention_forward(&ad, in->dev, kk->dev, v->dev, out->dev, ds->stream);
-                }
-                break;
-            }
-            case STEP_CONV_ADD: { /* the add and the activation read what the convolution (+ folded activation) would have written */
-                struct shl_node *relu = s->c >= 0 ? g->layer[s->c] : NULL;
-                const int ks = s->d; /* the add's operand that is the skip tensor */
-                struct dev_tensor *skip = ks == 0 || ks == 1 ? lookup(ds, nx->in[ks]) : NULL;
-                if (skip == NULL) {
-                    rc = CSINN_FALSE;
-                    break;
-                }
-                struct csinn_tensor *tskip = nx->in[ks]->data, *tsum = nx->out[0]->data, *tout = relu ? relu->out[0]->data : tsum;
-                struct shl_mi355x_residual_desc rd = {ks == 1, tskip->qinfo->scale, tskip->qinfo->zero_point, tsum->qinfo->scale,
-                                                      tsum->qinfo->zero_point, relu ? (relu->type == CSINN_OP_RELU6 ? 2 : 1) : 0,
-                                                      tout->qinfo->scale, tout->qinfo->zero_point};
-                /* (the plan's dtype is the sum's: binary16 has entry points of its own, which read conv_first and act alone) */
-                rc = status_of(tsum->dtype == CSINN_DTYPE_FLOAT16
-                                   ? shl_mi355x_conv_add_f16_forward(shl_mi355x_registry_get(n->data), in->dev, skip->dev, out->dev, batch, &rd,
-                                                                     ds->stream)
-                                   : shl_mi355x_conv_add_forward(shl_mi355x_registry_get(n->data), in->dev, skip->dev, out->dev, batch, &rd,
-                                                                 ds->stream));
-                break;
-            }
-            case STEP_CONV_LUT: { /* the table's input is what the convolution (+ folded activation) would have written */
-                shl_mi355x_conv_plan *plan = shl_mi355x_registry_get(n->data);
-                rc = status_of(shl_mi355x_conv_plan_algo(plan) == SHL_MI355X_ALGO_DW
-                                   ? shl_mi355x_dwconv_lut_forward(plan, in->dev, out->dev, batch, s->lut, ds->stream)
-                                   : shl_mi355x_conv_lut_forward(plan, in->dev, out->dev, batch, s->lut, ds->stream));
-                break;
-            }
-            case STEP_PWDW:
-                rc = status_of(shl_mi355x_pwdw_forward(shl_mi355x_registry_get(n->data), shl_mi355x_registry_get(nx->data), in->dev,
-                                                       out->dev, batch, ds->stream));
-                break;
-            default:
-                rc = run_layer(ds, n, out);
+        struct shl_node *n = g->layer[s->layer[0]];
+        struct dev_tensor *in[STEP_SOURCES], *out = lookup(ds, s->out);
+        int rc = out ? CSINN_TRUE : CSINN_FALSE;
+        for (int i = 0; i < STEP_SOURCES; i++) {
+            in[i] = s->src[i] ? lookup(ds, s->src[i]) : NULL;
+            if (s->src[i] && in[i] == NULL) rc = CSINN_FALSE;
         }
+        if (rc == CSINN_TRUE) rc = s->rule ? s->rule->launch(ds, g, s, in, out) : run_layer(ds, n, out);
         if (rc != CSINN_TRUE) {
-            shl_debug_error("mi355x: layer %d (%s) failed while building the device graph\n", s->a, n->name ? n->name : "?");
+            shl_debug_error("mi355x: layer %d (%s) failed while building the device graph\n", s->layer[0], n->name ? n->name : "?");
             return CSINN_FALSE;
         }
     }
@@ -1094,67 +1129,45 @@ void shl_mi355x_session_deinit(struct csinn_session *sess)
     if (gref_deinit) gref_deinit(sess);
 }
 
-/* number of global_avgpool2d layers of `sess` that run inside the launch of the layer in front of or behind them */
-int shl_mi355x_session_fused_pools(struct csinn_session *sess)
+/* the planner's counters: how many steps of each rule `sess` has, and what else its plan folded */
+static int steps_of(struct csinn_session *sess, int rule)
 {
     struct dev_session *ds = find_session(sess);
-    return ds ? ds->npool : 0;
+    return ds ? ds->count[rule] : 0;
 }
 
-/* number of depthwise + pointwise pairs that run as one launch in `sess` */
-int shl_mi355x_session_fused_pairs(struct csinn_session *sess)
-{
-    struct dev_session *ds = find_session(sess);
-    return ds ? ds->nfused : 0;
-}
+/* global_avgpool2d layers that run inside the launch of the layer in front of or behind them */
+int shl_mi355x_session_fused_pools(struct csinn_session *sess) { return steps_of(sess, R_POOL_CONV) + steps_of(sess, R_CONV_POOL); }
+/* depthwise + pointwise pairs that run as one launch */
+int shl_mi355x_session_fused_pairs(struct csinn_session *sess) { return steps_of(sess, R_PAIR); }
+/* matmul layers that add the constant bias behind them inside their own launch */
+int shl_mi355x_session_fused_linears(struct csinn_session *sess) { return steps_of(sess, R_LINEAR); }
+/* Q K^T -> [scale] -> [+ bias] -> softmax -> P V chains that run as one launch */
+int shl_mi355x_session_fused_attentions(struct csinn_session *sess) { return steps_of(sess, R_ATTENTION); }
+/* convolution -> add -> [relu | relu6] tails of skip connections that run as one launch */
+int shl_mi355x_session_fused_residuals(struct csinn_session *sess) { return steps_of(sess, R_RESIDUAL); }
+/* table activations (gates included) that run inside their convolution's launch */
+int shl_mi355x_session_fused_activations(struct csinn_session *sess) { return steps_of(sess, R_TABLE); }
 
-/* number of relu / relu6 layers of `sess` that run inside the epilogue of the convolution in front of them */
+/* relu / relu6 layers that run inside the epilogue of the convolution in front of them */
 int shl_mi355x_session_folded_activations(struct csinn_session *sess)
 {
     struct dev_session *ds = find_session(sess);
     return ds ? ds->nfolded : 0;
 }
 
-/* number of matmul layers of `sess` that add the constant bias behind them inside their own launch */
-int shl_mi355x_session_fused_linears(struct csinn_session *sess)
-{
-    struct dev_session *ds = find_session(sess);
-    return ds ? ds->nlinear : 0;
-}
-
-/* number of Q K^T -> [scale] -> [+ bias] -> softmax -> P V chains of `sess` that run as one launch */
-int shl_mi355x_session_fused_attentions(struct csinn_session *sess)
-{
-    struct dev_session *ds = find_session(sess);
-    return ds ? ds->nattention : 0;
-}
-
-/* how many reshape / transpose layers around those cores run inside their launches (shl_mi355x_attention_layout) */
-int shl_mi355x_session_folded_head_moves(struct csinn_session *sess)
-{
-    struct dev_session *ds = find_session(sess);
-    return ds ? ds->nhead_moves : 0;
-}
-
-/* ... and how many of those carry the add of a bias or mask (shl_mi355x_attention_bias) */
+/* how many of the attention steps carry the add of a bias or mask (shl_mi355x_attention_bias) */
 int shl_mi355x_session_fused_attention_biases(struct csinn_session *sess)
 {
     struct dev_session *ds = find_session(sess);
     return ds ? ds->nattention_bias : 0;
 }
 
-/* number of convolution -> add -> [relu | relu6] tails of skip connections of `sess` that run as one launch */
-int shl_mi355x_session_fused_residuals(struct csinn_session *sess)
+/* how many reshape / transpose layers around attention cores run inside their launches (shl_mi355x_attention_layout) */
+int shl_mi355x_session_folded_head_moves(struct csinn_session *sess)
 {
     struct dev_session *ds = find_session(sess);
-    return ds ? ds->nresidual : 0;
-}
-
-/* number of table activations (gates included) of `sess` that run inside their convolution's launch */
-int shl_mi355x_session_fused_activations(struct csinn_session *sess)
-{
-    struct dev_session *ds = find_session(sess);
-    return ds ? ds->nactivation : 0;
+    return ds ? ds->nhead_moves : 0;
 }
 
 /* 2 when `sess` executes as one device-resident hipGraph, 1 when device-resident with every run enqueueing its layers
@@ -1163,4 +1176,27 @@ int shl_mi355x_session_is_device_resident(struct csinn_session *sess)
 {
     struct dev_session *ds = find_session(sess);
     return ds ? (ds->graph_exec ? 2 : 1) : 0;
+}
+
+/* the plan of `sess` as text: one line per step, then the folded-activation count */
+int shl_mi355x_session_describe(struct csinn_session *sess, char *buf, int len)
+{
+    struct dev_session *ds = find_session(sess);
+    int at = 0;
+    if (ds == NULL) return 0;
+#define PUT(...) at += snprintf(at < len ? buf + at : NULL, at < len ? (size_t)(len - at) : 0, __VA_ARGS__)
+    for (int k = 0; k < ds->nsteps; k++) {
+        const struct step *s = &ds->steps[k];
+        PUT("%s", s->rule ? s->rule->name : "layer");
+        for (int i = 0; i < s->nlayers; i++) PUT("%c%d", i ? ',' : ' ', s->layer[i]);
+        PUT(" -> %s", s->out->name ? s->out->name : "?");
+        if (s->rule == &rules[R_ATTENTION]) {
+            const int *fold = s->u.attention.fold;
+            PUT(" fold %d,%d,%d,%d bias %d", fold[0], fold[1], fold[2], fold[3], s->src[3] != NULL);
+        }
+        PUT("\n");
+    }
+    PUT("folded %d\n", ds->nfolded);
+#undef PUT
+    return at + 1;
 }

@@ -232,6 +232,11 @@ int shl_mi355x_session_fused_residuals(struct csinn_session *sess);
  * faster on (shl_mi355x_conv_lut_by_default, shl_mi355x_dwconv_lut_by_default); at setup SHL_MI355X_ACT_FUSE=1 merges every one the kernel takes,
  * SHL_MI355X_ACT_FUSE=0 or SHL_MI355X_NO_FUSION=1 keeps the layers apart */
 int shl_mi355x_session_fused_activations(struct csinn_session *sess);
+/* the plan of `sess` as text, for tests and for reading: one line per step in launch order -- the rule's name ("layer": a plain
+ * layer), the layers it stands for, " -> " and the name of the tensor it writes, for an attention step also the layers folded in
+ * front of q, k, v and behind the output and whether it carries a bias -- then "folded <n>", the count of folded activations.
+ * Writes at most len bytes, the terminator included; returns the length needed, 0 for a host-staged session */
+int shl_mi355x_session_describe(struct csinn_session *sess, char *buf, int len);
 
 #ifdef __cplusplus
 }

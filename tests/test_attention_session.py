@@ -7,6 +7,7 @@ faster on, which are all the planner merges unasked), as one hipGraph whose four
 bit, the same net built under SHL_MI355X_ATTENTION=0; the other planner counters do not move.  matmul_cases.attention_block
 (K = 32 at 17 tokens is the chain form's, and p is a graph output) and a net whose scaled scores have a second consumer keep
 their layers apart.  Also behind the genuine front-end and graph executor."""
+import ctypes as C
 import os
 import subprocess
 import sys
@@ -202,6 +203,44 @@ def test_the_class_fused_unasked_runs_and_equals_the_layers_apart(gpu, dtype, la
     spread = np.unique(mc.bits(res["p"])).size
     assert spread > 8, "the layers-apart p holds %d different values: it would tell nothing" % spread
     shown.close(fe)
+    net.close(fe)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("moves", ["0", "1"])
+def test_the_fused_step_survives_the_recapture_around_a_callers_hbm_buffer(gpu, moves, monkeypatch):
+    """update_input with a device pointer rebinds the graph input, and the session captures its steps again from what the plan
+    stored -- the core's descriptors and, with the moves folded, the layout's.  The int8 block runs on two inputs from host
+    buffers, then on fresh copies of them from the caller's HBM buffer: the same bytes, and the oracle chain's"""
+    fe, hip, opt = gpu
+    for var in ("SHL_MI355X_HOST_SESSION", "SHL_MI355X_MATMUL_FORM", "SHL_MI355X_NO_FUSION"):
+        monkeypatch.delenv(var, raising=False)
+    monkeypatch.setenv(SWITCH, "1")
+    monkeypatch.setenv("SHL_MI355X_ATTENTION_LAYOUT", moves)
+    net = attention_net("int8", "NHWC")
+    sess = net.build(fe, pkg.API_MI355X)
+    assert opt.shl_mi355x_session_is_device_resident(sess) == 2
+    assert opt.shl_mi355x_session_fused_attentions(sess) == 1
+    assert opt.shl_mi355x_session_folded_head_moves(sess) == (8 if moves == "1" else 0)
+    from_host = [net.run(fe, net.input(k))["out"] for k in (0, 1)]
+    dev = cases.HipDevice(hip)
+    d_in = dev.alloc(net.input(0).nbytes)
+    scale, zp = net.rec("x")
+    feed = pkg.make_tensor(fe, net._keep, net.shape("x"), pkg.DTYPE_INT8, pkg.LAYOUT_NHWC, sess=sess, scales=(scale,), zps=(zp,), device_ptr=d_in)
+    got = pkg.make_tensor(fe, net._keep, (1,), pkg.DTYPE_INT8, pkg.LAYOUT_NHWC, sess=sess)
+    for k in (1, 0):
+        dev.upload(d_in, net.input(k))
+        fe.csinn_update_input(0, feed, sess)
+        assert fe.csinn_session_run(sess) == pkg.CSINN_TRUE  # (the first of them captures again)
+        assert opt.shl_mi355x_session_is_device_resident(sess) == 2
+        fe.csinn_get_output(0, got, sess)
+        shape = net.shape("out")
+        res = np.ctypeslib.as_array(C.cast(got.contents.data, C.POINTER(C.c_int8)), (int(np.prod(shape)),)).copy().reshape(shape)
+        fe.shl_mem_free(got.contents.data)
+        assert np.array_equal(res, from_host[k]), "input %d: from the caller's HBM buffer vs from a host buffer" % k
+        assert np.array_equal(res, net.oracle(net.input(k))["out"]), "input %d: the output differs from the oracle chain" % k
+    assert not np.array_equal(from_host[0], from_host[1]), "the two inputs must tell runs apart"
+    dev.free(d_in)
     net.close(fe)
 
 
