@@ -397,6 +397,7 @@ def load_hip():
         "shl_mi355x_pwdw_fusable": (C.c_int, [vp, vp, i32]),
         "shl_mi355x_pwdw_form": (C.c_int, [vp, vp, i32]),
         "shl_mi355x_pwdw_geometry": (C.c_int, [vp, vp, i32, C.POINTER(i32), i32]),
+        "shl_mi355x_pwdw_launch_form": (C.c_int, [vp, vp, i32, C.POINTER(i32), i32]),
         "shl_mi355x_pool_conv_fusable": (C.c_int, [vp, i32, i32]),
         "shl_mi355x_pool_conv_forward": (C.c_int, [vp, vp, vp, i32, i32, f32, i32, f32, i32, vp]),
         "shl_mi355x_conv_pool_fusable": (C.c_int, [vp, i32]),

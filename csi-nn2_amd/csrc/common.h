@@ -590,6 +590,8 @@ bool pwdw_fusable(const ConvArgs &pw, const ConvArgs &dw, int pw_is_igemm, int d
 int launch_pwdw_fused(const ConvArgs &pw, const ConvArgs &dw, hipStream_t s);
 constexpr int SHL_PWDW_GEOMETRY_FIELDS = 12;  // shl_mi355x_pwdw_geometry (shl_mi355x.h)
 bool pwdw_fused_geometry(const ConvArgs &pw, const ConvArgs &dw, int32_t out[SHL_PWDW_GEOMETRY_FIELDS]);
+constexpr int SHL_PWDW_LAUNCH_FIELDS = 5;  // shl_mi355x_pwdw_launch_form (shl_mi355x.h)
+bool pwdw_fused_launch_form(const ConvArgs &pw, const ConvArgs &dw, int32_t out[SHL_PWDW_LAUNCH_FIELDS]);
 // binary16 NCHW: the 3-channel stem + the depthwise 3x3 consuming it in one launch (stemdw_f16_nchw.hip)
 bool stemdw_f16_nchw_fusable(const ConvArgs &stem, const ConvArgs &dw);
 int launch_stemdw_f16_nchw(const ConvArgs &stem, const ConvArgs &dw, hipStream_t s);

@@ -1532,6 +1532,29 @@ int shl_mi355x_pwdw_geometry(const shl_mi355x_conv_plan *pw, const shl_mi355x_co
     return SHL_MI355X_OK;
 }
 
+int shl_mi355x_pwdw_launch_form(const shl_mi355x_conv_plan *pw, const shl_mi355x_conv_plan *dw, int32_t batch, int32_t *out, int32_t count)
+{
+    using namespace shl;
+    if (!out || count < SHL_PWDW_LAUNCH_FIELDS) {
+        set_error("pwdw_launch_form: room for 5 values is needed");
+        return SHL_MI355X_EINVAL;
+    }
+    if (shl_mi355x_pwdw_form(pw, dw, batch) != 1) {
+        set_error("pwdw_launch_form: the pair does not run the latency form");
+        return SHL_MI355X_ENOTSUP;
+    }
+    ConvArgs a, b;
+    static char dummy[16];
+    int rc = fill_args(pw, dummy, dummy, batch, a);
+    if (rc == SHL_MI355X_OK) rc = fill_args(dw, dummy, dummy, batch, b);
+    if (rc != SHL_MI355X_OK) return rc;
+    if (!pwdw_fused_launch_form(a, b, out)) {
+        set_error("pwdw_launch_form: the pair does not qualify");
+        return SHL_MI355X_ENOTSUP;
+    }
+    return SHL_MI355X_OK;
+}
+
 int shl_mi355x_pwdw_forward(const shl_mi355x_conv_plan *pw, const shl_mi355x_conv_plan *dw, const void *input_dev,
                             void *output_dev, int32_t batch, void *stream)
 {

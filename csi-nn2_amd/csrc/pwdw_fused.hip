@@ -125,15 +125,22 @@ constexpr int PWDW_PAD_DWORDS = 3;
 // in LDS slots nothing reads: the host sizes the partial-sum area for the padded count): no tile guards around the loads, the
 // MFMAs and the LDS writes (four scalar instructions per MFMA in the generic form), the sums over the K parts unrolled.
 // 0: run-time values (eight waves, deeper patches).
-// EMT: the window has exactly TPW 4 / KSV tiles (the finishing loop's trip count is a compile-time value as well: 0.1 us per launch).
+// NT: the window's true tile count as a compile-time value, 0: read at run time.  With it the patch slot of every tile is computed
+// in the MFMAs' block and the finishing between the two barriers is straight-line code, two tiles per round, an odd NT's last tile
+// alone: no row / column division, no window test and no branch there (the run-time count's finishing loop is ~104 instructions per
+// two tiles against 30 - 38 per tile: profiles/pwdw_nt_notes.md).  The waves still run TPW tiles each; the rounds past NT are
+// dummies as above, and the padding fill covers NT tiles' worth of patch.  Two __global__ templates below instantiate the body:
+// pwdw_fused_kernel (its EMT = true: NT = TPW 4 / KSV, its EMT = false: NT = 0) and pwdw_fused_nt_kernel (any other NT).
 // EPQ / EPD: the two layers' epilogue flavours (common.h; -1: chosen at run time) -- with all four flavours of three requantisation
 // sites inline the kernel is 1 500 instructions, a third of which one launch runs, fetched cold by every workgroup.
-template <int MTW, int NSW, int MAXT, bool EXACT, int KSV = 0, int TPW = 0, bool EMT = false, int EPQ = -1, int EPD = -1>
-__global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
+template <int MTW, int NSW, int MAXT, bool EXACT, int KSV, int TPW, int NT, int EPQ, int EPD>
+__device__ __forceinline__ void pwdw_fused_body(const PwDwArgs &f)
 {
     static_assert((KSV == 0) == (TPW == 0) && (TPW == 0 || (TPW == MTW && EXACT)), "pwdw_fused: KSV and TPW come together, with MTW = TPW");
     constexpr bool FIXED = TPW != 0;
     constexpr int NFT_ALL = FIXED ? TPW * (4 / (KSV ? KSV : 1)) : 1;  // tiles the compile-time forms run
+    constexpr bool CT = NT != 0;                                      // the window's tile count is a compile-time value
+    static_assert(!CT || (FIXED && NT <= NFT_ALL && NT > NFT_ALL - 4 / (KSV ? KSV : 1)), "pwdw_fused: NT tiles take exactly TPW rounds of the wave groups");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const ConvArgs &q = f.pw;
     const ConvArgs &d = f.dw;
@@ -165,7 +172,21 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
     // behind the MFMAs and the barriers -- four exposed scalar round trips.  They get a batch of their own BEHIND the fragment loads:
     // "the shadow" below.)
     int slice = blockIdx.x, tx = blockIdx.y, ty = blockIdx.z;
-    {
+    // (the uneven NT forms split the rectangle into its row and column BEHIND the weight loads, which need the slice only: their
+    // first load must stand no later than in the padded forms they replace -- tests/test_pwdw_nt_build.py -- and their
+    // straight-line finishing changes how the compiler lays out the exit below.  The older forms keep their text, and with it their code.)
+    constexpr bool LATE_RECT = CT && NT != NFT_ALL;
+    int late_rect = 0;
+    if constexpr (LATE_RECT) {
+        const int L = blockIdx.x;
+        const int x = L & 7, j = L >> 3;
+        const int b = (int)(((uint32_t)j * e.spg_magic) >> 20);
+        const int xslice = (x & (e.xg - 1)) * e.spg + (j - b * e.spg);
+        late_rect = b * (8 >> e.xg_log2) + (x >> e.xg_log2);
+        const bool mapped = e.xg != 0;
+        if (mapped && late_rect >= e.nrect) return;
+        slice = mapped ? xslice : slice;
+    } else {
         // (computed whether or not the grid is XCD-mapped and then selected: inside `if (xg)` the fields below were fetched
         // from the kernel arguments in two further dependent s_load / s_waitcnt round trips, ~200 cycles each)
         const int L = blockIdx.x;
@@ -191,7 +212,7 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
     const int mw = wave >> (FIXED ? (KSV == 4 ? 2 : (KSV == 2 ? 1 : 0)) : f.ks_log2);  // wave group over tiles
     const int mwn = FIXED ? 4 / (KSV ? KSV : 1) : f.mwn;                                // number of wave groups = nwaves / ks
     const int mtp = FIXED ? TPW * (4 / (KSV ? KSV : 1)) : e.mt;                         // tiles the waves run (padded)
-    const int mt = (FIXED && EMT) ? mtp : e.mt;                                         // tiles of the patch
+    const int mt = CT ? NT : e.mt;                                                      // tiles of the patch
     const int sub0 = kpart * (EXACT ? NSW : e.nsw);         // (EXACT: every wave has NSW sub-steps, nsub = ks NSW)
     const int nsub = FIXED ? KSV * NSW : e.nsub;
     int nsw = NSW;
@@ -209,6 +230,12 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
     for (int s = 0; s < NSW; ++s)
         if (s < nsw) fa[s] = *(GlobalV4)(wp + s * wstep);
     if constexpr (FIXED) __builtin_amdgcn_sched_barrier(0);  // (the weight fragments are requested before anything of the pixel addresses is computed)
+    if constexpr (LATE_RECT) {
+        const int xty = (int)(((uint32_t)late_rect * e.tx_magic) >> 20);
+        const int xtx = late_rect - xty * e.tiles_x;
+        ty = e.xg != 0 ? xty : ty;
+        tx = e.xg != 0 ? xtx : tx;
+    }
     // the image: ty counts the rectangle rows of all images.  Without a branch (a division by a magic, and at batch 1 a product
     // with zero): the conditional forms stood in front of the weight loads as three blocks and eleven instructions.
     int n = (int)__umulhi((uint32_t)ty, e.ty_magic);
@@ -300,9 +327,9 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
     const int wslot0 = (wy0 - ry0) * fl.rw + (wx0 - rx0) + (2 * fgrp + fhalf) * ppitch;
     auto win_has = [&](int r, int c) { return wy0 + r < wye && wx0 + c < wxe; };
     auto win_slot = [&](int r, int c) { return (uint32_t)(wslot0 + r * fl.rw + c); };
-    constexpr int NFT = (FIXED && EMT) ? TPW * (4 / (KSV ? KSV : 1)) : 1;  // compile-time tile rounds
+    constexpr int NFT = CT ? NT : 1;  // compile-time tile rounds
     uint32_t fslot[NFT];  // per tile: the dword slot of this lane's pixel
-    if constexpr (FIXED && EMT) {
+    if constexpr (CT) {
         const uint32_t spare = (uint32_t)((2 * fgrp + fhalf) * ppitch + ppitch - 1);
 #pragma unroll
         for (int t = 0; t < NFT; ++t) {
@@ -320,7 +347,7 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
     uint32_t *patch = reinterpret_cast<uint32_t *>(smem + (size_t)mtp * ks * 4096);  // eight dword planes (dw_patch.h)
     if constexpr (FIXED) {
 #pragma unroll
-        for (int k = 0; k < PWDW_PAD_DWORDS * NFT_ALL; ++k) patch[tid + 256 * k] = zpad;
+        for (int k = 0; k < PWDW_PAD_DWORDS * (CT ? NT : NFT_ALL); ++k) patch[tid + 256 * k] = zpad;
     } else {
         for (int i = tid; i < 8 * ppitch; i += nwaves * 64) patch[i] = zpad;
     }
@@ -379,7 +406,7 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
     {
         // the window's pixels only: the rest of the patch holds the padding value since the shadow
         auto put = [&](int tile, int j, uint32_t pk) {
-            if constexpr (FIXED && EMT) {
+            if constexpr (CT) {
                 patch[fslot[tile]] = pk;
             } else {
                 int r, c;
@@ -388,29 +415,37 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
             }
         };
         const int tstep = nwaves >> 2;
-        for (int tile = FIXED ? 0 : wave >> 2; tile < mt; tile += 2 * tstep) {  // (four waves: wave >> 2 = 0)
-            const int tile1 = tile + tstep;
-            const int j0 = tile * 32 + frow;
-            v4i v0 = part[((tile * ks) * 4 + fgrp) * 64 + lane];
-            if (tile1 < mt) {
-                v4i v1 = part[((tile1 * ks) * 4 + fgrp) * 64 + lane];
+        // one round, as text: the uneven NT forms below unroll their rounds whatever they cost (five tiles with the four run-time
+        // flavours inline were left a loop), every older form keeps the loop it had -- as a lambda, the round changed their code
+#define SHL_PWDW_ROUND(tile)                                                                                                              \
+    {                                                                                                                                     \
+        const int tile1 = tile + tstep;                                                                                                   \
+        const int j0 = tile * 32 + frow;                                                                                                  \
+        v4i v0 = part[((tile * ks) * 4 + fgrp) * 64 + lane];                                                                              \
+        if (tile1 < mt) {                                                                                                                 \
+            v4i v1 = part[((tile1 * ks) * 4 + fgrp) * 64 + lane];                                                                         \
+            _Pragma("unroll") for (int k = 1; k < ks; ++k) {                                                                              \
+                v0 += part[((tile * ks + k) * 4 + fgrp) * 64 + lane];                                                                     \
+                v1 += part[((tile1 * ks + k) * 4 + fgrp) * 64 + lane];                                                                    \
+            }                                                                                                                             \
+            const uint32_t pk0 = requant4_i8_sel<EPQ>(v0[0] + p_ai.x, v0[1] + p_ai.y, v0[2] + p_ai.z, v0[3] + p_ai.w, p_mu, p_bi, ql);   \
+            const uint32_t pk1 = requant4_i8_sel<EPQ>(v1[0] + p_ai.x, v1[1] + p_ai.y, v1[2] + p_ai.z, v1[3] + p_ai.w, p_mu, p_bi, ql);   \
+            const int j1 = tile1 * 32 + frow;                                                                                             \
+            put(tile, j0, pk0);                                                                                                           \
+            put(tile1, j1, pk1);                                                                                                          \
+        } else { /* the odd last tile alone (it used to be computed twice: ~50 instructions of a wave that issues one per ~5.8 cycles) */ \
+            _Pragma("unroll") for (int k = 1; k < ks; ++k) v0 += part[((tile * ks + k) * 4 + fgrp) * 64 + lane];                         \
+            const uint32_t pk0 = requant4_i8_sel<EPQ>(v0[0] + p_ai.x, v0[1] + p_ai.y, v0[2] + p_ai.z, v0[3] + p_ai.w, p_mu, p_bi, ql);   \
+            put(tile, j0, pk0);                                                                                                           \
+        }                                                                                                                                 \
+    }
+        if constexpr (LATE_RECT) {
 #pragma unroll
-                for (int k = 1; k < ks; ++k) {
-                    v0 += part[((tile * ks + k) * 4 + fgrp) * 64 + lane];
-                    v1 += part[((tile1 * ks + k) * 4 + fgrp) * 64 + lane];
-                }
-                const uint32_t pk0 = requant4_i8_sel<EPQ>(v0[0] + p_ai.x, v0[1] + p_ai.y, v0[2] + p_ai.z, v0[3] + p_ai.w, p_mu, p_bi, ql);
-                const uint32_t pk1 = requant4_i8_sel<EPQ>(v1[0] + p_ai.x, v1[1] + p_ai.y, v1[2] + p_ai.z, v1[3] + p_ai.w, p_mu, p_bi, ql);
-                const int j1 = tile1 * 32 + frow;
-                put(tile, j0, pk0);
-                put(tile1, j1, pk1);
-            } else {  // the odd last tile alone (it used to be computed twice: ~50 instructions of a wave that issues one per ~5.8 cycles)
-#pragma unroll
-                for (int k = 1; k < ks; ++k) v0 += part[((tile * ks + k) * 4 + fgrp) * 64 + lane];
-                const uint32_t pk0 = requant4_i8_sel<EPQ>(v0[0] + p_ai.x, v0[1] + p_ai.y, v0[2] + p_ai.z, v0[3] + p_ai.w, p_mu, p_bi, ql);
-                put(tile, j0, pk0);
-            }
+            for (int tile = 0; tile < NT; tile += 2) SHL_PWDW_ROUND(tile)
+        } else {
+            for (int tile = FIXED ? 0 : wave >> 2; tile < mt; tile += 2 * tstep) SHL_PWDW_ROUND(tile)  // (four waves: wave >> 2 = 0)
         }
+#undef SHL_PWDW_ROUND
     }
     __syncthreads();
 
@@ -418,6 +453,22 @@ __global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
         if (q.debug & 1024) return;  // ablation: stop after the pointwise epilogue
     // ---- depthwise 3x3 on the slice's 32 channels, from the LDS patch (dw_patch.h)
     depthwise_from_patch<EPD>(dl, patch, g, dwk, dwp, tid, nwaves * 64);
+}
+
+// the run-time form (KSV = TPW = 0) and the fixed forms whose tile count is TPW 4 / KSV (EMT) or padded to it (the body above)
+template <int MTW, int NSW, int MAXT, bool EXACT, int KSV = 0, int TPW = 0, bool EMT = false, int EPQ = -1, int EPD = -1>
+__global__ __launch_bounds__(MAXT) void pwdw_fused_kernel(PwDwArgs f)
+{
+    pwdw_fused_body<MTW, NSW, MAXT, EXACT, KSV, TPW, (TPW != 0 && EMT) ? TPW * (4 / (KSV ? KSV : 1)) : 0, EPQ, EPD>(f);
+}
+
+// the fixed forms of a window of NT tiles, NT no multiple of the 4 / KSV wave groups: ceil(NT / (4 / KSV)) tiles per wave
+template <int NSW, int KSV, int NT, int EPQ = -1, int EPD = -1>
+__global__ __launch_bounds__(512) void pwdw_fused_nt_kernel(PwDwArgs f)
+{
+    constexpr int TPW = (NT + 4 / KSV - 1) / (4 / KSV);
+    static_assert(NT % (4 / KSV) != 0, "pwdw_fused: an even tile count is pwdw_fused_kernel's EMT form");
+    pwdw_fused_body<TPW, NSW, 512, true, KSV, TPW, NT, EPQ, EPD>(f);
 }
 
 // ---- host side ---------------------------------------------------------------------------------
@@ -622,6 +673,51 @@ bool pwdw_fused_geometry(const ConvArgs &q, const ConvArgs &d, int32_t out[SHL_P
     return true;
 }
 
+// Which instantiation a geometry launches (launch_pwdw_fused, pwdw_fused_launch_form).  The fixed forms: four waves, every wave
+// exactly nsw sub-steps and tpw tiles, K split ks; `tiles` is the count the form was compiled for -- tpw 4 / ks (the window has
+// exactly as many: FIXED_EXACT, or fewer: FIXED_PADDED, which reads the true count at run time) or the window's own uneven count (NT).
+struct PwDwForm {
+    int kind;  // SHL_MI355X_PWDW_LAUNCH_*
+    int nsw, ks, tpw, tiles;
+    size_t lds;  // bytes of LDS of a fixed form: partial sums of the tiles the waves run + the area the padding fill covers
+};
+// (NSW, KS, TPW) of the pwdw_fused_kernel forms and (NSW, KS, NT) of the pwdw_fused_nt_kernel forms: what launch_pwdw_fused instantiates
+static const int PWDW_FIXED_FORMS[][3] = {{4, 4, 2}, {4, 4, 1}, {2, 4, 2}, {2, 4, 1}, {2, 2, 2}, {2, 2, 1}, {2, 1, 1}, {2, 1, 2}, {1, 1, 1}, {1, 1, 2}};
+// An uneven count arises for ks = 1 (1 - 3, 5 - 7 tiles) and ks = 2 (1, 3 tiles) only.  Instantiated: MobileNetV1's 32 -> 64 @112
+// stride 2 (5 tiles), 64 -> 128 @56 (3) and 128 -> 128 @56 stride 2 (3, ks 2); the rest keeps the padded forms.
+static const int PWDW_NT_FORMS[][3] = {{1, 1, 5}, {2, 1, 3}, {2, 2, 3}};
+static PwDwForm choose_form(const PwDwArgs &f)
+{
+    PwDwForm r = {SHL_MI355X_PWDW_LAUNCH_RUNTIME, 0, 0, 0, 0, 0};
+    const char *nofix = getenv("SHL_MI355X_PWDW_GENERIC");  // "1": the run-time form everywhere (A/B, tests; read per call)
+    if ((nofix && nofix[0] == '1') || f.nwaves != 4) return r;
+    const size_t patch = dw_patch_bytes(f.late.npx);
+    for (const auto &k : PWDW_FIXED_FORMS) {
+        const int nsw = k[0], ks = k[1], tpw = k[2], t = tpw * (4 / ks);
+        if (f.nsw != nsw || f.nsub != ks * nsw || f.ks != ks || f.mt > t || f.mt <= t - 4 / ks || patch > (size_t)1024 * PWDW_PAD_DWORDS * t) continue;
+        r = {f.mt == t ? SHL_MI355X_PWDW_LAUNCH_FIXED_EXACT : SHL_MI355X_PWDW_LAUNCH_FIXED_PADDED, nsw, ks, tpw, t, (size_t)t * (ks * 4096 + 1024 * PWDW_PAD_DWORDS)};
+        for (const auto &n : PWDW_NT_FORMS)
+            // the fill covers NT tiles' worth of patch; the partial sums keep room for the dummy rounds' tiles
+            if (n[0] == nsw && n[1] == ks && n[2] == f.mt && patch <= (size_t)1024 * PWDW_PAD_DWORDS * f.mt) {
+                r.kind = SHL_MI355X_PWDW_LAUNCH_NT, r.tiles = f.mt;
+                r.lds = (size_t)t * ks * 4096 + (size_t)1024 * PWDW_PAD_DWORDS * f.mt;
+            }
+        return r;
+    }
+    return r;
+}
+
+// what launch_pwdw_fused would launch for the pair (tests, tools): the kind of form and what it was compiled for
+bool pwdw_fused_launch_form(const ConvArgs &q, const ConvArgs &d, int32_t out[SHL_PWDW_LAUNCH_FIELDS])
+{
+    PwDwArgs f;
+    if (!shapes_pair(q, d) || !choose_rect(q, d, f)) return false;
+    const PwDwForm r = choose_form(f);
+    const int32_t v[SHL_PWDW_LAUNCH_FIELDS] = {r.kind, r.nsw, r.ks, r.tpw, r.tiles};
+    for (int i = 0; i < SHL_PWDW_LAUNCH_FIELDS; ++i) out[i] = v[i];
+    return true;
+}
+
 // the early block: copies of what the kernel's prologue reads (PwDwEarlyArgs), from the two layers and the chosen geometry
 static void fill_early(const ConvArgs &q, const ConvArgs &d, PwDwArgs &f)
 {
@@ -654,12 +750,13 @@ int launch_pwdw_fused(const ConvArgs &q, const ConvArgs &d, hipStream_t s)
         grid = dim3((unsigned)(8 * f.spg * ((f.nrect + rpg - 1) / rpg)), 1, 1);
     }
     size_t lds = (size_t)f.mt * f.ks * 4096 + dw_patch_bytes(f.late.npx);
+    const PwDwForm form = choose_form(f);
     {
         static const char *pr = getenv("SHL_MI355X_PWDW_PRINT");  // "1": the geometry of every launch (tools/dev)
         if (pr && pr[0] == '1')
-            fprintf(stderr, "pwdw_fused %d->%d @%dx%d s%d: %dx%d rects of %dx%d (+%d/+%d, +%d/+%d at the borders), npx %d, nwin %d, mt %d, ks %d, nsw %d, nsub %d, mwn %d, xg %d, grid %u\n",
+            fprintf(stderr, "pwdw_fused %d->%d @%dx%d s%d: %dx%d rects of %dx%d (+%d/+%d, +%d/+%d at the borders), npx %d, nwin %d, mt %d, ks %d, nsw %d, nsub %d, mwn %d, xg %d, grid %u, form %d (%d tiles)\n",
                     q.C, q.Co, d.H, d.W, d.sh, f.tiles_y, f.tiles_x, f.bh, f.bw, f.ey_lo, f.ey_hi, f.ex_lo, f.ex_hi, f.late.npx, f.nwin, f.mt, f.ks, f.nsw, f.nsub,
-                    f.mwn, f.xg, grid.x * grid.y * grid.z);
+                    f.mwn, f.xg, grid.x * grid.y * grid.z, form.kind, form.tiles);
     }
 #define SHL_PWDW2(NSWV, MAXT, EX)                                                                                    \
     do {                                                                                                       \
@@ -673,35 +770,39 @@ int launch_pwdw_fused(const ConvArgs &q, const ConvArgs &d, hipStream_t s)
         if (f.nsw == NSWV && f.nsub == f.ks * NSWV) SHL_PWDW2(NSWV, MAXT, true); \
         else SHL_PWDW2(NSWV, MAXT, false);                            \
     } while (0)
-    // the fully specialised forms: four waves, every wave exactly NSWV sub-steps and TPWV tiles, K split KSV (MobileNetV1 at batch
-    // 1: nine of its twelve pairs)
+    // the fully specialised forms: four waves, every wave exactly NSWV sub-steps and TPWV tiles, K split KSV (choose_form;
+    // MobileNetV1 at batch 1: nine of its twelve pairs on the forms with exactly TPWV 4 / KSV tiles, the other three -- 5, 3 and
+    // 3 tiles -- on the NT forms)
     // ... with both layers' epilogues compiled in for the two flavours whole models come in: clamp epilogues with power-of-two
     // output scales (3) and with general scales (0)
     const int epq = (q.act != SHL_MI355X_ACT_NONE && !q.act_clamp) ? -1 : (q.div_exact ? 3 : 0);
     const int epd = (d.act != SHL_MI355X_ACT_NONE && !d.act_clamp) ? -1 : (d.div_exact ? 3 : 0);
-#define SHL_PWDW_EPI(TPWV, NSWV, KSV, EMTV)                                                                              \
-    do {                                                                                                                \
-        if (epq == 3 && epd == 3)                                                                                       \
-            hipLaunchKernelGGL((pwdw_fused_kernel<TPWV, NSWV, 512, true, KSV, TPWV, EMTV, 3, 3>), grid, dim3(256), lds, s, f); \
-        else if (epq == 0 && epd == 0)                                                                                  \
-            hipLaunchKernelGGL((pwdw_fused_kernel<TPWV, NSWV, 512, true, KSV, TPWV, EMTV, 0, 0>), grid, dim3(256), lds, s, f); \
-        else                                                                                                            \
-            hipLaunchKernelGGL((pwdw_fused_kernel<TPWV, NSWV, 512, true, KSV, TPWV, EMTV>), grid, dim3(256), lds, s, f);    \
+#define SHL_PWDW_EPI(KERNEL, ...)                                                                  \
+    do {                                                                                           \
+        if (epq == 3 && epd == 3)                                                                  \
+            hipLaunchKernelGGL((KERNEL<__VA_ARGS__, 3, 3>), grid, dim3(256), lds, s, f);           \
+        else if (epq == 0 && epd == 0)                                                             \
+            hipLaunchKernelGGL((KERNEL<__VA_ARGS__, 0, 0>), grid, dim3(256), lds, s, f);           \
+        else                                                                                       \
+            hipLaunchKernelGGL((KERNEL<__VA_ARGS__>), grid, dim3(256), lds, s, f);                 \
+        SHL_HIP(hipGetLastError());                                                                \
+        return SHL_MI355X_OK;                                                                      \
     } while (0)
-#define SHL_PWDW_FIXED(NSWV, KSV, TPWV)                                                                                  \
-    if (f.nwaves == 4 && f.nsw == NSWV && f.nsub == KSV * NSWV && f.ks == KSV && f.mt <= TPWV * (4 / KSV) &&            \
-        f.mt > (TPWV - 1) * (4 / KSV) && dw_patch_bytes(f.late.npx) <= (size_t)1024 * PWDW_PAD_DWORDS * (TPWV * (4 / KSV))) {                                                                         \
-        /* partial sums of the padded tiles + the area the padding fill covers */                                       \
-        lds = (size_t)(TPWV * (4 / KSV)) * (f.ks * 4096 + 1024 * PWDW_PAD_DWORDS);                                        \
-        if (f.mt == TPWV * (4 / KSV))                                                                                   \
-            SHL_PWDW_EPI(TPWV, NSWV, KSV, true);                                                                        \
-        else                                                                                                            \
-            SHL_PWDW_EPI(TPWV, NSWV, KSV, false);                                                                       \
-        SHL_HIP(hipGetLastError());                                                                                     \
-        return SHL_MI355X_OK;                                                                                           \
+#define SHL_PWDW_FIXED(NSWV, KSV, TPWV)                                                            \
+    if (form.kind != SHL_MI355X_PWDW_LAUNCH_NT && form.nsw == NSWV && form.ks == KSV && form.tpw == TPWV) { \
+        if (form.kind == SHL_MI355X_PWDW_LAUNCH_FIXED_EXACT)                                       \
+            SHL_PWDW_EPI(pwdw_fused_kernel, TPWV, NSWV, 512, true, KSV, TPWV, true);               \
+        else                                                                                       \
+            SHL_PWDW_EPI(pwdw_fused_kernel, TPWV, NSWV, 512, true, KSV, TPWV, false);              \
     }
-    const char *nofix = getenv("SHL_MI355X_PWDW_GENERIC");  // "1": the run-time form everywhere (A/B, tests; read per call)
-    if (!(nofix && nofix[0] == '1')) {
+#define SHL_PWDW_NT(NSWV, KSV, NTV)                                                                \
+    if (form.kind == SHL_MI355X_PWDW_LAUNCH_NT && form.nsw == NSWV && form.ks == KSV && form.tiles == NTV) \
+        SHL_PWDW_EPI(pwdw_fused_nt_kernel, NSWV, KSV, NTV);
+    if (form.kind != SHL_MI355X_PWDW_LAUNCH_RUNTIME) {
+        lds = form.lds;
+        SHL_PWDW_NT(1, 1, 5)
+        SHL_PWDW_NT(2, 1, 3)
+        SHL_PWDW_NT(2, 2, 3)
         SHL_PWDW_FIXED(4, 4, 2)
         SHL_PWDW_FIXED(4, 4, 1)
         SHL_PWDW_FIXED(2, 4, 2)
@@ -712,7 +813,10 @@ int launch_pwdw_fused(const ConvArgs &q, const ConvArgs &d, hipStream_t s)
         SHL_PWDW_FIXED(2, 1, 2)
         SHL_PWDW_FIXED(1, 1, 1)
         SHL_PWDW_FIXED(1, 1, 2)
+        set_error("pwdw_fused: choose_form names a form that is not instantiated");  // (its tables and the lists above differ)
+        return SHL_MI355X_ENOTSUP;
     }
+#undef SHL_PWDW_NT
 #undef SHL_PWDW_FIXED
 #undef SHL_PWDW_EPI
     if (f.nsw <= 2)

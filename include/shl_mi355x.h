@@ -447,6 +447,18 @@ int shl_mi355x_pwdw_form(const shl_mi355x_conv_plan *pw, const shl_mi355x_conv_p
  * 32-pixel MFMA tiles per workgroup, K split, pixels of the largest in-image window, workgroups of the launch.  `count` >= 12.
  * SHL_MI355X_ENOTSUP when the pair runs another form or none. */
 int shl_mi355x_pwdw_geometry(const shl_mi355x_conv_plan *pw, const shl_mi355x_conv_plan *dw, int32_t batch, int32_t *out, int32_t count);
+/* which instantiation of the latency form (1) would launch for the pair, read-only, for tools and tests: out[0] = one of the
+ * kinds below, out[1..4] = what a fixed form was compiled for -- K sub-steps per wave, K split, tiles per wave, tiles per window
+ * (all 0 for the run-time form).  FIXED_EXACT: the window has exactly tiles-per-wave x wave-groups tiles; FIXED_PADDED: fewer, the
+ * form reads the count at run time; NT: the window's own, uneven count is compiled in.  SHL_MI355X_PWDW_GENERIC=1 gives RUNTIME
+ * everywhere.  `count` >= 5.  SHL_MI355X_ENOTSUP when the pair runs another form or none. */
+enum {
+    SHL_MI355X_PWDW_LAUNCH_RUNTIME = 0,
+    SHL_MI355X_PWDW_LAUNCH_FIXED_PADDED = 1,
+    SHL_MI355X_PWDW_LAUNCH_FIXED_EXACT = 2,
+    SHL_MI355X_PWDW_LAUNCH_NT = 3
+};
+int shl_mi355x_pwdw_launch_form(const shl_mi355x_conv_plan *pw, const shl_mi355x_conv_plan *dw, int32_t batch, int32_t *out, int32_t count);
 int shl_mi355x_pwdw_forward(const shl_mi355x_conv_plan *pw, const shl_mi355x_conv_plan *dw,
                             const void *input_dev, void *output_dev, int32_t batch, void *stream);
 
