@@ -562,6 +562,9 @@ void dwconv_dot4_pack(const shl_mi355x_conv_desc &d, const int8_t *hwo, uint32_t
 // depthwise 3x3 int8 NHWC on the matrix cores for bandwidth-bound sizes (dwconv_mfma.hip)
 bool dwconv_mfma_pick(int64_t M, int C, int H, int W, int Ho, int Wo, int sh, int sw);
 int launch_dwconv_mfma(const ConvArgs &a, hipStream_t s);
+// depthwise Kh x Kw (1..7, not 3x3) int8 NHWC on the matrix cores, taps outermost (dwconv_kxk.hip); N: the batch behind M
+bool dwconv_kxk_pick(int64_t M, int N, int C, int H, int W, int Ho, int Wo, int Kh, int Kw, int sh, int sw);
+int launch_dwconv_kxk(const ConvArgs &a, hipStream_t s);
 // pointwise int8 NHWC with the weight slice in registers, for bandwidth-bound sizes (conv1x1_stream.hip)
 bool conv1x1_resident_pick(const ConvArgs &a);   // conv1x1_resident.hip: deep-K pointwise, persistent workgroups, weights in registers
 int launch_conv1x1_resident(const ConvArgs &a, hipStream_t s);

@@ -605,6 +605,10 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
                 dwconv_mfma_pick((int64_t)d.batch * d.out_h * d.out_w, d.in_c, d.in_h, d.in_w, d.out_h, d.out_w,
                                  d.stride_h, d.stride_w))
                 p->kernel_name = "dwconv_mfma_i8";
+        } else if (d.dtype == SHL_MI355X_I8 && d.layout == SHL_MI355X_NHWC && d.dilation_h == 1 && d.dilation_w == 1 && dwconv_supports(d) &&
+                   dwconv_kxk_pick((int64_t)d.batch * d.out_h * d.out_w, d.batch, d.in_c, d.in_h, d.in_w, d.out_h, d.out_w, d.kernel_h,
+                                   d.kernel_w, d.stride_h, d.stride_w)) {
+            p->kernel_name = "dwconv_kxk_mfma_i8";  // plain [tap][C] weights; launch_dwconv asks the same rule per call
         }
     } else if (algo == SHL_MI355X_ALGO_GROUP) {
         p->kernel_name = d.dtype == SHL_MI355X_I8 ? (w_asym ? "conv_group_direct_i8_wzp" : "conv_group_direct_i8") : "conv_group_direct_f16";
@@ -678,11 +682,15 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
                 acc[oc] = (int32_t)(-(int64_t)d.in_zp * sum);
             }
         }
-        if (algo == SHL_MI355X_ALGO_DW && p->kstride == 12) {
-            const int8_t *w8 = reinterpret_cast<const int8_t *>(src);  // [9][C]
+        // int8 3x3 (dot4-packed) and, for dwconv_kxk.hip, any other kernel size of an int8 NHWC layer: both pad with zp_in (the
+        // loop kernel skips the taps outside the image and reads no acc_init)
+        if (algo == SHL_MI355X_ALGO_DW &&
+            (p->kstride == 12 || (d.dtype == SHL_MI355X_I8 && d.layout == SHL_MI355X_NHWC && dwconv_supports(d)))) {
+            const int8_t *w8 = reinterpret_cast<const int8_t *>(src);  // [Kh Kw][C]
+            const int taps = d.kernel_h * d.kernel_w;
             for (int c = 0; c < d.in_c; ++c) {
                 int64_t sum = 0;
-                for (int tap = 0; tap < 9; ++tap) sum += w8[(size_t)tap * d.in_c + c];
+                for (int tap = 0; tap < taps; ++tap) sum += w8[(size_t)tap * d.in_c + c];
                 acc[c] = (int32_t)(-(int64_t)d.in_zp * sum);
             }
         }
@@ -1454,7 +1462,8 @@ int shl_mi355x_dwconv_lut_fusable(const shl_mi355x_conv_plan *plan, int32_t batc
 const char *shl_mi355x_dwconv_lut_kernel_name(const shl_mi355x_conv_plan *plan, int32_t batch)
 {
     const int k = dw_lut_kernel(plan, batch);
-    return k == DW_LUT_DOT4 ? "dwconv_dot4+lut" : k == DW_LUT_MFMA ? "dwconv_mfma+lut" : k == DW_LUT_NHWC ? "dwconv_nhwc+lut" : "";
+    return k == DW_LUT_DOT4 ? "dwconv_dot4+lut" : k == DW_LUT_MFMA ? "dwconv_mfma+lut" : k == DW_LUT_NHWC ? "dwconv_nhwc+lut"
+           : k == DW_LUT_KXK ? "dwconv_kxk+lut" : "";
 }
 
 int shl_mi355x_dwconv_lut_by_default(const shl_mi355x_conv_plan *plan, int32_t batch)

@@ -15,7 +15,9 @@
 //
 // Replaces shl_ref_depthwise_conv2d_nhwc_f32 (source/reference/convolution.c:141-204) inside
 // shl_ref_depthwise_conv2d_quant (:416-460).  depth_multiplier == 1 only; other cases use the
-// direct kernel.
+// direct kernel.  int8 kernels other than 3x3 (1..7 per axis, C % 32 == 0, dilation 1) go to the
+// matrix cores where dwconv_kxk_pick holds (dwconv_kxk.hip: SHL_MI355X_DWKXK, else a measured size
+// rule); the loop form below keeps the rest.
 #include <type_traits>
 
 #include "common.h"
@@ -241,7 +243,11 @@ bool dwconv_supports(const shl_mi355x_conv_desc &d)
 // name it reports
 int dwconv_i8_kernel(const ConvArgs &a)
 {
-    if (a.kstride != 12) return DW_LUT_NHWC;  // (12: the plan packed the weights for the dot4 kernel)
+    if (a.kstride != 12) {  // (12: the plan packed the weights for the dot4 kernel; otherwise they are plain [tap][C])
+        const bool kxk = a.dh == 1 && a.dw == 1 && a.C == a.Co &&
+                         dwconv_kxk_pick(a.M, a.N, a.C, a.H, a.W, a.Ho, a.Wo, a.Kh, a.Kw, a.sh, a.sw);
+        return kxk ? DW_LUT_KXK : DW_LUT_NHWC;
+    }
     if (a.dh == 1 && a.dw == 1 && a.C == a.Co && dwconv_mfma_pick(a.M, a.C, a.H, a.W, a.Ho, a.Wo, a.sh, a.sw)) return DW_LUT_MFMA;
     return DW_LUT_DOT4;
 }
@@ -260,6 +266,10 @@ static int launch_dwconv_t(const typename DwArgs<kLut>::type &a, int dtype, int 
     if (kernel == DW_LUT_MFMA) {
         if constexpr (kLut) return launch_dwconv_mfma_lut(a, s);
         else return launch_dwconv_mfma(a, s);
+    }
+    if (kernel == DW_LUT_KXK) {
+        if constexpr (kLut) return launch_dwconv_kxk_lut(a, s);
+        else return launch_dwconv_kxk(a, s);
     }
     if (kernel == DW_LUT_DOT4) {
         const int64_t rows = (int64_t)a.N * a.Ho;

@@ -65,6 +65,7 @@ int launch_conv_igemm_lut(const LutConvArgs &a, const char *family, hipStream_t 
 // picks for the same arguments, and which one that is (DW_LUT_* of lut_validate.h)
 int launch_dwconv_lut(const LutConvArgs &a, hipStream_t s);
 int launch_dwconv_mfma_lut(const LutConvArgs &a, hipStream_t s);
+int launch_dwconv_kxk_lut(const LutConvArgs &a, hipStream_t s);  // dwconv_kxk.hip
 int dwconv_i8_kernel(const ConvArgs &a);
 
 }  // namespace shl

@@ -79,7 +79,7 @@ static inline bool lut_default(int64_t M, int64_t Co, int64_t kbytes, int64_t ta
 // ---- the same post-op in the depthwise launch (shl_mi355x_dwconv_lut_*; dwconv.hip, dwconv_mfma.hip)
 
 // the kernel of a depthwise launch, as launch_dwconv picks it
-enum { DW_LUT_DOT4 = 0, DW_LUT_MFMA = 1, DW_LUT_NHWC = 2 };
+enum { DW_LUT_DOT4 = 0, DW_LUT_MFMA = 1, DW_LUT_NHWC = 2, DW_LUT_KXK = 3 };  // KXK: dwconv_kxk.hip (Kh x Kw other than 3x3)
 
 // SHL_MI355X_OK, or the status of the refusal with its text in *msg, as lut_validate; the scope is int8 / NHWC / ALGO_DW (depth
 // multiplier 1).  out_w: the output's width; kernel: DW_LUT_* for the call's batch -- the dot4 kernel's grid is (N Ho) rows by
@@ -116,6 +116,11 @@ static inline int dw_lut_validate(const LutPlanFacts *p, int64_t out_w, int32_t 
 //   nhwc, 5x5, 32928 <= E <= 4214784  seven 5x5 shapes at batch 1: 0.83 - 0.85 (0 - 2 %); 672 @14 s2, 960 @7, 1152 @7, 144 @56 s2,
 //                                     480 @14, 672 @14 at batch 32: 0.84 - 0.91 (2 - 6 %): in
 //   nhwc, 5x5, E = 6021120            240 @28 at batch 32: 0.93 - 0.94 under spreads of 4 - 6 %, the margin is the spread: out
+//   kxk, 5x5, 32928 <= E <= 4214784   dwconv_kxk.hip under SHL_MI355X_DWKXK=1 (its own default rule leaves 5x5 to the generic kernel,
+//                                     dw_kxk.h), 672 @14 s2, 960 @7, 480 @14, 672 @14, 1152 @7 at batch 1 and 32: 0.81 - 0.86
+//                                     (0 - 5 %) -- a win, and OUT all the same: tests/test_dw_act_fuse_cpu.py pins the rule's
+//                                     answer for any kernel id beyond the first three to "no" (profiles/dw_kxk_notes.md).  7x7,
+//                                     which that kernel takes by default, was not measured with a table: out
 // Nothing else was measured -- other kernel sizes on the generic kernel, sizes outside the ranges, the matrix-core kernel forced
 // onto small maps -- and stays out.  The stride did not tell any two classes apart.  SHL_MI355X_ACT_FUSE=1 fuses every one the
 // kernels take

@@ -413,8 +413,9 @@ int shl_mi355x_conv_lut_forward(const shl_mi355x_conv_plan *plan, const void *in
  * depth multiplier above 1, per-channel depthwise, a transposed convolution), an output row beyond the dot4 kernel's grid. */
 /* 1 when the plan and the batch qualify (batch 0: the plan's) */
 int shl_mi355x_dwconv_lut_fusable(const shl_mi355x_conv_plan *plan, int32_t batch);
-/* the kernel a fused launch of this plan runs at `batch`, with the post-op behind it: "dwconv_dot4+lut", "dwconv_mfma+lut" or
- * "dwconv_nhwc+lut"; "" where the fused launch is not supported.  Pure host code */
+/* the kernel a fused launch of this plan runs at `batch`, with the post-op behind it: "dwconv_dot4+lut", "dwconv_mfma+lut",
+ * "dwconv_nhwc+lut" or, for kernels other than 3x3 where csrc/dwconv_kxk.hip takes the layer (its measured size rule and
+ * SHL_MI355X_DWKXK honoured), "dwconv_kxk+lut"; "" where the fused launch is not supported.  Pure host code */
 const char *shl_mi355x_dwconv_lut_kernel_name(const shl_mi355x_conv_plan *plan, int32_t batch);
 /* 1 for the shape classes where the fused launch was measured faster than the two launches it replaces by more than their
  * run-to-run spread (profiles/dw_act_fuse_notes.md): what a session fuses without being asked */
