@@ -49,7 +49,8 @@ NO_SPILL_SOURCES = ("conv_igemm.hip", "conv_igemm_pp.hip", "conv_igemm_pc.hip",
                     "reduce.hip",  # (its chains wait on one addition per element: a scratch reload in the loop would double that)
                     "matmul.hip",  # (the chain likewise; the mfma form's K loop holds one slab's pieces in flight in registers)
                     "attention.hip",  # (the same K loops twice, and sixteen accumulators live across the softmax's f64 work)
-                    "dwconv_kxk.hip")  # (four tiles' accumulators live across the tap loop: a spill there is the whole loop's cost)
+                    "dwconv_kxk.hip",  # (four tiles' accumulators live across the tap loop: a spill there is the whole loop's cost)
+                    "conv_group_mfma.hip")  # (the same four accumulators beside the next slab's patch in registers)
 
 
 def spilled_kernels(usage_file):

@@ -550,6 +550,12 @@ inline void lds_opt_in(LdsOptIn &st, const void *kernel, int bytes = 160 * 1024)
 int launch_conv_direct(const ConvArgs &a, int dtype, int layout, int dw_nhwc_weights,
                        hipStream_t s);
 int launch_conv_group_direct(const ConvArgs &a, int dtype, int layout, hipStream_t s);  // SHL_MI355X_ALGO_GROUP
+// grouped int8 on the matrix cores over the NHWC view of an NCHW layer (conv_group_mfma.hip; geometry, packing and the default
+// rule: group_mfma.h).  N: the plan's batch.  The caller vouches for int8, symmetric weights and the fast epilogue.
+bool conv_group_mfma_pick(int N, int C, int Co, int G, int H, int W, int Ho, int Wo, int Kh, int Kw, int sh, int sw, int dh, int dw);
+size_t conv_group_mfma_weight_bytes(int C, int Co, int G, int Kh, int Kw);
+void conv_group_mfma_pack(const int8_t *oihw, int C, int Co, int G, int Kh, int Kw, int in_zp, int8_t *dst, int32_t *acc_init);
+int launch_conv_group_mfma(const ConvArgs &a, hipStream_t s);
 int launch_conv_igemm(const ConvArgs &a, int dtype, int layout, hipStream_t s);
 int launch_dwconv(const ConvArgs &a, int dtype, int layout, hipStream_t s);
 bool igemm_supports(const shl_mi355x_conv_desc &d);

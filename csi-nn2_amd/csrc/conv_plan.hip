@@ -69,6 +69,16 @@ static int esize_of(const shl_mi355x_conv_desc &d) { return d.dtype == SHL_MI355
 
 static bool is_depthwise(const shl_mi355x_conv_desc &d) { return d.group > 1 && d.group == d.in_c; }
 
+// The one rule of conv_group_mfma.hip for an ALGO_GROUP plan, asked by plan_create_impl (kernel name, fragment packing, re-layout
+// scratch) and by the launch switch with the same arguments.  Symmetric weights and the fast epilogue are the plan's to add.
+constexpr int32_t GROUP_MFMA_KSTRIDE = 32;  // plan->kstride of such a plan: K bytes per fragment row (marks the packing)
+static bool group_mfma_takes(const shl_mi355x_conv_desc &d)
+{
+    return d.dtype == SHL_MI355X_I8 && d.layout == SHL_MI355X_NCHW && d.group > 1 && !is_depthwise(d) &&
+           conv_group_mfma_pick(d.batch, d.in_c, d.out_c, d.group, d.in_h, d.in_w, d.out_h, d.out_w, d.kernel_h, d.kernel_w, d.stride_h,
+                                d.stride_w, d.dilation_h, d.dilation_w);
+}
+
 // a transposed convolution's plan (deconv.hip): no partner of any pair or pool fusion
 static bool is_deconv(const shl_mi355x_conv_plan *p)
 {
@@ -612,6 +622,11 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
         }
     } else if (algo == SHL_MI355X_ALGO_GROUP) {
         p->kernel_name = d.dtype == SHL_MI355X_I8 ? (w_asym ? "conv_group_direct_i8_wzp" : "conv_group_direct_i8") : "conv_group_direct_f16";
+        if (!w_asym && fast_epilogue_ok && group_mfma_takes(d)) {
+            p->kernel_name = "conv_group_mfma_i8_mfma32x32x32";
+            p->kstride = GROUP_MFMA_KSTRIDE;
+            w_bytes = conv_group_mfma_weight_bytes(d.in_c, d.out_c, d.group, d.kernel_h, d.kernel_w);
+        }
     } else {
         p->kernel_name = d.dtype == SHL_MI355X_I8 ? (w_asym ? "conv_direct_i8_wzp" : "conv_direct_i8") : "conv_direct_f16";
     }
@@ -626,6 +641,7 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
     // pointwise layers whose K row is a multiple of 32 bytes: a second copy of the weights in fragment order
     // [32-channel group][K / 32][64 lanes][16 B] so that a wave fetches an A fragment with one coalesced
     // 1 KiB load (from [Cout][K] rows it is 64 lines per load instruction)
+    const bool group_mfma = algo == SHL_MI355X_ALGO_GROUP && p->kstride == GROUP_MFMA_KSTRIDE;
     const bool frag_copy = algo == SHL_MI355X_ALGO_IGEMM && d.kernel_h == 1 && d.kernel_w == 1 &&
                            (d.in_c * es) % 32 == 0 && d.in_c * es <= 4096 && d.out_c % 32 == 0;
     if (frag_copy) {
@@ -669,10 +685,13 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
         else if (algo == SHL_MI355X_ALGO_DW && p->kstride == 12)
             dwconv_dot4_pack(d, reinterpret_cast<const int8_t *>(src),
                              reinterpret_cast<uint32_t *>(host.data() + p->off_w));
-        else
+        else if (!group_mfma)
             memcpy(host.data() + p->off_w, src, raw_w);
         int32_t *acc = reinterpret_cast<int32_t *>(host.data() + p->off_acc);
         for (int oc = 0; oc < d.out_c; ++oc) acc[oc] = w_asym ? kernel_zp[oc] : 0;  // DIRECT / GROUP: the kernel's zero point per output channel
+        if (group_mfma)  // fragment order, block-diagonal where the groups are narrow; padding is materialised as zp_in here too
+            conv_group_mfma_pack(reinterpret_cast<const int8_t *>(src), d.in_c, d.out_c, d.group, d.kernel_h, d.kernel_w, d.in_zp,
+                                 reinterpret_cast<int8_t *>(host.data() + p->off_w), acc);
         if (algo == SHL_MI355X_ALGO_STEM) {
             // padding is materialised as zp_in here too
             const int8_t *w8 = reinterpret_cast<const int8_t *>(src);
@@ -706,7 +725,7 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
             }
         }
     }
-    if (algo == SHL_MI355X_ALGO_IGEMM && d.layout == SHL_MI355X_NCHW && d.batch > 0) {
+    if ((algo == SHL_MI355X_ALGO_IGEMM || group_mfma) && d.layout == SHL_MI355X_NCHW && d.batch > 0) {
         const size_t in_b = (size_t)d.batch * d.in_c * d.in_h * d.in_w * es;
         const size_t out_b = (size_t)d.batch * d.out_c * d.out_h * d.out_w * es;
         if (hipMalloc((void **)&p->scratch_in, in_b) != hipSuccess ||
@@ -1101,8 +1120,21 @@ static int conv_forward_impl(const shl_mi355x_conv_plan *plan, const void *input
             return launch_conv_stem(a, s);
         case SHL_MI355X_ALGO_DW_CHANNEL:
             return launch_dwconv_channel(a, s);
-        case SHL_MI355X_ALGO_GROUP:
-            return launch_conv_group_direct(a, d.dtype, d.layout, s);
+        case SHL_MI355X_ALGO_GROUP: {
+            if (plan->kstride != GROUP_MFMA_KSTRIDE) return launch_conv_group_direct(a, d.dtype, d.layout, s);
+            // conv_group_mfma.hip on the NHWC view: [C][HW] -> [HW][C] scratch, the kernel, [HoWo][Co] -> [Co][HoWo]
+            if (!group_mfma_takes(d) || a.N > d.batch || !plan->scratch_in) {
+                set_error("conv_forward: grouped NCHW plan was packed for conv_group_mfma and batch %d, got batch %d", d.batch, a.N);
+                return SHL_MI355X_EINVAL;
+            }
+            int rc = launch_transpose(input_dev, plan->scratch_in, a.N, a.C, a.H * a.W, 1, s, 1);
+            if (rc != SHL_MI355X_OK) return rc;
+            a.in = plan->scratch_in;
+            a.out = plan->scratch_out;
+            rc = launch_conv_group_mfma(a, s);
+            if (rc != SHL_MI355X_OK) return rc;
+            return launch_transpose(plan->scratch_out, output_dev, a.N, a.Ho * a.Wo, a.Co, 1, s, 0);
+        }
         case SHL_MI355X_ALGO_DECONV_GATHER:
             return launch_deconv_gather(a, d.dtype, d.layout, s);
         case SHL_MI355X_ALGO_DECONV_PHASE:

@@ -70,6 +70,10 @@ enum shl_mi355x_algo {
      *         usual grouped convolution);
      *   NHWC  the buffers are G consecutive tensors [N, H, W, C/G] -> [N, Ho, Wo, Cout/G] (NOT channel-interleaved
      *         groups): restated literally, identical results are the contract.
+     * Two kernels: conv_group_direct_* (one output per thread, VALU: every layer) and, for int8 NCHW layers with symmetric
+     * weights, the fast epilogue, C/G == Cout/G in {4, 8, 16} or both multiples of 32, kernels up to 7x7, strides <= 2 and
+     * dilation 1, conv_group_mfma_i8_mfma32x32x32 (csrc/conv_group_mfma.hip: matrix cores over an LDS patch, between two
+     * re-layout launches) where its measured rule takes the layer.  SHL_MI355X_GROUPMFMA=0 / 1: never / wherever it fits.
      * Never chosen by ALGO_AUTO: a descriptor with group > 1 alone cannot say which of the two the caller means */
     SHL_MI355X_ALGO_GROUP = 7,
     /* transposed convolution (shl_mi355x_deconv_plan_create; never chosen for a convolution descriptor) */
