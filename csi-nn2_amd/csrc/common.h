@@ -556,6 +556,12 @@ bool conv_group_mfma_pick(int N, int C, int Co, int G, int H, int W, int Ho, int
 size_t conv_group_mfma_weight_bytes(int C, int Co, int G, int Kh, int Kw);
 void conv_group_mfma_pack(const int8_t *oihw, int C, int Co, int G, int Kh, int Kw, int in_zp, int8_t *dst, int32_t *acc_init);
 int launch_conv_group_mfma(const ConvArgs &a, hipStream_t s);
+// grouped binary16 likewise (conv_group_mfma_f16.hip; group_mfma_f16.h).  by_rule: ask the measured default rule as well as the
+// geometry (plan creation with SHL_MI355X_GROUPMFMA_F16 unset); the launch asks the geometry alone.
+bool conv_group_mfma_f16_pick(int N, int C, int Co, int G, int H, int W, int Ho, int Wo, int Kh, int Kw, int sh, int sw, int dh, int dw, bool by_rule);
+size_t conv_group_mfma_f16_weight_bytes(int C, int Co, int G, int Kh, int Kw);
+void conv_group_mfma_f16_pack(const uint16_t *oihw, int C, int Co, int G, int Kh, int Kw, uint16_t *dst);
+int launch_conv_group_mfma_f16(const ConvArgs &a, hipStream_t s);
 int launch_conv_igemm(const ConvArgs &a, int dtype, int layout, hipStream_t s);
 int launch_dwconv(const ConvArgs &a, int dtype, int layout, hipStream_t s);
 bool igemm_supports(const shl_mi355x_conv_desc &d);

@@ -79,6 +79,17 @@ static bool group_mfma_takes(const shl_mi355x_conv_desc &d)
                                 d.stride_w, d.dilation_h, d.dilation_w);
 }
 
+// The one rule of conv_group_mfma_f16.hip, likewise.  SHL_MI355X_GROUPMFMA_F16 ("0" never, "1" wherever the geometry fits,
+// unset: the measured rule) is read by plan_create_impl at EACH plan creation and ends up in the plan's marker; the launch goes
+// by the marker and asks the geometry alone (by_rule = false), never the environment.
+constexpr int32_t GROUP_MFMA_F16_KSTRIDE = 64;  // plan->kstride of such a plan: K bytes per fragment row
+static bool group_mfma_f16_takes(const shl_mi355x_conv_desc &d, bool by_rule)
+{
+    return d.dtype == SHL_MI355X_F16 && d.layout == SHL_MI355X_NCHW && d.group > 1 && !is_depthwise(d) &&
+           conv_group_mfma_f16_pick(d.batch, d.in_c, d.out_c, d.group, d.in_h, d.in_w, d.out_h, d.out_w, d.kernel_h, d.kernel_w, d.stride_h,
+                                    d.stride_w, d.dilation_h, d.dilation_w, by_rule);
+}
+
 // a transposed convolution's plan (deconv.hip): no partner of any pair or pool fusion
 static bool is_deconv(const shl_mi355x_conv_plan *p)
 {
@@ -627,6 +638,12 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
             p->kstride = GROUP_MFMA_KSTRIDE;
             w_bytes = conv_group_mfma_weight_bytes(d.in_c, d.out_c, d.group, d.kernel_h, d.kernel_w);
         }
+        const char *f16_switch = getenv("SHL_MI355X_GROUPMFMA_F16");  // per plan, not per process
+        if (!(f16_switch && f16_switch[0] == '0') && group_mfma_f16_takes(d, !(f16_switch && f16_switch[0] == '1'))) {
+            p->kernel_name = "conv_group_mfma_f16_mfma16x16x32";
+            p->kstride = GROUP_MFMA_F16_KSTRIDE;
+            w_bytes = conv_group_mfma_f16_weight_bytes(d.in_c, d.out_c, d.group, d.kernel_h, d.kernel_w);
+        }
     } else {
         p->kernel_name = d.dtype == SHL_MI355X_I8 ? (w_asym ? "conv_direct_i8_wzp" : "conv_direct_i8") : "conv_direct_f16";
     }
@@ -642,6 +659,7 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
     // [32-channel group][K / 32][64 lanes][16 B] so that a wave fetches an A fragment with one coalesced
     // 1 KiB load (from [Cout][K] rows it is 64 lines per load instruction)
     const bool group_mfma = algo == SHL_MI355X_ALGO_GROUP && p->kstride == GROUP_MFMA_KSTRIDE;
+    const bool group_mfma_f16 = algo == SHL_MI355X_ALGO_GROUP && p->kstride == GROUP_MFMA_F16_KSTRIDE;
     const bool frag_copy = algo == SHL_MI355X_ALGO_IGEMM && d.kernel_h == 1 && d.kernel_w == 1 &&
                            (d.in_c * es) % 32 == 0 && d.in_c * es <= 4096 && d.out_c % 32 == 0;
     if (frag_copy) {
@@ -685,6 +703,9 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
         else if (algo == SHL_MI355X_ALGO_DW && p->kstride == 12)
             dwconv_dot4_pack(d, reinterpret_cast<const int8_t *>(src),
                              reinterpret_cast<uint32_t *>(host.data() + p->off_w));
+        else if (group_mfma_f16)  // fragment order, one group per matrix block
+            conv_group_mfma_f16_pack(reinterpret_cast<const uint16_t *>(src), d.in_c, d.out_c, d.group, d.kernel_h, d.kernel_w,
+                                     reinterpret_cast<uint16_t *>(host.data() + p->off_w));
         else if (!group_mfma)
             memcpy(host.data() + p->off_w, src, raw_w);
         int32_t *acc = reinterpret_cast<int32_t *>(host.data() + p->off_acc);
@@ -725,7 +746,7 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
             }
         }
     }
-    if ((algo == SHL_MI355X_ALGO_IGEMM || group_mfma) && d.layout == SHL_MI355X_NCHW && d.batch > 0) {
+    if ((algo == SHL_MI355X_ALGO_IGEMM || group_mfma || group_mfma_f16) && d.layout == SHL_MI355X_NCHW && d.batch > 0) {
         const size_t in_b = (size_t)d.batch * d.in_c * d.in_h * d.in_w * es;
         const size_t out_b = (size_t)d.batch * d.out_c * d.out_h * d.out_w * es;
         if (hipMalloc((void **)&p->scratch_in, in_b) != hipSuccess ||
@@ -1121,6 +1142,19 @@ static int conv_forward_impl(const shl_mi355x_conv_plan *plan, const void *input
         case SHL_MI355X_ALGO_DW_CHANNEL:
             return launch_dwconv_channel(a, s);
         case SHL_MI355X_ALGO_GROUP: {
+            if (plan->kstride == GROUP_MFMA_F16_KSTRIDE) {  // conv_group_mfma_f16.hip, between the same two re-layout launches
+                if (!group_mfma_f16_takes(d, false) || a.N > d.batch || !plan->scratch_in) {
+                    set_error("conv_forward: grouped NCHW plan was packed for conv_group_mfma_f16 and batch %d, got batch %d", d.batch, a.N);
+                    return SHL_MI355X_EINVAL;
+                }
+                int rc = launch_transpose(input_dev, plan->scratch_in, a.N, a.C, a.H * a.W, 2, s, 1);
+                if (rc != SHL_MI355X_OK) return rc;
+                a.in = plan->scratch_in;
+                a.out = plan->scratch_out;
+                rc = launch_conv_group_mfma_f16(a, s);
+                if (rc != SHL_MI355X_OK) return rc;
+                return launch_transpose(plan->scratch_out, output_dev, a.N, a.Ho * a.Wo, a.Co, 2, s, 0);
+            }
             if (plan->kstride != GROUP_MFMA_KSTRIDE) return launch_conv_group_direct(a, d.dtype, d.layout, s);
             // conv_group_mfma.hip on the NHWC view: [C][HW] -> [HW][C] scratch, the kernel, [HoWo][Co] -> [Co][HoWo]
             if (!group_mfma_takes(d) || a.N > d.batch || !plan->scratch_in) {

@@ -74,6 +74,9 @@ enum shl_mi355x_algo {
      * weights, the fast epilogue, C/G == Cout/G in {4, 8, 16} or both multiples of 32, kernels up to 7x7, strides <= 2 and
      * dilation 1, conv_group_mfma_i8_mfma32x32x32 (csrc/conv_group_mfma.hip: matrix cores over an LDS patch, between two
      * re-layout launches) where its measured rule takes the layer.  SHL_MI355X_GROUPMFMA=0 / 1: never / wherever it fits.
+     * binary16 NCHW layers of the same geometry have conv_group_mfma_f16_mfma16x16x32 (csrc/conv_group_mfma_f16.hip: one
+     * group per matrix block, so non-finite inputs stay inside their group; fp32 sums in the MFMA's order) under a rule and
+     * a switch of its own, SHL_MI355X_GROUPMFMA_F16=0 / 1, read at each plan creation.
      * Never chosen by ALGO_AUTO: a descriptor with group > 1 alone cannot say which of the two the caller means */
     SHL_MI355X_ALGO_GROUP = 7,
     /* transposed convolution (shl_mi355x_deconv_plan_create; never chosen for a convolution descriptor) */

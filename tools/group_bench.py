@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Grouped int8 NCHW convolution on the matrix cores (csrc/conv_group_mfma.hip) against the direct kernel it replaces, through the
-C-ABI (no torch).
+C-ABI (no torch); with --dtype f16 the binary16 twin (csrc/conv_group_mfma_f16.hip, switch SHL_MI355X_GROUPMFMA_F16, whose results
+differ from the direct kernel's by summation order: the two sides' sum |y| must agree to 1e-3 instead of their CRCs).
 
-    python tools/group_bench.py [--reps 4] [--only NAME[,NAME]] [--out FILE.md]
+    python tools/group_bench.py [--dtype int8|f16] [--reps 4] [--only NAME[,NAME]] [--out FILE.md]
 SHL_MI355X_GROUPMFMA is read once per process, so the two sides are two worker processes of this script on the same build: one
 under =1 (conv_group_mfma_i8_mfma32x32x32 wherever the geometry fits), one under =0 (exactly the parent commit's code path, the
 baseline).  Per shape each worker captures one hipGraph holding `reps` shl_mi355x_conv_forward calls that rotate over three
@@ -59,7 +60,7 @@ def worker(a, shapes):
     ev0, ev1 = hip.shl_mi355x_event_create(), hip.shl_mi355x_event_create()
     ms = C.c_float()
     for name, n, hw, c, groups, stride in shapes:
-        cv = cases.make_case(9779, layout="NCHW", n=n, h=hw, w=hw, c=c, co=c, groups=groups, stride=(stride, stride), exact=False, act=1)
+        cv = cases.make_case(9779, layout="NCHW", dtype=a.dtype, n=n, h=hw, w=hw, c=c, co=c, groups=groups, stride=(stride, stride), exact=False, act=1)
         count = int(np.prod(cv["out_shape"]))
         desc, plan = rc.conv_desc(cv), C.c_void_p()
         desc.algo = ALGO_GROUP
@@ -69,7 +70,7 @@ def worker(a, shapes):
                                                   C.byref(plan)), hip, "conv_plan_create")
         bufs = []
         for _ in range(SETS):
-            b = dict(x=dev.alloc(cv["input"].nbytes), y=dev.alloc(count))
+            b = dict(x=dev.alloc(cv["input"].nbytes), y=dev.alloc(count * (2 if a.dtype == "f16" else 1)))
             dev.upload(b["x"], cv["input"])
             bufs.append(b)
 
@@ -78,7 +79,10 @@ def worker(a, shapes):
             pkg.check(hip.shl_mi355x_conv_forward(plan, b["x"], b["y"], 0, stream), hip, "conv_forward")
         enqueue(0)
         pkg.check(hip.shl_mi355x_stream_sync(stream), hip, "warm-up")
-        crc = zlib.crc32(dev.download(bufs[0]["y"], (count,), np.int8).tobytes())
+        if a.dtype == "f16":  # (summation order differs between the two kernels: a norm instead of a CRC)
+            crc = "%.6e" % float(np.abs(dev.download(bufs[0]["y"], (count,), np.float16).astype(np.float64)).sum())
+        else:
+            crc = zlib.crc32(dev.download(bufs[0]["y"], (count,), np.int8).tobytes())
         pkg.check(hip.shl_mi355x_graph_begin(stream), hip, "graph_begin")
         for kk in range(a.reps):
             enqueue(kk)
@@ -111,6 +115,7 @@ def worker(a, shapes):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=4)
+    ap.add_argument("--dtype", default="int8", choices=("int8", "f16"))
     ap.add_argument("--only", default="")
     ap.add_argument("--out", default="")
     ap.add_argument("--worker", action="store_true")
@@ -119,8 +124,9 @@ def main():
     shapes = [s for s in SHAPES if not only or s[0] in only]
     if a.worker:
         return worker(a, shapes)
-    cmd = [sys.executable, os.path.abspath(__file__), "--worker", "--reps", str(a.reps), "--only", a.only]
-    sides = [subprocess.Popen(cmd, stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True, env=dict(os.environ, SHL_MI355X_GROUPMFMA=v))
+    cmd = [sys.executable, os.path.abspath(__file__), "--worker", "--reps", str(a.reps), "--only", a.only, "--dtype", a.dtype]
+    switch = "SHL_MI355X_GROUPMFMA" if a.dtype == "int8" else "SHL_MI355X_GROUPMFMA_F16"
+    sides = [subprocess.Popen(cmd, stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True, env=dict(os.environ, **{switch: v}))
              for v in ("0", "1")]
 
     def ask(p, text=None):
@@ -145,8 +151,9 @@ def main():
         ho = (hw + 2 - 3) // stride + 1
         dims = "%d x %d / %d x 9" % (n * ho * ho, c, groups)
         ready = [ask(p) for p in sides]
-        if ready[0][1] != "conv_group_direct_i8" or ready[0][2] != ready[1][2]:
-            raise SystemExit("group_bench: %s: baseline kernel %s, CRCs %s / %s" % (name, ready[0][1], ready[0][2], ready[1][2]))
+        same = ready[0][2] == ready[1][2] if a.dtype == "int8" else abs(float(ready[0][2]) - float(ready[1][2])) <= 1e-3 * float(ready[0][2])
+        if ready[0][1] != "conv_group_direct_" + ("i8" if a.dtype == "int8" else "f16") or not same:
+            raise SystemExit("group_bench: %s: baseline kernel %s, checksums %s / %s" % (name, ready[0][1], ready[0][2], ready[1][2]))
         replays = []
         for p in sides:  # an untimed window sizes the timed ones to ~50 ms
             t20 = float(ask(p, "w 20")[0])
