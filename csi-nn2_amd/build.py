@@ -51,7 +51,8 @@ NO_SPILL_SOURCES = ("conv_igemm.hip", "conv_igemm_pp.hip", "conv_igemm_pc.hip",
                     "attention.hip",  # (the same K loops twice, and sixteen accumulators live across the softmax's f64 work)
                     "dwconv_kxk.hip",  # (four tiles' accumulators live across the tap loop: a spill there is the whole loop's cost)
                     "conv_group_mfma.hip",  # (the same four accumulators beside the next slab's patch in registers)
-                    "conv_group_mfma_f16.hip")  # (eight accumulators and their B fragments beside the next slab's patch)
+                    "conv_group_mfma_f16.hip",  # (eight accumulators and their B fragments beside the next slab's patch)
+                    "conv_stem_kxk.hip")  # (four accumulators and the five dwords of each unaligned B fragment across the K loop)
 
 
 def spilled_kernels(usage_file):

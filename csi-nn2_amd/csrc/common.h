@@ -595,6 +595,14 @@ bool stem_supports(const shl_mi355x_conv_desc &d);
 void stem_pack_weights(const shl_mi355x_conv_desc &d, const int8_t *ohwi, int32_t *dst);
 size_t stem_weight_bytes(const shl_mi355x_conv_desc &d);
 int launch_conv_stem(const ConvArgs &a, hipStream_t s);
+// Kh x Kw with 1..4 input channels, int8, on the matrix cores over the NHWC view (conv_stem_kxk.hip; scope, geometry, packing and
+// the default rule: stem_kxk.h).  N: the plan's batch; nchw: the layer pays two re-layout launches; by_rule: ask the measured
+// default rule as well as the geometry.  The caller vouches for int8, group 1, symmetric weights and the fast epilogue.
+bool conv_stem_kxk_pick(int N, int C, int Co, int H, int W, int Ho, int Wo, int Kh, int Kw, int sh, int sw, int dh, int dw, int in_zp,
+                        bool nchw, bool by_rule);
+size_t conv_stem_kxk_weight_bytes(int C, int Co, int Kh, int Kw);
+void conv_stem_kxk_pack(const int8_t *ohwi, int C, int Co, int Kh, int Kw, int in_zp, int8_t *dst, int32_t *acc_init);
+int launch_conv_stem_kxk(const ConvArgs &a, hipStream_t s);
 // NCHW-native kernels for latency-bound sizes (nchw_small.hip)
 bool conv1x1_nchw_eligible(const ConvArgs &a);
 int launch_conv1x1_nchw(const ConvArgs &a, int dtype, hipStream_t s);

@@ -90,6 +90,17 @@ static bool group_mfma_f16_takes(const shl_mi355x_conv_desc &d, bool by_rule)
                                     d.stride_w, d.dilation_h, d.dilation_w, by_rule);
 }
 
+// The one rule of conv_stem_kxk.hip, the second form of an ALGO_STEM plan, likewise.  SHL_MI355X_STEMKXK ("0" never, "1" wherever
+// the scope fits, unset: the measured rule) is read by plan_create_impl at EACH plan creation and ends up in the plan's marker;
+// the launch goes by the marker and asks the geometry alone (by_rule = false), never the environment.
+constexpr int32_t STEM_KXK_KSTRIDE = 32;  // plan->kstride of such a plan: K bytes per fragment row (the 3x3 stem plans carry 0)
+static bool stem_kxk_takes(const shl_mi355x_conv_desc &d, bool by_rule)
+{
+    return d.dtype == SHL_MI355X_I8 && d.group == 1 &&
+           conv_stem_kxk_pick(d.batch, d.in_c, d.out_c, d.in_h, d.in_w, d.out_h, d.out_w, d.kernel_h, d.kernel_w, d.stride_h, d.stride_w,
+                              d.dilation_h, d.dilation_w, d.in_zp, d.layout == SHL_MI355X_NCHW, by_rule);
+}
+
 // a transposed convolution's plan (deconv.hip): no partner of any pair or pool fusion
 static bool is_deconv(const shl_mi355x_conv_plan *p)
 {
@@ -236,6 +247,10 @@ static int choose_algo(const shl_mi355x_conv_desc &d)
     if (is_depthwise(d)) return (dwconv_supports(d) || dwconv_nchw_supports(d)) ? SHL_MI355X_ALGO_DW : SHL_MI355X_ALGO_DIRECT;
     if (d.group != 1) return -1;  // grouped convolution: SURVEY 8f3
     if (stem_supports(d)) return SHL_MI355X_ALGO_STEM;
+    {  // Kh x Kw with 1..4 input channels on the matrix cores (conv_stem_kxk.hip): the switch is read per plan, not per process
+        const char *sk = getenv("SHL_MI355X_STEMKXK");
+        if (!(sk && sk[0] == '0') && stem_kxk_takes(d, !(sk && sk[0] == '1'))) return SHL_MI355X_ALGO_STEM;
+    }
     return igemm_supports(d) ? SHL_MI355X_ALGO_IGEMM : SHL_MI355X_ALGO_DIRECT;
 }
 
@@ -504,8 +519,9 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
         set_error("conv_plan_create: DW kernel needs NHWC, multiplier 1 and C %% 4 == 0");
         return SHL_MI355X_ENOTSUP;
     }
-    if (algo == SHL_MI355X_ALGO_STEM && !stem_supports(d)) {
-        set_error("conv_plan_create: STEM kernel needs int8 NHWC 3x3 with 3 input channels, Cout <= 64");
+    if (algo == SHL_MI355X_ALGO_STEM && !stem_supports(d) && !stem_kxk_takes(d, false)) {
+        set_error("conv_plan_create: STEM kernels need int8 NHWC 3x3 with 3 input channels, Cout <= 64, or int8 with 1..4 input channels, "
+                  "not 3x3, a filter row of at most 64 bytes, strides up to 16 and no dilation");
         return SHL_MI355X_ENOTSUP;
     }
     if (algo == SHL_MI355X_ALGO_GROUP && d.group < 2) {
@@ -607,6 +623,10 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
             if (conv1x1_resident_pick(probe)) p->kernel_name = "conv1x1_resident_i8_mfma32x32x32";
             if (conv1x1_latency_pick(probe)) p->kernel_name = "conv1x1_latency_i8_mfma32x32x32";
         }
+    } else if (algo == SHL_MI355X_ALGO_STEM && !stem_supports(d)) {  // the Kh x Kw form (the two scopes are disjoint: it excludes 3x3)
+        p->kernel_name = "conv_stem_kxk_i8_mfma32x32x32";
+        p->kstride = STEM_KXK_KSTRIDE;
+        w_bytes = conv_stem_kxk_weight_bytes(d.in_c, d.out_c, d.kernel_h, d.kernel_w);
     } else if (algo == SHL_MI355X_ALGO_STEM) {
         w_bytes = stem_weight_bytes(d);
         p->kernel_name = "conv_stem_i8_dot4";
@@ -660,6 +680,7 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
     // 1 KiB load (from [Cout][K] rows it is 64 lines per load instruction)
     const bool group_mfma = algo == SHL_MI355X_ALGO_GROUP && p->kstride == GROUP_MFMA_KSTRIDE;
     const bool group_mfma_f16 = algo == SHL_MI355X_ALGO_GROUP && p->kstride == GROUP_MFMA_F16_KSTRIDE;
+    const bool stem_kxk = algo == SHL_MI355X_ALGO_STEM && p->kstride == STEM_KXK_KSTRIDE;
     const bool frag_copy = algo == SHL_MI355X_ALGO_IGEMM && d.kernel_h == 1 && d.kernel_w == 1 &&
                            (d.in_c * es) % 32 == 0 && d.in_c * es <= 4096 && d.out_c % 32 == 0;
     if (frag_copy) {
@@ -697,6 +718,8 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
                 patch_pack_weights(d, p->pt_geom, reinterpret_cast<const int8_t *>(src),
                                    reinterpret_cast<int8_t *>(host.data() + p->off_wpatch));
         }
+        else if (stem_kxk)
+            ;  // packed below, with its acc_init
         else if (algo == SHL_MI355X_ALGO_STEM)
             stem_pack_weights(d, reinterpret_cast<const int8_t *>(src),
                               reinterpret_cast<int32_t *>(host.data() + p->off_w));
@@ -713,7 +736,19 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
         if (group_mfma)  // fragment order, block-diagonal where the groups are narrow; padding is materialised as zp_in here too
             conv_group_mfma_pack(reinterpret_cast<const int8_t *>(src), d.in_c, d.out_c, d.group, d.kernel_h, d.kernel_w, d.in_zp,
                                  reinterpret_cast<int8_t *>(host.data() + p->off_w), acc);
-        if (algo == SHL_MI355X_ALGO_STEM) {
+        if (stem_kxk) {  // fragment order from OHWI (an NCHW layer's weights arrive OIHW); padding is materialised as zp_in here too
+            const int8_t *w8 = reinterpret_cast<const int8_t *>(src);
+            std::vector<int8_t> ohwi;
+            if (d.layout == SHL_MI355X_NCHW) {
+                const int taps = d.kernel_h * d.kernel_w;
+                ohwi.resize(raw_w);
+                for (int oc = 0; oc < d.out_c; ++oc)
+                    for (int ic = 0; ic < d.in_c; ++ic)
+                        for (int t = 0; t < taps; ++t) ohwi[((size_t)oc * taps + t) * d.in_c + ic] = w8[((size_t)oc * d.in_c + ic) * taps + t];
+                w8 = ohwi.data();
+            }
+            conv_stem_kxk_pack(w8, d.in_c, d.out_c, d.kernel_h, d.kernel_w, d.in_zp, reinterpret_cast<int8_t *>(host.data() + p->off_w), acc);
+        } else if (algo == SHL_MI355X_ALGO_STEM) {
             // padding is materialised as zp_in here too
             const int8_t *w8 = reinterpret_cast<const int8_t *>(src);
             for (int oc = 0; oc < d.out_c; ++oc) {
@@ -746,7 +781,7 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
             }
         }
     }
-    if ((algo == SHL_MI355X_ALGO_IGEMM || group_mfma || group_mfma_f16) && d.layout == SHL_MI355X_NCHW && d.batch > 0) {
+    if ((algo == SHL_MI355X_ALGO_IGEMM || group_mfma || group_mfma_f16 || stem_kxk) && d.layout == SHL_MI355X_NCHW && d.batch > 0) {
         const size_t in_b = (size_t)d.batch * d.in_c * d.in_h * d.in_w * es;
         const size_t out_b = (size_t)d.batch * d.out_c * d.out_h * d.out_w * es;
         if (hipMalloc((void **)&p->scratch_in, in_b) != hipSuccess ||
@@ -1137,8 +1172,22 @@ static int conv_forward_impl(const shl_mi355x_conv_plan *plan, const void *input
         case SHL_MI355X_ALGO_DW:
             if (d.layout == SHL_MI355X_NCHW) return launch_dwconv_nchw(a, d.dtype, s);
             return launch_dwconv(a, d.dtype, d.layout, s);
-        case SHL_MI355X_ALGO_STEM:
-            return launch_conv_stem(a, s);
+        case SHL_MI355X_ALGO_STEM: {
+            if (plan->kstride != STEM_KXK_KSTRIDE) return launch_conv_stem(a, s);
+            if (d.layout == SHL_MI355X_NHWC) return launch_conv_stem_kxk(a, s);
+            // conv_stem_kxk.hip on the NHWC view: [C][HW] -> [HW][C] scratch, the kernel, [HoWo][Co] -> [Co][HoWo]
+            if (a.N > d.batch || !plan->scratch_in) {
+                set_error("conv_forward: NCHW plan was created for batch %d, got %d", d.batch, a.N);
+                return SHL_MI355X_EINVAL;
+            }
+            int rc = launch_transpose(input_dev, plan->scratch_in, a.N, a.C, a.H * a.W, 1, s, 1);
+            if (rc != SHL_MI355X_OK) return rc;
+            a.in = plan->scratch_in;
+            a.out = plan->scratch_out;
+            rc = launch_conv_stem_kxk(a, s);
+            if (rc != SHL_MI355X_OK) return rc;
+            return launch_transpose(plan->scratch_out, output_dev, a.N, a.Ho * a.Wo, a.Co, 1, s, 0);
+        }
         case SHL_MI355X_ALGO_DW_CHANNEL:
             return launch_dwconv_channel(a, s);
         case SHL_MI355X_ALGO_GROUP: {
@@ -1218,7 +1267,7 @@ static int pwdw_kernel_for(const shl_mi355x_conv_plan *pw, const shl_mi355x_conv
         // consumers, a non-1x1 layer behind it: shl_mi355x_conv_plan_set_no_stream_consumer; without the hint both fusions were lost)
         if (!(sel && sel[0] == '2') && dw_dot4 && (dwpw_stream_takes(b) || dwpw_resident_takes(b)) && !dw->no_stream_consumer) return 0;
     }
-    if (pw->algo == SHL_MI355X_ALGO_STEM) return dw_dot4 && stemdw_fusable(a, b) ? 3 : 0;  // stem + depthwise
+    if (pw->algo == SHL_MI355X_ALGO_STEM) return pw->kstride == 0 && dw_dot4 && stemdw_fusable(a, b) ? 3 : 0;  // stem (3x3 form) + depthwise
     return pwdw_fusable(a, b, pw_igemm, dw_dot4) ? 1 : 0;
 }
 

@@ -62,7 +62,8 @@ enum shl_mi355x_algo {
     SHL_MI355X_ALGO_IGEMM = 2,  /* LDS-staged implicit GEMM on MFMA */
     SHL_MI355X_ALGO_DW = 3,     /* bandwidth-tuned depthwise kernel */
     SHL_MI355X_ALGO_GEMV = 4,   /* fullyconnected, small batch (reserved) */
-    SHL_MI355X_ALGO_STEM = 5,   /* 3x3 conv with 3 input channels (image stem), v_dot4 */
+    SHL_MI355X_ALGO_STEM = 5,   /* image stems, int8: 3x3 with 3 input channels NHWC (v_dot4 / MFMA from registers), or Kh x Kw (not 3x3)
+                                   with 1..4 input channels, NHWC or NCHW, on the matrix cores over an LDS patch (conv_stem_kxk.hip) */
     SHL_MI355X_ALGO_DW_CHANNEL = 6, /* CSINN_OP_DEPTHWISE_CONV2D_CHANNEL: int64 accumulation (plan_create_dw_channel) */
     /* grouped convolution (1 < group, not depthwise) with shl_ref_group_conv2d_quant's slice semantics
      * (source/reference/convolution.c:271-354, 476-508), ONE launch per layer:
