@@ -52,7 +52,8 @@ NO_SPILL_SOURCES = ("conv_igemm.hip", "conv_igemm_pp.hip", "conv_igemm_pc.hip",
                     "dwconv_kxk.hip",  # (four tiles' accumulators live across the tap loop: a spill there is the whole loop's cost)
                     "conv_group_mfma.hip",  # (the same four accumulators beside the next slab's patch in registers)
                     "conv_group_mfma_f16.hip",  # (eight accumulators and their B fragments beside the next slab's patch)
-                    "conv_stem_kxk.hip")  # (four accumulators and the five dwords of each unaligned B fragment across the K loop)
+                    "conv_stem_kxk.hip",  # (four accumulators and the five dwords of each unaligned B fragment across the K loop)
+                    "conv_igemm_cpad.hip")  # (four accumulators across the K loop; sixteen staging dwords in flight in front of it)
 
 
 def spilled_kernels(usage_file):

@@ -603,6 +603,13 @@ bool conv_stem_kxk_pick(int N, int C, int Co, int H, int W, int Ho, int Wo, int 
 size_t conv_stem_kxk_weight_bytes(int C, int Co, int Kh, int Kw);
 void conv_stem_kxk_pack(const int8_t *ohwi, int C, int Co, int Kh, int Kw, int in_zp, int8_t *dst, int32_t *acc_init);
 int launch_conv_stem_kxk(const ConvArgs &a, hipStream_t s);
+// dense int8 layers with 8 <= in_c, in_c % 16 != 0 on the matrix cores over a re-pitched LDS patch (conv_igemm_cpad.hip; scope,
+// geometry, LDS budget, packing and the default rule: cpad.h), the second form of an ALGO_DIRECT plan.  Arguments as above.
+bool conv_igemm_cpad_pick(int N, int C, int Co, int H, int W, int Ho, int Wo, int Kh, int Kw, int sh, int sw, int pt, int pl, int dh, int dw,
+                          int in_zp, bool nchw, bool by_rule);
+size_t conv_igemm_cpad_weight_bytes(int C, int Co, int Kh, int Kw);
+void conv_igemm_cpad_pack(const int8_t *ohwi, int C, int Co, int Kh, int Kw, int in_zp, int8_t *dst, int32_t *acc_init);
+int launch_conv_igemm_cpad(const ConvArgs &a, hipStream_t s);
 // NCHW-native kernels for latency-bound sizes (nchw_small.hip)
 bool conv1x1_nchw_eligible(const ConvArgs &a);
 int launch_conv1x1_nchw(const ConvArgs &a, int dtype, hipStream_t s);

@@ -2,7 +2,11 @@
 //
 // The safety net of the backend: covers every shape the MFMA / depthwise kernels decline
 // (Cin not a multiple of the MFMA chunk, depth multipliers, grouped convolution, odd
-// channel counts).  Replaces shl_ref_conv2d_nhwc_f32 / shl_ref_depthwise_conv2d_*_f32 /
+// channel counts).  Dense int8 layers with 8 <= Cin, Cin % 16 != 0 (symmetric weights, fast
+// epilogue, no dilation, kernels up to 7x7, strides up to 4) have a matrix-core kernel of their
+// own, conv_igemm_cpad.hip, a second form of an ALGO_DIRECT plan: they come here when the caller
+// asks for ALGO_DIRECT, under SHL_MI355X_CPAD=0, where cpad.h's geometry or default rule declines
+// them, and always for binary16, asymmetric weights and dilation.  Replaces shl_ref_conv2d_nhwc_f32 / shl_ref_depthwise_conv2d_*_f32 /
 // shl_ref_group_conv2d_*_f32 (source/reference/convolution.c:28-354) inside
 // shl_ref_*_quant (:370-508).
 //

@@ -101,6 +101,19 @@ static bool stem_kxk_takes(const shl_mi355x_conv_desc &d, bool by_rule)
                               d.dilation_h, d.dilation_w, d.in_zp, d.layout == SHL_MI355X_NCHW, by_rule);
 }
 
+// The one rule of conv_igemm_cpad.hip, the second form of an ALGO_DIRECT plan, likewise: dense int8 layers whose channel count is
+// no multiple of 16.  SHL_MI355X_CPAD ("0" never, "1" wherever the geometry fits, unset: the measured rule) is read by
+// plan_create_impl at EACH plan creation, for SHL_MI355X_ALGO_AUTO only -- a caller who asks for ALGO_DIRECT keeps the direct
+// kernel -- and ends up in the plan's marker; the launch goes by the marker and asks the geometry alone, never the environment.
+// The plan's algo stays ALGO_DIRECT, so every fusion rule that asks for an implicit-GEMM plan keeps declining these layers.
+constexpr int32_t CPAD_KSTRIDE = 16;  // plan->kstride of such a plan: bytes per K chunk (the direct kernel's plans carry 0)
+static bool cpad_takes(const shl_mi355x_conv_desc &d, bool by_rule)
+{
+    return d.dtype == SHL_MI355X_I8 && d.group == 1 &&
+           conv_igemm_cpad_pick(d.batch, d.in_c, d.out_c, d.in_h, d.in_w, d.out_h, d.out_w, d.kernel_h, d.kernel_w, d.stride_h, d.stride_w,
+                                d.pad_top, d.pad_left, d.dilation_h, d.dilation_w, d.in_zp, d.layout == SHL_MI355X_NCHW, by_rule);
+}
+
 // a transposed convolution's plan (deconv.hip): no partner of any pair or pool fusion
 static bool is_deconv(const shl_mi355x_conv_plan *p)
 {
@@ -498,6 +511,11 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
         algo = choose_algo(d);
         if (algo >= 0 && (!fast_epilogue_ok || w_asym)) algo = SHL_MI355X_ALGO_DIRECT;
     }
+    bool cpad = false;  // conv_igemm_cpad.hip: the matrix-core form of an ALGO_DIRECT plan
+    if (d.algo == SHL_MI355X_ALGO_AUTO && algo == SHL_MI355X_ALGO_DIRECT && fast_epilogue_ok && !w_asym) {
+        const char *cs = getenv("SHL_MI355X_CPAD");
+        cpad = !(cs && cs[0] == '0') && cpad_takes(d, !(cs && cs[0] == '1'));
+    }
     if (w_asym && algo >= 0 && algo != SHL_MI355X_ALGO_DIRECT && algo != SHL_MI355X_ALGO_GROUP) {
         set_error("conv_plan_create: asymmetric weights run on the DIRECT / GROUP kernels only");
         return SHL_MI355X_ENOTSUP;
@@ -664,6 +682,10 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
             p->kstride = GROUP_MFMA_F16_KSTRIDE;
             w_bytes = conv_group_mfma_f16_weight_bytes(d.in_c, d.out_c, d.group, d.kernel_h, d.kernel_w);
         }
+    } else if (cpad) {
+        p->kernel_name = "conv_igemm_cpad_i8_mfma32x32x32";
+        p->kstride = CPAD_KSTRIDE;
+        w_bytes = conv_igemm_cpad_weight_bytes(d.in_c, d.out_c, d.kernel_h, d.kernel_w);
     } else {
         p->kernel_name = d.dtype == SHL_MI355X_I8 ? (w_asym ? "conv_direct_i8_wzp" : "conv_direct_i8") : "conv_direct_f16";
     }
@@ -718,7 +740,7 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
                 patch_pack_weights(d, p->pt_geom, reinterpret_cast<const int8_t *>(src),
                                    reinterpret_cast<int8_t *>(host.data() + p->off_wpatch));
         }
-        else if (stem_kxk)
+        else if (stem_kxk || cpad)
             ;  // packed below, with its acc_init
         else if (algo == SHL_MI355X_ALGO_STEM)
             stem_pack_weights(d, reinterpret_cast<const int8_t *>(src),
@@ -736,7 +758,7 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
         if (group_mfma)  // fragment order, block-diagonal where the groups are narrow; padding is materialised as zp_in here too
             conv_group_mfma_pack(reinterpret_cast<const int8_t *>(src), d.in_c, d.out_c, d.group, d.kernel_h, d.kernel_w, d.in_zp,
                                  reinterpret_cast<int8_t *>(host.data() + p->off_w), acc);
-        if (stem_kxk) {  // fragment order from OHWI (an NCHW layer's weights arrive OIHW); padding is materialised as zp_in here too
+        if (stem_kxk || cpad) {  // fragment order from OHWI (an NCHW layer's weights arrive OIHW); padding is materialised as zp_in here too
             const int8_t *w8 = reinterpret_cast<const int8_t *>(src);
             std::vector<int8_t> ohwi;
             if (d.layout == SHL_MI355X_NCHW) {
@@ -747,7 +769,8 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
                         for (int t = 0; t < taps; ++t) ohwi[((size_t)oc * taps + t) * d.in_c + ic] = w8[((size_t)oc * d.in_c + ic) * taps + t];
                 w8 = ohwi.data();
             }
-            conv_stem_kxk_pack(w8, d.in_c, d.out_c, d.kernel_h, d.kernel_w, d.in_zp, reinterpret_cast<int8_t *>(host.data() + p->off_w), acc);
+            (cpad ? conv_igemm_cpad_pack : conv_stem_kxk_pack)(w8, d.in_c, d.out_c, d.kernel_h, d.kernel_w, d.in_zp,
+                                                               reinterpret_cast<int8_t *>(host.data() + p->off_w), acc);
         } else if (algo == SHL_MI355X_ALGO_STEM) {
             // padding is materialised as zp_in here too
             const int8_t *w8 = reinterpret_cast<const int8_t *>(src);
@@ -781,7 +804,7 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
             }
         }
     }
-    if ((algo == SHL_MI355X_ALGO_IGEMM || group_mfma || group_mfma_f16 || stem_kxk) && d.layout == SHL_MI355X_NCHW && d.batch > 0) {
+    if ((algo == SHL_MI355X_ALGO_IGEMM || group_mfma || group_mfma_f16 || stem_kxk || cpad) && d.layout == SHL_MI355X_NCHW && d.batch > 0) {
         const size_t in_b = (size_t)d.batch * d.in_c * d.in_h * d.in_w * es;
         const size_t out_b = (size_t)d.batch * d.out_c * d.out_h * d.out_w * es;
         if (hipMalloc((void **)&p->scratch_in, in_b) != hipSuccess ||
@@ -1222,9 +1245,23 @@ static int conv_forward_impl(const shl_mi355x_conv_plan *plan, const void *input
             return launch_deconv_gather(a, d.dtype, d.layout, s);
         case SHL_MI355X_ALGO_DECONV_PHASE:
             return launch_deconv_phase(a, d, s);
-        default:
-            return launch_conv_direct(a, d.dtype, d.layout,
-                                      is_depthwise(d) && d.layout == SHL_MI355X_NHWC, s);
+        default: {
+            if (plan->algo != SHL_MI355X_ALGO_DIRECT || plan->kstride != CPAD_KSTRIDE)
+                return launch_conv_direct(a, d.dtype, d.layout, is_depthwise(d) && d.layout == SHL_MI355X_NHWC, s);
+            if (d.layout == SHL_MI355X_NHWC) return launch_conv_igemm_cpad(a, s);
+            // conv_igemm_cpad.hip on the NHWC view: [C][HW] -> [HW][C] scratch, the kernel, [HoWo][Co] -> [Co][HoWo]
+            if (a.N > d.batch || !plan->scratch_in) {
+                set_error("conv_forward: NCHW plan was created for batch %d, got %d", d.batch, a.N);
+                return SHL_MI355X_EINVAL;
+            }
+            int rc = launch_transpose(input_dev, plan->scratch_in, a.N, a.C, a.H * a.W, 1, s, 1);
+            if (rc != SHL_MI355X_OK) return rc;
+            a.in = plan->scratch_in;
+            a.out = plan->scratch_out;
+            rc = launch_conv_igemm_cpad(a, s);
+            if (rc != SHL_MI355X_OK) return rc;
+            return launch_transpose(plan->scratch_out, output_dev, a.N, a.Ho * a.Wo, a.Co, 1, s, 0);
+        }
     }
 }
 
