@@ -610,6 +610,14 @@ bool conv_igemm_cpad_pick(int N, int C, int Co, int H, int W, int Ho, int Wo, in
 size_t conv_igemm_cpad_weight_bytes(int C, int Co, int Kh, int Kw);
 void conv_igemm_cpad_pack(const int8_t *ohwi, int C, int Co, int Kh, int Kw, int in_zp, int8_t *dst, int32_t *acc_init);
 int launch_conv_igemm_cpad(const ConvArgs &a, hipStream_t s);
+// depthwise NCHW layers whose kernel is not 3x3 (1..7 taps per axis, strides 1 / 2), int8 and binary16, over an LDS patch per plane
+// (dwconv_kxk_nchw.hip; scope, geometry, LDS budget, packing and the default rule: dw_nchw_kxk.h), another second form of an
+// ALGO_DIRECT plan.  The caller vouches for symmetric weights and the fast epilogue (int8).
+bool dwconv_kxk_nchw_pick(bool i8, int N, int C, int Co, int group, int H, int W, int Ho, int Wo, int Kh, int Kw, int sh, int sw, int dh, int dw,
+                          int in_zp, bool by_rule);
+size_t dwconv_kxk_nchw_weight_bytes(int C, int Kh);
+void dwconv_kxk_nchw_pack(const int8_t *o1hw, int C, int Kh, int Kw, int in_zp, uint32_t *dst, int32_t *acc_init);
+int launch_dwconv_kxk_nchw(const ConvArgs &a, int dtype, hipStream_t s);
 // NCHW-native kernels for latency-bound sizes (nchw_small.hip)
 bool conv1x1_nchw_eligible(const ConvArgs &a);
 int launch_conv1x1_nchw(const ConvArgs &a, int dtype, hipStream_t s);

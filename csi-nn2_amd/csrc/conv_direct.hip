@@ -6,7 +6,11 @@
 // epilogue, no dilation, kernels up to 7x7, strides up to 4) have a matrix-core kernel of their
 // own, conv_igemm_cpad.hip, a second form of an ALGO_DIRECT plan: they come here when the caller
 // asks for ALGO_DIRECT, under SHL_MI355X_CPAD=0, where cpad.h's geometry or default rule declines
-// them, and always for binary16, asymmetric weights and dilation.  Replaces shl_ref_conv2d_nhwc_f32 / shl_ref_depthwise_conv2d_*_f32 /
+// them, and always for binary16, asymmetric weights and dilation.  Depthwise NCHW layers (multiplier 1) whose kernel is not
+// 3x3 -- 1..7 taps per axis, strides 1 / 2, int8 and binary16 -- have dwconv_kxk_nchw.hip, another second form of an
+// ALGO_DIRECT plan: they come here when the caller asks for ALGO_DIRECT, under SHL_MI355X_DWNCHW=0, where dw_nchw_kxk.h's
+// geometry or default rule declines them, and always with dilation, a depth multiplier, asymmetric weights or the
+// hardware-division epilogue.  Replaces shl_ref_conv2d_nhwc_f32 / shl_ref_depthwise_conv2d_*_f32 /
 // shl_ref_group_conv2d_*_f32 (source/reference/convolution.c:28-354) inside
 // shl_ref_*_quant (:370-508).
 //

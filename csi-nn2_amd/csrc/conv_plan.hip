@@ -114,6 +114,18 @@ static bool cpad_takes(const shl_mi355x_conv_desc &d, bool by_rule)
                                 d.pad_top, d.pad_left, d.dilation_h, d.dilation_w, d.in_zp, d.layout == SHL_MI355X_NCHW, by_rule);
 }
 
+// The one rule of dwconv_kxk_nchw.hip, a second form of an ALGO_DIRECT plan as well: depthwise NCHW layers (multiplier 1) whose
+// kernel is not 3x3, int8 and binary16.  SHL_MI355X_DWNCHW ("0" never, "1" wherever scope and geometry fit, unset: the measured
+// rule) is read by plan_create_impl at EACH plan creation, for SHL_MI355X_ALGO_AUTO only, and ends up in the plan's marker; the
+// launch goes by the marker and asks scope and geometry alone, never the environment.
+constexpr int32_t DWNCHW_KSTRIDE = 8;  // plan->kstride of such a plan: bytes per packed int8 filter row (binary16: the marker alone)
+static bool dw_nchw_kxk_takes(const shl_mi355x_conv_desc &d, bool by_rule)
+{
+    return d.layout == SHL_MI355X_NCHW && is_depthwise(d) &&
+           dwconv_kxk_nchw_pick(d.dtype == SHL_MI355X_I8, d.batch, d.in_c, d.out_c, d.group, d.in_h, d.in_w, d.out_h, d.out_w, d.kernel_h,
+                                d.kernel_w, d.stride_h, d.stride_w, d.dilation_h, d.dilation_w, d.in_zp, by_rule);
+}
+
 // a transposed convolution's plan (deconv.hip): no partner of any pair or pool fusion
 static bool is_deconv(const shl_mi355x_conv_plan *p)
 {
@@ -516,6 +528,11 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
         const char *cs = getenv("SHL_MI355X_CPAD");
         cpad = !(cs && cs[0] == '0') && cpad_takes(d, !(cs && cs[0] == '1'));
     }
+    bool dw_nchw = false;  // dwconv_kxk_nchw.hip: the LDS-patch form of an ALGO_DIRECT plan (depthwise: never a cpad layer)
+    if (d.algo == SHL_MI355X_ALGO_AUTO && algo == SHL_MI355X_ALGO_DIRECT && fast_epilogue_ok && !w_asym) {
+        const char *ds = getenv("SHL_MI355X_DWNCHW");
+        dw_nchw = !(ds && ds[0] == '0') && dw_nchw_kxk_takes(d, !(ds && ds[0] == '1'));
+    }
     if (w_asym && algo >= 0 && algo != SHL_MI355X_ALGO_DIRECT && algo != SHL_MI355X_ALGO_GROUP) {
         set_error("conv_plan_create: asymmetric weights run on the DIRECT / GROUP kernels only");
         return SHL_MI355X_ENOTSUP;
@@ -686,6 +703,10 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
         p->kernel_name = "conv_igemm_cpad_i8_mfma32x32x32";
         p->kstride = CPAD_KSTRIDE;
         w_bytes = conv_igemm_cpad_weight_bytes(d.in_c, d.out_c, d.kernel_h, d.kernel_w);
+    } else if (dw_nchw) {
+        p->kernel_name = d.dtype == SHL_MI355X_I8 ? "dwconv_kxk_nchw_i8" : "dwconv_kxk_nchw_f16";
+        p->kstride = DWNCHW_KSTRIDE;
+        if (d.dtype == SHL_MI355X_I8) w_bytes = dwconv_kxk_nchw_weight_bytes(d.in_c, d.kernel_h);  // binary16: O1HW as it came
     } else {
         p->kernel_name = d.dtype == SHL_MI355X_I8 ? (w_asym ? "conv_direct_i8_wzp" : "conv_direct_i8") : "conv_direct_f16";
     }
@@ -740,7 +761,7 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
                 patch_pack_weights(d, p->pt_geom, reinterpret_cast<const int8_t *>(src),
                                    reinterpret_cast<int8_t *>(host.data() + p->off_wpatch));
         }
-        else if (stem_kxk || cpad)
+        else if (stem_kxk || cpad || (dw_nchw && d.dtype == SHL_MI355X_I8))
             ;  // packed below, with its acc_init
         else if (algo == SHL_MI355X_ALGO_STEM)
             stem_pack_weights(d, reinterpret_cast<const int8_t *>(src),
@@ -758,6 +779,9 @@ static int plan_create_impl(const struct shl_mi355x_conv_desc *desc, const void 
         if (group_mfma)  // fragment order, block-diagonal where the groups are narrow; padding is materialised as zp_in here too
             conv_group_mfma_pack(reinterpret_cast<const int8_t *>(src), d.in_c, d.out_c, d.group, d.kernel_h, d.kernel_w, d.in_zp,
                                  reinterpret_cast<int8_t *>(host.data() + p->off_w), acc);
+        if (dw_nchw && d.dtype == SHL_MI355X_I8)  // two dwords per filter row from O1HW; padding is materialised as zp_in here too
+            dwconv_kxk_nchw_pack(reinterpret_cast<const int8_t *>(src), d.in_c, d.kernel_h, d.kernel_w, d.in_zp,
+                                 reinterpret_cast<uint32_t *>(host.data() + p->off_w), acc);
         if (stem_kxk || cpad) {  // fragment order from OHWI (an NCHW layer's weights arrive OIHW); padding is materialised as zp_in here too
             const int8_t *w8 = reinterpret_cast<const int8_t *>(src);
             std::vector<int8_t> ohwi;
@@ -1246,6 +1270,7 @@ static int conv_forward_impl(const shl_mi355x_conv_plan *plan, const void *input
         case SHL_MI355X_ALGO_DECONV_PHASE:
             return launch_deconv_phase(a, d, s);
         default: {
+            if (plan->algo == SHL_MI355X_ALGO_DIRECT && plan->kstride == DWNCHW_KSTRIDE) return launch_dwconv_kxk_nchw(a, d.dtype, s);
             if (plan->algo != SHL_MI355X_ALGO_DIRECT || plan->kstride != CPAD_KSTRIDE)
                 return launch_conv_direct(a, d.dtype, d.layout, is_depthwise(d) && d.layout == SHL_MI355X_NHWC, s);
             if (d.layout == SHL_MI355X_NHWC) return launch_conv_igemm_cpad(a, s);

@@ -60,7 +60,10 @@ enum shl_mi355x_algo {
     SHL_MI355X_ALGO_AUTO = 0,
     SHL_MI355X_ALGO_DIRECT = 1, /* one thread per output, any shape (VALU).  A plan that ALGO_AUTO resolved to this value may run dense int8
                                    layers with 8 <= in_c, in_c % 16 != 0 on the matrix cores instead (conv_igemm_cpad.hip; the kernel name
-                                   says which); a plan REQUESTED as ALGO_DIRECT always runs the one-output-per-thread kernel */
+                                   says which; marker kstride == 16), and depthwise NCHW layers whose kernel is not 3x3 (1..7 taps per
+                                   axis, strides 1 / 2, int8 and binary16) over an LDS patch per plane (dwconv_kxk_nchw.hip, kernel names
+                                   dwconv_kxk_nchw_i8 / _f16; marker kstride == 8); a plan REQUESTED as ALGO_DIRECT always runs the
+                                   one-output-per-thread kernel */
     SHL_MI355X_ALGO_IGEMM = 2,  /* LDS-staged implicit GEMM on MFMA */
     SHL_MI355X_ALGO_DW = 3,     /* bandwidth-tuned depthwise kernel */
     SHL_MI355X_ALGO_GEMV = 4,   /* fullyconnected, small batch (reserved) */
